@@ -10,9 +10,12 @@ with N GPUs every rank imputes its own batch (weak scaling), no collective on th
 that way already (the driver launches it as `python -m torch.distributed.run ... bench.py --gpus N`).
 
 Prints ONE JSON line (rank 0) with the contract fields plus `roofline` (dominant kernel, HIP-event
-timed inside the library on its launch stream), `cpu_baseline` (the fp64 C oracle, one sample per
-physical host core, on a bounded share of the same workload; N = 1 only) and `parity_vs_cpu_path`
-(the GPU re-running the baseline's own calls: labels, dosage r2).
+timed inside the library on its launch stream).  A plain run does only what that line needs: set up, warm
+up, time the steps, write `--dump-outputs DIR` if given, print.  `--full` adds what takes runs of its own:
+`cpu_baseline` (the fp64 C oracle, one sample per usable physical host core; N = 1 only),
+`parity_vs_cpu_path` (the GPU re-running the baseline's own calls: labels, dosage r2),
+`dosage_r2_vs_cpu_pipeline`, `kernels_alone`, `one_sample_latency_s` and, with --mspbwt, the comparison with
+the neighbour scan.
 """
 import argparse
 import json
@@ -82,15 +85,27 @@ def workload_label(mode, K, batch, mspbwt=False, rare_common=False):
     return base + ", per-GPU share"
 
 
+def usable_cpus():
+    """The logical CPUs this process may run on: its affinity mask, bounded by a cgroup v2 CPU quota where one is set."""
+    n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    try:
+        quota, period = open("/sys/fs/cgroup/cpu.max").read().split()[:2]
+        if quota != "max":
+            n = min(n, max(1, int(quota) // int(period)))
+    except (OSError, ValueError):
+        pass
+    return max(1, n)
+
+
 def physical_cores():
+    """Physical cores, but no more than the CPUs this process may use (a worker per core beyond them only queues)."""
+    n = None
     try:
         import psutil
         n = psutil.cpu_count(logical=False)
-        if n:
-            return int(n)
     except Exception:
         pass
-    return os.cpu_count() or 1
+    return max(1, min(int(n or os.cpu_count() or 1), usable_cpus()))
 
 
 def _cpu_inputs(panel, n_reads, i, Ksubset, ff):
@@ -155,15 +170,31 @@ def _sample_worker(args):
     return s
 
 
-def make_samples(panel, seeds, n_reads, n_proc, mode="short", rare_common=None, bam_dir=None):
-    """Synthetic samples, generated by forked workers (before any HIP context exists in this process)."""
+def make_samples(panel, seeds, n_reads, n_proc, mode="short", rare_common=None, bam_dir=None, defer=False):
+    """Synthetic samples, generated by forked workers (forked before any HIP context exists in this process).  defer: return
+    at once a function wait(n) that returns the first n samples (all by default) as soon as they exist, so that the caller can
+    set the device up and warm it up while the workers run."""
     import multiprocessing as mp
     global _CPU_PANEL, _CPU_RC, _BAM_DIR
     _CPU_PANEL = panel
     _CPU_RC = rare_common
     _BAM_DIR = bam_dir
-    with mp.get_context("fork").Pool(max(1, n_proc)) as pool:
-        return pool.map(_sample_worker, [(sd, n_reads, mode) for sd in seeds], chunksize=4)
+    pool = mp.get_context("fork").Pool(max(1, n_proc))
+    it = pool.imap(_sample_worker, [(sd, n_reads, mode) for sd in seeds], chunksize=4)
+    got = []
+
+    def wait(n=len(seeds)):
+        try:
+            while len(got) < n:
+                got.append(next(it))
+        except BaseException:
+            pool.terminate()
+            raise
+        if len(got) == len(seeds):
+            pool.terminate()
+            pool.join()
+        return got[:n]
+    return wait if defer else wait()
 
 
 def reload_from_bams(panel, flat, seeds, bam_dir):
@@ -462,7 +493,17 @@ def main():
                          "an N-rank run and a 1-rank run over the same global steps must write the same files")
     ap.add_argument("--stub", action="store_true",
                     help="test hook: no device work at all (gloo rendezvous, a driver that returns zeros); value is 0")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure as well: the CPU baseline (--cpu-baseline, --no-cpu-baseline), parity "
+                         "with the CPU path, the dosage r2 vs the CPU pipeline (--r2-vs-cpu), the stand-alone kernel timings (--no-alone), "
+                         "the one-sample latency and, with --mspbwt, the comparison with the neighbour scan (--no-scan-check).  Without "
+                         "it a run sets up, warms up, times the steps, writes --dump-outputs and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the timed path returned for its last step as DIR/<name>.npy (float64): "
+                         "dosage, gp_t, phasing_haps, read_labels (+ read_label_ptr), nDosage and, with --mode nipt, fet_dosage and "
+                         "fet_gp_t, for a fixed seeded choice of the step's samples (sample_index) that keeps the files under 64 MB")
     a = ap.parse_args()
+    t_start = time.perf_counter()
     if a.fp64_dosage:
         a.precision = "fp64"
     maybe_spawn(a, sys.argv[1:])
@@ -506,6 +547,7 @@ def main():
     # everything that forks happens before any HIP context exists in this process
     from quilt_amd.synth import make_synthetic_panel
     panel = make_synthetic_panel(K=a.K, nSNPs=a.nsnps, seed=4916)
+    setup_s = {"panel_done": time.perf_counter() - t_start}   # (seconds since the arguments were parsed)
     if a.mode == "nipt":
         params["method"] = "nipt"
     rc = None
@@ -524,7 +566,7 @@ def main():
     cpu_flag = None
     if world > 1:
         cpu_flag = f"/tmp/quilt_amd_bench_{os.getppid()}_{os.environ.get('MASTER_PORT', '0')}.cpu_done"
-    if rank == 0 and not a.no_cpu_baseline and rc is None and not a.stub:
+    if a.full and rank == 0 and not a.no_cpu_baseline and rc is None and not a.stub:
         cpu, keep = cpu_baseline(panel, a.reads, params, full_chains, ff=ff, mspbwt=a.mspbwt)
     if cpu_flag is not None:
         if rank == 0:
@@ -543,15 +585,25 @@ def main():
         if rc is not None:
             raise SystemExit("--bam is not combined with --rare-common")
         bam_dir = tempfile.mkdtemp(prefix="quilt_amd_bams_")
-    flat = make_samples(panel, seeds, a.reads, min(32, max(1, physical_cores() // max(world, 1))), a.mode, rc, bam_dir)
+    # (a plain run sets the device up while the workers generate the samples; the CPU legs of --full need them first)
+    flat = make_samples(panel, seeds, a.reads, min(32, max(1, physical_cores() // max(world, 1))), a.mode, rc, bam_dir,
+                        defer=not (a.full or a.bam))
     if a.bam:
         import torch  # noqa: F401  (before libquilt_amd.so is loaded: both must resolve the HIP runtime torch ships, see main())
         flat, bam_load_s = reload_from_bams(panel, flat, seeds, bam_dir)
         a.bam_load_s = bam_load_s
         a.bam_dir = bam_dir   # (kept for the I/O-inclusive leg after the timed region; removed there)
-    samples = [flat[st * a.batch:(st + 1) * a.batch] for st in range(n_steps)]
+    pending = flat if callable(flat) else None
+    samples = [None] * n_steps if pending else [flat[st * a.batch:(st + 1) * a.batch] for st in range(n_steps)]
+
+    def samples_up_to(n):
+        """(a plain run) wait until the first n steps' samples exist"""
+        if pending is not None and n > 0 and samples[n - 1] is None:
+            got = pending(n * a.batch)
+            for st in range(n):
+                samples[st] = got[st * a.batch:(st + 1) * a.batch]
     cpu_pipeline = None
-    if (rank == 0 and world == 1 and not a.no_cpu_baseline and not a.stub and a.cpu_baseline == "whole" and
+    if (a.full and rank == 0 and world == 1 and not a.no_cpu_baseline and not a.stub and a.cpu_baseline == "whole" and
             (not a.mspbwt or a.mspbwt_search == "scan")):
         # the baseline proper: whole samples, one per physical core, all cores at once; the composed figure stays beside it
         cores = physical_cores()
@@ -567,7 +619,7 @@ def main():
             cpu = whole
         if ref is not None:
             cpu_pipeline = ref
-    if cpu_pipeline is None and rank == 0 and world == 1 and a.r2_vs_cpu > 0 and rc is None and not a.stub and not a.mspbwt:
+    if a.full and cpu_pipeline is None and rank == 0 and world == 1 and a.r2_vs_cpu > 0 and rc is None and not a.stub and not a.mspbwt:
         cpu_pipeline = cpu_pipeline_reference(a, panel, params, samples)
     import torch
     import torch.distributed as dist
@@ -601,6 +653,7 @@ def main():
                             cu_partition=a.cu_partition, fp64_dosage=a.precision != "mixed", split=a.split, gibbs_gate=a.gibbs_gate,
                             pass_priority=bool(a.pass_priority), exclusive=bool(a.exclusive),
                             fuse_tails=bool(a.fuse_tails), split_remainder=bool(a.split_remainder))
+    setup_s["device_ready"] = time.perf_counter() - t_start
 
     def barrier():
         if not a.stub:
@@ -617,13 +670,17 @@ def main():
             yield [smp for q in range(st, top) for smp in samples[q]], (rank * n_steps + st) * a.batch
 
     alone = None
-    if native is not None and rank == 0 and not a.no_alone and hasattr(drv, "drivers"):
+    if a.full and native is not None and rank == 0 and not a.no_alone and hasattr(drv, "drivers"):
         alone = kernels_alone(native, drv, samples)
 
     def timed_region(n_warm):
         """n_warm untimed batches, then the K timed batches bracketed by barriers; returns what report() needs."""
+        samples_up_to(n_warm)   # (a plain run warms up while the workers still generate the timed steps' samples)
         for _ in drv.run_stream(stream(0, n_warm)):
             pass
+        setup_s.setdefault("warmup_done", time.perf_counter() - t_start)
+        samples_up_to(n_steps)
+        setup_s.setdefault("samples_ready", time.perf_counter() - t_start)
         if native is not None:
             native.lib().qa_profile_reset()
             native.gate_stats(local_rank_dev, reset=True)
@@ -636,6 +693,7 @@ def main():
         timed_input = drv.prepare(stream(a.warmup, n_steps)) if hasattr(drv, "prepare") else None
         barrier()
         t0 = time.perf_counter()
+        setup_s.setdefault("clock_started", t0 - t_start)
         t0_gate = time.monotonic() * 1e3   # (std::chrono::steady_clock on Linux: the gate trace's clock)
         last = None
         # the K timed steps are K whole batches: the driver pipelines consecutive batches (phasing rounds of one fused
@@ -681,6 +739,8 @@ def main():
         return reg
 
     main_reg = timed_region(a.warmup)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, main_reg["last"])
     mixed_reg = None
     if a.precision == "both" and native is not None:
         for d in drv.devs:   # the same K batches again with the mixed dosage passes, in a timed region of their own
@@ -692,6 +752,7 @@ def main():
     if rank == 0:
         out = report(a, panel, params, native, drv, samples, main_reg, world, rc, cpu, keep, ff, full_chains, alone,
                      fp64=a.precision != "mixed")
+        out["setup_s"] = {k: round(v, 2) for k, v in setup_s.items()}
         if a.host_share > 1:
             out["host_share"] = {"of": a.host_share, "logical_cpus_used": len(os.sched_getaffinity(0)),
                                  "QA_HOST_THREADS": int(os.environ.get("QA_HOST_THREADS", "0")),
@@ -714,7 +775,7 @@ def main():
                                                                     "max_abs_diff": float(np.abs(a_ - b_).max())}
         if a.dotcall is None:
             a.dotcall = 0   # (80 s; off by default since round 5 -- `--dotcall 16` measures it: profiles/r05_bench_line_dotcall.json)
-        if native is not None and world == 1 and a.driver == "native" and hasattr(drv, "devs"):
+        if a.full and native is not None and world == 1 and a.driver == "native" and hasattr(drv, "devs"):
             # one sample alone on the device (the quick-start's shape): the latency of the whole per-sample pipeline
             from quilt_amd.impute import impute_samples
             t_l = time.perf_counter()
@@ -798,6 +859,30 @@ def main():
         if rank == 0 and cpu_flag is not None and os.path.exists(cpu_flag):
             os.remove(cpu_flag)
         dist.destroy_process_group()
+
+
+DUMP_BYTES = 60 * 2 ** 20   # --dump-outputs: the files of one run stay under 64 MB
+
+
+def dump_outputs(out_dir, last):
+    """--dump-outputs: the last timed step's results as a caller receives them (SampleResult), float64, for a fixed seeded
+    choice of the step's samples -- all of them when they fit in DUMP_BYTES -- so that two builds can be compared output for
+    output.  Each per-sample array is stacked over the chosen samples; the ragged read labels are concatenated, read_label_ptr
+    delimits them."""
+    fields = ["dosage", "gp_t", "phasing_haps", "nDosage"]
+    if last and last[0].fet_dosage is not None:
+        fields += ["fet_dosage", "fet_gp_t"]
+    per_sample = max(8 * (sum(np.size(getattr(r, f)) for f in fields) + np.size(r.read_labels) + 2) for r in last)
+    n = max(1, min(len(last), DUMP_BYTES // per_sample))
+    pick = np.arange(len(last)) if n == len(last) else np.sort(np.random.default_rng(20261016).choice(len(last), n, replace=False))
+    chosen = [last[i] for i in pick]
+    arrays = {f: np.stack([np.asarray(getattr(r, f), dtype=np.float64) for r in chosen]) for f in fields}
+    arrays["read_labels"] = np.concatenate([np.asarray(r.read_labels, dtype=np.float64) for r in chosen])
+    arrays["read_label_ptr"] = np.r_[0, np.cumsum([np.size(r.read_labels) for r in chosen])].astype(np.float64)
+    arrays["sample_index"] = pick.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(arr))
 
 
 def read_profile(native):
@@ -1042,7 +1127,7 @@ def report(a, panel, params, native, drv, samples, reg, world, rc, cpu, keep, ff
     truth = (samples[-1][0].all_snp if rc is not None else samples[-1][0]).truth_haps[:2].sum(axis=0)
     out["dosage_r2_vs_truth_sample0"] = float(np.corrcoef(last[0].dosage, truth)[0, 1] ** 2)
     out["cpu_baseline"] = cpu
-    if a.mspbwt and fp64 and native is not None and rc is None and not getattr(a, "no_scan_check", False):
+    if a.full and a.mspbwt and fp64 and native is not None and rc is None and not getattr(a, "no_scan_check", False):
         out["mspbwt_search_vs_neighbour_scan"] = search_vs_scan(drv.devs[0], panel, params, last[0])
     if keep is not None:
         dev = drv.devs[0]

@@ -4,7 +4,7 @@
 TAG=${1:-r05}
 OUT=$PWD/gpurun_out/$TAG; mkdir -p $OUT
 C="--no-alone --precision fp64 --dotcall 0 --r2-vs-cpu 0 --no-cpu-baseline"
-run() { local N=$1; shift; python bench.py $* > $OUT/bench_line_$N.json 2> $OUT/bench_$N.err; python - <<PY
+run() { local N=$1; shift; python bench.py --full $* > $OUT/bench_line_$N.json 2> $OUT/bench_$N.err; python - <<PY
 import json
 try:
     b=json.load(open("$OUT/bench_line_$N.json")); r=b["roofline"]

@@ -3,7 +3,7 @@
 OUT=$PWD/gpurun_out/r05; mkdir -p $OUT
 for CFG in "$@"; do
   set -- $CFG
-  python bench.py --mspbwt --rare-common 2 --steps 8 --warmup 2 --no-alone --precision fp64 --dotcall 0 --r2-vs-cpu 0 --no-cpu-baseline --workers $1 --fuse $2 --gate-trace $OUT/q2_gate_w$1_f$2.npy > $OUT/q2_w$1_f$2.json 2> $OUT/q2_w$1_f$2.err
+  python bench.py --full --mspbwt --rare-common 2 --steps 8 --warmup 2 --no-alone --precision fp64 --dotcall 0 --r2-vs-cpu 0 --no-cpu-baseline --workers $1 --fuse $2 --gate-trace $OUT/q2_gate_w$1_f$2.npy > $OUT/q2_w$1_f$2.json 2> $OUT/q2_w$1_f$2.err
   python - <<PY
 import json
 b=json.load(open("$OUT/q2_w$1_f$2.json"))

@@ -110,3 +110,54 @@ def test_bench_whole_sample_cpu_baseline_small():
     assert ref["n"] == 1 and ref["ref"][0].dosage.shape == (panel.nSNPs,)
     out2, ref2 = bench.cpu_baseline_whole(panel, params, work, 2, 0.01, 1)
     assert out2 is None and ref2 is None
+
+
+def _stub_bench(tmp_path, *extra):
+    import subprocess
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--stub", "--gpus", "1", "--K", "300", "--nsnps", "640",
+                          "--batch", "4", "--reads", "40", "--steps", "3", "--warmup", "1"] + list(extra),
+                         capture_output=True, text=True, timeout=600, env=env, cwd=str(tmp_path))
+    assert out.returncode == 0, out.stderr[-2000:]
+    return json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+
+
+def test_bench_plain_full_and_dump_outputs_on_the_stub(tmp_path):
+    """bench.py without a device (--stub): --steps sets the timed steps and ms_per_step is in the line; --dump-outputs writes the last
+    step's results as float64 .npy files, the same from run to run; --full is accepted and keeps the contract fields."""
+    import numpy as np
+    lines = [_stub_bench(tmp_path, "--dump-outputs", str(tmp_path / d)) for d in ("a", "b")]
+    for rec in lines:
+        assert rec["steps"] == 3 and rec["warmup"] == 1 and rec["ms_per_step"] >= 0 and rec["unit"] == "samples/sec"
+        assert "cpu_baseline" in rec and rec["cpu_baseline"] is None
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b"))
+    assert {"dosage.npy", "gp_t.npy", "phasing_haps.npy", "read_labels.npy", "read_label_ptr.npy", "sample_index.npy"} <= set(names)
+    for n in names:
+        x, y = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert x.dtype == np.float64 and np.array_equal(x, y), n
+    assert np.load(tmp_path / "a" / "dosage.npy").shape == (4, 640) and np.load(tmp_path / "a" / "gp_t.npy").shape == (4, 3, 640)
+    full = _stub_bench(tmp_path, "--full")
+    assert {k: full[k] for k in ("metric", "unit", "higher_is_better", "dtype", "steps")} == \
+           {k: lines[0][k] for k in ("metric", "unit", "higher_is_better", "dtype", "steps")}
+
+
+def test_bench_dump_outputs_keeps_a_seeded_sample_under_the_cap(tmp_path, monkeypatch):
+    """A step whose results exceed the cap is dumped as a fixed seeded choice of its samples: the same choice every time."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    from quilt_amd.driver import SampleResult
+    T = 1000
+    last = [SampleResult(np.full(T, i, dtype=np.float64), np.zeros((3, T)), np.zeros((T, 2)), np.arange(i + 1, dtype=np.int32), 1)
+            for i in range(10)]
+    monkeypatch.setattr(bench, "DUMP_BYTES", 3 * 8 * (6 * T + 20))
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), last)
+    idx = np.load(tmp_path / "a" / "sample_index.npy")
+    assert len(idx) == 3 and np.all(np.diff(idx) > 0) and np.array_equal(idx, np.load(tmp_path / "b" / "sample_index.npy"))
+    dos = np.load(tmp_path / "a" / "dosage.npy")
+    assert np.array_equal(dos[:, 0], idx)
+    ptr = np.load(tmp_path / "a" / "read_label_ptr.npy")
+    assert np.array_equal(np.diff(ptr), idx + 1) and len(np.load(tmp_path / "a" / "read_labels.npy")) == ptr[-1]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) < 64 * 10 ** 6

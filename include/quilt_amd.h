@@ -346,6 +346,27 @@ int qa_fullpass_reads_select_batch(qa_panel_t *panel, int32_t n_chain, int32_t n
                                    const uint64_t *seed_select, int32_t *which_next, int32_t *select_status);
 
 /*
+ * qa_fullpass_reads_select_batch that also returns, for every dosage pass, the reference's gamma_t column at ONE grid: what
+ * hla_run = TRUE keeps of the last seek iteration's passes (QUILT/R/functions.R:713-724 return_gamma_t = TRUE, :1261-1272
+ * gammaMT_t[, iGrid] / gammaMU_t[, iGrid]).  The value is reference-single.cpp's gamma_t_col(k) = alphaHat_t(k, iGrid) *
+ * betaHat_t_col(k) (:2045-2050) times that grid's not_jump_prob (:2170-2172), for the K haplotypes of the full panel in panel
+ * order.  Every other output is the one qa_fullpass_reads_select_batch returns for the same arguments.
+ *   gamma_grid        0-based grid, in [0, nGrids)
+ *   gamma_col         out n_chain x n_label x K; rows of chains without want_dosage are left untouched
+ * The column comes from the fp64 dosage passes (k_bwd64d) or, in validation mode (qa_panel_set_sum_order 1 or 2), from the
+ * reference-order kernels: a handle with fp32 dosage passes (or fp32 ranking beside fp64 dosage) is refused with
+ * QA_ERR_UNSUPPORTED -- call qa_panel_set_dosage_precision(panel, 64) first.
+ */
+int qa_fullpass_reads_select_gamma_batch(qa_panel_t *panel, int32_t n_chain, int32_t n_label, int32_t n_sample,
+                                         const int32_t *chain_sample, const int32_t *read_off, const int32_t *read_ptr,
+                                         const int32_t *u, const int32_t *bq, const int32_t *H, const int32_t *want_dosage,
+                                         const int32_t *want_top, const int32_t *gammaSmall_cols_to_get, int32_t K_top_matches,
+                                         double minGLValue, double *dosage, int32_t top_width, int32_t *top_idx, float *top_val,
+                                         int32_t *top_cnt, int32_t Ksubset, int32_t Knew, const int32_t *which_haps_to_use,
+                                         const uint64_t *seed_select, int32_t *which_next, int32_t *select_status,
+                                         int32_t gamma_grid, double *gamma_col);
+
+/*
  * The haplotype search of the msPBWT mode (use_mspbwt = TRUE): stands in for mspbwt::Rcpp_find_good_matches_without_a as
  * `select_new_haps_mspbwt_v3` calls it (QUILT/R/mspbwt.R:265-301).  The mspbwt package (a
  * positional-BWT index over the panel's per-grid symbols) is not in the reference tree; here the query is compared with
@@ -759,6 +780,32 @@ int qa_impute_samples(qa_panel_t *const *panels, int32_t n_panels, const qa_impu
                       int64_t sample_offset, const int32_t *read_off, const int32_t *read_ptr, const int32_t *u, const int32_t *bq,
                       const int32_t *wif, double *dosage, double *gp_t, double *phasing_haps, int32_t *read_labels,
                       int32_t *nDosage, int64_t *stats);
+
+/*
+ * hla_run = TRUE (QUILT-HLA's QUILT() call, QUILT/R/quilt-hla.R:192-212) with method = "diploid" and full-panel passes: what
+ * get_and_impute_one_sample adds to each sample's result (functions.R:1261-1280, :1489-1494).  For every Gibbs sample
+ * i = 1 .. nGibbsSamples + 1, the last seek iteration's full-panel passes give gamma1 = gammaMT_t[, iGrid] (read label 1) and
+ * gamma2 = gammaMU_t[, iGrid] (label 2), K values each (the full panel, panel order; qa_fullpass_reads_select_gamma_batch).
+ *   grid              iGrid - 1: 0-based, in [0, nGrids).  The reference's iGrid is round(nGrids / 2) when
+ *                     gamma_physically_closest_to is NA, else grid[which.min(abs(L - gamma_physically_closest_to))] + 1
+ *   gamma1, gamma2    out n_sample x K: the PHASING iteration's columns (the last values the reference assigns)
+ *   gamma_total       out n_sample x K: ((0 + gamma1_1) + gamma2_1) + gamma1_2 + ... over i = 1 .. nGibbsSamples, elementwise,
+ *                     in Gibbs-sample order, added left to right (functions.R:1273-1275)
+ *   list_of_gammas    out n_sample x nGibbsSamples x 2 x K: list_of_gammas[[i]] = list(gamma1_i, gamma2_i) (:1276-1278)
+ * Refused (QA_ERR_INVALID or QA_ERR_UNSUPPORTED, text in qa_last_error): use_mspbwt, nipt, rare_common, a grid outside
+ * [0, nGrids), and a run whose last seek iteration is not a dosage pass (n_burn_in_seek_its >= n_seek_its).
+ */
+typedef struct {
+    int32_t grid;
+    double *gamma1, *gamma2, *gamma_total, *list_of_gammas;
+} qa_impute_hla_t;
+
+/* qa_impute_samples with hla_run = TRUE: the same arguments and outputs (bit-identical: hla_run changes nothing else in the
+ * loop), plus *hla.  The handles must yield the gamma column (qa_fullpass_reads_select_gamma_batch: fp64 dosage passes). */
+int qa_impute_samples_hla(qa_panel_t *const *panels, int32_t n_panels, const qa_impute_params_t *params, int32_t n_sample,
+                          int64_t sample_offset, const int32_t *read_off, const int32_t *read_ptr, const int32_t *u, const int32_t *bq,
+                          const int32_t *wif, double *dosage, double *gp_t, double *phasing_haps, int32_t *read_labels,
+                          int32_t *nDosage, int64_t *stats, const qa_impute_hla_t *hla);
 
 /* The host threads' marshalling and pinned transfer buffers are kept per panel handle between calls (a launch set of 2 048
  * chains moves ~3.5 GB through them): this frees them all.  Call it when no qa_impute_samples call is running. */

@@ -807,13 +807,14 @@ __global__ void k_unpermute(const TS *src, double *dst, int K, int Kq, int NT, i
 // host side
 // ---------------------------------------------------------------------------------------------
 struct qa_panel::Scratch {
-    qa::ABuf<double> gl, c, dosage, escale0, unperm, emin, emin_b1, spill, fw_add, fw_xs;
+    qa::ABuf<double> gl, c, dosage, escale0, unperm, emin, emin_b1, spill, fw_add, fw_xs, gamma_col;
     qa::ABuf<char> emat, esp, alpha, gamma, beta, beta_thin, top_val, mg, gsp;   // fp32 or fp64 elements (the launch decides)
     qa::ABuf<int32_t> thin_col, flags, alpha_slot, top_cnt, top_idx;
     qa::DBuf<int32_t> todo;   // (grid, pass) pairs handed to k_topk: persistent, grow-only
     hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     explicit Scratch(qa::Arena *a) {
         gl.arena = c.arena = dosage.arena = escale0.arena = unperm.arena = emin.arena = emin_b1.arena = spill.arena = fw_add.arena = fw_xs.arena = a;
+        gamma_col.arena = a;
         emat.arena = esp.arena = alpha.arena = mg.arena = gsp.arena = gamma.arena = beta.arena = beta_thin.arena = top_val.arena = a;
         thin_col.arena = flags.arena = alpha_slot.arena = top_cnt.arena = top_idx.arena = a;
     }
@@ -883,7 +884,7 @@ Geometry pick_geometry(int K, PassKind kind = KIND_F32) {
 
 // device bytes one pass needs in run_passes (mirrors its carves, with alignment slack)
 size_t pass_bytes(const qa_panel *pn, const Geometry &geo, int n_thin, bool stores_all, bool gamma, bool beta,
-                  bool device_gl) {
+                  bool device_gl, bool gamma_col = false) {
     const size_t Kq = (size_t)geo.NT * geo.NCH * 16, G = pn->G, T = pn->T, es = geo.f64() ? 8 : 4;
     const size_t cols = stores_all ? G : (size_t)std::max(n_thin, 1);
     (void)device_gl;
@@ -892,6 +893,7 @@ size_t pass_bytes(const qa_panel *pn, const Geometry &geo, int n_thin, bool stor
     size_t b = T * 16 + G * 4 + G * kMaxRow * (es + 8) + 8 + nsp * (es + 8) + cols * col * es + G * 16 + T * 8;
     if (gamma) b += G * Kq * es;
     if (beta) b += G * Kq * es;
+    if (gamma_col) b += Kq * 8;
     if (n_thin > 0) b += (size_t)n_thin * Kq * es + (size_t)n_thin * (4 + 8 + 64 * 12);   // (lists of up to 64 entries)
     if (geo.kind == KIND_F64_RANK || geo.kind == KIND_F64_DOS) b += (size_t)qa::fb64_spill_rows(pn->K) * 8192 * 8;   // streamed chunk rows
     if (geo.kind == KIND_F64_REF) b += qa::fb_ref_state_doubles((int)Kq) * 8;   // state + gamma column in k order
@@ -1008,6 +1010,11 @@ struct BatchOut {
     std::vector<double> *flat_val = nullptr;
     bool order_by_value = false;
     std::vector<int32_t> *true_counts = nullptr;   // untruncated list lengths  // lists ordered as everything_per_hap_rejig_haps wants (else ascending k)
+    // hla_run: gamma_t_col of grid gamma_grid for every pass (fp64 dosage or validation passes), K doubles to row gamma_rows[p]
+    // (p when null) of gamma_col
+    double *gamma_col = nullptr;
+    int gamma_grid = -1;
+    const int32_t *gamma_rows = nullptr;
 };
 
 // runs P passes; flags per pass as in PassParams
@@ -1030,6 +1037,12 @@ int run_passes(qa_panel *pn, int P, const double *gl, const int32_t *h_flags, co
     if (kind == KIND_F64_RANK)
         for (int p = 0; p < P; p++)
             if (h_flags[p] & 15) throw std::runtime_error("fp64 ranking passes carry no dosage / gamma / beta outputs");
+    if (out.gamma_col) {
+        if (kind != KIND_F64_DOS && kind != KIND_F64_REF) throw std::runtime_error("internal: a gamma column from passes other than the fp64 dosage passes");
+        if (out.gamma_grid < 0 || out.gamma_grid >= pn->G) throw std::runtime_error("internal: gamma grid out of range");
+        for (int p = 0; p < P; p++)
+            if (!(h_flags[p] & 1)) throw std::runtime_error("internal: a gamma column from a pass without dosage");
+    }
     if (kind == KIND_F64_DOS) {
         for (int p = 0; p < P; p++)
             if (!(h_flags[p] & 1) || (h_flags[p] & 12)) throw std::runtime_error("fp64 dosage passes yield the dosage (and c) only");
@@ -1099,6 +1112,7 @@ int run_passes(qa_panel *pn, int P, const double *gl, const int32_t *h_flags, co
     if (any_gamma) S.gamma.ensure((size_t)P * G * Kq * es);
     if (any_beta) S.beta.ensure((size_t)P * G * Kq * es);
     if (any_top) S.beta_thin.ensure((size_t)P * n_thin * Kq * es);
+    if (out.gamma_col) S.gamma_col.ensure((size_t)P * Kq);
     int top_cap = out.top_cap;
     S.top_cnt.ensure(std::max<size_t>((size_t)P * std::max(n_thin, 1), 1));
     const size_t spill_stride = kind == KIND_F64_REF ? qa::fb_ref_state_doubles(Kq)   // the validation kernels' state (when not in LDS)
@@ -1123,6 +1137,7 @@ int run_passes(qa_panel *pn, int P, const double *gl, const int32_t *h_flags, co
     prm.alpha_pass_stride = alpha_stride; prm.Kq = Kq; prm.alpha_col_elems = alpha_col;
     prm.hist_unit = kind == KIND_F64_DOS ? 1.0 / 2251799813685248.0 /* 2^-51: k_bwd64d */ : 1.0 / kHistScale64; prm.c = S.c.p; prm.mg = S.mg.p; prm.gsp = S.gsp.p;
     prm.gamma_out = any_gamma ? S.gamma.p : nullptr; prm.beta_out = any_beta ? S.beta.p : nullptr;
+    prm.gamma_col = out.gamma_col ? S.gamma_col.p : nullptr; prm.gamma_grid = out.gamma_col ? out.gamma_grid : -1;
     // Dosage rows that go to consecutive rows of a qa_host_alloc buffer are written there by k_dosage itself (every element
     // once, 4 KiB of consecutive bytes per workgroup): the transfer rides under the kernel instead of following it.
     bool dosage_direct = false;
@@ -1236,6 +1251,17 @@ int run_passes(qa_panel *pn, int P, const double *gl, const int32_t *h_flags, co
 
     // ---- copy results back
     if (out.c) S.c.download(out.c, (size_t)P * G, st);
+    if (out.gamma_col) {   // rows of Kq (the kernels' 16-byte stores) -> rows of K: one 2-D copy per run of consecutive destination rows
+        auto row_of = [&](int p) { return (size_t)(out.gamma_rows ? out.gamma_rows[p] : p); };
+        for (int p = 0; p < P;) {
+            int n = 1;
+            while (p + n < P && row_of(p + n) == row_of(p) + (size_t)n) n++;
+            QA_HIP(hipMemcpy2DAsync(out.gamma_col + row_of(p) * K, sizeof(double) * K, S.gamma_col.p + (size_t)p * Kq, sizeof(double) * Kq,
+                                    sizeof(double) * K, n, hipMemcpyDeviceToHost, st));
+            p += n;
+        }
+        QA_HIP(hipStreamSynchronize(st));
+    }
     if (out.dosage && !dosage_direct) {
         // runs of consecutive dosage passes come back in one staged transfer each, then scatter to their rows
         // (a run whose destination rows are consecutive too -- the batch calls' layout -- lands in the caller's buffer
@@ -1338,6 +1364,23 @@ int run_passes(qa_panel *pn, int P, const double *gl, const int32_t *h_flags, co
 }
 
 }  // namespace
+
+// hla_run: can this handle's dosage passes keep a gamma column?  Only the fp64 dosage kernels (k_bwd64d) and the validation
+// kernels (k_bwd_ro) store one; QA_ERR_UNSUPPORTED with the cause named otherwise.
+int qa::gamma_column_check(const qa_panel *pn, const char *who) {
+    const PassKind dk = dosage_kind(pn);
+    if (dk == KIND_F64_REF || (dk == KIND_F64_DOS && pn->rank_fp64)) return QA_OK;
+    if (dk == KIND_F32)
+        qa::set_error("%s: the handle's dosage passes are fp32; the gamma column comes from the fp64 dosage passes: call "
+                      "qa_panel_set_dosage_precision(64) on the handle first", who);
+    else if (!pn->rank_fp64)
+        qa::set_error("%s: with fp32 ranking the dosage passes run the generic fp64 kernels, which keep no gamma column: call "
+                      "qa_panel_set_ranking_precision(panel, 64) first", who);
+    else
+        qa::set_error("%s: K = %d haplotypes is served by the generic fp64 kernels (the fp64 dosage kernels' on-chip layout does not "
+                      "hold this K), which keep no gamma column", who, pn->K);
+    return QA_ERR_UNSUPPORTED;
+}
 
 extern "C" {
 
@@ -1563,7 +1606,7 @@ static int fullpass_reads_impl(qa_panel_t *panel, int32_t n_chain, int32_t n_lab
                                const int32_t *u, const int32_t *bq, const int32_t *H, const int32_t *want_dosage,
                                const int32_t *want_top, const int32_t *gammaSmall_cols_to_get, int32_t K_top_matches,
                                double minGLValue, double *dosage, int32_t top_width, int32_t *top_idx, float *top_val,
-                               int32_t *top_cnt, const SelectArgs *sel) {
+                               int32_t *top_cnt, const SelectArgs *sel, int32_t gamma_grid = -1, double *gamma_col = nullptr) {
     if (!qa::device_ready()) return QA_ERR_NO_DEVICE;
     if (!panel || n_chain <= 0 || n_label < 1 || n_label > 3 || n_sample <= 0 || !chain_sample || !read_off || !read_ptr ||
         !u || !bq || !H || !want_dosage || !gammaSmall_cols_to_get || top_width < K_top_matches || top_width > 64) {
@@ -1574,6 +1617,14 @@ static int fullpass_reads_impl(qa_panel_t *panel, int32_t n_chain, int32_t n_lab
                 !sel->seed || !sel->which_next || !sel->status || K_top_matches < 1)) {
         qa::set_error("qa_fullpass_reads_select_batch: bad selection argument");
         return QA_ERR_INVALID;
+    }
+    if (gamma_col) {
+        if (gamma_grid < 0 || gamma_grid >= panel->G) {
+            qa::set_error("qa_fullpass_reads_select_gamma_batch: gamma_grid = %d outside [0, nGrids = %d)", gamma_grid, panel->G);
+            return QA_ERR_INVALID;
+        }
+        const int st = qa::gamma_column_check(panel, "qa_fullpass_reads_select_gamma_batch");
+        if (st != QA_OK) return st;
     }
     if (sel)
         for (size_t i = 0; i < (size_t)n_chain * sel->Ksubset; i++)
@@ -1748,7 +1799,8 @@ static int fullpass_reads_impl(qa_panel_t *panel, int32_t n_chain, int32_t n_lab
             const int nt_grp = grp.K_top > 0 ? n_thin : 0;
             int done = 0;
             while (done < n_grp && status == QA_OK) {
-                const int n = plan_chunk(panel, pass_bytes(panel, geo, nt_grp, grp.flag != 0, false, false, true), n_grp - done);
+                const bool gc = gamma_col && grp.flag != 0;
+                const int n = plan_chunk(panel, pass_bytes(panel, geo, nt_grp, grp.flag != 0, false, false, true, gc), n_grp - done);
                 S.gl.ensure((size_t)n * T * 2);
                 GlParams gp{};
                 gp.P = n; gp.T = T; gp.pass_sample = d_ps.p + done; gp.pass_label = d_pl.p + done; gp.pass_hoff = d_ph.p + done;
@@ -1759,6 +1811,11 @@ static int fullpass_reads_impl(qa_panel_t *panel, int32_t n_chain, int32_t n_lab
                 BatchOut out;
                 out.dosage = grp.flag ? dosage : nullptr;
                 out.dosage_rows = grp.ids.data() + done;
+                if (gc) {
+                    out.gamma_col = gamma_col;
+                    out.gamma_grid = gamma_grid;
+                    out.gamma_rows = grp.ids.data() + done;
+                }
                 std::vector<int32_t> fidx;
                 std::vector<double> fval;
                 if (lists_to_host) {   // with the selection on the device the lists need not cross PCIe
@@ -1862,6 +1919,25 @@ int qa_fullpass_reads_select_batch(qa_panel_t *panel, int32_t n_chain, int32_t n
     return fullpass_reads_impl(panel, n_chain, n_label, n_sample, chain_sample, read_off, read_ptr, u, bq, H, want_dosage,
                                want_top, gammaSmall_cols_to_get, K_top_matches, minGLValue, dosage, top_width, top_idx,
                                top_val, top_cnt, &sel);
+}
+
+int qa_fullpass_reads_select_gamma_batch(qa_panel_t *panel, int32_t n_chain, int32_t n_label, int32_t n_sample,
+                                         const int32_t *chain_sample, const int32_t *read_off, const int32_t *read_ptr,
+                                         const int32_t *u, const int32_t *bq, const int32_t *H, const int32_t *want_dosage,
+                                         const int32_t *want_top, const int32_t *gammaSmall_cols_to_get, int32_t K_top_matches,
+                                         double minGLValue, double *dosage, int32_t top_width, int32_t *top_idx, float *top_val,
+                                         int32_t *top_cnt, int32_t Ksubset, int32_t Knew, const int32_t *which_haps_to_use,
+                                         const uint64_t *seed_select, int32_t *which_next, int32_t *select_status,
+                                         int32_t gamma_grid, double *gamma_col) {
+    if (!qa::device_ready()) return QA_ERR_NO_DEVICE;
+    if (!gamma_col) {
+        qa::set_error("qa_fullpass_reads_select_gamma_batch: gamma_col is NULL");
+        return QA_ERR_INVALID;
+    }
+    const SelectArgs sel{Ksubset, Knew, which_haps_to_use, seed_select, which_next, select_status};
+    return fullpass_reads_impl(panel, n_chain, n_label, n_sample, chain_sample, read_off, read_ptr, u, bq, H, want_dosage,
+                               want_top, gammaSmall_cols_to_get, K_top_matches, minGLValue, dosage, top_width, top_idx,
+                               top_val, top_cnt, &sel, gamma_grid, gamma_col);
 }
 
 }  // extern "C"

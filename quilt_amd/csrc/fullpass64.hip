@@ -865,7 +865,18 @@ __device__ __forceinline__ void reform_alpha(double2 (&a)[4], uint32_t w0, uint3
     }
 }
 
-template <int NR, int NL, bool SP = false>
+// hla_run: the reference's gamma_t_col at the requested grid (reference-single.cpp:2045-2050 alpha * beta, then :2170-2172 times
+// not_jump_prob) of half a chunk -- eight haplotypes consecutive in k, so four 16-byte stores per lane.  x, v: the state and the
+// addend before this grid's update (beta = x + v, as half_step_dos forms it); a: the grid's alpha; fs: its not_jump_prob
+__device__ __forceinline__ void store_gamma_half(double *dst, const double (&x)[8], double v, const double2 *a, double fs) {
+    double2 *d2 = reinterpret_cast<double2 *>(dst);
+#pragma unroll
+    for (int q = 0; q < 4; q++) d2[q] = make_double2((a[q].x * (x[2 * q] + v)) * fs, (a[q].y * (x[2 * q + 1] + v)) * fs);
+}
+
+// GCOL: also store gamma of grid prm.gamma_grid for every haplotype into prm.gamma_col[p][Kq] (a separate instantiation: the
+// kernels without it are unchanged)
+template <int NR, int NL, bool SP = false, bool GCOL = false>
 __global__ __launch_bounds__(kNT) void k_bwd64d(PassParams prm, int n_last) {
     constexpr int NCH = NR + NL, NT = kNT, nwaves = NT >> 6;
     const int NS = SP ? prm.Kq / kRowHaps - NCH : 0;   // chunk rows streamed through HBM
@@ -886,6 +897,12 @@ __global__ __launch_bounds__(kNT) void k_bwd64d(PassParams prm, int n_last) {
     const double double_K = uniform((double)K);
     const bool last_row_wave = wave * 64 < n_last;   // the last chunk row holds n_last lanes only
     const bool half_cols = prm.fw_add != nullptr;    // alpha handed over at the even grids only
+    double *gcol = nullptr;
+    int gcol_grid = -1;
+    if constexpr (GCOL) {
+        gcol = prm.gamma_col + (size_t)p * prm.Kq;
+        gcol_grid = prm.gamma_grid;
+    }
 
     double b[NR][16];
 #pragma unroll
@@ -971,6 +988,9 @@ __global__ __launch_bounds__(kNT) void k_bwd64d(PassParams prm, int n_last) {
                 if (sp) {
                     if (on) special_gammas(x, w0, w1, v, a, gsp, at - 16 * sp_g, k0 + 8 * h, K);
                 }
+                if constexpr (GCOL) {
+                    if (gp == gcol_grid && on) store_gamma_half(gcol + k0 + 8 * h, x, v, a, fs);
+                }
                 half_step_dos<EMIT>(x, w0, w1, et, v, s, a, scale, hl, on);
                 if (EMIT) {
                     if (sp) n_sp += special_half(x, w0, w1, esp + at);
@@ -1030,6 +1050,9 @@ __global__ __launch_bounds__(kNT) void k_bwd64d(PassParams prm, int n_last) {
                     if (recomp) reform_alpha(a, w0, w1, et, esp + at, sp, f_add, f_xs);
                     if (sp) {
                         if (on) special_gammas(x, w0, w1, v, a, gsp, at - 16 * sp_g, k0 + 8 * h, K);
+                    }
+                    if constexpr (GCOL) {
+                        if (gp == gcol_grid && on) store_gamma_half(gcol + k0 + 8 * h, x, v, a, fs);
                     }
                     half_step_dos<EMIT>(x, w0, w1, et, v, s, a, scale, hl, on);
                     if (EMIT) {
@@ -1122,15 +1145,15 @@ __global__ __launch_bounds__(kNT) void k_bwd64d(PassParams prm, int n_last) {
     }
 }
 
-template <int NR, int NL, bool SP = false>
+template <int NR, int NL, bool SP = false, bool GCOL = false>
 void launch_dos(const PassParams &prm, const Geo64 &geo, hipStream_t s, hipEvent_t e_mid) {
     const size_t lds = lds_bytes(geo), lds_d = lds_bytes_d(geo);
     QA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_fwd64<NR, NL, SP>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL((k_fwd64<NR, NL, SP>), dim3(prm.P), dim3(kNT), lds, s, prm, geo.n_last);
     QA_HIP(hipGetLastError());
     if (e_mid) QA_HIP(hipEventRecord(e_mid, s));
-    QA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_bwd64d<NR, NL, SP>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_d));
-    hipLaunchKernelGGL((k_bwd64d<NR, NL, SP>), dim3(prm.P), dim3(kNT), lds_d, s, prm, geo.n_last);
+    QA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_bwd64d<NR, NL, SP, GCOL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_d));
+    hipLaunchKernelGGL((k_bwd64d<NR, NL, SP, GCOL>), dim3(prm.P), dim3(kNT), lds_d, s, prm, geo.n_last);
     QA_HIP(hipGetLastError());
 }
 
@@ -1144,6 +1167,27 @@ void launch(const PassParams &prm, const Geo64 &geo, hipStream_t s, hipEvent_t e
     QA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_bwd64<NR, NL, SP>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL((k_bwd64<NR, NL, SP>), dim3(prm.P), dim3(kNT), lds, s, prm, geo.n_last);
     QA_HIP(hipGetLastError());
+}
+
+template <bool GCOL>
+void launch_dos_geo(const PassParams &prm, const Geo64 &geo, hipStream_t st, hipEvent_t e_mid) {
+    if (geo.NS > 0) {
+        launch_dos<5, 2, true, GCOL>(prm, geo, st, e_mid);
+        return;
+    }
+    switch (geo.NR * 10 + geo.NL) {
+#ifndef QA_FAST_BUILD
+        case 10: launch_dos<1, 0, false, GCOL>(prm, geo, st, e_mid); break;
+        case 20: launch_dos<2, 0, false, GCOL>(prm, geo, st, e_mid); break;
+        case 30: launch_dos<3, 0, false, GCOL>(prm, geo, st, e_mid); break;
+        case 40: launch_dos<4, 0, false, GCOL>(prm, geo, st, e_mid); break;
+        case 41: launch_dos<4, 1, false, GCOL>(prm, geo, st, e_mid); break;
+        case 42: launch_dos<4, 2, false, GCOL>(prm, geo, st, e_mid); break;
+#endif
+        case 52: launch_dos<5, 2, false, GCOL>(prm, geo, st, e_mid); break;
+        case 43: launch_dos<4, 3, false, GCOL>(prm, geo, st, e_mid); break;
+        default: throw std::runtime_error("fp64 geometry not built");
+    }
 }
 
 }  // namespace
@@ -1171,24 +1215,9 @@ void launch_fb64_dosage(const void *pass_params, hipStream_t st, hipEvent_t e_mi
     if (geo.NCH == 7 && geo.NS == 0 && geo.NR == 4 && lds_bytes_d(geo) > kLdsMax) { geo.NR = 5; geo.NL = 2; }
     if (geo.NCH == 0 || lds_bytes_d(geo) > kLdsMax) throw std::runtime_error("K exceeds the on-chip capacity of the fp64 dosage kernels");
     if (prm.Kq != (geo.NCH + geo.NS) * kRowHaps) throw std::runtime_error("internal: Kq does not match the fp64 geometry");
-    if (geo.NS > 0) {
-        if (!prm.spill) throw std::runtime_error("internal: streamed chunk rows without their buffer");
-        launch_dos<5, 2, true>(prm, geo, st, e_mid);
-        return;
-    }
-    switch (geo.NR * 10 + geo.NL) {
-#ifndef QA_FAST_BUILD
-        case 10: launch_dos<1, 0>(prm, geo, st, e_mid); break;
-        case 20: launch_dos<2, 0>(prm, geo, st, e_mid); break;
-        case 30: launch_dos<3, 0>(prm, geo, st, e_mid); break;
-        case 40: launch_dos<4, 0>(prm, geo, st, e_mid); break;
-        case 41: launch_dos<4, 1>(prm, geo, st, e_mid); break;
-        case 42: launch_dos<4, 2>(prm, geo, st, e_mid); break;
-#endif
-        case 52: launch_dos<5, 2>(prm, geo, st, e_mid); break;
-        case 43: launch_dos<4, 3>(prm, geo, st, e_mid); break;
-        default: throw std::runtime_error("fp64 geometry not built");
-    }
+    if (geo.NS > 0 && !prm.spill) throw std::runtime_error("internal: streamed chunk rows without their buffer");
+    if (prm.gamma_col) launch_dos_geo<true>(prm, geo, st, e_mid);
+    else launch_dos_geo<false>(prm, geo, st, e_mid);
 }
 
 void launch_fb64(const void *pass_params, hipStream_t st, hipEvent_t e_mid) {

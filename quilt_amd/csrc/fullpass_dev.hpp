@@ -89,6 +89,10 @@ struct PassParams {
     double *fw_add, *fw_xs;  // [P][G] or null (every column handed over)
     double *spill;
     size_t spill_pass_stride;  // doubles
+    // hla_run (functions.R:1261-1272): the reference's gamma_t_col (reference-single.cpp:2045-2050, :2170-2172) of ONE grid per
+    // dosage pass, [P][Kq] in haplotype order (k_bwd64d<..., GCOL = true>, k_bwd_ro<true>); null: not wanted
+    double *gamma_col;
+    int gamma_grid;            // 0-based
 };
 
 // Emission of one distinct word (reference-single.cpp:294-327): the product over the grid's SNPs of P(reads | allele), with

@@ -203,6 +203,9 @@ __global__ __launch_bounds__(kRT) void k_fwd_ro(PassParams prm, int NT, int stat
 // ---------------------------------------------------------------------------------------------
 // backward (reference-single.cpp:1854-2177)
 // ---------------------------------------------------------------------------------------------
+// GCOL (hla_run): gamma_t_col of grid prm.gamma_grid alone, in haplotype order, to prm.gamma_col[p][Kq] (a separate
+// instantiation: the kernel without it is unchanged)
+template <bool GCOL = false>
 __global__ __launch_bounds__(kRT) void k_bwd_ro(PassParams prm, int NT, int state_in_lds, int Kpad) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const Smem L(smem);
@@ -265,12 +268,17 @@ __global__ __launch_bounds__(kRT) void k_bwd_ro(PassParams prm, int NT, int stat
             double *dst = static_cast<double *>(prm.beta_thin) + ((size_t)p * prm.n_thin + tcol) * prm.Kq;
             for (int k = t; k < K; k += kRT) dst[perm_index(k, NT)] = state[k];
         }
-        if ((want_dosage || want_gamma) && sl >= 0) {
+        const bool gcol_here = GCOL && g == prm.gamma_grid;
+        if ((want_dosage || want_gamma || gcol_here) && sl >= 0) {
             const double *acol = ain + (size_t)sl * prm.alpha_col_elems;
             for (int k = t; k < K; k += kRT) gam[k] = acol[perm_index(k, NT)] * state[k];
             if (want_gamma) {
                 double *dst = static_cast<double *>(prm.gamma_out) + ((size_t)p * G + g) * prm.Kq;
                 for (int k = t; k < K; k += kRT) dst[perm_index(k, NT)] = gam[k] * not_jump_prob;
+            }
+            if (gcol_here) {
+                double *dst = prm.gamma_col + (size_t)p * prm.Kq;
+                for (int k = t; k < K; k += kRT) dst[k] = gam[k] * not_jump_prob;
             }
         }
         if (want_dosage && sl >= 0) {
@@ -330,11 +338,14 @@ void launch_fb_ref(const void *pass_params, int NT, hipStream_t st, hipEvent_t e
         lds += 2 * (size_t)Kpad * 8;
     }
     QA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_fwd_ro), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    QA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_bwd_ro), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    QA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_bwd_ro<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (prm.gamma_col)
+        QA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_bwd_ro<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(k_fwd_ro, dim3(prm.P), dim3(kRT), lds, st, prm, NT, in_lds, Kpad);
     QA_HIP(hipGetLastError());
     if (e_mid) QA_HIP(hipEventRecord(e_mid, st));
-    hipLaunchKernelGGL(k_bwd_ro, dim3(prm.P), dim3(kRT), lds, st, prm, NT, in_lds, Kpad);
+    if (prm.gamma_col) hipLaunchKernelGGL(k_bwd_ro<true>, dim3(prm.P), dim3(kRT), lds, st, prm, NT, in_lds, Kpad);
+    else hipLaunchKernelGGL(k_bwd_ro<false>, dim3(prm.P), dim3(kRT), lds, st, prm, NT, in_lds, Kpad);
     QA_HIP(hipGetLastError());
 }
 

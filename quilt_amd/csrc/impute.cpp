@@ -44,7 +44,15 @@
 #include "../../include/quilt_amd_io.h"
 #include "impute_testhook.h"   // the table of entry points this loop runs over (private: tests fill it with a checker's)
 
-namespace qa { void set_error(const char *fmt, ...); }
+namespace qa {
+void set_error(const char *fmt, ...);
+__attribute__((visibility("hidden"))) int impute_samples_product(qa_panel_t *const *panels, int32_t n_panels, const qa_impute_params_t *params,
+                                                                int32_t n_sample, int64_t sample_offset, const int32_t *read_off,
+                                                                const int32_t *read_ptr, const int32_t *u, const int32_t *bq,
+                                                                const int32_t *wif, double *dosage, double *gp_t, double *phasing_haps,
+                                                                int32_t *read_labels, int32_t *nDosage, int64_t *stats,
+                                                                const qa_impute_hla_t *hla, qa_fullpass_select_gamma_fn select_gamma);
+}
 
 namespace {
 
@@ -217,6 +225,10 @@ struct Ctx {
     double t_gibbs = 0, t_fullpass = 0, t_host = 0, t_consensus = 0, t_finish = 0, t_accumulate = 0;
     Tail tail;
     bool use_tail = false;
+    // hla_run (qa_impute_samples_hla): the last seek iteration's passes go through select_gamma, which also returns the gamma
+    // column of grid hla->grid per pass
+    const qa_impute_hla_t *hla = nullptr;
+    qa_fullpass_select_gamma_fn select_gamma = nullptr;
 };
 
 template <typename T>
@@ -431,7 +443,8 @@ struct WorkerBuffers {
     HostBuf<double> dos;          // the round's haploid dosages [chain][label][T]
     HostBuf<double> conf;         // read confidence [reads][K]
     HostBuf<double> dos_all;      // impute_rare_common: the all-SNP round's haploid dosages [chain][2][all SNPs]
-    explicit WorkerBuffers(const qa_impute_backend_t *be) { dos.be = be; conf.be = be; dos_all.be = be; }
+    HostBuf<double> gcol;         // hla_run: the last seek iteration's gamma columns [chain][label][K]
+    explicit WorkerBuffers(const qa_impute_backend_t *be) { dos.be = be; conf.be = be; dos_all.be = be; gcol.be = be; }
 };
 // product backend only: handle -> its thread's buffers.  Never destroyed: a static's destructor would free pinned memory after
 // the HIP runtime (and the library's own registry of pinned regions) may be gone; qa_impute_release_buffers frees in time.
@@ -452,7 +465,7 @@ struct Worker {
     std::vector<int32_t> &g_which, &g_read_off, &g_read_ptr, &g_u, &g_bq, &g_wif, &g_first, &g_H, &g_uf, &g_words;
     std::vector<uint64_t> &g_sr, &g_ss, &seed_sel;
     std::vector<int32_t> &f_cs, &f_read_off, &f_read_ptr, &f_u, &f_bq, &f_H, &f_wd, &f_wt, &f_cnt, &f_next, &f_status;
-    HostBuf<double> &dos, &conf, &dos_all;
+    HostBuf<double> &dos, &conf, &dos_all, &gcol;
     std::function<void()> on_first_launch;
     double t_gibbs = 0, t_fullpass = 0, t_host = 0, t_consensus = 0, t_finish = 0, t_accumulate = 0;
 
@@ -473,7 +486,7 @@ struct Worker {
           g_read_off(B.g_read_off), g_read_ptr(B.g_read_ptr), g_u(B.g_u), g_bq(B.g_bq), g_wif(B.g_wif), g_first(B.g_first), g_H(B.g_H),
           g_uf(B.g_uf), g_words(B.g_words), g_sr(B.g_sr), g_ss(B.g_ss), seed_sel(B.seed_sel), f_cs(B.f_cs), f_read_off(B.f_read_off),
           f_read_ptr(B.f_read_ptr), f_u(B.f_u), f_bq(B.f_bq), f_H(B.f_H), f_wd(B.f_wd), f_wt(B.f_wt), f_cnt(B.f_cnt), f_next(B.f_next),
-          f_status(B.f_status), dos(B.dos), conf(B.conf), dos_all(B.dos_all) {}
+          f_status(B.f_status), dos(B.dos), conf(B.conf), dos_all(B.dos_all), gcol(B.gcol) {}
 
     // ---- the Gibbs call of a round with impute_one_sample's underflow retry (functions.R:2612-2716)
     // rare: the all-SNP call (qa_gibbs_batch_rare_common on the samples' all-SNP reads, labels given, read categories off:
@@ -811,14 +824,26 @@ struct Worker {
             const double t3 = now_s();
             t_host += t3 - t2;
             CallSpan span_f("fullpass_select", w, C);
-            check(cx.be->fullpass_reads_select_batch(handle, C, nL, nS, f_cs.data(), f_read_off.data(), f_read_ptr.data(), f_u.data(),
-                                                     f_bq.data(), f_H.data(), f_wd.data(), f_wt.data(), cx.cols.data(), P.K_top_matches,
-                                                     P.minGLValue, hap, cx.top_width, nullptr, nullptr, f_cnt.data(), P.Ksubset, P.Knew,
-                                                     g_which.data(), seed_sel.data(), f_next.data(), f_status.data()),
-                  "qa_fullpass_reads_select_batch");
+            // hla_run: the last seek iteration's passes also return gammaMT_t / gammaMU_t at the grid (functions.R:713-724)
+            const bool hla_it = cx.hla && i_it == P.n_seek_its;
+            if (hla_it) {
+                double *gc = gcol.get((size_t)C * nL * K);
+                check(cx.select_gamma(handle, C, nL, nS, f_cs.data(), f_read_off.data(), f_read_ptr.data(), f_u.data(), f_bq.data(),
+                                      f_H.data(), f_wd.data(), f_wt.data(), cx.cols.data(), P.K_top_matches, P.minGLValue, hap,
+                                      cx.top_width, nullptr, nullptr, f_cnt.data(), P.Ksubset, P.Knew, g_which.data(), seed_sel.data(),
+                                      f_next.data(), f_status.data(), cx.hla->grid, gc),
+                      "qa_fullpass_reads_select_gamma_batch");
+            } else {
+                check(cx.be->fullpass_reads_select_batch(handle, C, nL, nS, f_cs.data(), f_read_off.data(), f_read_ptr.data(), f_u.data(),
+                                                         f_bq.data(), f_H.data(), f_wd.data(), f_wt.data(), cx.cols.data(), P.K_top_matches,
+                                                         P.minGLValue, hap, cx.top_width, nullptr, nullptr, f_cnt.data(), P.Ksubset, P.Knew,
+                                                         g_which.data(), seed_sel.data(), f_next.data(), f_status.data()),
+                      "qa_fullpass_reads_select_batch");
+            }
             span_f.end();
             const double t4 = now_s();
             t_fullpass += t4 - t3;
+            if (hla_it) scatter_gammas(ch, cur);
             if (return_dosage) {   // functions.R:2072-2075
                 std::atomic<bool> bad{false};
                 parallel_for((size_t)C, n_help, [&](size_t i) {
@@ -868,6 +893,35 @@ struct Worker {
             t_accumulate += now_s() - ta;
         }
         return return_dosage;
+    }
+
+    // hla_run: the round's gamma columns to their samples' outputs (functions.R:1261-1280): a main chain's pair to
+    // list_of_gammas[[i_chain]], the phasing chain's to gamma1 / gamma2; once a set's main chains are final, gamma_total in the
+    // reference's order -- Gibbs sample after Gibbs sample, (total + gamma1) + gamma2 -- whatever order the chains ran in
+    void scatter_gammas(const std::vector<Chain *> &ch, const Batch *cur) {
+        const qa_impute_hla_t &h = *cx.hla;
+        const size_t K = (size_t)cx.K, nG = (size_t)cx.P.nGibbsSamples;
+        const double *gc = gcol.p;
+        parallel_for(ch.size(), n_help, [&](size_t i) {
+            const Chain &c = *ch[i];
+            const double *g = gc + i * 2 * K;
+            if (c.phasing) {
+                std::memcpy(h.gamma1 + (size_t)c.sample * K, g, sizeof(double) * K);
+                std::memcpy(h.gamma2 + (size_t)c.sample * K, g + K, sizeof(double) * K);
+            } else {
+                std::memcpy(h.list_of_gammas + ((size_t)c.sample * nG + (size_t)(c.i_chain - 1)) * 2 * K, g, sizeof(double) * 2 * K);
+            }
+        });
+        if (!cur || cur->chains.empty()) return;
+        parallel_for((size_t)(cur->hi - cur->lo), n_help, [&](size_t si) {
+            const size_t s = (size_t)cur->lo + si;
+            double *tot = h.gamma_total + s * K;
+            std::fill(tot, tot + K, 0.0);   // numeric(K)
+            for (size_t i = 0; i < nG; i++) {
+                const double *g1 = h.list_of_gammas + (s * nG + i) * 2 * K, *g2 = g1 + K;
+                for (size_t k = 0; k < K; k++) tot[k] = (tot[k] + g1[k]) + g2[k];
+            }
+        });
     }
 
     // impute_final_gibbs_with_rare_common (rare_common.R:109-420), once per Gibbs sample after its seek iterations
@@ -1234,7 +1288,8 @@ std::vector<std::pair<int, int>> sample_ranges(int n, int parts) {
 int impute_impl(bool keep_buffers, const qa_impute_backend_t *be, void *const *handles, int32_t n_handles, int32_t K, int32_t G, int32_t T,
                 const qa_impute_params_t *params, int32_t n_sample, int64_t sample_offset, const int32_t *read_off,
                 const int32_t *read_ptr, const int32_t *u, const int32_t *bq, const int32_t *wif, double *dosage, double *gp_t,
-                double *phasing_haps, int32_t *read_labels, int32_t *nDosage, int64_t *stats) {
+                double *phasing_haps, int32_t *read_labels, int32_t *nDosage, int64_t *stats,
+                const qa_impute_hla_t *hla = nullptr, qa_fullpass_select_gamma_fn select_gamma = nullptr) {
     const bool flat = !(params && params->sample_source);
     if (!be || !handles || n_handles < 1 || n_handles > 16 || !params || n_sample < 0 ||
         (flat && (!read_off || !read_ptr || !u || !bq || !wif || !read_labels)) || (!flat && !params->sample_source->acquire) ||
@@ -1251,6 +1306,11 @@ int impute_impl(bool keep_buffers, const qa_impute_backend_t *be, void *const *h
     // QUILT()'s argument handling (quilt.R:248-250, :453-471)
     if (P.n_burn_in_seek_its < 0) P.n_burn_in_seek_its = P.n_seek_its - 1;
     if (K < P.Ksubset) { P.n_seek_its = 1; P.n_burn_in_seek_its = 0; P.Ksubset = K; P.Knew = K; }
+    if (hla && P.n_burn_in_seek_its >= P.n_seek_its) {   // (the gamma columns are kept from the last seek iteration's dosage passes)
+        qa::set_error("qa_impute_samples_hla: the last seek iteration is not a dosage pass (n_burn_in_seek_its = %d >= n_seek_its = %d)",
+                      P.n_burn_in_seek_its, P.n_seek_its);
+        return QA_ERR_INVALID;
+    }
     if (P.Knew > P.Ksubset) P.Knew = P.Ksubset;
     if (P.n_seek_its < 1 || P.n_burn_in_seek_its < 0 || P.n_burn_in_seek_its >= P.n_seek_its || P.nGibbsSamples < 1 || P.Ksubset < 1 ||
         P.Knew < 1 || P.K_top_matches < 1 || P.n_block_gibbs_iterations < 0 ||
@@ -1259,11 +1319,29 @@ int impute_impl(bool keep_buffers, const qa_impute_backend_t *be, void *const *h
                       "K_top_matches >= 1");
         return QA_ERR_INVALID;
     }
+    if (hla) {   // hla_run: what the range call covers (functions.R:713-724, :1261-1280 with method = "diploid", full-panel passes)
+        const char *why = !select_gamma ? "no gamma-column entry point"
+                          : !hla->gamma1 || !hla->gamma2 || !hla->gamma_total || !hla->list_of_gammas ? "missing output array"
+                          : P.use_mspbwt ? "use_mspbwt = TRUE is not covered (the gamma columns come from the full-panel passes)"
+                          : P.nipt ? "method = \"nipt\" is not covered (diploid only)"
+                          : P.rare_common ? "impute_rare_common = TRUE is not covered"
+                          : hla->grid < 0 || hla->grid >= G ? "grid outside [0, nGrids)"
+                          : nullptr;
+        if (why) {
+            if (hla->grid < 0 || hla->grid >= G)
+                qa::set_error("qa_impute_samples_hla: %s (grid = %d, nGrids = %d)", why, hla->grid, G);
+            else
+                qa::set_error("qa_impute_samples_hla: %s", why);
+            return QA_ERR_INVALID;
+        }
+    }
     if (P.use_mspbwt && (!P.mspbwt_index || P.Knew != P.Ksubset || P.mspbwtL < 1 || P.mspbwtL > 64 || P.mspbwtM < 1)) {
         qa::set_error("qa_impute_samples: use_mspbwt needs the panel's index (qa_mspbwt_create), Knew == Ksubset, 1 <= mspbwtL <= 64, mspbwtM >= 1");
         return QA_ERR_INVALID;
     }
     cx.n_burn = P.n_burn_in_seek_its;
+    cx.hla = hla;
+    cx.select_gamma = select_gamma;
     cx.blocks.assign(P.small_ref_panel_block_gibbs_iterations, P.small_ref_panel_block_gibbs_iterations + P.n_block_gibbs_iterations);
     cx.cols = thinned_grid_columns(G, P.heuristic_match_thin);
     cx.n_thin = 0;
@@ -1530,10 +1608,14 @@ int qa_impute_params_default(qa_impute_params_t *p) {
     return QA_OK;
 }
 
-int qa_impute_samples(qa_panel_t *const *panels, int32_t n_panels, const qa_impute_params_t *params, int32_t n_sample,
-                      int64_t sample_offset, const int32_t *read_off, const int32_t *read_ptr, const int32_t *u, const int32_t *bq,
-                      const int32_t *wif, double *dosage, double *gp_t, double *phasing_haps, int32_t *read_labels, int32_t *nDosage,
-                      int64_t *stats) {
+}   // extern "C"
+
+// the product's loop over the library's own entry points: qa_impute_samples, and (hla, select_gamma) qa_impute_samples_hla of
+// csrc/impute_hla.cpp -- internal to the library, not exported
+int qa::impute_samples_product(qa_panel_t *const *panels, int32_t n_panels, const qa_impute_params_t *params, int32_t n_sample,
+                              int64_t sample_offset, const int32_t *read_off, const int32_t *read_ptr, const int32_t *u, const int32_t *bq,
+                              const int32_t *wif, double *dosage, double *gp_t, double *phasing_haps, int32_t *read_labels,
+                              int32_t *nDosage, int64_t *stats, const qa_impute_hla_t *hla, qa_fullpass_select_gamma_fn select_gamma) {
     if (!panels || n_panels < 1 || !panels[0]) {
         qa::set_error("qa_impute_samples: no panel handle");
         return QA_ERR_INVALID;
@@ -1558,7 +1640,17 @@ int qa_impute_samples(qa_panel_t *const *panels, int32_t n_panels, const qa_impu
                 return QA_ERR_INVALID;
             }
     return impute_impl(true, &kProduct, reinterpret_cast<void *const *>(panels), n_panels, K, G, T, params, n_sample, sample_offset, read_off,
-                       read_ptr, u, bq, wif, dosage, gp_t, phasing_haps, read_labels, nDosage, stats);
+                       read_ptr, u, bq, wif, dosage, gp_t, phasing_haps, read_labels, nDosage, stats, hla, select_gamma);
+}
+
+extern "C" {
+
+int qa_impute_samples(qa_panel_t *const *panels, int32_t n_panels, const qa_impute_params_t *params, int32_t n_sample,
+                      int64_t sample_offset, const int32_t *read_off, const int32_t *read_ptr, const int32_t *u, const int32_t *bq,
+                      const int32_t *wif, double *dosage, double *gp_t, double *phasing_haps, int32_t *read_labels, int32_t *nDosage,
+                      int64_t *stats) {
+    return qa::impute_samples_product(panels, n_panels, params, n_sample, sample_offset, read_off, read_ptr, u, bq, wif, dosage, gp_t,
+                                      phasing_haps, read_labels, nDosage, stats, nullptr, nullptr);
 }
 
 int qa_impute_release_buffers(void) {
@@ -1593,6 +1685,22 @@ int qa_impute_samples_backend(const qa_impute_backend_t *backend, void *const *h
     }
     return impute_impl(false, backend, handles, n_handles, K, nGrids, nSNPs, params, n_sample, sample_offset, read_off, read_ptr, u, bq, wif,
                        dosage, gp_t, phasing_haps, read_labels, nDosage, stats);
+}
+
+int qa_impute_samples_backend_hla(const qa_impute_backend_t *backend, qa_fullpass_select_gamma_fn select_gamma, void *const *handles,
+                                  int32_t n_handles, int32_t K, int32_t nGrids, int32_t nSNPs, const qa_impute_params_t *params,
+                                  int32_t n_sample, int64_t sample_offset, const int32_t *read_off, const int32_t *read_ptr,
+                                  const int32_t *u, const int32_t *bq, const int32_t *wif, double *dosage, double *gp_t,
+                                  double *phasing_haps, int32_t *read_labels, int32_t *nDosage, int64_t *stats,
+                                  const qa_impute_hla_t *hla) {
+    if (!backend || !backend->gibbs_batch || !backend->fullpass_reads_select_batch || !backend->fullpass_batch ||
+        !backend->make_eMatRead_t_hap_major || !backend->mspbwt_select_new_haps || !backend->accumulate_dosage ||
+        !backend->consensus_read_labels || !backend->host_alloc || !backend->host_free || !select_gamma || !hla) {
+        qa::set_error("qa_impute_samples_backend_hla: incomplete table");
+        return QA_ERR_INVALID;
+    }
+    return impute_impl(false, backend, handles, n_handles, K, nGrids, nSNPs, params, n_sample, sample_offset, read_off, read_ptr, u, bq, wif,
+                       dosage, gp_t, phasing_haps, read_labels, nDosage, stats, hla, select_gamma);
 }
 
 }   // extern "C"

@@ -62,11 +62,28 @@ typedef struct {
                        const int32_t *bq, double maxDifferenceBetweenReads, int32_t Jmax, int32_t rescale_eMatRead_t,
                        double *eMatRead_t);
 } qa_impute_backend_t;
+
+/* qa_fullpass_reads_select_gamma_batch, with an opaque handle in place of the panel (hla_run's last seek iteration) */
+typedef int (*qa_fullpass_select_gamma_fn)(void *handle, int32_t n_chain, int32_t n_label, int32_t n_sample, const int32_t *chain_sample,
+                       const int32_t *read_off, const int32_t *read_ptr, const int32_t *u, const int32_t *bq, const int32_t *H,
+                       const int32_t *want_dosage, const int32_t *want_top, const int32_t *gammaSmall_cols_to_get,
+                       int32_t K_top_matches, double minGLValue, double *dosage, int32_t top_width, int32_t *top_idx,
+                       float *top_val, int32_t *top_cnt, int32_t Ksubset, int32_t Knew, const int32_t *which_haps_to_use,
+                       const uint64_t *seed_select, int32_t *which_next, int32_t *select_status, int32_t gamma_grid,
+                       double *gamma_col);
 int qa_impute_samples_backend(const qa_impute_backend_t *backend, void *const *handles, int32_t n_handles, int32_t K, int32_t nGrids,
                               int32_t nSNPs, const qa_impute_params_t *params, int32_t n_sample, int64_t sample_offset,
                               const int32_t *read_off, const int32_t *read_ptr, const int32_t *u, const int32_t *bq,
                               const int32_t *wif, double *dosage, double *gp_t, double *phasing_haps, int32_t *read_labels,
                               int32_t *nDosage, int64_t *stats);
+/* qa_impute_samples_hla over the same kind of table; select_gamma stands in for qa_fullpass_reads_select_gamma_batch at the last
+ * seek iteration (a separate argument: qa_impute_backend_t keeps its layout) */
+int qa_impute_samples_backend_hla(const qa_impute_backend_t *backend, qa_fullpass_select_gamma_fn select_gamma, void *const *handles,
+                                  int32_t n_handles, int32_t K, int32_t nGrids, int32_t nSNPs, const qa_impute_params_t *params,
+                                  int32_t n_sample, int64_t sample_offset, const int32_t *read_off, const int32_t *read_ptr,
+                                  const int32_t *u, const int32_t *bq, const int32_t *wif, double *dosage, double *gp_t,
+                                  double *phasing_haps, int32_t *read_labels, int32_t *nDosage, int64_t *stats,
+                                  const qa_impute_hla_t *hla);
 
 
 /* qa_impute_bam_range (include/quilt_amd_io.h) with its imputation step on a caller's table: the loader, the bookkeeping of

@@ -78,6 +78,8 @@ namespace qa {
 void finish_panel_tables(qa_panel *p);
 // fullpass.hip: delete the handle's full-pass scratch views (re-created on the next call, over the arena then in use)
 void drop_pass_scratch(qa_panel *p);
+// fullpass.hip: QA_OK when the handle's dosage passes keep a gamma column (hla_run), else QA_ERR_UNSUPPORTED with the cause set
+__attribute__((visibility("hidden"))) int gamma_column_check(const qa_panel *p, const char *who);
 }
 
 // The all-SNP side of a QUILT2 panel (rare + common SNPs): what the final all-SNP Gibbs call needs on top of the

@@ -67,6 +67,8 @@ class DriverParams:
     # "exhaustive" = every haplotype's longest run, searched on the device (csrc/match.hip; this library's own definition)
     mspbwt_search: str = "scan"
     mspbwt_max_matches: Optional[int] = None   # matches per (haplotype, index) from the device search; None: 50 * mspbwtL
+    # hla_run = FALSE here; HlaDriverParams below sets it (a subclass: the fields of this class are the loop's classified switches)
+    hla_grid = None
 
     def resolved(self, K: int) -> "DriverParams":
         p = DriverParams(**self.__dict__)
@@ -98,6 +100,25 @@ class DriverParams:
             raise ValueError("mspbwt_search is 'scan' (the msPBWT neighbour scan) or 'exhaustive' (the device search)")
         if p.use_mspbwt and p.mspbwt_search == "scan" and p.mspbwtL > 64:
             raise ValueError("mspbwtL <= 64")
+        return p
+
+
+@dataclass
+class HlaDriverParams(DriverParams):
+    """DriverParams with hla_run = TRUE (QUILT-HLA's QUILT() call, quilt-hla.R:192-212).  ``hla_grid``: the 0-based grid iGrid - 1
+    whose gamma column every Gibbs sample's last seek iteration keeps (functions.R:713-724, :1261-1280).  The reference's iGrid is
+    round(nGrids / 2) when gamma_physically_closest_to is NA, else grid[which.min(abs(L - gamma_physically_closest_to))] + 1."""
+
+    hla_grid: Optional[int] = None
+
+    def resolved(self, K: int) -> "HlaDriverParams":
+        base = {k: v for k, v in self.__dict__.items() if k != "hla_grid"}
+        p = HlaDriverParams(**DriverParams(**base).resolved(K).__dict__, hla_grid=self.hla_grid)
+        if p.hla_grid is None:
+            raise ValueError("HlaDriverParams needs hla_grid (0-based)")
+        # what the range call covers of hla_run: the gamma columns of the full-panel passes
+        if p.use_mspbwt or p.method != "diploid" or p.impute_rare_common:
+            raise ValueError("hla_grid (hla_run = TRUE) needs method = 'diploid', use_mspbwt = FALSE and impute_rare_common = FALSE")
         return p
 
 
@@ -445,6 +466,7 @@ class ChainState:
     read_labels: Optional[np.ndarray] = None
     hap: Optional[List[np.ndarray]] = None           # dosage1, dosage2 of the latest full pass
     hap_all: Optional[List[np.ndarray]] = None       # hap1_all, hap2_all of the rare + common call (all SNPs)
+    gamma: Optional[np.ndarray] = None               # hla_run: [2, K] gamma columns of the last seek iteration
 
     _phasing: bool = False
 
@@ -464,6 +486,20 @@ class SampleResult:
     # method = "nipt": dosage / gp_t are the mother's; the fetus':
     fet_dosage: Optional[np.ndarray] = None
     fet_gp_t: Optional[np.ndarray] = None
+    # hla_run (functions.R:1489-1494): the phasing iteration's gamma columns, their sum over the Gibbs samples and every
+    # Gibbs sample's pair (list_of_gammas[i] = (gamma1_i, gamma2_i): nGibbsSamples x 2 x K)
+    gamma1: Optional[np.ndarray] = None
+    gamma2: Optional[np.ndarray] = None
+    gamma_total: Optional[np.ndarray] = None
+    list_of_gammas: Optional[np.ndarray] = None
+
+
+def hla_gamma_total(list_of_gammas: np.ndarray) -> np.ndarray:
+    """functions.R:1273-1275: gamma_total <- gamma_total + gamma1 + gamma2 over the Gibbs samples in order, from numeric(K)."""
+    tot = np.zeros(list_of_gammas.shape[-1])
+    for g1, g2 in list_of_gammas:
+        tot = (tot + g1) + g2
+    return tot
 
 
 @dataclass
@@ -482,6 +518,7 @@ class _Batch:
     dosage_all: Optional[np.ndarray] = None     # impute_rare_common: the same accumulators over ALL SNPs
     gp_t_all: Optional[np.ndarray] = None
     nDosage_all: Optional[np.ndarray] = None
+    list_of_gammas: Optional[list] = None       # hla_run: per sample nGibbsSamples x 2 x K, once the main chains are done
 
 
 def get_initial_read_labels(e: np.ndarray, runif: np.ndarray) -> np.ndarray:
@@ -600,6 +637,8 @@ class Driver:
         if self.params.method not in ("diploid", "nipt"):
             raise ValueError("method is 'diploid' or 'nipt'")
         self.n_label = 3 if self.params.method == "nipt" else 2
+        if self.params.hla_grid is not None and not 0 <= self.params.hla_grid < panel.nGrids:
+            raise ValueError(f"hla_grid = {self.params.hla_grid} outside [0, nGrids = {panel.nGrids})")
         self.cols = thinned_grid_columns(panel.nGrids, self.params.heuristic_match_thin)
         self.n_thin = int((self.cols >= 0).sum())
         self.top_width = max(8, self.params.K_top_matches)   # entries kept per (label, thinned grid) list
@@ -687,14 +726,22 @@ class Driver:
         # everything_select_good_haps: one selection stream per chain and round; its draws are keyed (quilt_amd/rng.py), so
         # the device (csrc/select.hip, behind the full-panel call) and the host make the same choice
         seed_sel = [int(ch.rng.integers(0, 2 ** 63)) for ch in chains]
-        on_device = bool(getattr(self.backend, "select_on_device", False)) and any(want_top)
+        # hla_run: the last seek iteration's passes also return gammaMT_t / gammaMU_t at the grid (functions.R:713-724)
+        hla_it = P.hla_grid is not None and i_it == P.n_seek_its
+        on_device = bool(getattr(self.backend, "select_on_device", False)) and (any(want_top) or hla_it)
         select = None
         if on_device:
             select = dict(Ksubset=P.Ksubset, Knew=P.Knew, which=[ch.which_haps_to_use for ch in chains], seeds=seed_sel)
+        kw = {"select": select} if on_device else {}
+        if hla_it:
+            kw["gamma_grid"] = int(P.hla_grid)
         out = self.backend.fullpass_reads_batch(
             sample_list, [uniq[id(ch.sample)] for ch in chains], [ch.read_labels for ch in chains],
             [return_dosage] * len(chains), want_top, self.cols, P.K_top_matches, P.minGLValue, self.top_width,
-            n_label=self.n_label, **({"select": select} if on_device else {}))
+            n_label=self.n_label, **kw)
+        if hla_it:   # (the gamma columns come last)
+            for ci, ch in enumerate(chains):
+                ch.gamma = np.array(out[-1][ci], dtype=np.float64)
         dosages, top, top_cnt = out[:3]
         which_next, sel_status = out[3:5] if on_device else (None, None)
         t4 = time.perf_counter()
@@ -932,6 +979,9 @@ class Driver:
             b.phasing.append(ChainState(smp, i, P.nGibbsSamples + 1, chain_rng(P.seed, b.offset + i, P.nGibbsSamples + 1),
                                         which_haps_to_use=last.which_haps_to_use.copy(), read_labels=labels, _phasing=True))
         b.consensus = [ph.read_labels.copy() for ph in b.phasing]
+        if P.hla_grid is not None:   # functions.R:1276-1278: the main chains' pairs, Gibbs sample by Gibbs sample
+            b.list_of_gammas = [np.stack([b.chains[k].gamma for k in sorted(by_sample.get(i, []), key=lambda k: b.chains[k].i_chain)])
+                                for i in range(len(b.samples))]
         b.chains = []   # the main chains are done
 
     def _finish(self, b: _Batch) -> List[SampleResult]:
@@ -962,6 +1012,10 @@ class Driver:
                 continue
             h1, h2 = recast_haps(b.phasing[i].hap[0], b.phasing[i].hap[1], g.T)   # functions.R:1207-1217
             out.append(SampleResult(d, g, np.stack([h1, h2], axis=1), b.consensus[i], int(b.nDosage[i])))
+            if self.params.hla_grid is not None:   # functions.R:1489-1494
+                lg = b.list_of_gammas[i]
+                out[-1].gamma1, out[-1].gamma2 = b.phasing[i].gamma[0], b.phasing[i].gamma[1]
+                out[-1].gamma_total, out[-1].list_of_gammas = hla_gamma_total(lg), lg
         return out
 
     def run_stream(self, batches):
@@ -1163,12 +1217,14 @@ class HipBackend:
         return list(dosage), best
 
     def fullpass_reads_batch(self, samples, chain_sample, labels, want_dosage, want_top, cols, K_top_matches, minGLValue,
-                             top_width, n_label=2, select=None):
+                             top_width, n_label=2, select=None, gamma_grid=None):
         """impute_using_everything for every chain: returns dosage [n_chain, n_label, T], the ordered top matches
         [n_chain, n_label, n_thin, top_width] (0-based, -1 padded; only for chains with want_top) and the full list lengths.
         With ``select`` (Ksubset, Knew, which, seeds) the re-selection of the small panels runs on the device behind the
         passes (qa_fullpass_reads_select_batch): the lists stay there (``top`` is None) and the call also returns
-        which_next [n_chain, Ksubset] and the per-chain selection status.
+        which_next [n_chain, Ksubset] and the per-chain selection status.  With ``gamma_grid`` (hla_run; needs ``select``) the
+        passes also return gamma_t[, gamma_grid + 1] per chain and label (qa_fullpass_reads_select_gamma_batch), appended last:
+        [n_chain, n_label, K].
 
         The dosage array is a view of this backend's pinned transfer buffer (``qa_host_alloc``): it is valid until the
         next call that asks for dosages -- copy what must outlive that (the driver consumes a round before the next)."""
@@ -1214,11 +1270,21 @@ class HipBackend:
             seeds = np.ascontiguousarray(select["seeds"], dtype=np.uint64)
             nxt = np.zeros((n_chain, Ks), dtype=np.int32)
             status = np.full(n_chain, -1, dtype=np.int32)
+            if gamma_grid is not None:
+                gamma = np.zeros((n_chain, n_label, P.K))
+                lib().qa_fullpass_reads_select_gamma_batch.restype = C.c_int
+                with span("device:fullpass"):
+                    check(lib().qa_fullpass_reads_select_gamma_batch(*head, None, None, ptr(cnt), C.c_int32(Ks),
+                                                                     C.c_int32(int(select["Knew"])), ptr(which), ptr(seeds), ptr(nxt),
+                                                                     ptr(status), C.c_int32(int(gamma_grid)), ptr(gamma)))
+                return dosage, None, cnt, nxt, status, gamma
             with span("device:fullpass"):
                 check(lib().qa_fullpass_reads_select_batch(*head, None, None, ptr(cnt), C.c_int32(Ks),
                                                            C.c_int32(int(select["Knew"])), ptr(which), ptr(seeds), ptr(nxt),
                                                            ptr(status)))
             return dosage, None, cnt, nxt, status
+        if gamma_grid is not None:
+            raise ValueError("gamma_grid: the gamma columns come with the device-side selection (select=...)")
         top = np.full((n_chain, n_label, n_thin, top_width), -1, dtype=np.int32)
         val = np.zeros((n_chain, n_label, n_thin, top_width), dtype=np.float32)
         with span("device:fullpass"):

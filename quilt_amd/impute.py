@@ -94,6 +94,18 @@ class ImputeRareCommon(C.Structure):
                 ("L_grid_all", C.c_void_p)]
 
 
+class ImputeHla(C.Structure):   # qa_impute_hla_t
+    _fields_ = [("grid", C.c_int32), ("gamma1", C.c_void_p), ("gamma2", C.c_void_p), ("gamma_total", C.c_void_p),
+                ("list_of_gammas", C.c_void_p)]
+
+
+def make_hla(grid: int, n_sample: int, nGibbsSamples: int, K: int):
+    """(ImputeHla, (gamma1, gamma2, gamma_total, list_of_gammas)) for qa_impute_samples_hla: the struct over fresh output arrays
+    (n x K, n x K, n x K, n x nGibbsSamples x 2 x K)."""
+    arrs = (np.zeros((n_sample, K)), np.zeros((n_sample, K)), np.zeros((n_sample, K)), np.zeros((n_sample, nGibbsSamples, 2, K)))
+    return ImputeHla(int(grid), *[a.ctypes.data for a in arrs]), arrs
+
+
 STAT_NAMES = ("underflow_retries", "full_list_refetches", "device_selections", "gibbs_chain_calls", "gibbs_launches",
               "ms_gibbs", "ms_fullpass", "ms_host", "ms_consensus", "ms_finish", "ms_accumulate")
 
@@ -153,12 +165,16 @@ def make_params(P: DriverParams, samples_per_launch_set: int, mspbwt_index=None,
     return q, (blocks, mspbwt_index, rare_common, nipt)
 
 
-def wrap_results(samples, dosage, gp_t, haps, labels, nDosage, read_off, fet_dosage=None, fet_gp_t=None) -> List[SampleResult]:
+def wrap_results(samples, dosage, gp_t, haps, labels, nDosage, read_off, fet_dosage=None, fet_gp_t=None, hla=None) -> List[SampleResult]:
     """One SampleResult per sample over the call's output arrays: rows and slices of them, no copies (``phasing_haps`` is the
-    nSNPs x n_label transposed VIEW of the library's n_label x nSNPs rows)."""
-    return [SampleResult(dosage[i], gp_t[i], haps[i].T, labels[read_off[i]:read_off[i + 1]],
-                         int(nDosage[i]), fet_dosage=None if fet_dosage is None else fet_dosage[i],
-                         fet_gp_t=None if fet_gp_t is None else fet_gp_t[i]) for i in range(len(samples))]
+    nSNPs x n_label transposed VIEW of the library's n_label x nSNPs rows).  ``hla``: make_hla's arrays (hla_run)."""
+    out = [SampleResult(dosage[i], gp_t[i], haps[i].T, labels[read_off[i]:read_off[i + 1]],
+                        int(nDosage[i]), fet_dosage=None if fet_dosage is None else fet_dosage[i],
+                        fet_gp_t=None if fet_gp_t is None else fet_gp_t[i]) for i in range(len(samples))]
+    if hla is not None:
+        for i, r in enumerate(out):
+            r.gamma1, r.gamma2, r.gamma_total, r.list_of_gammas = hla[0][i], hla[1][i], hla[2][i], hla[3][i]
+    return out
 
 
 class PreparedRange:
@@ -193,7 +209,8 @@ def prepare_range(devs: Sequence, samples: Sequence, params: Optional[DriverPara
     nL = 3 if P.method == "nipt" else 2
     return PreparedRange(devs=list(devs), samples=list(samples), q=q, keep=(keep, keep_rc, keep_n), sample_offset=int(sample_offset),
                          read_off=read_off, read_ptr=read_ptr, u=u, bq=bq, wif=wif, n=n, T=T, nL=nL, fd=fd, fg=fg,
-                         handles=(C.c_void_p * len(devs))(*[d.handle for d in devs]))
+                         handles=(C.c_void_p * len(devs))(*[d.handle for d in devs]), hla_grid=P.hla_grid, nG=P.nGibbsSamples,
+                         K=panel.K)
 
 
 def run_prepared(r: PreparedRange, return_stats: bool = False, one_by_one: bool = False):
@@ -206,7 +223,11 @@ def run_prepared(r: PreparedRange, return_stats: bool = False, one_by_one: bool 
     stats = np.zeros(11, dtype=np.int64)
     L = lib()
     L.qa_impute_samples.restype = C.c_int
+    L.qa_impute_samples_hla.restype = C.c_int
     flat = (ptr(r.read_off), ptr(r.read_ptr), ptr(r.u), ptr(r.bq), ptr(r.wif))
+    hq = hla = None
+    if getattr(r, "hla_grid", None) is not None:   # hla_run: qa_impute_samples_hla with the gamma outputs
+        hq, hla = make_hla(r.hla_grid, n, r.nG, r.K)
     keep_s = None
     if one_by_one:
         views = [labels[r.read_off[i]:r.read_off[i + 1]] for i in range(n)]   # (contiguous slices of the flat label array)
@@ -214,12 +235,13 @@ def run_prepared(r: PreparedRange, return_stats: bool = False, one_by_one: bool 
         r.q.sample_source = C.cast(C.pointer(src), C.c_void_p)
         flat = (None,) * 5
     try:
-        check(L.qa_impute_samples(r.handles, C.c_int32(len(r.devs)), C.byref(r.q), C.c_int32(n), C.c_int64(r.sample_offset), *flat,
-                                  ptr(dosage), ptr(gp_t), ptr(haps), None if one_by_one else ptr(labels), ptr(nDosage), ptr(stats)))
+        args = (r.handles, C.c_int32(len(r.devs)), C.byref(r.q), C.c_int32(n), C.c_int64(r.sample_offset), *flat,
+                ptr(dosage), ptr(gp_t), ptr(haps), None if one_by_one else ptr(labels), ptr(nDosage), ptr(stats))
+        check(L.qa_impute_samples(*args) if hq is None else L.qa_impute_samples_hla(*args, C.byref(hq)))
     finally:
         r.q.sample_source = None
         del keep_s
-    out = wrap_results(r.samples, dosage, gp_t, haps, labels, nDosage, r.read_off, r.fd, r.fg)
+    out = wrap_results(r.samples, dosage, gp_t, haps, labels, nDosage, r.read_off, r.fd, r.fg, hla)
     return (out, dict(zip(STAT_NAMES, stats.tolist()))) if return_stats else out
 
 

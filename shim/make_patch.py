@@ -20,7 +20,7 @@ The diff is written with zero lines of context: it holds the changed rows only, 
 It also writes shim/QUILT-R.patch: the R side of the FAST path.
   * QUILT/R/quilt.R -- inside the mclapply body (:692-990), in front of the loop over a core's samples (:832), the whole range
     goes through ONE `.Call("qa_impute_sample_range", ...)` (quilt_amd_impute_sample_range, new file below) whenever the run
-    asks for nothing the range call does not cover (quilt_amd_range_is_covered: no plots, no HLA run, no phasefile / genfile
+    asks for nothing the range call does not cover (quilt_amd_range_is_covered: no plots, no phasefile / genfile
     truth, no per-read outputs, ...); the loop then takes each sample's result from that call instead of calling
     get_and_impute_one_sample (:835).  Otherwise -- and always with QUILT_AMD_RANGE=0 -- the unpatched loop runs, through the
     four per-call entries of QUILT-src.patch.
@@ -102,7 +102,10 @@ R_RANGE_CALL = '''        ## libquilt_amd: the whole sample range as ONE call (q
             estimate_bq_using_truth_read_labels = estimate_bq_using_truth_read_labels, addOptimalHapsToVCF = addOptimalHapsToVCF,
             use_splitreadgl = use_splitreadgl, small_ref_panel_skip_equally_likely_reads = small_ref_panel_skip_equally_likely_reads,
             shard_check_every_pair = shard_check_every_pair, use_hapMatcherR = use_hapMatcherR,
-            calculate_gamma_on_the_fly = calculate_gamma_on_the_fly, RData_objects_to_save = RData_objects_to_save
+            calculate_gamma_on_the_fly = calculate_gamma_on_the_fly, RData_objects_to_save = RData_objects_to_save,
+            use_mspbwt = use_mspbwt, impute_rare_common = impute_rare_common, n_seek_its = n_seek_its,
+            n_burn_in_seek_its = n_burn_in_seek_its, gamma_physically_closest_to = gamma_physically_closest_to, L = L, grid = grid,
+            hapMatcherR = hapMatcherR
         )) {
             amd_results <- quilt_amd_impute_sample_range(
                 sampleRange = sampleRange, n_handles = 3L, device = iCore - 1L,
@@ -123,7 +126,8 @@ R_RANGE_CALL = '''        ## libquilt_amd: the whole sample range as ONE call (q
                 sampleNames = sampleNames, downsampleToCov = downsampleToCov, tempdir = tempdir, regionName = regionName,
                 chrStart = chrStart, chrEnd = chrEnd, use_bx_tag = use_bx_tag, bxTagUpperLimit = bxTagUpperLimit,
                 minimum_number_of_sample_reads = minimum_number_of_sample_reads,
-                output_gt_phased_genotypes = output_gt_phased_genotypes
+                output_gt_phased_genotypes = output_gt_phased_genotypes,
+                hla_run = hla_run, gamma_physically_closest_to = gamma_physically_closest_to
             )
             ## native I/O (quilt-amd.R, form (a)): the range's four count arrays come back summed (in sample order) -- added here
             ## once; the per-sample entries the loop below adds are exact zeros then

@@ -6,7 +6,8 @@
 ## `.Call("qa_impute_sample_range", ...)` (shim/quilt_amd_shim.c; csrc/impute.cpp is get_and_impute_one_sample's loop nest,
 ## functions.R:330-1300, in host C++ over the batched kernels).  This file holds
 ##   quilt_amd_range_is_covered()   -- may this run take the range call?  Anything it does not cover falls back to the
-##                                     unpatched loop (plots, HLA, truth haplotypes / genotypes, per-read outputs, ...)
+##                                     unpatched loop (plots, truth haplotypes / genotypes, per-read outputs, ...)
+##   quilt_amd_hla_iGrid()          -- hla_run's grid (functions.R:1264-1268), 1-based as the reference forms it
 ##   quilt_amd_impute_sample_range() -- the range's samples through the ONE call.  Two forms:
 ##       (a) NATIVE I/O (the fast one; quilt_amd_native_io_is_covered): `.Call("qa_impute_bam_range", bam_files, ...)` reads the
 ##           BAM files on host threads (csrc/hostio.cpp), imputes, formats every sample's VCF column and sums the range's four
@@ -32,21 +33,45 @@ quilt_amd_range_is_covered <- function(
     record_interim_dosages, output_read_label_prob, record_read_label_usage, plot_per_sample_likelihoods,
     plot_p1, make_heuristic_plot, estimate_bq_using_truth_read_labels, addOptimalHapsToVCF, use_splitreadgl,
     small_ref_panel_skip_equally_likely_reads, shard_check_every_pair, use_hapMatcherR, calculate_gamma_on_the_fly,
-    RData_objects_to_save, n_gibbs_sample_its = 1
+    RData_objects_to_save, n_gibbs_sample_its = 1,
+    use_mspbwt = FALSE, impute_rare_common = FALSE, n_seek_its = 3, n_burn_in_seek_its = NA,
+    gamma_physically_closest_to = NA, L = NULL, grid = NULL, hapMatcherR = NULL
 ) {
     if (Sys.getenv("QUILT_AMD_RANGE", "1") == "0") return(FALSE)            ## opt out: the unpatched loop
     if (!is.loaded("qa_impute_sample_range", PACKAGE = "QUILT")) return(FALSE) ## built without QUILT-src.patch
+    ## hla_run (QUILT-HLA's QUILT() call, quilt-hla.R:192-212): the range call keeps fbsoL$gammaMT_t / gammaMU_t at one grid
+    ## (functions.R:1261-1280) from the last seek iteration's full-panel passes -- diploid, full-panel passes, no rare + common,
+    ## a last seek iteration that is a dosage pass, a grid that exists; QUILT-HLA's RData_objects_to_save then too
+    hla_ok <- !hla_run || (
+        method == "diploid" && !use_mspbwt && !impute_rare_common &&
+        (if (is.na(n_burn_in_seek_its)) n_seek_its - 1 else n_burn_in_seek_its) < n_seek_its &&
+        !is.null(hapMatcherR) &&
+        isTRUE(quilt_amd_hla_iGrid(gamma_physically_closest_to, L, grid, ncol(hapMatcherR)) >= 1)
+    )
+    rdata_ok <- is.null(RData_objects_to_save) ||
+        (hla_run && all(RData_objects_to_save %in% c("sampleNames", "final_set_of_results")))
     ok <- method %in% c("diploid", "nipt") &&
         !make_plots && !make_plots_block_gibbs &&      ## need gamma matrices (return_gamma_t) of every call
-        !hla_run &&                                     ## needs fbsoL$gammaMT_t / gammaMU_t at one grid (functions.R:1264-1283)
+        hla_ok &&
         !have_truth_haplotypes && !have_truth_genotypes && ## phasefile / genfile: per-iteration accuracy printing, truth labels
         !record_interim_dosages && !output_read_label_prob && !record_read_label_usage &&
         !plot_per_sample_likelihoods && !plot_p1 && !make_heuristic_plot &&
         !estimate_bq_using_truth_read_labels && !addOptimalHapsToVCF &&
         !use_splitreadgl && !small_ref_panel_skip_equally_likely_reads &&
         shard_check_every_pair && use_hapMatcherR && calculate_gamma_on_the_fly &&
-        is.null(RData_objects_to_save) && n_gibbs_sample_its == 1
+        rdata_ok && n_gibbs_sample_its == 1
     return(isTRUE(ok))
+}
+
+
+## functions.R:1264-1268, the reference's own two expressions (1-based; nGrids = ncol(hapMatcherR))
+quilt_amd_hla_iGrid <- function(gamma_physically_closest_to, L, grid, nGrids) {
+    if (is.na(gamma_physically_closest_to)) {
+        iGrid <- round(nGrids / 2)
+    } else {
+        iGrid <- grid[which.min(abs(L - gamma_physically_closest_to))] + 1
+    }
+    return(iGrid)
 }
 
 
@@ -98,7 +123,9 @@ quilt_amd_impute_sample_range <- function(
     ## loading and output
     L, pos, grid, bam_files, cram_files, reference, iSizeUpperLimit, bqFilter, useSoftClippedBases, chr, sampleNames,
     downsampleToCov, tempdir, regionName, chrStart, chrEnd, use_bx_tag, bxTagUpperLimit,
-    minimum_number_of_sample_reads, output_gt_phased_genotypes
+    minimum_number_of_sample_reads, output_gt_phased_genotypes,
+    ## hla_run (functions.R:1261-1280, :1489-1494)
+    hla_run = FALSE, gamma_physically_closest_to = NA
 ) {
     w <- sampleRange[1]:sampleRange[2]
     n <- length(w)
@@ -120,6 +147,10 @@ quilt_amd_impute_sample_range <- function(
         sum_order = sum_order
     )
     if (!is.na(n_burn_in_seek_its)) params[["n_burn_in_seek_its"]] <- n_burn_in_seek_its
+    if (hla_run) {
+        iGrid <- quilt_amd_hla_iGrid(gamma_physically_closest_to, L, grid, ncol(hapMatcherR))
+        params[["hla_grid"]] <- as.integer(iGrid - 1L)
+    }
     if (use_mspbwt) {
         params <- c(params, list(use_mspbwt = TRUE, mspbwtL = mspbwtL, mspbwtM = mspbwtM, mspbwt_nindices = mspbwt_nindices))
     }
@@ -137,7 +168,8 @@ quilt_amd_impute_sample_range <- function(
         )
     }
     ## ---- (a) native I/O: BAM paths in, VCF columns and the range's counts out (one call)
-    if (quilt_amd_native_io_is_covered(bam_files, cram_files, use_bx_tag, pos, pos_all, impute_rare_common)) {
+    ## (hla_run: the gammas come back through form (b); native I/O for it is not built)
+    if (!hla_run && quilt_amd_native_io_is_covered(bam_files, cram_files, use_bx_tag, pos, pos_all, impute_rare_common)) {
         sites <- list(
             chr = chr, L = as.integer(L), ref = as.character(pos[, 3]), alt = as.character(pos[, 4]), grid = as.integer(grid),
             bqFilter = bqFilter, iSizeUpperLimit = iSizeUpperLimit, useSoftClippedBases = useSoftClippedBases,
@@ -216,12 +248,22 @@ quilt_amd_impute_sample_range <- function(
         all_reads <- lapply(loaded_all[keep], "[[", "sampleReads")
     }
     print_message(paste0("Imputing samples ", w[keep[1]], " to ", w[keep[length(keep)]], " on the GPU (", length(keep), " samples in one call)"))
-    out <- .Call(
+    out <- tryCatch(.Call(
         "qa_impute_sample_range", lapply(loaded[keep], "[[", "sampleReads"), panel_objects, params,
         as.numeric(w[keep] - 1L),      ## every kept sample's own global index: its streams do not depend on which other samples
                                        ## of the range were skipped
         as.integer(n_handles), all_reads, PACKAGE = "QUILT"
-    )
+    ), error = function(e) {
+        ## hla_run on a panel whose dosage passes keep no gamma column (a K the fp64 dosage kernels do not hold): refused by the
+        ## library before any sample is imputed -- the range is not covered, the unpatched loop runs (NULL)
+        if (hla_run && grepl("keep no gamma column", conditionMessage(e), fixed = TRUE)) return(NULL)
+        stop(e)
+    })
+    if (is.null(out)) {
+        print_message(paste0("hla_run: this panel's full-panel passes keep no gamma column on the GPU; samples ", w[1], " to ", w[n],
+                             " take the per-sample loop"))
+        return(NULL)
+    }
     ## ---- 3. per sample, what get_and_impute_one_sample returns (functions.R:1304-1463)
     nL <- if (method == "nipt") 3 else 2
     for(j in seq_along(keep)) {
@@ -267,6 +309,15 @@ quilt_amd_impute_sample_range <- function(
             super_out_hap_dosages = NULL, super_out_read_labels = out[["read_labels"]][[j]],
             super_out_dosage_matrix = NULL, final_read_labels_prob = as.list(1:3)
         )
+        if (hla_run) {
+            ## functions.R:1489-1494: the phasing iteration's columns, their sum over the Gibbs samples, and every Gibbs sample's pair
+            K <- nrow(hapMatcherR)
+            g <- array(out[["list_of_gammas"]][, j], c(K, 2, nGibbsSamples))
+            results[[i]][["gamma1"]] <- out[["gamma1"]][, j]
+            results[[i]][["gamma2"]] <- out[["gamma2"]][, j]
+            results[[i]][["gamma_total"]] <- out[["gamma_total"]][, j]
+            results[[i]][["list_of_gammas"]] <- lapply(1:nGibbsSamples, function(i_gibbs) list(g[, 1, i_gibbs], g[, 2, i_gibbs]))
+        }
     }
     return(results)
 }

@@ -571,14 +571,17 @@ SEXP qa_QUILT_rcpp_make_eMatRead_t(SEXP eMatRead_tSEXP, SEXP sampleReadsSEXP, SE
  *                         minGLValue, Jmax, seed (a non-negative whole number below 2^53), samples_per_launch_set, device (0-based GPU of
  *                         this worker, taken modulo the number of devices: mclapply's iCore - 1; absent: the current device);
  *                         use_mspbwt, mspbwtL, mspbwtM, mspbwt_nindices;
- *                         impute_rare_common; method ("diploid" / "nipt"), ff (one fetal fraction per sample), shuffle_bin_radius
+ *                         impute_rare_common; method ("diploid" / "nipt"), ff (one fetal fraction per sample), shuffle_bin_radius;
+ *                         hla_grid (hla_run = TRUE: iGrid - 1, 0-based; qa_impute_samples_hla)
  *   sample_offset         0-based index of the range's first sample among ALL samples (keys the random streams: a sample's
  *                         result does not depend on the range it lands in)
  *   list_of_allSNP_sampleReads   impute_rare_common = TRUE: allSNP_sampleReads per sample (functions.R:162-172: u over all SNPs,
  *                         wif on the all-SNP grid); NULL otherwise
  * Returns list(dosage = nSNPs x n, gp_t = 3 nSNPs x n (per sample 3 x nSNPs, row-major as the library writes it),
  * phasing_haps = 2 nSNPs x n (nipt: 3 nSNPs x n), read_labels = list of integer vectors, nDosage, stats[, fet_dosage, fet_gp_t]);
- * nSNPs = all SNPs with impute_rare_common.  Draws: the library's counter streams (R's stream cannot be handed to 2 048 chains
+ * nSNPs = all SNPs with impute_rare_common.  With params$hla_grid also gamma1, gamma2, gamma_total (K x n: a sample's column is
+ * its vector) and list_of_gammas ((K x 2 x nGibbsSamples) x n: per sample the nGibbsSamples pairs (gamma1, gamma2) of
+ * functions.R:1276-1278, each column an R array of dim c(K, 2, nGibbsSamples)).  Draws: the library's counter streams (R's stream cannot be handed to 2 048 chains
  * advancing in lock-step); `seed` plays set.seed's part.  use_mspbwt: the panel's msPBWT indices are built here by
  * qa_mspbwt_create (the `ms_indices` the reference loads are the mspbwt package's own structures). */
 
@@ -908,6 +911,17 @@ SEXP qa_impute_sample_range(SEXP readsListSEXP, SEXP panelSEXP, SEXP paramsSEXP,
         Rf_error("quilt_amd: %s: sample_offset must be one number or one global index per sample", who);
     if (flag(paramsSEXP, "impute_rare_common", 0) && (allReadsListSEXP == R_NilValue || Rf_length(allReadsListSEXP) != n))
         Rf_error("quilt_amd: %s: impute_rare_common needs one allSNP_sampleReads per sample", who);
+    /* hla_run (functions.R:1261-1280): params$hla_grid, the 0-based grid of gamma1 / gamma2 -- checked before anything is made */
+    SEXP hgSEXP = list_get(paramsSEXP, "hla_grid");
+    const int hla = hgSEXP != R_NilValue;
+    int hla_grid = -1;
+    if (hla) {
+        const double hg = Rf_length(hgSEXP) == 1 && (TYPEOF(hgSEXP) == INTSXP || TYPEOF(hgSEXP) == REALSXP) ? Rf_asReal(hgSEXP) : -1;
+        const int G = Rf_ncols(list_get(panelSEXP, "hapMatcherR"));
+        if (!(hg >= 0 && hg < G && hg == floor(hg)))
+            Rf_error("quilt_amd: %s: params$hla_grid must be one whole number in [0, nGrids = %d) (iGrid - 1)", who, G);
+        hla_grid = (int)hg;
+    }
     range_ctx_t cx;
     int st = range_setup(&cx, panelSEXP, paramsSEXP, Rf_asInteger(n_handlesSEXP), n);
     if (st != QA_OK) Rf_error("quilt_amd: %s: %s", who, cx.msg);
@@ -935,6 +949,18 @@ SEXP qa_impute_sample_range(SEXP readsListSEXP, SEXP panelSEXP, SEXP paramsSEXP,
     SEXP dosage = PROTECT(Rf_allocMatrix(REALSXP, T_out, n)), gp_t = PROTECT(Rf_allocMatrix(REALSXP, 3 * T_out, n));
     SEXP haps = PROTECT(Rf_allocMatrix(REALSXP, nL * T_out, n)), nDosage = PROTECT(Rf_allocVector(INTSXP, n));
     SEXP stats = PROTECT(Rf_allocVector(REALSXP, 11));
+    SEXP g1 = R_NilValue, g2 = R_NilValue, gtot = R_NilValue, glist = R_NilValue;
+    qa_impute_hla_t hq;
+    memset(&hq, 0, sizeof hq);
+    if (hla) {
+        g1 = PROTECT(Rf_allocMatrix(REALSXP, cx.K, n));
+        g2 = PROTECT(Rf_allocMatrix(REALSXP, cx.K, n));
+        gtot = PROTECT(Rf_allocMatrix(REALSXP, cx.K, n));
+        glist = PROTECT(Rf_allocMatrix(REALSXP, cx.K * 2 * cx.ip.nGibbsSamples, n));
+        n_prot += 4;
+        hq.grid = hla_grid;
+        hq.gamma1 = REAL(g1); hq.gamma2 = REAL(g2); hq.gamma_total = REAL(gtot); hq.list_of_gammas = REAL(glist);
+    }
     int32_t *labels = (int32_t *)malloc(sizeof(int32_t) * (size_t)(totR > 0 ? totR : 1));
     int64_t *sidx = sample_index_of(sample_offsetSEXP, n);
     char msg[512];
@@ -943,9 +969,14 @@ SEXP qa_impute_sample_range(SEXP readsListSEXP, SEXP panelSEXP, SEXP paramsSEXP,
     int64_t st64[11] = {0};
     if (st == QA_OK) {
         cx.ip.sample_index = sidx;
-        st = qa_impute_samples(cx.handles, cx.n_handles, &cx.ip, n, sidx ? 0 : (int64_t)Rf_asReal(sample_offsetSEXP), read_off, fr.read_ptr, fr.u,
-                               fr.bq, fr.wif, REAL(dosage), REAL(gp_t), REAL(haps), labels, INTEGER(nDosage), st64);
-        if (st != QA_OK) snprintf(msg, sizeof msg, "qa_impute_samples: %s", qa_last_error());
+        const int64_t off = sidx ? 0 : (int64_t)Rf_asReal(sample_offsetSEXP);
+        if (hla)
+            st = qa_impute_samples_hla(cx.handles, cx.n_handles, &cx.ip, n, off, read_off, fr.read_ptr, fr.u, fr.bq, fr.wif, REAL(dosage),
+                                       REAL(gp_t), REAL(haps), labels, INTEGER(nDosage), st64, &hq);
+        else
+            st = qa_impute_samples(cx.handles, cx.n_handles, &cx.ip, n, off, read_off, fr.read_ptr, fr.u, fr.bq, fr.wif, REAL(dosage),
+                                   REAL(gp_t), REAL(haps), labels, INTEGER(nDosage), st64);
+        if (st != QA_OK) snprintf(msg, sizeof msg, "%s: %s", hla ? "qa_impute_samples_hla" : "qa_impute_samples", qa_last_error());
     }
     range_teardown(&cx);
     free(sidx);
@@ -967,10 +998,13 @@ SEXP qa_impute_sample_range(SEXP readsListSEXP, SEXP panelSEXP, SEXP paramsSEXP,
     }
     for (int i = 0; i < 11; i++) REAL(stats)[i] = (double)st64[i];
     const char *names[] = {"dosage", "gp_t", "phasing_haps", "read_labels", "nDosage", "stats", "fet_dosage", "fet_gp_t"};
-    SEXP out = PROTECT(named_list(cx.nipt ? 8 : 6, names));
+    const char *names_hla[] = {"dosage", "gp_t", "phasing_haps", "read_labels", "nDosage", "stats", "gamma1", "gamma2", "gamma_total",
+                               "list_of_gammas"};
+    SEXP out = PROTECT(hla ? named_list(10, names_hla) : named_list(cx.nipt ? 8 : 6, names));
     SET_VECTOR_ELT(out, 0, dosage); SET_VECTOR_ELT(out, 1, gp_t); SET_VECTOR_ELT(out, 2, haps);
     SET_VECTOR_ELT(out, 3, lab); SET_VECTOR_ELT(out, 4, nDosage); SET_VECTOR_ELT(out, 5, stats);
-    if (cx.nipt) { SET_VECTOR_ELT(out, 6, fet_dosage); SET_VECTOR_ELT(out, 7, fet_gp_t); }
+    if (hla) { SET_VECTOR_ELT(out, 6, g1); SET_VECTOR_ELT(out, 7, g2); SET_VECTOR_ELT(out, 8, gtot); SET_VECTOR_ELT(out, 9, glist); }
+    else if (cx.nipt) { SET_VECTOR_ELT(out, 6, fet_dosage); SET_VECTOR_ELT(out, 7, fet_gp_t); }
     UNPROTECT(7 + n_prot);
     return out;
 }

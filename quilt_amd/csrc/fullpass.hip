@@ -1655,44 +1655,31 @@ static int fullpass_reads_impl(qa_panel_t *panel, int32_t n_chain, int32_t n_lab
         {
             // a counting sort per sample, samples independent: spread over host threads (0.3 s on one thread for 256 samples of
             // 50 000 bases -- in front of every full-panel launch set, and uncovered whenever one host thread has the device to itself)
-            const int n_thr = std::max(1, std::min<int>(qa::host_threads_cap(), n_sample));
-            std::vector<std::string> errs(n_thr);
-            auto work = [&](int tid) {
-                try {
-                    std::vector<int32_t> fill;
-                    for (int s = tid; s < n_sample; s += n_thr) {
-                        const int R = read_off[s + 1] - read_off[s];
-                        const int32_t *rp = read_ptr + read_off[s] + s;
-                        const int32_t *su = u + base_off[s], *sb = bq + base_off[s];
-                        int32_t *sp = snp_ptr.data() + (size_t)s * (T + 1);
-                        ent_off[s] = base_off[s];
-                        for (int i = 0; i < rp[R]; i++) {
-                            if (su[i] < 0 || su[i] >= T) throw std::runtime_error("SNP index out of range");
-                            if (sb[i] > 255 || sb[i] < -255) throw std::runtime_error("|base quality| > 255");
-                            sp[su[i] + 1]++;
-                        }
-                        for (int t = 0; t < T; t++) sp[t + 1] += sp[t];
-                        fill.assign(sp, sp + T);
-                        for (int r = 0; r < R; r++)
-                            for (int i = rp[r]; i < rp[r + 1]; i++) {
-                                const int at = fill[su[i]]++;
-                                ent_read[(size_t)base_off[s] + at] = r;
-                                ent_bq[(size_t)base_off[s] + at] = sb[i];
-                            }
+            // (one task per thread, each taking every n_thr-th sample: `fill` is allocated once per thread, not once per sample)
+            const int n_thr = std::max(1, std::min<int>(qa::host_threads(), n_sample));
+            qa::parallel_for((size_t)n_thr, n_thr, [&](size_t tid) {
+                std::vector<int32_t> fill;
+                for (int s = (int)tid; s < n_sample; s += n_thr) {
+                    const int R = read_off[s + 1] - read_off[s];
+                    const int32_t *rp = read_ptr + read_off[s] + s;
+                    const int32_t *su = u + base_off[s], *sb = bq + base_off[s];
+                    int32_t *sp = snp_ptr.data() + (size_t)s * (T + 1);
+                    ent_off[s] = base_off[s];
+                    for (int i = 0; i < rp[R]; i++) {
+                        if (su[i] < 0 || su[i] >= T) throw std::runtime_error("SNP index out of range");
+                        if (sb[i] > 255 || sb[i] < -255) throw std::runtime_error("|base quality| > 255");
+                        sp[su[i] + 1]++;
                     }
-                } catch (const std::exception &e) {
-                    errs[tid] = e.what();
+                    for (int t = 0; t < T; t++) sp[t + 1] += sp[t];
+                    fill.assign(sp, sp + T);
+                    for (int r = 0; r < R; r++)
+                        for (int i = rp[r]; i < rp[r + 1]; i++) {
+                            const int at = fill[su[i]]++;
+                            ent_read[(size_t)base_off[s] + at] = r;
+                            ent_bq[(size_t)base_off[s] + at] = sb[i];
+                        }
                 }
-            };
-            if (n_thr == 1) {
-                work(0);
-            } else {
-                std::vector<std::thread> th;
-                for (int t = 0; t < n_thr; t++) th.emplace_back(work, t);
-                for (auto &t : th) t.join();
-            }
-            for (const auto &e : errs)
-                if (!e.empty()) throw std::runtime_error(e);
+            });
         }
         // chain -> offset of its labels in H (chains are laid out back to back, each with its sample's R)
         std::vector<int32_t> hoff(n_chain + 1, 0);

@@ -36,7 +36,6 @@
 
 #include <chrono>
 #include <functional>
-#include <thread>
 
 #include <algorithm>
 #include <cmath>
@@ -1053,11 +1052,6 @@ namespace {
 
 thread_local std::unique_ptr<GibbsHolder> g_gibbs;
 
-// the reference carries pR / pA over bases with bq == 0, even across reads (gibbs-small.cpp:139-181,
-// copied-from-stitch.cpp:139-175): fold that rule into an "effective" base quality (input marshalling)
-// The bq == 0 carry-over ("fold_zero_base_qualities"): a base without a quality takes the last quality seen in its chain's reads
-// (0 until one is seen); |bq| <= 255.  Applied per chain by the callers' host threads (gibbs_chunk, make_eMatRead_t_impl).
-
 // eps tables with the host libm (what the reference's pow() is), so the device needs no pow:
 // [0..255] pR for bq < 0, [256..511] pR for bq > 0, [512..767] pA for bq < 0, [768..1023] pA for bq > 0
 std::vector<double> base_quality_tables() {
@@ -1178,523 +1172,674 @@ void launch_gibbs(const GibbsParams &prm, int maxR, hipStream_t st, hipEvent_t *
     QA_HIP(hipEventRecord(ev[3], st));
 }
 
-}  // namespace
+double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
-static int gibbs_chunk(qa_panel_t *pn, size_t arena_need, const qa_rare_common *rc, const qa_gibbs_opts_t *o, const double *ff_chain, const int64_t *rep_off, const int32_t *rep_id, int per_it_off, int32_t n_chain, const int32_t *which_haps_to_use_1based,
-                   const int32_t *read_off, const int32_t *read_ptr, const int32_t *u, const int32_t *bq,
-                   const int32_t *wif, const double *runif_reads, const int32_t *first_read,
-                   const double *runif_shard, int32_t *H, int32_t *H_class, double *hapProbs_t,
-                   double *genProbsM_t, double *genProbsF_t, int32_t *underflow_problem, double *state_out,
-                   const uint64_t *seed_reads, const uint64_t *seed_shard) {
-    {
-        if (!g_gibbs) g_gibbs.reset(new GibbsHolder());
-        auto &S = g_gibbs->s;
-        const bool tmg = getenv("QA_TIMING") != nullptr;
-        auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-        const double T0 = now();
-        // the Gibbs launches of a handle that shares the device go to its own CU partition (qa_panel_set_cu_partition): the
-        // chains hold whole register files for the launch's lifetime, and spread over every CU they would leave no CU free
-        // for the other handle's full-panel workgroups
-        hipStream_t st = pn->gibbs_stream ? pn->gibbs_stream : pn->stream;
-        const int C = n_chain, G = rc ? rc->G_all : pn->G, T = rc ? rc->T_all : pn->T, Ks = o->Ks;
-        const int Ksp = (Ks + 63) / 64 * 64, NE = Ksp / 64;
-        const int rc_words = rc ? (T + 31) / 32 : 0;
-        std::vector<uint32_t> rc_any((size_t)C * rc_words, 0u);
-        const int n_its = o->n_gibbs_burn_in_its + o->n_gibbs_sample_its;
-        const int totR = read_off[C];
-        // bases: per chain the CSR block read_ptr[read_off[c] + c .. read_off[c+1] + c] is local (starts at 0)
-        std::vector<int32_t> base_off(C + 1, 0), which0((size_t)C * Ks), bq_eff;
-        std::vector<size_t> eoff(C), ixoff(C);
-        std::vector<uint8_t> ghr((size_t)C * G, 0);
-        std::vector<int32_t> dense_of(std::max(totR, 1), -1);
-        const int nw = o->ff != 0.0 ? qa::gibbs3_waves(Ksp, C, pn->sharers()) : choose_gibbs_waves(Ksp, C, pn->exclusive ? 0 : pn->share);
-        const int er_nt = 64 * nw, er_padb = padb_of(NE / nw);
-        int maxR = 0;
-        size_t etot = 0, ixtot = 0;
-        for (int c = 0; c < C; c++) {   // offsets first (cheap), then the per-chain passes over the reads in parallel
-            const int R = read_off[c + 1] - read_off[c];
-            maxR = std::max(maxR, R);
-            const int32_t *rp = read_ptr + read_off[c] + c;
-            base_off[c + 1] = base_off[c] + rp[R];
-            ixoff[c] = ixtot;
-            ixtot += (size_t)R * er_nt * er_padb;
-        }
-        const int totB = base_off[C];
-        // opts->reads_same_as: chains that share their sample's reads.  rep[c] = the first chain OF THIS LAUNCH with chain c's
-        // reads (c itself without the option); only the representatives' bases are looked at and uploaded.
-        std::vector<int32_t> rep(C);
-        std::vector<int64_t> hbase(C);   // where a chain's bases are looked at on the host, relative to this launch's u / bq
-        bool aliased = false;
-        {
-            // keyed on the representative's INDEX in the call (reads_same_as[c]), not on where its bases lie: a chain without
-            // bases has the offset of the chain behind it and would be taken for sharing that chain's reads
-            std::map<int32_t, int32_t> first_of;
-            for (int c = 0; c < C; c++) {
-                rep[c] = c;
-                hbase[c] = rep_off ? rep_off[c] : (int64_t)base_off[c];
-                if (!rep_off) continue;
-                auto it = first_of.find(rep_id[c]);
-                if (it == first_of.end()) { first_of.emplace(rep_id[c], c); aliased |= rep_off[c] != (int64_t)base_off[c]; continue; }
-                const int r0 = it->second;
-                const int R = read_off[c + 1] - read_off[c];
-                // the same reads means the same read boundaries, not just as many reads and bases
-                if (read_off[r0 + 1] - read_off[r0] != R || base_off[r0 + 1] - base_off[r0] != base_off[c + 1] - base_off[c] ||
-                    std::memcmp(read_ptr + read_off[r0] + r0, read_ptr + read_off[c] + c, sizeof(int32_t) * ((size_t)R + 1)) != 0)
-                    throw std::runtime_error("reads_same_as names a chain with other reads");
-                rep[c] = r0;
-                aliased = true;
-            }
-        }
-        bq_eff.resize((size_t)std::max(totB, 1));
-        std::vector<int32_t> n_dense(C, 0);
-        {
-            // validation, grid_has_read, 0-based haplotypes, the bq == 0 carry-over (fold_zero_base_qualities) and the
-            // choice of the reads that keep a dense column (more informative bases -- k_ematread skips bq == 0 -- than the
-            // pattern width): independent per chain, spread over host threads
-            const int n_thr = std::max(1, std::min<int>(qa::host_threads_cap(), C));
-            std::vector<std::string> errs(n_thr);
-            int pass = 0;   // 0: the representatives (they fold their base qualities in place); 1: the chains that share a representative's
-            auto work = [&](int tid) {
-                try {
-                    for (int c = tid; c < C; c += n_thr) {
-                        if ((rep[c] == c) != (pass == 0)) continue;
-                        const int R = read_off[c + 1] - read_off[c];
-                        const int32_t *rp = read_ptr + read_off[c] + c;
-                        const int64_t hb = hbase[c];          // where this chain's bases are looked at (u, bq)
-                        const size_t fb = (size_t)base_off[rep[c]];   // the representative's block of bq_eff
-                        if (pass == 0) std::memcpy(&bq_eff[fb], bq + hb, sizeof(int32_t) * (size_t)(base_off[c + 1] - base_off[c]));
-                        for (int r = 0; r < R; r++) {
-                            const int g = wif[read_off[c] + r];
-                            if (g < 0 || g >= G) throw std::runtime_error("read grid index out of range");
-                            if (r > 0 && g < wif[read_off[c] + r - 1]) throw std::runtime_error("reads must be sorted by grid");
-                            ghr[(size_t)c * G + g] = 1;
-                        }
-                        for (int k = 0; k < Ks; k++) {
-                            const int v = which_haps_to_use_1based[(size_t)c * Ks + k] - 1;
-                            if (v < 0 || v >= pn->K) throw std::runtime_error("which_haps_to_use out of range");
-                            which0[(size_t)c * Ks + k] = v;
-                            if (rc)   // rare SNPs some selected haplotype carries the alt of (rare_per_snp_info, rare_common.R:313-322)
-                                for (int64_t i = rc->h_rare_ptr[v]; i < rc->h_rare_ptr[v + 1]; i++) {
-                                    const int t = rc->h_rare_snp[i];
-                                    rc_any[(size_t)c * rc_words + (t >> 5)] |= 1u << (t & 31);
-                                }
-                        }
-                        const int32_t *cu = u + hb;
-                        int last = 0, nd = 0;
-                        for (int r = 0; r < R; r++) {
-                            int J = rp[r + 1] - rp[r] - 1;
-                            if (J >= o->Jmax) J = o->Jmax;
-                            int n_inf = 0;
-                            for (int j = 0; j <= J; j++) {
-                                int32_t b = bq_eff[fb + rp[r] + j];
-                                if (b == 0) b = last; else last = b;
-                                if (pass == 0) bq_eff[fb + rp[r] + j] = b;   // (a sharing chain reads the folded values: folding them again changes nothing)
-                                if (b > 255 || b < -255) throw std::runtime_error("|base quality| > 255");
-                                const int t = cu[rp[r] + j];
-                                if (t < 0 || t >= T) throw std::runtime_error("read SNP index out of range");
-                                // a rare SNP nobody selected carries is a common factor: no pattern bit (k_ematread)
-                                const bool informative = !rc || rc->h_common_index[t] >= 0 ||
-                                                         ((rc_any[(size_t)c * rc_words + (t >> 5)] >> (t & 31)) & 1u);
-                                n_inf += (b != 0) && informative;
-                            }
-                            if (n_inf > kMaxPatternBits) dense_of[read_off[c] + r] = nd++;
-                        }
-                        n_dense[c] = nd;
-                    }
-                } catch (const std::exception &e) {
-                    errs[tid] = e.what();
-                }
-            };
-            for (pass = 0; pass < (aliased ? 2 : 1); pass++) {
-                std::vector<std::thread> th;
-                for (int i = 1; i < n_thr; i++) th.emplace_back(work, i);
-                work(0);
-                for (auto &t : th) t.join();
-                for (auto &e : errs) if (!e.empty()) throw std::runtime_error(e);
-            }
-        }
-        for (int c = 0; c < C; c++) {
-            eoff[c] = etot;
-            etot += (size_t)n_dense[c] * Ksp;
-        }
-        const double T1 = now();
-        const std::vector<double> tabs = base_quality_tables();
-        std::vector<double> tm((size_t)2 * std::max(G - 1, 1));
-        for (int g = 0; g < G - 1; g++) {
-            tm[g] = rc ? rc->h_sigma[g] : pn->h_sigma[g];
-            tm[(size_t)G - 1 + g] = rc ? rc->h_tm1[g] : pn->h_tm1[g];
-        }
+// The per-call arrays of qa_gibbs_batch / qa_gibbs_batch_rare_common (include/quilt_amd.h); inside a GibbsLaunch, one launch's
+// part of them
+struct GibbsCall {
+    const int32_t *which, *read_off, *read_ptr, *u, *bq, *wif;
+    const double *runif_reads;
+    const int32_t *first_read;
+    const double *runif_shard;
+    int32_t *H, *H_class;
+    double *hapProbs_t, *genProbsM_t, *genProbsF_t;
+    int32_t *underflow_problem;
+    double *state_out;
+    const uint64_t *seed_reads, *seed_shard;
+};
 
-        S.which.ensure(which0.size()); S.which.upload(which0.data(), which0.size(), st);
-        S.read_off.ensure(C + 1); S.read_off.upload(read_off, C + 1, st);
-        S.read_ptr.ensure(totR + C); S.read_ptr.upload(read_ptr, totR + C, st);
-        if (!aliased) {
-            S.base_off.ensure(C + 1); S.base_off.upload(base_off.data(), C + 1, st);
-            S.u.ensure(std::max(totB, 1)); S.u.upload(u, totB, st);
-            S.bq.ensure(std::max(totB, 1)); S.bq.upload(bq_eff.data(), totB, st);
-        } else {
-            // the representatives' bases back to back; every chain's device offset is its representative's (the kernels take
-            // base_off[c] as the start of the chain's bases and nothing else)
-            std::vector<int32_t> dev_off(C + 1, 0), cu_h, cb_h;
-            int at = 0;
-            for (int c = 0; c < C; c++)
-                if (rep[c] == c) { dev_off[c] = at; at += base_off[c + 1] - base_off[c]; }
-            for (int c = 0; c < C; c++) dev_off[c] = dev_off[rep[c]];
-            dev_off[C] = at;
-            cu_h.resize((size_t)std::max(at, 1)); cb_h.resize((size_t)std::max(at, 1));
-            for (int c = 0; c < C; c++)
-                if (rep[c] == c) {
-                    const size_t nb_c = (size_t)(base_off[c + 1] - base_off[c]);
-                    std::memcpy(&cu_h[(size_t)dev_off[c]], u + hbase[c], sizeof(int32_t) * nb_c);
-                    std::memcpy(&cb_h[(size_t)dev_off[c]], &bq_eff[(size_t)base_off[c]], sizeof(int32_t) * nb_c);
-                }
-            S.base_off.ensure(C + 1); S.base_off.upload(dev_off.data(), C + 1, st);
-            S.u.ensure(std::max(at, 1)); S.u.upload(cu_h.data(), at, st);
-            S.bq.ensure(std::max(at, 1)); S.bq.upload(cb_h.data(), at, st);
-        }
-        S.wif.ensure(std::max(totR, 1)); S.wif.upload(wif, totR, st);
-        S.ghr.ensure(ghr.size()); S.ghr.upload(ghr.data(), ghr.size(), st);
-        S.tabs.ensure(tabs.size()); S.tabs.upload(tabs.data(), tabs.size(), st);
-        S.tm.ensure(tm.size()); S.tm.upload(tm.data(), tm.size(), st);
-        S.block_its.ensure(std::max(o->n_block_gibbs_iterations, 1));
-        S.block_its.upload(o->block_gibbs_iterations, o->n_block_gibbs_iterations, st);
-        S.first_read.ensure(C); S.first_read.upload(first_read, C, st);
-        if (!seed_reads) {
-            S.runif_reads.ensure(std::max<size_t>((size_t)totR * n_its, 1));
-            S.runif_reads.upload(runif_reads, (size_t)totR * n_its, st);
-        } else {
-            S.runif_reads.ensure(1);
-            S.seeds.ensure((size_t)2 * C);
-            S.seeds.upload(seed_reads, C, st);
-            qa::staged_upload(S.seeds.p + C, seed_shard ? seed_shard : seed_reads, sizeof(uint64_t) * C, st);
-        }
-        // diploid: the shard passes' uniforms; NIPT: the block passes' (include/quilt_amd.h)
-        const bool nipt = o->ff != 0.0;
-        const size_t nshard_used = nipt ? (size_t)totR * o->n_block_gibbs_iterations * 2
-                                        : (size_t)C * o->n_block_gibbs_iterations * (G - 1);
-        S.runif_shard.ensure(std::max<size_t>(nshard_used, 1));
-        // (read only when a pass will draw from it: a caller that switches the passes off may hand over anything -- an array
-        // shorter than the passes would need was read past its end here until round 6: found by AddressSanitizer on the host code)
-        if (runif_shard && !seed_shard && o->n_block_gibbs_iterations > 0 && o->perform_block_gibbs && (nipt || o->do_shard_block_gibbs))
-            S.runif_shard.upload(runif_shard, nshard_used, st);
-        S.eread_off.ensure(C); S.eread_off.upload(eoff.data(), C, st);
-        S.eridx_off.ensure(C); S.eridx_off.upload(ixoff.data(), C, st);
-        S.dense_of.ensure(dense_of.size()); S.dense_of.upload(dense_of.data(), dense_of.size(), st);
-        S.is_cat1.ensure(std::max(totR, 1));
-        S.er_nent.ensure(std::max(totR, 1));
-        const int nH = o->ff != 0.0 ? 3 : 2;
-        const size_t mat = (size_t)C * nH * G * Ksp;
-        S.H.ensure(std::max(totR, 1)); S.H.upload(H, totR, st);
-        S.H_class.ensure(std::max(totR, 1));
-        S.status.ensure(C);
-        if (o->per_it_out) S.per_it.ensure((size_t)C * n_its * 8);
-        if (ff_chain) { S.ff_chain.ensure(C); S.ff_chain.upload(ff_chain, C, st); }
-        if (rc) { S.rc_any.ensure(std::max<size_t>(rc_any.size(), 1)); S.rc_any.upload(rc_any.data(), rc_any.size(), st); }
-        // (SNP, row) pairs per chain for k_happrobs_rc (only when the probabilities are asked for)
-        const bool want_pairs = rc && (hapProbs_t || genProbsM_t || genProbsF_t || o->hap_words_out || o->hap_major_out) && Ks <= 1024;
-        if (want_pairs) {
-            std::vector<size_t> pbase((size_t)C + 1, 0);
-            std::vector<std::vector<uint32_t>> keys((size_t)C);   // SNP << 10 | row, sorted
-            {
-                const int n_thr = std::max(1, std::min<int>(qa::host_threads_cap(), C));
-                auto work = [&](int tid) {
-                    for (int c = tid; c < C; c += n_thr) {
-                        auto &kv = keys[(size_t)c];
-                        for (int k = 0; k < Ks; k++) {
-                            const int v = which0[(size_t)c * Ks + k];
-                            for (int64_t i = rc->h_rare_ptr[v]; i < rc->h_rare_ptr[v + 1]; i++) kv.push_back(((uint32_t)rc->h_rare_snp[i] << 10) | (uint32_t)k);
-                        }
-                        std::sort(kv.begin(), kv.end());
-                    }
-                };
-                std::vector<std::thread> th;
-                for (int i = 1; i < n_thr; i++) th.emplace_back(work, i);
-                work(0);
-                for (auto &t : th) t.join();
-            }
-            for (int c = 0; c < C; c++) pbase[(size_t)c + 1] = pbase[(size_t)c] + keys[(size_t)c].size();
-            std::vector<uint16_t> pairs(std::max<size_t>(pbase[(size_t)C], 1));
-            std::vector<int32_t> poff((size_t)C * (G + 1), 0);
-            for (int c = 0; c < C; c++) {
-                const auto &kv = keys[(size_t)c];
-                int32_t *po = poff.data() + (size_t)c * (G + 1);
-                size_t i = 0;
-                for (int g = 0; g < G; g++) {
-                    po[g] = (int32_t)i;
-                    while (i < kv.size() && (int)((kv[i] >> 10) >> 5) == g) {
-                        pairs[pbase[(size_t)c] + i] = (uint16_t)((((kv[i] >> 10) & 31u) << 10) | (kv[i] & 1023u));
-                        i++;
-                    }
-                }
-                po[G] = (int32_t)i;
-            }
-            S.rc_pairs.ensure(pairs.size()); S.rc_pairs.upload(pairs.data(), pairs.size(), st);
-            S.rc_pair_off.ensure(poff.size()); S.rc_pair_off.upload(poff.data(), poff.size(), st);
-            S.rc_pair_base.ensure((size_t)C); S.rc_pair_base.upload(pbase.data(), (size_t)C, st);
-        }
-        // ---- everything above is host work and uploads into this thread's own buffers; from here on the launch set has the
-        // device (exclusive phases: queue behind the other handles' launch sets) and the arena
-        const double hold_t0 = now();
-        qa::GateHold hold;
-        hold.acquire(pn->gate(), &pn->arena, C * nw, arena_need);
-        const double T1g = now();
-        qa::Arena &arena = hold.arena();
-        S.er_idx.arena = S.er_tab.arena = &arena;
-        S.eMatRead.arena = S.alpha.arena = S.beta.arena = S.eg.arena = S.cvec.arena = S.hap.arena = S.gm.arena = S.gf.arena = &arena;
-        arena.require(arena_need);
-        arena.reset();
-        S.eMatRead.ensure(std::max<size_t>(etot, 1));
-        S.er_idx.ensure(std::max<size_t>(ixtot, 1));
-        S.er_tab.ensure(std::max<size_t>((size_t)totR * 64, 1));
-        S.alpha.ensure(mat); S.beta.ensure(mat); S.eg.ensure(mat);
-        S.cvec.ensure((size_t)C * 3 * G);
-        if (hapProbs_t || genProbsM_t || genProbsF_t || o->hap_words_out || o->hap_major_out) {
-            S.hap.ensure((size_t)C * T * 3); S.gm.ensure((size_t)C * T * 3); S.gf.ensure((size_t)C * T * 3);
-        }
+// return_hapProbs / return_genProbs (functions.R:2566-2599): skipped when nobody asks
+bool wants_probs(const GibbsCall &a, const qa_gibbs_opts_t *o) {
+    return a.hapProbs_t || a.genProbsM_t || a.genProbsF_t || o->hap_words_out || o->hap_major_out;
+}
 
-        GibbsParams prm{};
-        prm.hm = pn->hm.p; prm.B = pn->B.p; prm.sp_off = pn->sp_off.p; prm.sp_k = pn->sp_k.p;
-        prm.sp_word = pn->sp_word.p; prm.sigma = S.tm.p; prm.Kp = pn->Kp; prm.G = G; prm.T = T;
-        prm.nMaxDH = pn->nMaxDH; prm.ref_error = pn->ref_error;
-        prm.C = C; prm.Ks = Ks; prm.Ksp = Ksp; prm.NE = NE; prm.which = S.which.p;
-        prm.read_off = S.read_off.p; prm.read_ptr = S.read_ptr.p; prm.base_off = S.base_off.p;
-        prm.u = S.u.p; prm.bq = S.bq.p; prm.wif = S.wif.p; prm.grid_has_read = S.ghr.p;
-        prm.pR_tab = S.tabs.p; prm.pA_tab = S.tabs.p + 512;
-        prm.Jmax = o->Jmax; prm.inv_maxdiff = 1 / o->maxDifferenceBetweenReads; prm.rescale = o->rescale_eMatRead_t;
-        prm.n_its = n_its; prm.n_burn_in = o->n_gibbs_burn_in_its; prm.block_its = S.block_its.p;
-        prm.n_block = o->perform_block_gibbs ? o->n_block_gibbs_iterations : 0;
-        prm.do_shard = o->do_shard_block_gibbs; prm.init_iteratively = o->gibbs_initialize_iteratively;
-        prm.disable_read_category_usage = o->disable_read_category_usage;
-        prm.class_sum_cutoff = o->class_sum_cutoff;
-        prm.nH = nH;
-        prm.it_begin = 0; prm.it_end = n_its;
-        prm.ff = o->ff;
-        if (o->per_it_out) {
-            QA_HIP(hipMemsetAsync(S.per_it.p, 0, sizeof(double) * C * n_its * 8, st));
-            prm.per_it = S.per_it.p;
-        }
-        if (ff_chain) prm.ff_chain = S.ff_chain.p;
-        prm.runif_reads = S.runif_reads.p; prm.first_read = S.first_read.p; prm.runif_shard = S.runif_shard.p;
-        prm.seed_reads = seed_reads ? S.seeds.p : nullptr;
-        prm.seed_shard = (seed_reads && seed_shard) ? S.seeds.p + C : nullptr;
-        prm.eMatRead = S.eMatRead.p; prm.eread_off = S.eread_off.p; prm.is_cat1 = S.is_cat1.p; prm.er_nent = S.er_nent.p;
-        prm.er_idx = S.er_idx.p; prm.eridx_off = S.eridx_off.p; prm.er_tab = S.er_tab.p; prm.dense_of = S.dense_of.p;
-        prm.er_nt = er_nt; prm.er_padb = er_padb;
-        prm.alpha = S.alpha.p; prm.beta = S.beta.p; prm.eg = S.eg.p; prm.cvec = S.cvec.p;
-        prm.H = S.H.p; prm.H_class = S.H_class.p; prm.status = S.status.p;
-        prm.hapProbs = S.hap.p; prm.genProbsM = S.gm.p; prm.genProbsF = S.gf.p;
-        if (rc) {
-            prm.rc_common = rc->common_index.p; prm.rc_rare_ptr = rc->rare_ptr.p; prm.rc_rare_snp = rc->rare_snp.p;
-            prm.rc_any = S.rc_any.p; prm.rc_words = rc_words; prm.rc_Gc = pn->G;
-            if (want_pairs) { prm.rc_pairs = S.rc_pairs.p; prm.rc_pair_off = S.rc_pair_off.p; prm.rc_pair_base = S.rc_pair_base.p; }
-        }
+// Chains [c0, c0 + C) of a call: what one launch works on
+struct GibbsLaunch {
+    GibbsCall a{};                    // the call's arrays from chain c0 on; a.read_off is `read_off` below
+    int c0 = 0, C = 0;
+    const double *ff_chain = nullptr; // opts->ff_chain from chain c0 on, or null
+    const int32_t *rep_id = nullptr;  // opts->reads_same_as from chain c0 on (indices into the CALL), or null
+    std::vector<int32_t> read_off;    // [C + 1], starting at 0
+    std::vector<int64_t> rep_off;     // opts->reads_same_as: a chain's bases, relative to this launch's u / bq (may lie before them)
+    GibbsLaunch() = default;
+    GibbsLaunch(GibbsLaunch &&) = default;
+    GibbsLaunch(const GibbsLaunch &) = delete;   // (a.read_off points into read_off)
+};
 
-        for (auto &e : g_gibbs->ev) if (!e) QA_HIP(hipEventCreate(&e));
-        const bool want_probs = hapProbs_t || genProbsM_t || genProbsF_t || o->hap_words_out || o->hap_major_out;
-        QA_HIP(hipStreamSynchronize(st));
-        const double T2 = now();
-        // NIPT: the sweeps are cut at the block-Gibbs iterations; between two segments the switch rate per grid boundary
-        // comes back to the host, which defines the blocks (scalar logic per chain, gibbs_blocks.hpp) for the block kernel
-        auto nipt_sweeps = [&]() {
-            GibbsParams q = prm;
-            q.ff = o->ff;
-            // The three-label sampler's 256-register build (two chains per SIMD, gibbs3.hip) is built and tested but NOT chosen by
-            // default: alone on the device 1 792 chains take 2.33-2.58 s in it against 2 x 1.24 s for two launches of 896 at one
-            // chain per SIMD -- a sweep's grid steps are HBM-bound either way (5.6 TB/s) and the read visits, which two waves per
-            // SIMD should overlap, pay for eMatGrid's trips through LDS and ~600 bytes of scratch per lane.
-            // QA_GIBBS3_LEAN=1 selects it (tests, measurements).
-            const char *lean3_env = getenv("QA_GIBBS3_LEAN");   // (read per call: the tests switch it inside one process)
-            const bool lean3_on = lean3_env && atoi(lean3_env) != 0;
-            q.lean3 = (Ksp == 640 && nw == 1 && lean3_on) ? 1 : 0;
-            q.blk_n_pass = std::max(o->n_block_gibbs_iterations, 1);
-            std::vector<int> passes;
-            if (o->perform_block_gibbs)
-                for (int i = 0; i < o->n_block_gibbs_iterations; i++) {
-                    const int b = o->block_gibbs_iterations[i];
-                    if (b >= 0 && b < n_its && std::find(passes.begin(), passes.end(), b) == passes.end()) passes.push_back(b);
-                }
-            std::sort(passes.begin(), passes.end());
-            if (!passes.empty()) {
-                S.blk_rate2.ensure((size_t)C * G); S.blk_where.ensure((size_t)C * G);
-                S.blk_tab.ensure((size_t)C * 4 * G); S.blk_n.ensure(C);
-                q.blk_rate2 = S.blk_rate2.p; q.blk_where = S.blk_where.p; q.blk_tab = S.blk_tab.p; q.blk_n = S.blk_n.p;
-            }
-            std::vector<double> rate2;
-            std::vector<int32_t> h_where, h_tab, h_n;
-            int it0 = 0;
-            q.rebuild = 0;
-            for (size_t j = 0; j < passes.size(); j++) {
-                q.it_begin = it0; q.it_end = passes[j] + 1;
-                qa::launch_gibbs3(&q, st);
-                q.rebuild = 1;   // (what follows a block pass starts by re-forming the state from its labels)
-                qa::launch_block_rate3(&q, st);
-                rate2.resize((size_t)C * G);
-                S.blk_rate2.download(rate2.data(), rate2.size(), st);
-                std::vector<int32_t> seg_status(C);
-                S.status.download(seg_status.data(), C, st);
-                QA_HIP(hipStreamSynchronize(st));
-                const double tg0 = now();
-                h_where.assign((size_t)C * G, -1); h_tab.assign((size_t)C * 4 * G, 0); h_n.assign(C, 0);
-                const int n_thr = std::max(1, std::min<int>(qa::host_threads_cap(), C));
-                auto work = [&](int tid) {
-                    for (int c = tid; c < C; c += n_thr) {
-                        const int R = read_off[c + 1] - read_off[c];
-                        if (seg_status[c] != 0 || R < 1) continue;   // underflowed chain: stopped, the caller retries it
-                        const std::vector<int32_t> blocked = qa::define_blocked_grids(
-                            rate2.data() + (size_t)c * G, o->L_grid, G, o->shuffle_bin_radius, o->block_gibbs_quantile_prob);
-                        const qa::BlockTable T = qa::make_gibbs_considers(blocked, wif + read_off[c], R);
-                        h_n[c] = T.n_blocks;
-                        std::copy(T.grid_where.begin(), T.grid_where.end(), h_where.begin() + (size_t)c * G);
-                        int32_t *tb = h_tab.data() + (size_t)c * 4 * G;
-                        for (int b = 0; b < T.n_blocks; b++) {
-                            tb[b] = T.grid_start[b]; tb[G + b] = T.grid_end[b];
-                            tb[2 * G + b] = T.reads_start[b]; tb[3 * G + b] = T.reads_end[b];
-                        }
-                    }
-                };
-                std::vector<std::thread> th;
-                for (int i = 1; i < n_thr; i++) th.emplace_back(work, i);
-                work(0);
-                for (auto &t : th) t.join();
-                const double tg1 = now();
-                S.blk_where.upload(h_where.data(), h_where.size(), st);
-                S.blk_tab.upload(h_tab.data(), h_tab.size(), st);
-                S.blk_n.upload(h_n.data(), h_n.size(), st);
-                q.blk_pass = (int)j;
-                // opts->draw_uniforms: the pass's uniforms come from the caller WHEN THE REFERENCE DRAWS THEM -- runif_block now
-                // (gibbs-nipt.cpp:3016), the per-read re-draws after the relabelling, one for every read whose class leaves a choice, in
-                // read order (rcpp_sample_H_using_H_class, gibbs-nipt-block.cpp:213-246): an R caller's stream then stays in step
-                // with the CPU package's.  Chain by chain, from this (the calling) thread.
-                const bool draw_cb = o->draw_uniforms != nullptr;
-                q.defer_resample = draw_cb ? 1 : 0;
-                std::vector<double> ub;
-                if (draw_cb) {
-                    for (int c = 0; c < C; c++) {
-                        const int R = read_off[c + 1] - read_off[c];
-                        if (R < 1) continue;
-                        ub.assign((size_t)R, 0.0);
-                        o->draw_uniforms(o->draw_uniforms_ctx, per_it_off + c, (int)j, 0, R, ub.data());
-                        qa::staged_upload(S.runif_shard.p + ((size_t)read_off[c] * q.blk_n_pass + (size_t)j * R) * 2, ub.data(), sizeof(double) * (size_t)R, st);
-                    }
-                }
-                qa::launch_block3(&q, st);
-                if (draw_cb) {
-                    std::vector<int32_t> hc((size_t)std::max(totR, 1));
-                    S.H_class.download(hc.data(), totR, st);
-                    QA_HIP(hipStreamSynchronize(st));
-                    std::vector<double> draws;
-                    for (int c = 0; c < C; c++) {
-                        const int R = read_off[c + 1] - read_off[c];
-                        if (R < 1 || seg_status[c] != 0) continue;
-                        const int32_t *h = hc.data() + read_off[c];
-                        int n = 0;
-                        for (int r = 0; r < R; r++) n += !(h[r] >= 1 && h[r] <= 3);
-                        draws.assign((size_t)std::max(n, 1), 0.0);
-                        if (n > 0) o->draw_uniforms(o->draw_uniforms_ctx, per_it_off + c, (int)j, 1, n, draws.data());
-                        ub.assign((size_t)R, 0.0);
-                        for (int r = 0, k = 0; r < R; r++)
-                            if (!(h[r] >= 1 && h[r] <= 3)) ub[(size_t)r] = draws[(size_t)k++];
-                        qa::staged_upload(S.runif_shard.p + ((size_t)read_off[c] * q.blk_n_pass + (size_t)j * R) * 2 + R, ub.data(), sizeof(double) * (size_t)R, st);
-                    }
-                    qa::launch_resample3(&q, st);
-                }
-                if (tmg) fprintf(stderr, "[qa_gibbs C=%d] block pass %d: device idle for the host's block tables %.1f ms (tables %.1f on %d threads, uploads enqueued %.1f)\n",
-                                 C, (int)j, (now() - tg0) * 1e3, (tg1 - tg0) * 1e3, n_thr, (now() - tg1) * 1e3);
-                it0 = passes[j] + 1;
-            }
-            if (passes.empty() || it0 < n_its || q.rebuild) {   // (also with no sweeps left: the rebuild after the last pass)
-                q.it_begin = it0; q.it_end = n_its;
-                qa::launch_gibbs3(&q, st);
-            }
-        };
-        launch_gibbs(prm, maxR, st, g_gibbs->ev, want_probs, nw, nipt_sweeps);
-        S.H.download(H, totR, st);
-        if (H_class) S.H_class.download(H_class, totR, st);
-        if (o->per_it_out) S.per_it.download(o->per_it_out + (size_t)per_it_off * n_its * 8, (size_t)C * n_its * 8, st);
-        std::vector<int32_t> status(C);
-        S.status.download(status.data(), C, st);
-        QA_HIP(hipStreamSynchronize(st));
-        const double T3 = now();
-        hold.mark();
-        if (hapProbs_t) S.hap.download(hapProbs_t, (size_t)C * T * 3, st);
-        if (o->hap_words_out) {   // (the genotype-probability buffers are free by now: the words are staged in S.gm)
-            int32_t *d_words = reinterpret_cast<int32_t *>(S.gm.p);
-            hipLaunchKernelGGL(k_pack_hap_words, dim3((G + 255) / 256, 3, C), dim3(256), 0, st, S.hap.p, T, G, d_words);
-            QA_HIP(hipGetLastError());
-            if (genProbsM_t) throw std::runtime_error("hap_words_out cannot be combined with genProbs outputs");
-            qa::staged_download(o->hap_words_out + (size_t)per_it_off * 3 * G, d_words, sizeof(int32_t) * (size_t)C * 3 * G, st);
-        }
-        if (o->hap_major_out) {   // (staged in the free S.gf: label-major rows, then one transfer)
-            const int nL = o->hap_major_labels;
-            if (genProbsF_t || nL < 1 || nL > 3) throw std::runtime_error("hap_major_out: 1..3 labels, not combined with genProbs outputs");
-            hipLaunchKernelGGL(k_hap_major, dim3((T + 255) / 256, C), dim3(256), 0, st, S.hap.p, T, nL, S.gf.p);
-            QA_HIP(hipGetLastError());
-            qa::staged_download(o->hap_major_out + (size_t)per_it_off * nL * T, S.gf.p, sizeof(double) * (size_t)C * nL * T, st);
-        }
-        if (genProbsM_t) S.gm.download(genProbsM_t, (size_t)C * T * 3, st);
-        if (genProbsF_t) S.gf.download(genProbsF_t, (size_t)C * T * 3, st);
-        QA_HIP(hipStreamSynchronize(st));
-        if (!(state_out && C == 1)) hold.release();
-        {
-            float ms[3];
-            for (int i = 0; i < 3; i++) QA_HIP(hipEventElapsedTime(&ms[i], g_gibbs->ev[i], g_gibbs->ev[i + 1]));
-            // algorithmic bytes: per sweep and label 6 column streams of Ks x G fp64, plus every
-            // read's emission column once per sweep; initialisation and each shard pass ~ one sweep without reads
-            const double col = 2.0 * Ks * (double)G * 48.0;
-            const double sweeps = (double)n_its * (C * col + (double)totR * Ks * 8.0) +
-                                  (1.0 + 2.0 * prm.n_block) * C * col;
-            const double t_e = qa::profile_clock_ms(g_gibbs->ev[0]);
-            // work units: read visits + grid steps over all chains; serial: those of the longest chain (the launch's
-            // critical path: sweeps, initial forward / backward, shard or block passes)
-            const double passes = (double)n_its + 1.0 + 2.0 * prm.n_block;
-            const double units = (double)n_its * totR + passes * (double)C * G;
-            const double serial = (double)n_its * maxR + passes * (double)G;
-            qa::profile_add(qa::PK_EMATREAD, ms[0], (double)totR * Ks * 8.0, t_e);
-            qa::profile_add(nH == 3 ? qa::PK_GIBBS3 : ((Ksp / 64 == 10 && nw == 1 && use_lean_build(C)) ? qa::PK_GIBBS_LEAN : qa::PK_GIBBS), ms[1],
-                            sweeps * (nH / 2.0), t_e + ms[0], units, serial, (double)C);
-            if (want_probs) qa::profile_add(qa::PK_HAPPROBS, ms[2], C * (double)nH * Ks * (double)G * 16.0, t_e + ms[0] + ms[1]);
-            if (tmg)
-                fprintf(stderr, "[qa_gibbs C=%d] host prep %.3f s, tables+uploads %.3f s (of which queued for the device %.3f s), kernels %.3f s (events %.3f), downloads %.3f s\n", C,
-                        T1 - T0, T2 - T1, T1g - hold_t0, T3 - T2, (ms[0] + ms[1] + ms[2]) / 1e3, now() - T3);
-        }
-        int ret = QA_OK;
-        for (int c = 0; c < C; c++) {
-            if (underflow_problem) underflow_problem[c] = status[c];
-            if (status[c]) ret = QA_UNDERFLOW;
-        }
-        if (state_out && C == 1) {
-            // debugging / test aid: alpha, beta, eMatGrid of both labels ([6][G][Ks]) then c ([3][G])
-            std::vector<double> tmp((size_t)G * Ksp);
-            const qa::ABuf<double> *src[3] = {&S.alpha, &S.beta, &S.eg};
-            size_t o2 = 0;
-            for (int m = 0; m < 3; m++)
-                for (int h = 0; h < 2; h++) {
-                    QA_HIP(hipMemcpy(tmp.data(), src[m]->p + (size_t)h * G * Ksp, sizeof(double) * tmp.size(),
-                                     hipMemcpyDeviceToHost));
-                    for (int g = 0; g < G; g++)
-                        for (int k = 0; k < Ks; k++) state_out[o2 + (size_t)g * Ks + k] = tmp[(size_t)g * Ksp + k];
-                    o2 += (size_t)G * Ks;
-                }
-            QA_HIP(hipMemcpy(state_out + o2, S.cvec.p, sizeof(double) * 3 * G, hipMemcpyDeviceToHost));
-        }
-        return ret;
+// The one place where a call's arrays are cut for a launch.  base_of[c]: where chain c's bases start in the call's u / bq;
+// G, T: grids and SNPs of the form the call runs in (all SNPs with a qa_rare_common).
+GibbsLaunch launch_slice(const GibbsCall &a, const qa_gibbs_opts_t *o, const std::vector<size_t> &base_of, int G, int T, int c0, int c1) {
+    GibbsLaunch L;
+    L.c0 = c0; L.C = c1 - c0;
+    const size_t chain0 = (size_t)c0, read0 = (size_t)a.read_off[c0], base0 = base_of[chain0];
+    const size_t n_its = (size_t)(o->n_gibbs_burn_in_its + o->n_gibbs_sample_its), nb = (size_t)o->n_block_gibbs_iterations;
+    auto from = [](auto *p, size_t off) { return p ? p + off : nullptr; };   // (an array the caller left out stays left out)
+    // one entry (or one row) per chain
+    L.ff_chain = from(o->ff_chain, chain0);
+    L.rep_id = from(o->reads_same_as, chain0);
+    L.a.which = a.which + chain0 * o->Ks;
+    L.a.first_read = a.first_read + chain0;
+    L.a.underflow_problem = from(a.underflow_problem, chain0);
+    L.a.seed_reads = from(a.seed_reads, chain0);
+    L.a.seed_shard = from(a.seed_shard, chain0);
+    L.a.hapProbs_t = from(a.hapProbs_t, chain0 * T * 3);
+    L.a.genProbsM_t = from(a.genProbsM_t, chain0 * T * 3);
+    L.a.genProbsF_t = from(a.genProbsF_t, chain0 * T * 3);
+    L.a.state_out = a.state_out;   // (filled by a one-chain call only)
+    // one entry per read; read_ptr has one more per chain (every chain's CSR block is R + 1 long and starts at 0)
+    L.read_off.resize((size_t)L.C + 1);
+    for (int i = 0; i <= L.C; i++) L.read_off[(size_t)i] = a.read_off[c0 + i] - a.read_off[c0];
+    L.a.read_off = L.read_off.data();
+    L.a.read_ptr = a.read_ptr + read0 + chain0;
+    L.a.wif = a.wif + read0;
+    L.a.H = a.H + read0;
+    L.a.H_class = from(a.H_class, read0);
+    L.a.runif_reads = from(a.runif_reads, read0 * n_its);
+    // diploid: the shard passes' uniforms, per chain, pass and grid boundary; NIPT: the block passes', two per read and pass
+    // (include/quilt_amd.h)
+    L.a.runif_shard = from(a.runif_shard, o->ff != 0.0 ? read0 * nb * 2 : chain0 * nb * (size_t)(G - 1));
+    // one entry per base
+    L.a.u = a.u + base0;
+    L.a.bq = a.bq + base0;
+    if (o->reads_same_as) {   // the representative may belong to an earlier launch: its bases then lie before base0
+        L.rep_off.resize((size_t)L.C);
+        for (int c = c0; c < c1; c++) L.rep_off[(size_t)(c - c0)] = (int64_t)base_of[(size_t)o->reads_same_as[c]] - (int64_t)base0;
+    }
+    return L;
+}
+
+// One base of the reference's bq == 0 carry-over (see fold_zero_base_qualities): the quality it counts with; |bq| <= 255
+inline int32_t fold_base_quality(int32_t b, int32_t &last) {
+    if (b == 0) b = last; else last = b;
+    if (b > 255 || b < -255) throw std::runtime_error("|base quality| > 255");
+    return b;
+}
+
+// The reference carries pR / pA over bases with bq == 0, even across reads (gibbs-small.cpp:139-181, copied-from-stitch.cpp:139-175):
+// a base without a quality takes the last quality seen in its chain's reads (0 until one is seen).  In place, on one chain's block.
+void fold_zero_base_qualities(const int32_t *rp, int R, int Jmax, int32_t *bq_eff_block) {
+    int32_t last = 0;
+    for (int r = 0; r < R; r++) {
+        int J = rp[r + 1] - rp[r] - 1;
+        if (J >= Jmax) J = Jmax;
+        for (int j = 0; j <= J; j++) bq_eff_block[rp[r] + j] = fold_base_quality(bq_eff_block[rp[r] + j], last);
     }
 }
 
+// The dense-emission calls' qualities: per chain (or sample) its SNP indices checked, its qualities copied and folded, on the call's
+// host threads (the driver's read-confidence call carries every chain of a launch set: 90 M bases, 0.25 s on one thread -- and at
+// the end of a stream nothing runs beside it)
+std::vector<int32_t> checked_folded_qualities(int n, const int32_t *read_off, const int32_t *read_ptr, const int32_t *u, const int32_t *bq,
+                                              const std::vector<int32_t> &base_off, int T, int Jmax) {
+    std::vector<int32_t> bq_eff((size_t)std::max(base_off[n], 1));
+    qa::parallel_for((size_t)n, qa::host_threads(), [&](size_t c) {
+        const int R = read_off[c + 1] - read_off[c];
+        const int32_t *rp = read_ptr + read_off[c] + c;
+        const size_t b0 = (size_t)base_off[c];
+        for (int i = 0; i < rp[R]; i++) {
+            if (u[b0 + i] < 0 || u[b0 + i] >= T) throw std::runtime_error("read SNP index out of range");
+            bq_eff[b0 + i] = bq[b0 + i];
+        }
+        fold_zero_base_qualities(rp, R, Jmax, bq_eff.data() + b0);
+    });
+    return bq_eff;
+}
 
+// What the host works out for one launch before anything is uploaded: sizes, per-chain offsets, the marshalled inputs
+struct ChunkHost {
+    int C, G, T, Ks, Ksp, NE, nH, n_its, nw, er_nt, er_padb, rc_words, totR, totB, maxR = 0;
+    bool want_probs, want_pairs;   // want_pairs: (SNP, row) pairs per chain for k_happrobs_rc (only when the probabilities are asked for)
+    bool aliased = false;          // some chain's bases are another chain's, or lie elsewhere than base_off says
+    size_t etot = 0, ixtot = 0;
+    // bases: per chain the CSR block read_ptr[read_off[c] + c .. read_off[c+1] + c] is local (starts at 0)
+    std::vector<int32_t> base_off, which0, bq_eff, dense_of, n_dense;
+    std::vector<size_t> eoff, ixoff;
+    std::vector<uint8_t> ghr;
+    std::vector<uint32_t> rc_any;
+    // opts->reads_same_as: chains that share their sample's reads.  rep[c] = the first chain OF THIS LAUNCH with chain c's
+    // reads (c itself without the option); only the representatives' bases are looked at and uploaded.
+    std::vector<int32_t> rep;
+    std::vector<int64_t> hbase;   // where a chain's bases are looked at on the host, relative to this launch's u / bq
+};
 
-extern "C" {
+ChunkHost chunk_layout(qa_panel_t *pn, const qa_rare_common *rc, const qa_gibbs_opts_t *o, const GibbsLaunch &L) {
+    ChunkHost h;
+    const int C = h.C = L.C;
+    h.G = rc ? rc->G_all : pn->G; h.T = rc ? rc->T_all : pn->T; h.Ks = o->Ks;
+    h.Ksp = (h.Ks + 63) / 64 * 64; h.NE = h.Ksp / 64;
+    h.nH = o->ff != 0.0 ? 3 : 2;
+    h.rc_words = rc ? (h.T + 31) / 32 : 0;
+    h.n_its = o->n_gibbs_burn_in_its + o->n_gibbs_sample_its;
+    h.totR = L.a.read_off[C];
+    h.want_probs = wants_probs(L.a, o);
+    h.want_pairs = rc && h.want_probs && h.Ks <= 1024;
+    h.nw = o->ff != 0.0 ? qa::gibbs3_waves(h.Ksp, C, pn->sharers()) : choose_gibbs_waves(h.Ksp, C, pn->exclusive ? 0 : pn->share);
+    h.er_nt = 64 * h.nw; h.er_padb = padb_of(h.NE / h.nw);
+    h.rc_any.assign((size_t)C * h.rc_words, 0u);
+    h.base_off.assign(C + 1, 0); h.which0.resize((size_t)C * h.Ks);
+    h.eoff.resize(C); h.ixoff.resize(C);
+    h.ghr.assign((size_t)C * h.G, 0);
+    h.dense_of.assign(std::max(h.totR, 1), -1);
+    h.n_dense.assign(C, 0);
+    for (int c = 0; c < C; c++) {   // offsets first (cheap), then the per-chain passes over the reads in parallel
+        const int R = L.a.read_off[c + 1] - L.a.read_off[c];
+        h.maxR = std::max(h.maxR, R);
+        const int32_t *rp = L.a.read_ptr + L.a.read_off[c] + c;
+        h.base_off[c + 1] = h.base_off[c] + rp[R];
+        h.ixoff[c] = h.ixtot;
+        h.ixtot += (size_t)R * h.er_nt * h.er_padb;
+    }
+    h.totB = h.base_off[C];
+    h.bq_eff.resize((size_t)std::max(h.totB, 1));
+    return h;
+}
 
-static int gibbs_batch_impl(qa_panel_t *pn, const qa_rare_common *rc, const qa_gibbs_opts_t *o, int32_t n_chain,
-                   const int32_t *which_haps_to_use_1based,
-                   const int32_t *read_off, const int32_t *read_ptr, const int32_t *u, const int32_t *bq,
-                   const int32_t *wif, const double *runif_reads, const int32_t *first_read,
-                   const double *runif_shard, int32_t *H, int32_t *H_class, double *hapProbs_t,
-                   double *genProbsM_t, double *genProbsF_t, int32_t *underflow_problem, double *state_out,
-                   const uint64_t *seed_reads, const uint64_t *seed_shard) {
+// fills rep, hbase, aliased
+void find_shared_reads(const GibbsLaunch &L, ChunkHost &h) {
+    const int32_t *read_off = L.a.read_off, *read_ptr = L.a.read_ptr;
+    const auto &base_off = h.base_off;
+    h.rep.resize(h.C); h.hbase.resize(h.C);
+    // keyed on the representative's INDEX in the call (reads_same_as[c]), not on where its bases lie: a chain without
+    // bases has the offset of the chain behind it and would be taken for sharing that chain's reads
+    std::map<int32_t, int32_t> first_of;
+    for (int c = 0; c < h.C; c++) {
+        h.rep[c] = c;
+        h.hbase[c] = L.rep_id ? L.rep_off[c] : (int64_t)base_off[c];
+        if (!L.rep_id) continue;
+        auto it = first_of.find(L.rep_id[c]);
+        if (it == first_of.end()) { first_of.emplace(L.rep_id[c], c); h.aliased |= L.rep_off[c] != (int64_t)base_off[c]; continue; }
+        const int r0 = it->second;
+        const int R = read_off[c + 1] - read_off[c];
+        // the same reads means the same read boundaries, not just as many reads and bases
+        if (read_off[r0 + 1] - read_off[r0] != R || base_off[r0 + 1] - base_off[r0] != base_off[c + 1] - base_off[c] ||
+            std::memcmp(read_ptr + read_off[r0] + r0, read_ptr + read_off[c] + c, sizeof(int32_t) * ((size_t)R + 1)) != 0)
+            throw std::runtime_error("reads_same_as names a chain with other reads");
+        h.rep[c] = r0;
+        h.aliased = true;
+    }
+}
+
+// Chain c of a launch: validation, grid_has_read, 0-based haplotypes, the bq == 0 carry-over (fold_zero_base_qualities) and the
+// choice of the reads that keep a dense column (more informative bases -- k_ematread skips bq == 0 -- than the
+// pattern width).  Writes chain c's parts of ghr, which0, rc_any, dense_of, n_dense and, when c is a representative, its block
+// of bq_eff; a chain that shares its reads runs after its representative.
+void prepare_chain(const qa_panel_t *pn, const qa_rare_common *rc, const qa_gibbs_opts_t *o, const GibbsLaunch &L, ChunkHost &h, int c) {
+    const int32_t *read_off = L.a.read_off, *wif = L.a.wif;
+    const int G = h.G, T = h.T, Ks = h.Ks, rc_words = h.rc_words;
+    const bool is_rep = h.rep[c] == c;   // (the representatives fold their base qualities in place)
+    const int R = read_off[c + 1] - read_off[c];
+    const int32_t *rp = L.a.read_ptr + read_off[c] + c;
+    const int64_t hb = h.hbase[c];          // where this chain's bases are looked at (u, bq)
+    int32_t *bq_eff = h.bq_eff.data() + (size_t)h.base_off[h.rep[c]];   // the representative's block of bq_eff
+    if (is_rep) std::memcpy(bq_eff, L.a.bq + hb, sizeof(int32_t) * (size_t)(h.base_off[c + 1] - h.base_off[c]));
+    for (int r = 0; r < R; r++) {
+        const int g = wif[read_off[c] + r];
+        if (g < 0 || g >= G) throw std::runtime_error("read grid index out of range");
+        if (r > 0 && g < wif[read_off[c] + r - 1]) throw std::runtime_error("reads must be sorted by grid");
+        h.ghr[(size_t)c * G + g] = 1;
+    }
+    for (int k = 0; k < Ks; k++) {
+        const int v = L.a.which[(size_t)c * Ks + k] - 1;
+        if (v < 0 || v >= pn->K) throw std::runtime_error("which_haps_to_use out of range");
+        h.which0[(size_t)c * Ks + k] = v;
+        if (rc)   // rare SNPs some selected haplotype carries the alt of (rare_per_snp_info, rare_common.R:313-322)
+            for (int64_t i = rc->h_rare_ptr[v]; i < rc->h_rare_ptr[v + 1]; i++) {
+                const int t = rc->h_rare_snp[i];
+                h.rc_any[(size_t)c * rc_words + (t >> 5)] |= 1u << (t & 31);
+            }
+    }
+    // (the fold goes base by base here: it shares its pass over the bases -- 90 M per launch set -- with the informative-base count)
+    const int32_t *cu = L.a.u + hb;
+    int32_t last = 0;
+    int nd = 0;
+    for (int r = 0; r < R; r++) {
+        int J = rp[r + 1] - rp[r] - 1;
+        if (J >= o->Jmax) J = o->Jmax;
+        int n_inf = 0;
+        for (int j = 0; j <= J; j++) {
+            const int32_t b = fold_base_quality(bq_eff[rp[r] + j], last);
+            if (is_rep) bq_eff[rp[r] + j] = b;   // (a sharing chain reads the folded values: folding them again changes nothing)
+            const int t = cu[rp[r] + j];
+            if (t < 0 || t >= T) throw std::runtime_error("read SNP index out of range");
+            // a rare SNP nobody selected carries is a common factor: no pattern bit (k_ematread)
+            const bool informative = !rc || rc->h_common_index[t] >= 0 ||
+                                     ((h.rc_any[(size_t)c * rc_words + (t >> 5)] >> (t & 31)) & 1u);
+            n_inf += (b != 0) && informative;
+        }
+        if (n_inf > kMaxPatternBits) h.dense_of[read_off[c] + r] = nd++;
+    }
+    h.n_dense[c] = nd;
+}
+
+// independent per chain, spread over host threads: the representatives first, then the chains that share a representative's reads
+void prepare_chains(const qa_panel_t *pn, const qa_rare_common *rc, const qa_gibbs_opts_t *o, const GibbsLaunch &L, ChunkHost &h) {
+    const int n_thr = qa::host_threads();
+    qa::parallel_for((size_t)h.C, n_thr, [&](size_t c) { if (h.rep[c] == (int)c) prepare_chain(pn, rc, o, L, h, (int)c); });
+    if (h.aliased) qa::parallel_for((size_t)h.C, n_thr, [&](size_t c) { if (h.rep[c] != (int)c) prepare_chain(pn, rc, o, L, h, (int)c); });
+    for (int c = 0; c < h.C; c++) {
+        h.eoff[c] = h.etot;
+        h.etot += (size_t)h.n_dense[c] * h.Ksp;
+    }
+}
+
+// the launch's inputs into this thread's own device buffers
+void upload_inputs(qa::GibbsScratch &S, const qa_panel_t *pn, const qa_rare_common *rc, const qa_gibbs_opts_t *o, const GibbsLaunch &L,
+                   const ChunkHost &h, hipStream_t st) {
+    const GibbsCall &a = L.a;
+    const int C = h.C, G = h.G, totR = h.totR, totB = h.totB;
+    const std::vector<double> tabs = base_quality_tables();
+    std::vector<double> tm((size_t)2 * std::max(G - 1, 1));
+    for (int g = 0; g < G - 1; g++) {
+        tm[g] = rc ? rc->h_sigma[g] : pn->h_sigma[g];
+        tm[(size_t)G - 1 + g] = rc ? rc->h_tm1[g] : pn->h_tm1[g];
+    }
+
+    S.which.ensure(h.which0.size()); S.which.upload(h.which0.data(), h.which0.size(), st);
+    S.read_off.ensure(C + 1); S.read_off.upload(a.read_off, C + 1, st);
+    S.read_ptr.ensure(totR + C); S.read_ptr.upload(a.read_ptr, totR + C, st);
+    if (!h.aliased) {
+        S.base_off.ensure(C + 1); S.base_off.upload(h.base_off.data(), C + 1, st);
+        S.u.ensure(std::max(totB, 1)); S.u.upload(a.u, totB, st);
+        S.bq.ensure(std::max(totB, 1)); S.bq.upload(h.bq_eff.data(), totB, st);
+    } else {
+        // the representatives' bases back to back; every chain's device offset is its representative's (the kernels take
+        // base_off[c] as the start of the chain's bases and nothing else)
+        std::vector<int32_t> dev_off(C + 1, 0), cu_h, cb_h;
+        int at = 0;
+        for (int c = 0; c < C; c++)
+            if (h.rep[c] == c) { dev_off[c] = at; at += h.base_off[c + 1] - h.base_off[c]; }
+        for (int c = 0; c < C; c++) dev_off[c] = dev_off[h.rep[c]];
+        dev_off[C] = at;
+        cu_h.resize((size_t)std::max(at, 1)); cb_h.resize((size_t)std::max(at, 1));
+        for (int c = 0; c < C; c++)
+            if (h.rep[c] == c) {
+                const size_t nb_c = (size_t)(h.base_off[c + 1] - h.base_off[c]);
+                std::memcpy(&cu_h[(size_t)dev_off[c]], a.u + h.hbase[c], sizeof(int32_t) * nb_c);
+                std::memcpy(&cb_h[(size_t)dev_off[c]], &h.bq_eff[(size_t)h.base_off[c]], sizeof(int32_t) * nb_c);
+            }
+        S.base_off.ensure(C + 1); S.base_off.upload(dev_off.data(), C + 1, st);
+        S.u.ensure(std::max(at, 1)); S.u.upload(cu_h.data(), at, st);
+        S.bq.ensure(std::max(at, 1)); S.bq.upload(cb_h.data(), at, st);
+    }
+    S.wif.ensure(std::max(totR, 1)); S.wif.upload(a.wif, totR, st);
+    S.ghr.ensure(h.ghr.size()); S.ghr.upload(h.ghr.data(), h.ghr.size(), st);
+    S.tabs.ensure(tabs.size()); S.tabs.upload(tabs.data(), tabs.size(), st);
+    S.tm.ensure(tm.size()); S.tm.upload(tm.data(), tm.size(), st);
+    S.block_its.ensure(std::max(o->n_block_gibbs_iterations, 1));
+    S.block_its.upload(o->block_gibbs_iterations, o->n_block_gibbs_iterations, st);
+    S.first_read.ensure(C); S.first_read.upload(a.first_read, C, st);
+    if (!a.seed_reads) {
+        S.runif_reads.ensure(std::max<size_t>((size_t)totR * h.n_its, 1));
+        S.runif_reads.upload(a.runif_reads, (size_t)totR * h.n_its, st);
+    } else {
+        S.runif_reads.ensure(1);
+        S.seeds.ensure((size_t)2 * C);
+        S.seeds.upload(a.seed_reads, C, st);
+        qa::staged_upload(S.seeds.p + C, a.seed_shard ? a.seed_shard : a.seed_reads, sizeof(uint64_t) * C, st);
+    }
+    // diploid: the shard passes' uniforms; NIPT: the block passes' (include/quilt_amd.h)
+    const bool nipt = o->ff != 0.0;
+    const size_t nshard_used = nipt ? (size_t)totR * o->n_block_gibbs_iterations * 2
+                                    : (size_t)C * o->n_block_gibbs_iterations * (G - 1);
+    S.runif_shard.ensure(std::max<size_t>(nshard_used, 1));
+    // (read only when a pass will draw from it: a caller that switches the passes off may hand over anything -- an array
+    // shorter than the passes would need was read past its end here until round 6: found by AddressSanitizer on the host code)
+    if (a.runif_shard && !a.seed_shard && o->n_block_gibbs_iterations > 0 && o->perform_block_gibbs && (nipt || o->do_shard_block_gibbs))
+        S.runif_shard.upload(a.runif_shard, nshard_used, st);
+    S.eread_off.ensure(C); S.eread_off.upload(h.eoff.data(), C, st);
+    S.eridx_off.ensure(C); S.eridx_off.upload(h.ixoff.data(), C, st);
+    S.dense_of.ensure(h.dense_of.size()); S.dense_of.upload(h.dense_of.data(), h.dense_of.size(), st);
+    S.is_cat1.ensure(std::max(totR, 1));
+    S.er_nent.ensure(std::max(totR, 1));
+    S.H.ensure(std::max(totR, 1)); S.H.upload(a.H, totR, st);
+    S.H_class.ensure(std::max(totR, 1));
+    S.status.ensure(C);
+    if (o->per_it_out) S.per_it.ensure((size_t)C * h.n_its * 8);
+    if (L.ff_chain) { S.ff_chain.ensure(C); S.ff_chain.upload(L.ff_chain, C, st); }
+    if (rc) { S.rc_any.ensure(std::max<size_t>(h.rc_any.size(), 1)); S.rc_any.upload(h.rc_any.data(), h.rc_any.size(), st); }
+}
+
+// (SNP, row) pairs per chain for k_happrobs_rc: built over host threads, uploaded
+void upload_rare_pairs(qa::GibbsScratch &S, const qa_rare_common *rc, const ChunkHost &h, hipStream_t st) {
+    const int C = h.C, G = h.G, Ks = h.Ks;
+    std::vector<size_t> pbase((size_t)C + 1, 0);
+    std::vector<std::vector<uint32_t>> keys((size_t)C);   // SNP << 10 | row, sorted
+    qa::parallel_for((size_t)C, qa::host_threads(), [&](size_t c) {
+        auto &kv = keys[c];
+        for (int k = 0; k < Ks; k++) {
+            const int v = h.which0[c * Ks + k];
+            for (int64_t i = rc->h_rare_ptr[v]; i < rc->h_rare_ptr[v + 1]; i++) kv.push_back(((uint32_t)rc->h_rare_snp[i] << 10) | (uint32_t)k);
+        }
+        std::sort(kv.begin(), kv.end());
+    });
+    for (int c = 0; c < C; c++) pbase[(size_t)c + 1] = pbase[(size_t)c] + keys[(size_t)c].size();
+    std::vector<uint16_t> pairs(std::max<size_t>(pbase[(size_t)C], 1));
+    std::vector<int32_t> poff((size_t)C * (G + 1), 0);
+    for (int c = 0; c < C; c++) {
+        const auto &kv = keys[(size_t)c];
+        int32_t *po = poff.data() + (size_t)c * (G + 1);
+        size_t i = 0;
+        for (int g = 0; g < G; g++) {
+            po[g] = (int32_t)i;
+            while (i < kv.size() && (int)((kv[i] >> 10) >> 5) == g) {
+                pairs[pbase[(size_t)c] + i] = (uint16_t)((((kv[i] >> 10) & 31u) << 10) | (kv[i] & 1023u));
+                i++;
+            }
+        }
+        po[G] = (int32_t)i;
+    }
+    S.rc_pairs.ensure(pairs.size()); S.rc_pairs.upload(pairs.data(), pairs.size(), st);
+    S.rc_pair_off.ensure(poff.size()); S.rc_pair_off.upload(poff.data(), poff.size(), st);
+    S.rc_pair_base.ensure((size_t)C); S.rc_pair_base.upload(pbase.data(), (size_t)C, st);
+}
+
+// the launch's working set, carved from the arena the gate handed over
+void carve_arena(qa::GibbsScratch &S, qa::Arena &arena, size_t arena_need, const ChunkHost &h) {
+    const size_t mat = (size_t)h.C * h.nH * h.G * h.Ksp;
+    S.er_idx.arena = S.er_tab.arena = &arena;
+    S.eMatRead.arena = S.alpha.arena = S.beta.arena = S.eg.arena = S.cvec.arena = S.hap.arena = S.gm.arena = S.gf.arena = &arena;
+    arena.require(arena_need);
+    arena.reset();
+    S.eMatRead.ensure(std::max<size_t>(h.etot, 1));
+    S.er_idx.ensure(std::max<size_t>(h.ixtot, 1));
+    S.er_tab.ensure(std::max<size_t>((size_t)h.totR * 64, 1));
+    S.alpha.ensure(mat); S.beta.ensure(mat); S.eg.ensure(mat);
+    S.cvec.ensure((size_t)h.C * 3 * h.G);
+    if (h.want_probs) {
+        S.hap.ensure((size_t)h.C * h.T * 3); S.gm.ensure((size_t)h.C * h.T * 3); S.gf.ensure((size_t)h.C * h.T * 3);
+    }
+}
+
+GibbsParams fill_params(const qa::GibbsScratch &S, const qa_panel_t *pn, const qa_rare_common *rc, const qa_gibbs_opts_t *o,
+                        const GibbsLaunch &L, const ChunkHost &h, hipStream_t st) {
+    const int C = h.C;
+    GibbsParams prm{};
+    prm.hm = pn->hm.p; prm.B = pn->B.p; prm.sp_off = pn->sp_off.p; prm.sp_k = pn->sp_k.p;
+    prm.sp_word = pn->sp_word.p; prm.sigma = S.tm.p; prm.Kp = pn->Kp; prm.G = h.G; prm.T = h.T;
+    prm.nMaxDH = pn->nMaxDH; prm.ref_error = pn->ref_error;
+    prm.C = C; prm.Ks = h.Ks; prm.Ksp = h.Ksp; prm.NE = h.NE; prm.which = S.which.p;
+    prm.read_off = S.read_off.p; prm.read_ptr = S.read_ptr.p; prm.base_off = S.base_off.p;
+    prm.u = S.u.p; prm.bq = S.bq.p; prm.wif = S.wif.p; prm.grid_has_read = S.ghr.p;
+    prm.pR_tab = S.tabs.p; prm.pA_tab = S.tabs.p + 512;
+    prm.Jmax = o->Jmax; prm.inv_maxdiff = 1 / o->maxDifferenceBetweenReads; prm.rescale = o->rescale_eMatRead_t;
+    prm.n_its = h.n_its; prm.n_burn_in = o->n_gibbs_burn_in_its; prm.block_its = S.block_its.p;
+    prm.n_block = o->perform_block_gibbs ? o->n_block_gibbs_iterations : 0;
+    prm.do_shard = o->do_shard_block_gibbs; prm.init_iteratively = o->gibbs_initialize_iteratively;
+    prm.disable_read_category_usage = o->disable_read_category_usage;
+    prm.class_sum_cutoff = o->class_sum_cutoff;
+    prm.nH = h.nH;
+    prm.it_begin = 0; prm.it_end = h.n_its;
+    prm.ff = o->ff;
+    if (o->per_it_out) {
+        QA_HIP(hipMemsetAsync(S.per_it.p, 0, sizeof(double) * C * h.n_its * 8, st));
+        prm.per_it = S.per_it.p;
+    }
+    if (L.ff_chain) prm.ff_chain = S.ff_chain.p;
+    prm.runif_reads = S.runif_reads.p; prm.first_read = S.first_read.p; prm.runif_shard = S.runif_shard.p;
+    prm.seed_reads = L.a.seed_reads ? S.seeds.p : nullptr;
+    prm.seed_shard = (L.a.seed_reads && L.a.seed_shard) ? S.seeds.p + C : nullptr;
+    prm.eMatRead = S.eMatRead.p; prm.eread_off = S.eread_off.p; prm.is_cat1 = S.is_cat1.p; prm.er_nent = S.er_nent.p;
+    prm.er_idx = S.er_idx.p; prm.eridx_off = S.eridx_off.p; prm.er_tab = S.er_tab.p; prm.dense_of = S.dense_of.p;
+    prm.er_nt = h.er_nt; prm.er_padb = h.er_padb;
+    prm.alpha = S.alpha.p; prm.beta = S.beta.p; prm.eg = S.eg.p; prm.cvec = S.cvec.p;
+    prm.H = S.H.p; prm.H_class = S.H_class.p; prm.status = S.status.p;
+    prm.hapProbs = S.hap.p; prm.genProbsM = S.gm.p; prm.genProbsF = S.gf.p;
+    if (rc) {
+        prm.rc_common = rc->common_index.p; prm.rc_rare_ptr = rc->rare_ptr.p; prm.rc_rare_snp = rc->rare_snp.p;
+        prm.rc_any = S.rc_any.p; prm.rc_words = h.rc_words; prm.rc_Gc = pn->G;
+        if (h.want_pairs) { prm.rc_pairs = S.rc_pairs.p; prm.rc_pair_off = S.rc_pair_off.p; prm.rc_pair_base = S.rc_pair_base.p; }
+    }
+    return prm;
+}
+
+// The block tables of one NIPT block pass from the switch rates the device sent back (rate2, and the chains' statuses): chains
+// over n_thr host threads
+void nipt_block_tables(const qa_gibbs_opts_t *o, const GibbsLaunch &L, const ChunkHost &h, const std::vector<double> &rate2,
+                       const std::vector<int32_t> &seg_status, int n_thr, std::vector<int32_t> &h_where, std::vector<int32_t> &h_tab,
+                       std::vector<int32_t> &h_n) {
+    const int C = h.C, G = h.G;
+    const int32_t *read_off = L.a.read_off;
+    h_where.assign((size_t)C * G, -1); h_tab.assign((size_t)C * 4 * G, 0); h_n.assign(C, 0);
+    qa::parallel_for((size_t)C, n_thr, [&](size_t c) {
+        const int R = read_off[c + 1] - read_off[c];
+        if (seg_status[c] != 0 || R < 1) return;   // underflowed chain: stopped, the caller retries it
+        const std::vector<int32_t> blocked = qa::define_blocked_grids(
+            rate2.data() + c * G, o->L_grid, G, o->shuffle_bin_radius, o->block_gibbs_quantile_prob);
+        const qa::BlockTable T = qa::make_gibbs_considers(blocked, L.a.wif + read_off[c], R);
+        h_n[c] = T.n_blocks;
+        std::copy(T.grid_where.begin(), T.grid_where.end(), h_where.begin() + c * G);
+        int32_t *tb = h_tab.data() + c * 4 * G;
+        for (int b = 0; b < T.n_blocks; b++) {
+            tb[b] = T.grid_start[b]; tb[G + b] = T.grid_end[b];
+            tb[2 * G + b] = T.reads_start[b]; tb[3 * G + b] = T.reads_end[b];
+        }
+    });
+}
+
+// NIPT: the sweeps are cut at the block-Gibbs iterations; between two segments the switch rate per grid boundary
+// comes back to the host, which defines the blocks (scalar logic per chain, gibbs_blocks.hpp) for the block kernel
+void nipt_sweeps(const GibbsParams &prm, qa::GibbsScratch &S, const qa_gibbs_opts_t *o, const GibbsLaunch &L, const ChunkHost &h,
+                 hipStream_t st, bool tmg) {
+    const int C = h.C, G = h.G, totR = h.totR, n_its = h.n_its;
+    const int32_t *read_off = L.a.read_off;
+    GibbsParams q = prm;
+    q.ff = o->ff;
+    // The three-label sampler's 256-register build (two chains per SIMD, gibbs3.hip) is built and tested but NOT chosen by
+    // default: alone on the device 1 792 chains take 2.33-2.58 s in it against 2 x 1.24 s for two launches of 896 at one
+    // chain per SIMD -- a sweep's grid steps are HBM-bound either way (5.6 TB/s) and the read visits, which two waves per
+    // SIMD should overlap, pay for eMatGrid's trips through LDS and ~600 bytes of scratch per lane.
+    // QA_GIBBS3_LEAN=1 selects it (tests, measurements).
+    const char *lean3_env = getenv("QA_GIBBS3_LEAN");   // (read per call: the tests switch it inside one process)
+    const bool lean3_on = lean3_env && atoi(lean3_env) != 0;
+    q.lean3 = (h.Ksp == 640 && h.nw == 1 && lean3_on) ? 1 : 0;
+    q.blk_n_pass = std::max(o->n_block_gibbs_iterations, 1);
+    std::vector<int> passes;
+    if (o->perform_block_gibbs)
+        for (int i = 0; i < o->n_block_gibbs_iterations; i++) {
+            const int b = o->block_gibbs_iterations[i];
+            if (b >= 0 && b < n_its && std::find(passes.begin(), passes.end(), b) == passes.end()) passes.push_back(b);
+        }
+    std::sort(passes.begin(), passes.end());
+    if (!passes.empty()) {
+        S.blk_rate2.ensure((size_t)C * G); S.blk_where.ensure((size_t)C * G);
+        S.blk_tab.ensure((size_t)C * 4 * G); S.blk_n.ensure(C);
+        q.blk_rate2 = S.blk_rate2.p; q.blk_where = S.blk_where.p; q.blk_tab = S.blk_tab.p; q.blk_n = S.blk_n.p;
+    }
+    std::vector<double> rate2;
+    std::vector<int32_t> h_where, h_tab, h_n;
+    int it0 = 0;
+    q.rebuild = 0;
+    for (size_t j = 0; j < passes.size(); j++) {
+        q.it_begin = it0; q.it_end = passes[j] + 1;
+        qa::launch_gibbs3(&q, st);
+        q.rebuild = 1;   // (what follows a block pass starts by re-forming the state from its labels)
+        qa::launch_block_rate3(&q, st);
+        rate2.resize((size_t)C * G);
+        S.blk_rate2.download(rate2.data(), rate2.size(), st);
+        std::vector<int32_t> seg_status(C);
+        S.status.download(seg_status.data(), C, st);
+        QA_HIP(hipStreamSynchronize(st));
+        const double tg0 = now_s();
+        const int n_thr = std::max(1, std::min<int>(qa::host_threads(), C));
+        nipt_block_tables(o, L, h, rate2, seg_status, n_thr, h_where, h_tab, h_n);
+        const double tg1 = now_s();
+        S.blk_where.upload(h_where.data(), h_where.size(), st);
+        S.blk_tab.upload(h_tab.data(), h_tab.size(), st);
+        S.blk_n.upload(h_n.data(), h_n.size(), st);
+        q.blk_pass = (int)j;
+        // opts->draw_uniforms: the pass's uniforms come from the caller WHEN THE REFERENCE DRAWS THEM -- runif_block now
+        // (gibbs-nipt.cpp:3016), the per-read re-draws after the relabelling, one for every read whose class leaves a choice, in
+        // read order (rcpp_sample_H_using_H_class, gibbs-nipt-block.cpp:213-246): an R caller's stream then stays in step
+        // with the CPU package's.  Chain by chain, from this (the calling) thread.
+        const bool draw_cb = o->draw_uniforms != nullptr;
+        q.defer_resample = draw_cb ? 1 : 0;
+        std::vector<double> ub;
+        if (draw_cb) {
+            for (int c = 0; c < C; c++) {
+                const int R = read_off[c + 1] - read_off[c];
+                if (R < 1) continue;
+                ub.assign((size_t)R, 0.0);
+                o->draw_uniforms(o->draw_uniforms_ctx, L.c0 + c, (int)j, 0, R, ub.data());
+                qa::staged_upload(S.runif_shard.p + ((size_t)read_off[c] * q.blk_n_pass + (size_t)j * R) * 2, ub.data(), sizeof(double) * (size_t)R, st);
+            }
+        }
+        qa::launch_block3(&q, st);
+        if (draw_cb) {
+            std::vector<int32_t> hc((size_t)std::max(totR, 1));
+            S.H_class.download(hc.data(), totR, st);
+            QA_HIP(hipStreamSynchronize(st));
+            std::vector<double> draws;
+            for (int c = 0; c < C; c++) {
+                const int R = read_off[c + 1] - read_off[c];
+                if (R < 1 || seg_status[c] != 0) continue;
+                const int32_t *hcl = hc.data() + read_off[c];
+                int n = 0;
+                for (int r = 0; r < R; r++) n += !(hcl[r] >= 1 && hcl[r] <= 3);
+                draws.assign((size_t)std::max(n, 1), 0.0);
+                if (n > 0) o->draw_uniforms(o->draw_uniforms_ctx, L.c0 + c, (int)j, 1, n, draws.data());
+                ub.assign((size_t)R, 0.0);
+                for (int r = 0, k = 0; r < R; r++)
+                    if (!(hcl[r] >= 1 && hcl[r] <= 3)) ub[(size_t)r] = draws[(size_t)k++];
+                qa::staged_upload(S.runif_shard.p + ((size_t)read_off[c] * q.blk_n_pass + (size_t)j * R) * 2 + R, ub.data(), sizeof(double) * (size_t)R, st);
+            }
+            qa::launch_resample3(&q, st);
+        }
+        if (tmg) fprintf(stderr, "[qa_gibbs C=%d] block pass %d: device idle for the host's block tables %.1f ms (tables %.1f on %d threads, uploads enqueued %.1f)\n",
+                         C, (int)j, (now_s() - tg0) * 1e3, (tg1 - tg0) * 1e3, n_thr, (now_s() - tg1) * 1e3);
+        it0 = passes[j] + 1;
+    }
+    if (passes.empty() || it0 < n_its || q.rebuild) {   // (also with no sweeps left: the rebuild after the last pass)
+        q.it_begin = it0; q.it_end = n_its;
+        qa::launch_gibbs3(&q, st);
+    }
+}
+
+// labels, per-iteration records and the chains' statuses: what has to be down before the device can be handed on
+std::vector<int32_t> download_labels(qa::GibbsScratch &S, const qa_gibbs_opts_t *o, const GibbsLaunch &L, const ChunkHost &h, hipStream_t st) {
+    S.H.download(L.a.H, h.totR, st);
+    if (L.a.H_class) S.H_class.download(L.a.H_class, h.totR, st);
+    if (o->per_it_out) S.per_it.download(o->per_it_out + (size_t)L.c0 * h.n_its * 8, (size_t)h.C * h.n_its * 8, st);
+    std::vector<int32_t> status(h.C);
+    S.status.download(status.data(), h.C, st);
+    QA_HIP(hipStreamSynchronize(st));
+    return status;
+}
+
+// the probabilities, in the forms the caller asked for
+void download_probs(qa::GibbsScratch &S, const qa_gibbs_opts_t *o, const GibbsLaunch &L, const ChunkHost &h, hipStream_t st) {
+    const GibbsCall &a = L.a;
+    const int C = h.C, G = h.G, T = h.T;
+    if (a.hapProbs_t) S.hap.download(a.hapProbs_t, (size_t)C * T * 3, st);
+    if (o->hap_words_out) {   // (the genotype-probability buffers are free by now: the words are staged in S.gm)
+        int32_t *d_words = reinterpret_cast<int32_t *>(S.gm.p);
+        hipLaunchKernelGGL(k_pack_hap_words, dim3((G + 255) / 256, 3, C), dim3(256), 0, st, S.hap.p, T, G, d_words);
+        QA_HIP(hipGetLastError());
+        if (a.genProbsM_t) throw std::runtime_error("hap_words_out cannot be combined with genProbs outputs");
+        qa::staged_download(o->hap_words_out + (size_t)L.c0 * 3 * G, d_words, sizeof(int32_t) * (size_t)C * 3 * G, st);
+    }
+    if (o->hap_major_out) {   // (staged in the free S.gf: label-major rows, then one transfer)
+        const int nL = o->hap_major_labels;
+        if (a.genProbsF_t || nL < 1 || nL > 3) throw std::runtime_error("hap_major_out: 1..3 labels, not combined with genProbs outputs");
+        hipLaunchKernelGGL(k_hap_major, dim3((T + 255) / 256, C), dim3(256), 0, st, S.hap.p, T, nL, S.gf.p);
+        QA_HIP(hipGetLastError());
+        qa::staged_download(o->hap_major_out + (size_t)L.c0 * nL * T, S.gf.p, sizeof(double) * (size_t)C * nL * T, st);
+    }
+    if (a.genProbsM_t) S.gm.download(a.genProbsM_t, (size_t)C * T * 3, st);
+    if (a.genProbsF_t) S.gf.download(a.genProbsF_t, (size_t)C * T * 3, st);
+    QA_HIP(hipStreamSynchronize(st));
+}
+
+// the launch into the per-kernel accumulators; returns the three kernels' event time in ms
+double profile_launch(hipEvent_t *ev, const ChunkHost &h, int n_block) {
+    const int C = h.C, G = h.G, Ks = h.Ks, nH = h.nH, totR = h.totR, n_its = h.n_its;
+    float ms[3];
+    for (int i = 0; i < 3; i++) QA_HIP(hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]));
+    // algorithmic bytes: per sweep and label 6 column streams of Ks x G fp64, plus every
+    // read's emission column once per sweep; initialisation and each shard pass ~ one sweep without reads
+    const double col = 2.0 * Ks * (double)G * 48.0;
+    const double sweeps = (double)n_its * (C * col + (double)totR * Ks * 8.0) +
+                          (1.0 + 2.0 * n_block) * C * col;
+    const double t_e = qa::profile_clock_ms(ev[0]);
+    // work units: read visits + grid steps over all chains; serial: those of the longest chain (the launch's
+    // critical path: sweeps, initial forward / backward, shard or block passes)
+    const double passes = (double)n_its + 1.0 + 2.0 * n_block;
+    const double units = (double)n_its * totR + passes * (double)C * G;
+    const double serial = (double)n_its * h.maxR + passes * (double)G;
+    qa::profile_add(qa::PK_EMATREAD, ms[0], (double)totR * Ks * 8.0, t_e);
+    qa::profile_add(nH == 3 ? qa::PK_GIBBS3 : ((h.Ksp / 64 == 10 && h.nw == 1 && use_lean_build(C)) ? qa::PK_GIBBS_LEAN : qa::PK_GIBBS), ms[1],
+                    sweeps * (nH / 2.0), t_e + ms[0], units, serial, (double)C);
+    if (h.want_probs) qa::profile_add(qa::PK_HAPPROBS, ms[2], C * (double)nH * Ks * (double)G * 16.0, t_e + ms[0] + ms[1]);
+    return ms[0] + ms[1] + ms[2];
+}
+
+// debugging / test aid (one-chain calls): alpha, beta, eMatGrid of both labels ([6][G][Ks]) then c ([3][G])
+void dump_state(const qa::GibbsScratch &S, const ChunkHost &h, double *state_out) {
+    const int G = h.G, Ks = h.Ks, Ksp = h.Ksp;
+    std::vector<double> tmp((size_t)G * Ksp);
+    const qa::ABuf<double> *src[3] = {&S.alpha, &S.beta, &S.eg};
+    size_t o2 = 0;
+    for (int m = 0; m < 3; m++)
+        for (int hl = 0; hl < 2; hl++) {
+            QA_HIP(hipMemcpy(tmp.data(), src[m]->p + (size_t)hl * G * Ksp, sizeof(double) * tmp.size(),
+                             hipMemcpyDeviceToHost));
+            for (int g = 0; g < G; g++)
+                for (int k = 0; k < Ks; k++) state_out[o2 + (size_t)g * Ks + k] = tmp[(size_t)g * Ksp + k];
+            o2 += (size_t)G * Ks;
+        }
+    QA_HIP(hipMemcpy(state_out + o2, S.cvec.p, sizeof(double) * 3 * G, hipMemcpyDeviceToHost));
+}
+
+// One launch: host preparation and uploads, then the device (held from the gate to the last download), then the accounting
+int gibbs_chunk(qa_panel_t *pn, size_t arena_need, const qa_rare_common *rc, const qa_gibbs_opts_t *o, const GibbsLaunch &L) {
+    if (!g_gibbs) g_gibbs.reset(new GibbsHolder());
+    auto &S = g_gibbs->s;
+    const bool tmg = getenv("QA_TIMING") != nullptr;
+    const double T0 = now_s();
+    // the Gibbs launches of a handle that shares the device go to its own CU partition (qa_panel_set_cu_partition): the
+    // chains hold whole register files for the launch's lifetime, and spread over every CU they would leave no CU free
+    // for the other handle's full-panel workgroups
+    hipStream_t st = pn->gibbs_stream ? pn->gibbs_stream : pn->stream;
+    ChunkHost h = chunk_layout(pn, rc, o, L);
+    find_shared_reads(L, h);
+    prepare_chains(pn, rc, o, L, h);
+    const double T1 = now_s();
+    upload_inputs(S, pn, rc, o, L, h, st);
+    if (h.want_pairs) upload_rare_pairs(S, rc, h, st);
+    // ---- everything above is host work and uploads into this thread's own buffers; from here on the launch set has the
+    // device (exclusive phases: queue behind the other handles' launch sets) and the arena
+    const double hold_t0 = now_s();
+    qa::GateHold hold;
+    hold.acquire(pn->gate(), &pn->arena, h.C * h.nw, arena_need);
+    const double T1g = now_s();
+    carve_arena(S, hold.arena(), arena_need, h);
+    const GibbsParams prm = fill_params(S, pn, rc, o, L, h, st);
+    for (auto &e : g_gibbs->ev) if (!e) QA_HIP(hipEventCreate(&e));
+    QA_HIP(hipStreamSynchronize(st));
+    const double T2 = now_s();
+    launch_gibbs(prm, h.maxR, st, g_gibbs->ev, h.want_probs, h.nw, [&] { nipt_sweeps(prm, S, o, L, h, st, tmg); });
+    const std::vector<int32_t> status = download_labels(S, o, L, h, st);
+    const double T3 = now_s();
+    hold.mark();
+    download_probs(S, o, L, h, st);
+    const bool dump = L.a.state_out && h.C == 1;   // (the state is read from the arena: the hold lasts until it is out)
+    if (!dump) hold.release();
+    const double kernel_ms = profile_launch(g_gibbs->ev, h, prm.n_block);
+    if (tmg)
+        fprintf(stderr, "[qa_gibbs C=%d] host prep %.3f s, tables+uploads %.3f s (of which queued for the device %.3f s), kernels %.3f s (events %.3f), downloads %.3f s\n", h.C,
+                T1 - T0, T2 - T1, T1g - hold_t0, T3 - T2, kernel_ms / 1e3, now_s() - T3);
+    int ret = QA_OK;
+    for (int c = 0; c < h.C; c++) {
+        if (L.a.underflow_problem) L.a.underflow_problem[c] = status[c];
+        if (status[c]) ret = QA_UNDERFLOW;
+    }
+    if (dump) dump_state(S, h, L.a.state_out);
+    return ret;
+}
+
+int gibbs_batch_impl(qa_panel_t *pn, const qa_rare_common *rc, const qa_gibbs_opts_t *o, int32_t n_chain, const GibbsCall &a) {
     if (!qa::device_ready()) return QA_ERR_NO_DEVICE;
-    if (!pn || !o || n_chain <= 0 || !which_haps_to_use_1based || !read_off || !read_ptr || !u || !bq || !wif ||
-        (!runif_reads && !seed_reads) || !first_read || !H) {
+    if (!pn || !o || n_chain <= 0 || !a.which || !a.read_off || !a.read_ptr || !a.u || !a.bq || !a.wif ||
+        (!a.runif_reads && !a.seed_reads) || !a.first_read || !a.H) {
         qa::set_error("qa_gibbs_batch: null argument");
         return QA_ERR_INVALID;
     }
@@ -1704,25 +1849,25 @@ static int gibbs_batch_impl(qa_panel_t *pn, const qa_rare_common *rc, const qa_g
     }
     if (o->ff != 0.0 && o->perform_block_gibbs && o->n_block_gibbs_iterations > 0 &&
         (!o->L_grid || o->shuffle_bin_radius <= 0 || !(o->block_gibbs_quantile_prob > 0 && o->block_gibbs_quantile_prob < 1) ||
-         (!runif_shard && !seed_shard && !seed_reads && !o->draw_uniforms))) {
+         (!a.runif_shard && !a.seed_shard && !a.seed_reads && !o->draw_uniforms))) {
         qa::set_error("qa_gibbs_batch: the NIPT block Gibbs needs opts->L_grid, shuffle_bin_radius, block_gibbs_quantile_prob "
                       "and the block passes' uniforms (runif_shard, seeds, or opts->draw_uniforms)");
         return QA_ERR_INVALID;
     }
-    if (o->draw_uniforms && (o->ff == 0.0 || seed_reads || seed_shard)) {
+    if (o->draw_uniforms && (o->ff == 0.0 || a.seed_reads || a.seed_shard)) {
         qa::set_error("qa_gibbs_batch: opts->draw_uniforms serves the NIPT block passes (ff > 0) of a call with explicit uniforms "
                       "(runif_reads given, no seeds)");
         return QA_ERR_INVALID;
     }
     // the uniforms of the shard passes (diploid) / block passes (NIPT): explicit, or the per-chain seed of the counter-based
     // stream -- never uninitialised device memory
-    if (seed_shard && !seed_reads) {
+    if (a.seed_shard && !a.seed_reads) {
         qa::set_error("qa_gibbs_batch: seed_shard goes with seed_reads (the two counter-based streams of a chain)");
         return QA_ERR_INVALID;
     }
     {
         const bool passes = o->perform_block_gibbs && o->n_block_gibbs_iterations > 0 && (o->ff != 0.0 || o->do_shard_block_gibbs);
-        if (passes && !runif_shard && !(seed_reads && seed_shard) && !(o->ff != 0.0 && o->draw_uniforms)) {
+        if (passes && !a.runif_shard && !(a.seed_reads && a.seed_shard) && !(o->ff != 0.0 && o->draw_uniforms)) {
             qa::set_error("qa_gibbs_batch: block / shard passes requested without their uniforms (runif_shard, or seed_reads and "
                           "seed_shard)");
             return QA_ERR_INVALID;
@@ -1736,6 +1881,7 @@ static int gibbs_batch_impl(qa_panel_t *pn, const qa_rare_common *rc, const qa_g
             return QA_ERR_INVALID;
         }
     }
+    const int32_t *read_off = a.read_off, *read_ptr = a.read_ptr;
     if (o->reads_same_as)
         for (int c = 0; c < n_chain; c++) {
             const int r0 = o->reads_same_as[c];
@@ -1751,9 +1897,7 @@ static int gibbs_batch_impl(qa_panel_t *pn, const qa_rare_common *rc, const qa_g
     return qa::guarded([&] {
         QA_HIP(hipSetDevice(pn->device));
         const int G = rc ? rc->G_all : pn->G, T = rc ? rc->T_all : pn->T, Ks = o->Ks, Ksp = (Ks + 63) / 64 * 64;
-        const int n_its = o->n_gibbs_burn_in_its + o->n_gibbs_sample_its;
-        const int nb = o->n_block_gibbs_iterations;
-        const bool want_probs = hapProbs_t || genProbsM_t || genProbsF_t || o->hap_words_out || o->hap_major_out;
+        const bool want_probs = wants_probs(a, o);
         // chains are processed in chunks that fit the device arena (read emissions + 6 Ks x G state matrices each)
         std::vector<size_t> base_of(n_chain + 1, 0);
         for (int c = 0; c < n_chain; c++) {
@@ -1774,52 +1918,42 @@ static int gibbs_batch_impl(qa_panel_t *pn, const qa_rare_common *rc, const qa_g
         // (round 5: 20 of the QUILT2-default bench's 44 launches).  So count as gibbs_chunk does, chains over host threads.
         std::vector<size_t> n_long_of(n_chain, 0);
         {
-            const int n_thr = std::max(1, std::min<int>(qa::host_threads_cap(), n_chain));
+            // (one task per thread, each taking every n_thr-th chain: `any` is allocated once per thread, not once per chain)
+            const int n_thr = std::max(1, std::min<int>(qa::host_threads(), n_chain));
             const int rc_words = rc ? (T + 31) / 32 : 0;
-            std::vector<std::string> errs(n_thr);
-            auto work = [&](int tid) {
-                try {
-                    std::vector<uint32_t> any(rc_words);
-                    for (int c = tid; c < n_chain; c += n_thr) {
-                        const size_t R = read_off[c + 1] - read_off[c];
-                        const int32_t *rp = read_ptr + read_off[c] + c;
-                        size_t n_long = 0;
-                        if (!rc) {
-                            for (size_t r = 0; r < R; r++) n_long += std::min(rp[r + 1] - rp[r], o->Jmax + 1) > kMaxPatternBits;
-                        } else {
-                            std::fill(any.begin(), any.end(), 0u);
-                            for (int k = 0; k < Ks; k++) {
-                                const int v = which_haps_to_use_1based[(size_t)c * Ks + k] - 1;
-                                if (v < 0 || v >= pn->K) throw std::runtime_error("which_haps_to_use out of range");
-                                for (int64_t i = rc->h_rare_ptr[v]; i < rc->h_rare_ptr[v + 1]; i++) {
-                                    const int t = rc->h_rare_snp[i];
-                                    any[t >> 5] |= 1u << (t & 31);
-                                }
-                            }
-                            const int32_t *cu = u + base_of[o->reads_same_as ? o->reads_same_as[c] : c];
-                            for (size_t r = 0; r < R; r++) {
-                                const int nb_r = std::min(rp[r + 1] - rp[r], o->Jmax + 1);
-                                int n_inf = 0;
-                                for (int j = 0; j < nb_r; j++) {   // (an upper bound of gibbs_chunk's count: it also drops bases of quality 0)
-                                    const int t = cu[rp[r] + j];
-                                    if (t < 0 || t >= T) throw std::runtime_error("read SNP index out of range");
-                                    n_inf += rc->h_common_index[t] >= 0 || ((any[t >> 5] >> (t & 31)) & 1u);
-                                }
-                                n_long += n_inf > kMaxPatternBits;
+            qa::parallel_for((size_t)n_thr, n_thr, [&](size_t tid) {
+                std::vector<uint32_t> any(rc_words);
+                for (int c = (int)tid; c < n_chain; c += n_thr) {
+                    const size_t R = read_off[c + 1] - read_off[c];
+                    const int32_t *rp = read_ptr + read_off[c] + c;
+                    size_t n_long = 0;
+                    if (!rc) {
+                        for (size_t r = 0; r < R; r++) n_long += std::min(rp[r + 1] - rp[r], o->Jmax + 1) > kMaxPatternBits;
+                    } else {
+                        std::fill(any.begin(), any.end(), 0u);
+                        for (int k = 0; k < Ks; k++) {
+                            const int v = a.which[(size_t)c * Ks + k] - 1;
+                            if (v < 0 || v >= pn->K) throw std::runtime_error("which_haps_to_use out of range");
+                            for (int64_t i = rc->h_rare_ptr[v]; i < rc->h_rare_ptr[v + 1]; i++) {
+                                const int t = rc->h_rare_snp[i];
+                                any[t >> 5] |= 1u << (t & 31);
                             }
                         }
-                        n_long_of[c] = n_long;
+                        const int32_t *cu = a.u + base_of[o->reads_same_as ? o->reads_same_as[c] : c];
+                        for (size_t r = 0; r < R; r++) {
+                            const int nb_r = std::min(rp[r + 1] - rp[r], o->Jmax + 1);
+                            int n_inf = 0;
+                            for (int j = 0; j < nb_r; j++) {   // (an upper bound of gibbs_chunk's count: it also drops bases of quality 0)
+                                const int t = cu[rp[r] + j];
+                                if (t < 0 || t >= T) throw std::runtime_error("read SNP index out of range");
+                                n_inf += rc->h_common_index[t] >= 0 || ((any[t >> 5] >> (t & 31)) & 1u);
+                            }
+                            n_long += n_inf > kMaxPatternBits;
+                        }
                     }
-                } catch (const std::exception &e) {
-                    errs[tid] = e.what();
+                    n_long_of[c] = n_long;
                 }
-            };
-            std::vector<std::thread> th;
-            for (int i = 1; i < n_thr; i++) th.emplace_back(work, i);
-            work(0);
-            for (auto &t : th) t.join();
-            for (const auto &e : errs)
-                if (!e.empty()) throw std::runtime_error(e);
+            });
         }
         for (int c = 0; c < n_chain; c++) {
             const size_t R = read_off[c + 1] - read_off[c];
@@ -1847,23 +1981,7 @@ static int gibbs_batch_impl(qa_panel_t *pn, const qa_rare_common *rc, const qa_g
                 need += adds[c1];
                 c1++;
             }
-            std::vector<int32_t> ro(c1 - c0 + 1);
-            for (int i = 0; i <= c1 - c0; i++) ro[i] = read_off[c0 + i] - read_off[c0];
-            std::vector<int64_t> rep_off;   // opts->reads_same_as: a chain's bases, relative to this launch's u / bq (may lie before them)
-            if (o->reads_same_as) {
-                rep_off.resize((size_t)(c1 - c0));
-                for (int c = c0; c < c1; c++) rep_off[(size_t)(c - c0)] = (int64_t)base_of[(size_t)o->reads_same_as[c]] - (int64_t)base_of[(size_t)c0];
-            }
-            const int st = gibbs_chunk(
-                pn, need, rc, o, o->ff_chain ? o->ff_chain + c0 : nullptr, o->reads_same_as ? rep_off.data() : nullptr, o->reads_same_as ? o->reads_same_as + c0 : nullptr, c0, c1 - c0, which_haps_to_use_1based + (size_t)c0 * Ks, ro.data(), read_ptr + read_off[c0] + c0,
-                u + base_of[c0], bq + base_of[c0], wif + read_off[c0],
-                runif_reads ? runif_reads + (size_t)read_off[c0] * n_its : nullptr, first_read + c0,
-                runif_shard ? runif_shard + (o->ff != 0.0 ? (size_t)read_off[c0] * nb * 2 : (size_t)c0 * nb * (G - 1)) : nullptr,
-                H + read_off[c0],
-                H_class ? H_class + read_off[c0] : nullptr, hapProbs_t ? hapProbs_t + (size_t)c0 * T * 3 : nullptr,
-                genProbsM_t ? genProbsM_t + (size_t)c0 * T * 3 : nullptr, genProbsF_t ? genProbsF_t + (size_t)c0 * T * 3 : nullptr,
-                underflow_problem ? underflow_problem + c0 : nullptr, state_out, seed_reads ? seed_reads + c0 : nullptr,
-                seed_shard ? seed_shard + c0 : nullptr);
+            const int st = gibbs_chunk(pn, need, rc, o, launch_slice(a, o, base_of, G, T, c0, c1));
             if (st < 0) return st;
             if (st == QA_UNDERFLOW) ret = QA_UNDERFLOW;
             c0 = c1;
@@ -1872,15 +1990,19 @@ static int gibbs_batch_impl(qa_panel_t *pn, const qa_rare_common *rc, const qa_g
     });
 }
 
+}  // namespace
+
+extern "C" {
+
 int qa_gibbs_batch(qa_panel_t *pn, const qa_gibbs_opts_t *o, int32_t n_chain, const int32_t *which_haps_to_use_1based,
                    const int32_t *read_off, const int32_t *read_ptr, const int32_t *u, const int32_t *bq,
                    const int32_t *wif, const double *runif_reads, const int32_t *first_read,
                    const double *runif_shard, int32_t *H, int32_t *H_class, double *hapProbs_t,
                    double *genProbsM_t, double *genProbsF_t, int32_t *underflow_problem, double *state_out,
                    const uint64_t *seed_reads, const uint64_t *seed_shard) {
-    return gibbs_batch_impl(pn, nullptr, o, n_chain, which_haps_to_use_1based, read_off, read_ptr, u, bq, wif, runif_reads,
-                            first_read, runif_shard, H, H_class, hapProbs_t, genProbsM_t, genProbsF_t, underflow_problem,
-                            state_out, seed_reads, seed_shard);
+    const GibbsCall a{which_haps_to_use_1based, read_off, read_ptr, u, bq, wif, runif_reads, first_read, runif_shard, H, H_class,
+                      hapProbs_t, genProbsM_t, genProbsF_t, underflow_problem, state_out, seed_reads, seed_shard};
+    return gibbs_batch_impl(pn, nullptr, o, n_chain, a);
 }
 
 int qa_gibbs_batch_rare_common(qa_panel_t *pn, const qa_rare_common_t *rc, const qa_gibbs_opts_t *o, int32_t n_chain,
@@ -1898,9 +2020,9 @@ int qa_gibbs_batch_rare_common(qa_panel_t *pn, const qa_rare_common_t *rc, const
         qa::set_error("qa_gibbs_batch_rare_common: the rare/common handle belongs to another panel or device");
         return QA_ERR_INVALID;
     }
-    return gibbs_batch_impl(pn, rc, o, n_chain, which_haps_to_use_1based, read_off, read_ptr, u, bq, wif, runif_reads,
-                            first_read, runif_shard, H, H_class, hapProbs_t, genProbsM_t, genProbsF_t, underflow_problem,
-                            state_out, seed_reads, seed_shard);
+    const GibbsCall a{which_haps_to_use_1based, read_off, read_ptr, u, bq, wif, runif_reads, first_read, runif_shard, H, H_class,
+                      hapProbs_t, genProbsM_t, genProbsF_t, underflow_problem, state_out, seed_reads, seed_shard};
+    return gibbs_batch_impl(pn, rc, o, n_chain, a);
 }
 
 int qa_rare_common_create(qa_panel_t *pn, int32_t nSNPs_all, const uint8_t *snp_is_common, const int64_t *rare_ptr,
@@ -1989,44 +2111,7 @@ static int make_eMatRead_t_impl(qa_panel_t *pn, int32_t nSNPs, int32_t n_chain, 
             base_off[c + 1] = base_off[c] + (read_ptr + read_off[c] + c)[R];
         }
         const int totR = read_off[C], totB = base_off[C];
-        // validation, the copy of the qualities and the bq == 0 carry-over are per chain: on the call's host threads (the driver's
-        // read-confidence call carries every chain of a launch set: 90 M bases, 0.25 s on one thread -- and at the end of a
-        // stream nothing runs beside it)
-        std::vector<int32_t> bq_eff((size_t)std::max(totB, 1));
-        {
-            const int n_thr = std::max(1, std::min<int>(qa::host_threads_cap(), C));
-            std::vector<std::string> errs(n_thr);
-            auto work = [&](int tid) {
-                try {
-                    for (int c = tid; c < C; c += n_thr) {
-                        const int R = read_off[c + 1] - read_off[c];
-                        const int32_t *rp = read_ptr + read_off[c] + c;
-                        const size_t b0 = (size_t)base_off[c];
-                        for (int i = 0; i < rp[R]; i++) {
-                            if (u[b0 + i] < 0 || u[b0 + i] >= T) throw std::runtime_error("read SNP index out of range");
-                            bq_eff[b0 + i] = bq[b0 + i];
-                        }
-                        int last = 0;   // fold_zero_base_qualities for this chain
-                        for (int r = 0; r < R; r++) {
-                            int J = rp[r + 1] - rp[r] - 1;
-                            if (J >= Jmax) J = Jmax;
-                            for (int j = 0; j <= J; j++) {
-                                int32_t &q = bq_eff[b0 + rp[r] + j];
-                                if (q == 0) q = last; else last = q;
-                                if (q > 255 || q < -255) throw std::runtime_error("|base quality| > 255");
-                            }
-                        }
-                    }
-                } catch (const std::exception &e) {
-                    errs[tid] = e.what();
-                }
-            };
-            std::vector<std::thread> th;
-            for (int i = 1; i < n_thr; i++) th.emplace_back(work, i);
-            work(0);
-            for (auto &t : th) t.join();
-            for (auto &e : errs) if (!e.empty()) throw std::runtime_error(e);
-        }
+        const std::vector<int32_t> bq_eff = checked_folded_qualities(C, read_off, read_ptr, u, bq, base_off, T, Jmax);
         const std::vector<double> tabs = base_quality_tables();
         // carved from the handle's arena (no launch set of this handle is in flight during this call): a call-local
         // hipMalloc / hipFree pair would synchronise the device with the other host threads' launches
@@ -2094,41 +2179,8 @@ int qa_rcpp_make_eMatRead_t_rare_common(qa_panel_t *pn, const qa_rare_common_t *
             out_off[c + 1] = out_off[c] + (read_off[chain_sample[c] + 1] - read_off[chain_sample[c]]);
         }
         const int totR = read_off[NS], totB = base_off[NS], totOut = out_off[C];
-        std::vector<int32_t> bq_eff((size_t)std::max(totB, 1));
-        {
-            const int n_thr = std::max(1, std::min<int>(qa::host_threads_cap(), NS));
-            std::vector<std::string> errs(n_thr);
-            auto work = [&](int tid) {
-                try {
-                    for (int i = tid; i < NS; i += n_thr) {
-                        const int R = read_off[i + 1] - read_off[i];
-                        const int32_t *rp = read_ptr + read_off[i] + i;
-                        const size_t b0 = (size_t)base_off[i];
-                        for (int q = 0; q < rp[R]; q++) {
-                            if (u[b0 + q] < 0 || u[b0 + q] >= T) throw std::runtime_error("read SNP index out of range");
-                            bq_eff[b0 + q] = bq[b0 + q];
-                        }
-                        int last = 0;   // fold_zero_base_qualities, per sample (a chain's reads are its sample's)
-                        for (int r = 0; r < R; r++) {
-                            int J = rp[r + 1] - rp[r] - 1;
-                            if (J >= Jmax) J = Jmax;
-                            for (int j = 0; j <= J; j++) {
-                                int32_t &q = bq_eff[b0 + rp[r] + j];
-                                if (q == 0) q = last; else last = q;
-                                if (q > 255 || q < -255) throw std::runtime_error("|base quality| > 255");
-                            }
-                        }
-                    }
-                } catch (const std::exception &e) {
-                    errs[tid] = e.what();
-                }
-            };
-            std::vector<std::thread> th;
-            for (int i = 1; i < n_thr; i++) th.emplace_back(work, i);
-            work(0);
-            for (auto &t : th) t.join();
-            for (auto &e : errs) if (!e.empty()) throw std::runtime_error(e);
-        }
+        // (per sample: a chain's reads are its sample's)
+        const std::vector<int32_t> bq_eff = checked_folded_qualities(NS, read_off, read_ptr, u, bq, base_off, T, Jmax);
         const std::vector<double> tabs = base_quality_tables();
         qa::ABuf<double> d_e, d_tabs, d_out;
         qa::ABuf<int32_t> d_ro, d_rp, d_bo, d_u, d_bq, d_cs, d_oo;

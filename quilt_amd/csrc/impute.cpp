@@ -42,6 +42,7 @@
 
 #include "../../include/quilt_amd.h"
 #include "../../include/quilt_amd_io.h"
+#include "host_threads.hpp"
 #include "impute_testhook.h"   // the table of entry points this loop runs over (private: tests fill it with a checker's)
 
 namespace qa {
@@ -250,37 +251,7 @@ struct HostBuf {   // grow-only transfer buffer from the backend's allocator (pi
 };
 
 // copies of many pieces into one array, on a few threads (a 2 048-chain Gibbs launch carries ~1.5 GB of per-chain read copies)
-void parallel_for(size_t n, int n_thr, const std::function<void(size_t)> &f) {
-    n_thr = (int)std::min<size_t>((size_t)std::max(n_thr, 1), std::max<size_t>(n, 1));
-    if (n_thr <= 1) {
-        for (size_t i = 0; i < n; i++) f(i);
-        return;
-    }
-    std::atomic<size_t> next{0};
-    std::exception_ptr err;
-    std::mutex mu;
-    std::vector<std::thread> th;
-    for (int t = 0; t < n_thr; t++)
-        th.emplace_back([&] {
-            try {
-                for (size_t i; (i = next.fetch_add(1)) < n;) f(i);
-            } catch (...) {
-                std::lock_guard<std::mutex> g(mu);
-                if (!err) err = std::current_exception();
-            }
-        });
-    for (auto &t : th) t.join();
-    if (err) std::rethrow_exception(err);
-}
-
-int helper_threads(int cap = 8) {
-    int c = std::min<int>(cap, std::max(1u, std::thread::hardware_concurrency()));
-    if (const char *e = getenv("QA_HOST_THREADS")) {
-        const int v = atoi(e);
-        if (v >= 1) c = std::min(c, v);
-    }
-    return c;
-}
+using qa::parallel_for;
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // host logic of the R driver
@@ -482,7 +453,7 @@ struct Worker {
     const void *rc_handle = nullptr;   // this thread's qa_rare_common_t (impute_rare_common)
     std::vector<double> eh;            // eHapsCurrent_tc of get_initial_read_labels: [chain][all SNPs][2]
     Worker(Ctx &c, void *h, int wi, bool keep)
-        : cx(c), handle(h), w(wi), n_help(helper_threads()), n_draw(helper_threads(24)), B(buffers_for(c, h, keep, own)), g_which(B.g_which),
+        : cx(c), handle(h), w(wi), n_help(qa::host_threads(8)), n_draw(qa::host_threads(24)), B(buffers_for(c, h, keep, own)), g_which(B.g_which),
           g_read_off(B.g_read_off), g_read_ptr(B.g_read_ptr), g_u(B.g_u), g_bq(B.g_bq), g_wif(B.g_wif), g_first(B.g_first), g_H(B.g_H),
           g_uf(B.g_uf), g_words(B.g_words), g_sr(B.g_sr), g_ss(B.g_ss), seed_sel(B.seed_sel), f_cs(B.f_cs), f_read_off(B.f_read_off),
           f_read_ptr(B.f_read_ptr), f_u(B.f_u), f_bq(B.f_bq), f_H(B.f_H), f_wd(B.f_wd), f_wt(B.f_wt), f_cnt(B.f_cnt), f_next(B.f_next),

@@ -28,12 +28,11 @@
 #include <cstdlib>
 #include <cstring>
 #include <exception>
-#include <mutex>
-#include <thread>
 #include <vector>
 
 #include "../../include/quilt_amd.h"
 #include "../../include/quilt_amd_io.h"
+#include "host_threads.hpp"
 
 namespace qa { void set_error(const char *fmt, ...); }
 
@@ -52,50 +51,6 @@ struct qa_mspbwt {
 };
 
 namespace {
-
-int n_threads(size_t n_tasks) {
-    int c = std::min<int>(16, std::max(1u, std::thread::hardware_concurrency()));
-    if (const char *e = getenv("QA_HOST_THREADS")) {
-        const int v = atoi(e);
-        if (v >= 1) c = std::min(c, v);
-    }
-    return (int)std::max<size_t>(1, std::min<size_t>((size_t)c, n_tasks));
-}
-
-template <class F>
-void parallel_tasks(size_t n, F &&f) {
-    const int nt = n_threads(n);
-    if (nt <= 1) {
-        for (size_t i = 0; i < n; i++) f(i);
-        return;
-    }
-    // an exception inside a task (std::bad_alloc: the index is 0.8 GB at K = 50 000) must not escape its thread -- that is
-    // std::terminate, and the host is R or Python: the first one is kept, the other tasks are skipped, and it is rethrown on the
-    // calling thread, whose callers map it to a status with qa::set_error
-    std::atomic<size_t> next{0};
-    std::atomic<bool> failed{false};
-    std::exception_ptr err;
-    std::mutex mu;
-    std::vector<std::thread> th;
-    auto work = [&] {
-        for (;;) {
-            const size_t i = next.fetch_add(1);
-            if (i >= n || failed.load()) return;
-            try {
-                f(i);
-            } catch (...) {
-                std::lock_guard<std::mutex> g(mu);
-                if (!err) err = std::current_exception();
-                failed.store(true);
-                return;
-            }
-        }
-    };
-    for (int t = 1; t < nt; t++) th.emplace_back(work);
-    work();
-    for (auto &t : th) t.join();
-    if (err) std::rethrow_exception(err);
-}
 
 struct Rep { int32_t k, s0, n; };
 
@@ -203,7 +158,7 @@ qa_mspbwt_t *qa_mspbwt_create(int32_t K, int32_t nGrids, const uint8_t *hapMatch
             std::sort(d, d + nMaxDH);
         }
         m->idx.resize((size_t)nindices);
-        parallel_tasks((size_t)nindices, [&](size_t i) {
+        qa::parallel_for((size_t)nindices, qa::host_threads(), [&](size_t i) {
             qa_mspbwt::Index &ix = m->idx[i];
             ix.Tp = (nGrids - (int)i + nindices - 1) / nindices;
             ix.a.resize((size_t)ix.Tp * K);
@@ -255,8 +210,8 @@ int64_t qa_mspbwt_find_good_matches(const qa_mspbwt_t *m, int32_t n_query, const
     const int ni = m->nindices;
     std::vector<std::vector<Rep>> found((size_t)n_query * ni);
     std::vector<uint8_t> zq((size_t)n_query * m->G);
-    parallel_tasks((size_t)n_query, [&](size_t q) { query_symbols(*m, Zs + q * (size_t)m->G, zq.data() + q * (size_t)m->G); });
-    parallel_tasks((size_t)n_query * ni, [&](size_t qi) {
+    qa::parallel_for((size_t)n_query, qa::host_threads(), [&](size_t q) { query_symbols(*m, Zs + q * (size_t)m->G, zq.data() + q * (size_t)m->G); });
+    qa::parallel_for((size_t)n_query * ni, qa::host_threads(), [&](size_t qi) {
         scan_one(*m, (int)(qi % (size_t)ni), zq.data() + (qi / (size_t)ni) * (size_t)m->G, L, M, found[qi]);
     });
     int64_t total = 0;
@@ -284,7 +239,7 @@ int qa_mspbwt_select_new_haps(const qa_mspbwt_t *m, int32_t n_chain, int32_t n_l
     try {
     const int ni = m->nindices, G = m->G;
     std::atomic<int> status{QA_OK};
-    parallel_tasks((size_t)n_chain, [&](size_t c) {
+    qa::parallel_for((size_t)n_chain, qa::host_threads(), [&](size_t c) {
         std::vector<std::vector<Rep>> found((size_t)n_label * ni);
         std::vector<uint8_t> zq((size_t)G);
         size_t mm = 1;

@@ -11,11 +11,14 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <stdexcept>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "../../include/quilt_amd.h"
 #include "../../include/quilt_amd_io.h"
+#include "../../quilt_amd/csrc/host_threads.hpp"
 #include "../../quilt_amd/csrc/impute_testhook.h"
 
 namespace qa {
@@ -243,6 +246,36 @@ int main(int argc, char **argv) {
                                               S.wif.data(), d.data(), g.data(), h.data(), lab.data(), nd.data(), stats) == QA_OK);
             REQUIRE(nd[0] == Q.nGibbsSamples);
         }
+    }
+    {   // csrc/host_threads.hpp: tasks that throw on threads other than the caller's while every thread is in the middle of a task --
+        // the first exception arrives here, every thread has been joined, and the helper can be used again
+        const size_t n = 4000;
+        const int n_thr = 4;
+        const std::thread::id caller = std::this_thread::get_id();
+        std::atomic<int> started{0}, finished{0};
+        std::vector<int> seen(n, 0);
+        bool caught = false;
+        try {
+            qa::parallel_for(n, n_thr, [&](size_t i) {
+                started++;
+                seen[i] = 1;   // (an index is handed to one task only: no two threads write one element)
+                while (started.load() < n_thr) std::this_thread::yield();   // all n_thr threads hold a task by now
+                if (std::this_thread::get_id() != caller) throw std::runtime_error("thrown on a helper thread");
+                finished++;
+            });
+        } catch (const std::runtime_error &e) {
+            caught = std::string(e.what()) == "thrown on a helper thread";
+        }
+        REQUIRE(caught);
+        REQUIRE(finished.load() >= 1);   // (the caller's own tasks ran to their end; what was left when the failure was seen is skipped)
+        qa::parallel_for(n, n_thr, [&](size_t i) { seen[i] = (int)i; });
+        long sum = 0;
+        for (size_t i = 0; i < n; i++) sum += seen[i];
+        REQUIRE(sum == (long)n * (long)(n - 1) / 2);   // every index once
+        qa::parallel_for(n, 1, [&](size_t i) { seen[i] += 1; });   // one thread: inline on the caller
+        REQUIRE(seen[n - 1] == (int)n);
+        REQUIRE(qa::host_threads(3) >= 1 && qa::host_threads(3) <= 3);
+        std::printf("tsan harness: parallel_for: exception of a helper thread caught on the caller after %d finished tasks\n", finished.load());
     }
     if (argc >= 3) {
         FILE *f = std::fopen(argv[1], "rb");

@@ -37,6 +37,11 @@ extern "C" {
 #define QA_ERR_HIP (-4)
 #define QA_ERR_CAPACITY (-5)
 
+/* Largest small panel (Ksubset) the Gibbs samplers are built for: every size from 1 up to these runs; a larger one is refused
+ * with QA_ERR_UNSUPPORTED before any device work (qa_gibbs_opts_t.Ks, qa_impute_params_t.Ksubset). */
+#define QA_KSUBSET_MAX 1024      /* two-label sampler: method = "diploid", common-SNP and rare + common form */
+#define QA_KSUBSET_MAX_NIPT 640  /* three-label sampler: method = "nipt" (ff > 0) */
+
 /* ---- library ------------------------------------------------------------ */
 
 /* ABI version of this header (bumped on any signature change). */
@@ -430,7 +435,9 @@ int qa_last_fullpass_timing_ms(double out[5]);
  * pass_in_alphaBeta = TRUE, record_read_set = TRUE, shard_check_every_pair = TRUE,
  * haploid_gibbs_equal_weighting = TRUE, use_starting_read_labels = TRUE. */
 typedef struct {
-    int32_t Ks;                      /* length(which_haps_to_use) (Ksubset) */
+    int32_t Ks;                      /* length(which_haps_to_use) (Ksubset): every value in 1..QA_KSUBSET_MAX (1024) runs with
+                                        ff == 0 and every value in 1..QA_KSUBSET_MAX_NIPT (640) with ff > 0; anything else is
+                                        QA_ERR_UNSUPPORTED before any device work, and qa_last_error names these ranges */
     double ff;                       /* fetal fraction; 0 = diploid */
     int32_t sample_is_diploid;
     int32_t Jmax;                    /* Jmax_local */
@@ -703,7 +710,9 @@ typedef struct {
     int32_t nGibbsSamples;                      /* 7 */
     int32_t n_seek_its;                         /* 3 */
     int32_t n_burn_in_seek_its;                 /* -1 = NA: n_seek_its - 1 (quilt.R:248-250) */
-    int32_t Ksubset, Knew;                      /* 600, 600; a panel with K < Ksubset: one seek iteration on all of it (quilt.R:453-471) */
+    int32_t Ksubset, Knew;                      /* 600, 600; a panel with K < Ksubset: one seek iteration on all of it (quilt.R:453-471).
+                                                   Ksubset AFTER that reset must be in 1..QA_KSUBSET_MAX (1024), with nipt set in
+                                                   1..QA_KSUBSET_MAX_NIPT (640): QA_ERR_UNSUPPORTED before the first sample otherwise */
     int32_t K_top_matches;                      /* 5 */
     double heuristic_match_thin;                /* 0.1 */
     int32_t small_ref_panel_gibbs_iterations;   /* 20 */

@@ -1132,9 +1132,14 @@ void launch_gibbs(const GibbsParams &prm, int maxR, hipStream_t st, hipEvent_t *
             else if (nw == 2) launch_ematread<10, 2>(prm, maxR, st);
             else launch_ematread<10, 1>(prm, maxR, st);
             break;
+        case 11: launch_ematread<11, 1>(prm, maxR, st); break;
         case 12: launch_ematread<12, 1>(prm, maxR, st); break;
+        case 13: launch_ematread<13, 1>(prm, maxR, st); break;
+        case 14: launch_ematread<14, 1>(prm, maxR, st); break;
+        case 15: launch_ematread<15, 1>(prm, maxR, st); break;
         case 16: launch_ematread<16, 1>(prm, maxR, st); break;
-        default: throw std::runtime_error("Ksubset geometry not built (Ksubset / 64 rounded up must be 1..10, 12 or 16)");
+        // (unreachable through the ABI: gibbs_batch_impl admits Ksubset 1..1024 only, i.e. 1..16 rows per lane)
+        default: throw std::runtime_error("Ksubset geometry not built (Ksubset / 64 rounded up must be 1..16)");
     }
     QA_HIP(hipEventRecord(ev[1], st));
     if (prm.nH == 3) {
@@ -1156,7 +1161,11 @@ void launch_gibbs(const GibbsParams &prm, int maxR, hipStream_t st, hipEvent_t *
             case 7: launch_gibbs_kernel<7, 1>(prm, st); break;
             case 8: launch_gibbs_kernel<8, 1>(prm, st); break;
             case 9: launch_gibbs_kernel<9, 1>(prm, st); break;
+            case 11: launch_gibbs_kernel<11, 1>(prm, st); break;
             case 12: launch_gibbs_kernel<12, 1>(prm, st); break;
+            case 13: launch_gibbs_kernel<13, 1>(prm, st); break;
+            case 14: launch_gibbs_kernel<14, 1>(prm, st); break;
+            case 15: launch_gibbs_kernel<15, 1>(prm, st); break;
             default: launch_gibbs_kernel<16, 1>(prm, st); break;
         }
     }
@@ -1890,8 +1899,14 @@ int gibbs_batch_impl(qa_panel_t *pn, const qa_rare_common *rc, const qa_gibbs_op
                 return QA_ERR_INVALID;
             }
         }
-    if (o->Ks <= 0 || o->Ks > 1024) {
-        qa::set_error("qa_gibbs_batch: Ksubset = %d outside 1..1024", o->Ks);
+    if (o->Ks <= 0 || o->Ks > QA_KSUBSET_MAX) {
+        qa::set_error("qa_gibbs_batch: Ksubset = %d outside 1..%d", o->Ks, QA_KSUBSET_MAX);
+        return QA_ERR_UNSUPPORTED;
+    }
+    // the three-label kernels hold three columns per row: ten rows per lane fill a SIMD's register file, and nothing larger is built
+    if (o->ff != 0.0 && o->Ks > QA_KSUBSET_MAX_NIPT) {
+        qa::set_error("qa_gibbs_batch: Ksubset = %d is not built for the NIPT sampler (ff > 0), which runs every Ksubset in 1..%d; "
+                      "the diploid sampler runs 1..%d", o->Ks, QA_KSUBSET_MAX_NIPT, QA_KSUBSET_MAX);
         return QA_ERR_UNSUPPORTED;
     }
     return qa::guarded([&] {

@@ -1051,13 +1051,16 @@ void launch_gibbs3(const void *params, hipStream_t st) {
         case 4: launch_one<4, 1>(prm, st); break;
         case 5: launch_one<5, 1>(prm, st); break;
         case 6: launch_one<6, 1>(prm, st); break;
+        case 7: launch_one<7, 1>(prm, st); break;
         case 8: launch_one<8, 1>(prm, st); break;
+        case 9: launch_one<9, 1>(prm, st); break;
         case 10:
             if (prm.er_nt == 64 && prm.lean3) launch_one<10, 1, true>(prm, st);
             else if (prm.er_nt == 64) launch_one<10, 1>(prm, st);
             else launch_one<5, 2>(prm, st);
             break;
-        default: throw std::runtime_error("NIPT sampler: Ksubset geometry not built (Ksubset / 64 rounded up must be 1..6, 8 or 10)");
+        // (unreachable through the ABI: gibbs_batch_impl refuses a NIPT call above kMaxKsubsetNipt before any device work)
+        default: throw std::runtime_error("NIPT sampler: Ksubset geometry not built (Ksubset / 64 rounded up must be 1..10)");
     }
 }
 
@@ -1082,9 +1085,11 @@ void launch_block3(const void *params, hipStream_t st) {
         case 4: launch_block<4, 1>(prm, st); break;
         case 5: launch_block<5, 1>(prm, st); break;
         case 6: launch_block<6, 1>(prm, st); break;
+        case 7: launch_block<7, 1>(prm, st); break;
         case 8: launch_block<8, 1>(prm, st); break;
+        case 9: launch_block<9, 1>(prm, st); break;
         case 10: launch_block<5, 2>(prm, st); break;
-        default: throw std::runtime_error("NIPT block Gibbs: Ksubset geometry not built");
+        default: throw std::runtime_error("NIPT block Gibbs: Ksubset geometry not built (Ksubset / 64 rounded up must be 1..10)");
     }
 }
 

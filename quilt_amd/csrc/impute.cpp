@@ -1290,6 +1290,14 @@ int impute_impl(bool keep_buffers, const qa_impute_backend_t *be, void *const *h
                       "K_top_matches >= 1");
         return QA_ERR_INVALID;
     }
+    // what the samplers are built for (qa_gibbs_opts_t.Ks), said before the first sample and not by its first Gibbs call
+    if (P.Ksubset > (P.nipt ? QA_KSUBSET_MAX_NIPT : QA_KSUBSET_MAX)) {
+        qa::set_error("qa_impute_samples: Ksubset = %d (after the reset to the panel's %d haplotypes when it has fewer) is not built "
+                      "for %s, which runs every Ksubset in 1..%d (method = \"diploid\": 1..%d, method = \"nipt\": 1..%d)",
+                      P.Ksubset, K, P.nipt ? "method = \"nipt\"" : "method = \"diploid\"", P.nipt ? QA_KSUBSET_MAX_NIPT : QA_KSUBSET_MAX,
+                      QA_KSUBSET_MAX, QA_KSUBSET_MAX_NIPT);
+        return QA_ERR_UNSUPPORTED;
+    }
     if (hla) {   // hla_run: what the range call covers (functions.R:713-724, :1261-1280 with method = "diploid", full-panel passes)
         const char *why = !select_gamma ? "no gamma-column entry point"
                           : !hla->gamma1 || !hla->gamma2 || !hla->gamma_total || !hla->list_of_gammas ? "missing output array"

@@ -28,6 +28,9 @@ import numpy as np
 from . import trace
 from .trace import span
 
+# largest small panel the Gibbs samplers are built for (include/quilt_amd.h: QA_KSUBSET_MAX, QA_KSUBSET_MAX_NIPT)
+KSUBSET_MAX, KSUBSET_MAX_NIPT = 1024, 640
+
 
 @dataclass
 class DriverParams:
@@ -86,6 +89,12 @@ class DriverParams:
                              "the dosages)")
         if p.nGibbsSamples < 1 or p.Ksubset < 1 or p.Knew < 1:
             raise ValueError("nGibbsSamples, Ksubset and Knew must be >= 1")
+        # what the Gibbs samplers are built for (include/quilt_amd.h: QA_KSUBSET_MAX, QA_KSUBSET_MAX_NIPT), after the reset above
+        ks_max = KSUBSET_MAX_NIPT if p.method == "nipt" else KSUBSET_MAX
+        if p.Ksubset > ks_max:
+            raise ValueError(f"Ksubset = {p.Ksubset} (after the reset to the panel's {K} haplotypes when it has fewer) is not built "
+                             f"for method = '{p.method}', which runs every Ksubset in 1..{ks_max} (method = 'diploid': "
+                             f"1..{KSUBSET_MAX}, method = 'nipt': 1..{KSUBSET_MAX_NIPT})")
         if p.K_top_matches < 1:
             raise ValueError("K_top_matches must be >= 1")
         if p.diploid_block_gibbs != "reference_noop":

@@ -712,6 +712,18 @@ static void range_validate(SEXP panelSEXP, SEXP paramsSEXP, const char *who) {
         SEXP ff = list_get(paramsSEXP, "ff");
         if (ff != R_NilValue && TYPEOF(ff) != REALSXP) Rf_error("quilt_amd: %s: params$ff must be numeric (as.numeric)", who);
     }
+    {   /* the small panel the samplers are built for (include/quilt_amd.h: QA_KSUBSET_MAX*), after quilt.R:453-463's reset to the
+         * panel's size: refused here, before the panel is uploaded, not by the first sample's first Gibbs call */
+        const int K = Rf_nrows(hapMatcherR);
+        const double ks_asked = num_or(paramsSEXP, "Ksubset", 600), ks = K < ks_asked ? K : ks_asked;
+        SEXP m = list_get(paramsSEXP, "method");
+        const int nipt = m != R_NilValue && TYPEOF(m) == STRSXP && Rf_length(m) == 1 && strcmp(CHAR(STRING_ELT(m, 0)), "nipt") == 0;
+        const int ks_max = nipt ? QA_KSUBSET_MAX_NIPT : QA_KSUBSET_MAX;
+        if (ks > ks_max)
+            Rf_error("quilt_amd: %s: Ksubset = %d (the smaller of params$Ksubset and the panel's %d haplotypes) is not built for "
+                     "method = \"%s\", which runs every Ksubset in 1..%d (method = \"diploid\": 1..%d, method = \"nipt\": 1..%d)",
+                     who, (int)ks, K, nipt ? "nipt" : "diploid", ks_max, QA_KSUBSET_MAX, QA_KSUBSET_MAX_NIPT);
+    }
     const double seed_d = num_or(paramsSEXP, "seed", 1);
     if (!(seed_d >= 0) || seed_d > 9007199254740992.0 /* 2^53 */ || seed_d != floor(seed_d))   /* (NA / NaN fail the first test) */
         Rf_error("quilt_amd: %s: params$seed must be a non-negative whole number below 2^53", who);

@@ -47,6 +47,14 @@ PYTHON_ONLY = {
 BASE = dict(nGibbsSamples=2, n_seek_its=2, Ksubset=64, Knew=64, seed=9, small_ref_panel_gibbs_iterations=4,
             small_ref_panel_block_gibbs_iterations=(2,), mspbwt_nindices=2, shuffle_bin_radius=4000, Jmax=5000)
 
+# small panels the samplers are not built for (include/quilt_amd.h: QA_KSUBSET_MAX_NIPT): (name, DriverParams keyword arguments,
+# haplotypes of the panel) -- BOTH statements of the loop refuse the range before its first sample.  The three-label sampler
+# stops at Ksubset = 640; here quilt.R:453-463's reset to the panel's size leaves 700.
+REFUSED = [
+    ("nipt:panel_of_700_below_Ksubset", dict(BASE, method="nipt", Ksubset=1024, Knew=1024), 700),
+    ("nipt:Ksubset_700", dict(BASE, method="nipt", Ksubset=700, Knew=700), 800),
+]
+
 
 def classified():
     return set(SWITCHES) | KNOBS | set(PYTHON_ONLY)

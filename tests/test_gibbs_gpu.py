@@ -18,30 +18,7 @@ def oracle():
     return O
 
 
-def _setup(panel, seed, Ks, n_reads, mode="short"):
-    from quilt_amd.synth import make_synthetic_sample
-    s = make_synthetic_sample(panel, seed=seed, n_reads=n_reads, mode=mode)
-    rng = np.random.default_rng(seed + 17)
-    which = np.sort(rng.choice(panel.K, Ks, replace=False)).astype(np.int32) + 1
-    H0 = rng.integers(1, 3, size=s.nReads).astype(np.int32)
-    ru = rng.random(s.nReads * 21)
-    rs = rng.random(3 * (panel.nGrids - 1))
-    fr = int(rng.integers(0, s.nReads))
-    return s, which, H0, ru, rs, fr
-
-
-def _compare(got, ref, Ks):
-    assert not got["underflow_problem"] and ref["status"] == 0
-    assert np.array_equal(got["H"], ref["H"]), f"{(got['H'] != ref['H']).sum()} labels differ"
-    assert np.array_equal(got["H_class"], ref["H_class"])
-    for h in range(2):
-        np.testing.assert_allclose(got[f"eMatGrid_t{h + 1}"], ref["eMatGrid_t"][h], rtol=RTOL)
-        np.testing.assert_allclose(got[f"alphaHat_t{h + 1}"], ref["alphaHat_t"][h], rtol=RTOL, atol=1e-300)
-        np.testing.assert_allclose(got[f"betaHat_t{h + 1}"], ref["betaHat_t"][h], rtol=RTOL, atol=1e-300)
-        np.testing.assert_allclose(got[f"c{h + 1}"], ref["c"][h], rtol=RTOL)
-    np.testing.assert_allclose(got["hapProbs_t"], ref["hapProbs_t"], rtol=RTOL, atol=1e-14)
-    np.testing.assert_allclose(got["genProbsM_t"], ref["genProbsM_t"], rtol=RTOL, atol=1e-14)
-    np.testing.assert_allclose(got["genProbsF_t"], ref["genProbsF_t"], rtol=RTOL, atol=1e-14)
+from tests.util import gibbs_compare as _compare, gibbs_setup as _setup   # (shared with tests/test_gibbs_geometry_gpu.py)
 
 
 @pytest.mark.parametrize("init_iter", [False, True])

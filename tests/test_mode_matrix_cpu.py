@@ -45,3 +45,21 @@ def test_both_loops_return_the_same_bytes(name, kw):
         assert tab.calls["gibbs_rc"] > 0
     if name.endswith("complete_lists"):
         assert stats["full_list_refetches"] > 0
+
+
+@pytest.mark.parametrize("name,kw,K", MM.REFUSED, ids=[n for n, _, _ in MM.REFUSED])
+def test_both_loops_refuse_a_small_panel_the_samplers_are_not_built_for(name, kw, K):
+    """A clean refusal before the first sample from both statements, each naming the sizes that run: no backend entry is called."""
+    from quilt_amd.driver import Driver
+    from tests.native_driver_backend import impute_samples_on_oracle
+    panel, rc, samples, P = MM.make_case(kw, K=K)
+    with pytest.raises(ValueError, match=r"1\.\.640"):
+        Driver(panel, OracleBackend(panel, rc), P, rare_common=rc).run(samples, sample_offset=3)
+    with pytest.raises(RuntimeError, match=r"status -3: .*1\.\.640"):   # QA_ERR_UNSUPPORTED
+        impute_samples_on_oracle(panel, samples, P, sample_offset=3, samples_per_launch_set=2, n_threads=2, rare_common=rc)
+    # the sizes either side: the same panel at Ksubset = 640 runs, and so does the refused size with method = "diploid"
+    for kw2 in (dict(kw, Ksubset=640, Knew=640), dict(kw, method="diploid")):
+        panel, rc, samples, P = MM.make_case(kw2, n_samples=1, K=K)
+        want = Driver(panel, OracleBackend(panel, rc), P, rare_common=rc).run(samples, sample_offset=3)
+        got, _, _ = impute_samples_on_oracle(panel, samples, P, sample_offset=3, samples_per_launch_set=2, n_threads=2, rare_common=rc)
+        assert np.array_equal(got[0].read_labels, want[0].read_labels) and np.array_equal(got[0].dosage, want[0].dosage)

@@ -50,3 +50,21 @@ def test_both_loops_return_the_same_bytes_on_the_device(rig, name, kw):
                 assert np.array_equal(getattr(a, f), getattr(b, f)), f"{name}: {f}"
             if P.method == "nipt":
                 assert np.array_equal(a.fet_dosage, b.fet_dosage) and np.array_equal(a.fet_gp_t, b.fet_gp_t), name
+
+
+@pytest.mark.parametrize("name,kw,K", MM.REFUSED, ids=[n for n, _, _ in MM.REFUSED])
+def test_both_loops_refuse_a_small_panel_the_samplers_are_not_built_for_on_the_device(name, kw, K):
+    """MM.REFUSED on the device: ValueError from quilt_amd/driver.py, QA_ERR_UNSUPPORTED from qa_impute_samples, both before the
+    first sample and both naming the sizes that run."""
+    from quilt_amd.driver import Driver, HipBackend
+    from quilt_amd.impute import impute_samples
+    from quilt_amd.native import DevicePanel, QuiltAmdError
+    panel, rc, samples, P = MM.make_case(kw, reads=300, seed0=70, K=K)
+    dev = DevicePanel(panel)
+    dev.set_dosage_precision(64)
+    with pytest.raises(ValueError, match=r"1\.\.640"):
+        Driver(panel, HipBackend(dev), P).run(samples, sample_offset=3)
+    with pytest.raises(QuiltAmdError, match=r"1\.\.640") as e:
+        impute_samples([dev], samples, P, sample_offset=3, samples_per_launch_set=2)
+    assert e.value.status == -3   # QA_ERR_UNSUPPORTED
+    dev.close()

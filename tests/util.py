@@ -88,3 +88,35 @@ def underflowing_sample(panel, seed=78, n_reads=300, per_type=115, n_snps=12):
     ptr = np.r_[0, np.cumsum([len(t[1]) for t in reads])]
     return sample_from_arrays(ptr, np.concatenate([t[1] for t in reads]), np.concatenate([t[2] for t in reads]),
                               [t[0] for t in reads])
+
+
+GIBBS_RTOL = 1e-9
+
+
+def gibbs_setup(panel, seed, Ks, n_reads, mode="short"):
+    """One chain's inputs for the small-panel sampler: reads, the haplotype subset, starting labels, the sweeps' and the shard
+    passes' uniforms, the read the iterative initialisation starts from."""
+    from quilt_amd.synth import make_synthetic_sample
+    s = make_synthetic_sample(panel, seed=seed, n_reads=n_reads, mode=mode)
+    rng = np.random.default_rng(seed + 17)
+    which = np.sort(rng.choice(panel.K, Ks, replace=False)).astype(np.int32) + 1
+    H0 = rng.integers(1, 3, size=s.nReads).astype(np.int32)
+    ru = rng.random(s.nReads * 21)
+    rs = rng.random(3 * (panel.nGrids - 1))
+    fr = int(rng.integers(0, s.nReads))
+    return s, which, H0, ru, rs, fr
+
+
+def gibbs_compare(got, ref, Ks):
+    """The diploid sampler's bar against the oracle: labels and classes identical, state and probabilities to 1e-9 relative."""
+    assert not got["underflow_problem"] and ref["status"] == 0
+    assert np.array_equal(got["H"], ref["H"]), f"{(got['H'] != ref['H']).sum()} labels differ"
+    assert np.array_equal(got["H_class"], ref["H_class"])
+    for h in range(2):
+        np.testing.assert_allclose(got[f"eMatGrid_t{h + 1}"], ref["eMatGrid_t"][h], rtol=GIBBS_RTOL)
+        np.testing.assert_allclose(got[f"alphaHat_t{h + 1}"], ref["alphaHat_t"][h], rtol=GIBBS_RTOL, atol=1e-300)
+        np.testing.assert_allclose(got[f"betaHat_t{h + 1}"], ref["betaHat_t"][h], rtol=GIBBS_RTOL, atol=1e-300)
+        np.testing.assert_allclose(got[f"c{h + 1}"], ref["c"][h], rtol=GIBBS_RTOL)
+    np.testing.assert_allclose(got["hapProbs_t"], ref["hapProbs_t"], rtol=GIBBS_RTOL, atol=1e-14)
+    np.testing.assert_allclose(got["genProbsM_t"], ref["genProbsM_t"], rtol=GIBBS_RTOL, atol=1e-14)
+    np.testing.assert_allclose(got["genProbsF_t"], ref["genProbsF_t"], rtol=GIBBS_RTOL, atol=1e-14)

@@ -300,8 +300,9 @@ struct Arena {
         cap = want;
         off = 0;
     }
+    static constexpr size_t kCarveAlign = 256;   // every carve starts at a multiple of this
     void *take(size_t bytes) {
-        const size_t a = (off + 255) & ~size_t(255);
+        const size_t a = (off + kCarveAlign - 1) & ~(kCarveAlign - 1);
         if (a + bytes > cap) throw std::runtime_error("device arena exhausted (internal sizing error)");
         off = a + bytes;
         return base + a;

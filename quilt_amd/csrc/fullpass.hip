@@ -28,10 +28,13 @@
 // Algorithmic HBM bytes: dosage pass 10 * K * G (1 B code + 4 B alpha store
 // forward; 1 B code + 4 B alpha load backward), ranking pass (1 + 0.1 * 8) * 2 * K * G.
 #include "fullpass_dev.hpp"
+#include "fullpass_testhook.h"
+#include "pass_layout.hpp"
 
 #include <algorithm>
 #include <chrono>
 #include <cmath>
+#include <functional>
 #include <memory>
 #include <utility>
 
@@ -839,18 +842,20 @@ namespace {
 
 thread_local double g_timing[6] = {0, 0, 0, 0, 0, 0};   // emat, forward, backward, dosage, separate top-K, total
 
-// Three families of kernels run a pass:
-//   KIND_F32       fp32 state (k_fwd / k_bwd<float>): the dosage passes, any output
-//   KIND_F64_RANK  fp64 state, the reference's lazy normalisation, fused top-K (fullpass64.hip): best-haplotype lists only
-//   KIND_F64_DOS   fp64 state, the reference's lazy normalisation, alpha stored at every second grid (k_bwd64d re-forms the
-//                  others: PassParams::fw_add), gamma histogram for the dosage
-//                  (k_fwd64 + k_bwd64d, fullpass64.hip): the DOSAGE passes of qa_panel_set_dosage_precision(64)
-//   KIND_F64_FULL  fp64 state through the generic kernels (k_fwd / k_bwd<double>, one wave per SIMD): any output in
-//                  double (alphaHat_t / betaHat_t / gamma_t of the single-pass entry point in that mode); not tuned (it spills)
-//   KIND_F64_REF   VALIDATION MODE (qa_panel_set_sum_order(panel, 1), fullpass_ref.hip): fp64 state, the reference's lazy
-//                  normalisation, every K-wide sum added in the reference's order by one lane; any output; slow on purpose
-enum PassKind { KIND_F32 = 0, KIND_F64_RANK = 1, KIND_F64_FULL = 2, KIND_F64_DOS = 3, KIND_F64_REF = 4 };
-struct Geometry { int NT, NCH; PassKind kind; bool f64() const { return kind != KIND_F32; } };
+// (the kinds of kernels that run a pass -- PassKind -- and the launch Geometry: pass_layout.hpp)
+using qa::PassKind; using qa::KIND_F32; using qa::KIND_F64_RANK; using qa::KIND_F64_FULL; using qa::KIND_F64_DOS; using qa::KIND_F64_REF;
+using qa::Geometry; using qa::PanelDims; using qa::PassLayout; using qa::Thin;
+static_assert(qa::kLayoutMaxRow == kMaxRow, "pass_layout.hpp sizes emat / mg rows of kMaxRow");
+
+// what a kind is called in messages, and its rows in the kernel profile
+struct KindInfo { const char *name; int pk_fwd, pk_bwd; };
+constexpr KindInfo kKindInfo[qa::KIND_COUNT] = {
+    /* KIND_F32      */ {"fp32", qa::PK_FWD, qa::PK_BWD},
+    /* KIND_F64_RANK */ {"fp64 ranking", qa::PK_FWD64, qa::PK_BWD64},
+    /* KIND_F64_FULL */ {"generic fp64", qa::PK_FWD64G, qa::PK_BWD64G},
+    /* KIND_F64_DOS  */ {"fp64 dosage", qa::PK_FWD64D, qa::PK_BWD64D},
+    /* KIND_F64_REF  */ {"reference-order validation", qa::PK_FWD64G, qa::PK_BWD64G},
+};
 
 // Register-resident geometry: NT threads (multiple of 64) x NCH chunks of 16 haplotypes per lane.  fp32 state:
 // NT <= 512 so that each wave may use 256 VGPRs.  The smallest NCH that covers K gives the most waves; tiny panels
@@ -882,27 +887,24 @@ Geometry pick_geometry(int K, PassKind kind = KIND_F32) {
 }
 
 
-// device bytes one pass needs in run_passes (mirrors its carves, with alignment slack)
-size_t pass_bytes(const qa_panel *pn, const Geometry &geo, int n_thin, bool stores_all, bool gamma, bool beta,
-                  bool device_gl, bool gamma_col = false) {
-    const size_t Kq = (size_t)geo.NT * geo.NCH * 16, G = pn->G, T = pn->T, es = geo.f64() ? 8 : 4;
-    const size_t cols = stores_all ? G : (size_t)std::max(n_thin, 1);
-    (void)device_gl;
-    const size_t nsp = (size_t)pn->n_special + 16 * (size_t)pn->n_sp_grids + 16;
-    const size_t col = geo.kind == KIND_F64_DOS ? qa::fb64_alpha_col_elems(pn->K) : Kq;
-    size_t b = T * 16 + G * 4 + G * kMaxRow * (es + 8) + 8 + nsp * (es + 8) + cols * col * es + G * 16 + T * 8;
-    if (gamma) b += G * Kq * es;
-    if (beta) b += G * Kq * es;
-    if (gamma_col) b += Kq * 8;
-    if (n_thin > 0) b += (size_t)n_thin * Kq * es + (size_t)n_thin * (4 + 8 + 64 * 12);   // (lists of up to 64 entries)
-    if (geo.kind == KIND_F64_RANK || geo.kind == KIND_F64_DOS) b += (size_t)qa::fb64_spill_rows(pn->K) * 8192 * 8;   // streamed chunk rows
-    if (geo.kind == KIND_F64_REF) b += qa::fb_ref_state_doubles((int)Kq) * 8;   // state + gamma column in k order
-    return b + 256 * 24;
+// the calling thread's last launch set as planned and as carved (fullpass_testhook.h)
+struct LastPlan { int64_t P = 0, per_pass = 0, fixed = 0, carved = 0, kind = 0; };
+thread_local LastPlan g_last_plan;
+
+PanelDims dims_of(const qa_panel *pn) { return {pn->K, pn->G, pn->T, pn->n_special, pn->n_sp_grids}; }
+
+// the plan of a launch set of passes that all carry `flag`: bytes per pass
+size_t plan_pass_bytes(const qa_panel *pn, const Geometry &geo, int32_t flag, const Thin &thin, int K_top, int top_cap = 64,
+                       bool gamma_col = false) {
+    return PassLayout(dims_of(pn), geo, qa::make_request(&flag, 1, thin, K_top, top_cap, gamma_col)).pass_bytes(qa::Arena::kCarveAlign);
 }
 
-// how many homogeneous passes fit, and make the arena big enough for them
-int plan_chunk(qa_panel *pn, size_t per_pass, int remaining) {
-    const size_t fixed = (size_t)pn->G * 8 + ((size_t)2 << 20);
+// how many homogeneous passes fit, and make the arena big enough for them.  The fixed term pays for what a launch set carves
+// once (pass_layout.hpp lists it); extra_fixed: the single-pass entry's un-permute staging.
+int plan_chunk(qa_panel *pn, size_t per_pass, int remaining, size_t extra_fixed = 0) {
+    const size_t fixed = (size_t)pn->G * 8 + ((size_t)2 << 20) + extra_fixed;
+    g_last_plan.per_pass = (int64_t)per_pass;
+    g_last_plan.fixed = (int64_t)fixed;
     const size_t budget = pn->plan_budget();
     long n = budget > fixed ? (long)((budget - fixed) / per_pass) : 0;
     n = std::max<long>(1, std::min<long>(n, remaining));
@@ -992,6 +994,34 @@ PassKind dosage_kind(const qa_panel *pn) {
 // the kernels behind the best-haplotype lists of a handle with fp64 ranking
 PassKind rank_kind(const qa_panel *pn) { return pn->sum_order_ref ? KIND_F64_REF : KIND_F64_RANK; }
 
+// Which kernels serve a request on this handle.  The tuned fp64 dosage kernels yield the dosage (and c) only, and the fp64
+// ranking kernels the lists only; every other kind yields anything.
+struct KindChoice {
+    PassKind dosage;   // the passes that yield the dosage (single-pass entry: and the K x nGrids matrices)
+    PassKind lists;    // the passes that yield best-haplotype lists only
+    bool one_pass;     // a pass that wants dosage and lists gets both from `dosage`; else it runs once with each kind
+};
+enum KindCaller { FOR_SINGLE_PASS, FOR_GL_BATCH, FOR_READS_BATCH };
+KindChoice choose_kinds(const qa_panel *pn, KindCaller who, bool want_dosage, bool want_lists, bool want_matrices) {
+    const bool rank64 = pn->rank_fp64 && want_lists;   // lists whose membership and order are the reference's: fp64 state
+    PassKind d = dosage_kind(pn);
+    if (who == FOR_SINGLE_PASS) {
+        // a call that wants alpha / beta / gamma matrices, or no dosage, takes the generic fp64 kernels
+        if (d == KIND_F64_DOS && (want_matrices || !want_dosage)) d = KIND_F64_FULL;
+        if (d == KIND_F64_DOS) return {d, pn->rank_fp64 ? rank_kind(pn) : KIND_F32, false};
+        if (rank64 && d == KIND_F32) return {d, rank_kind(pn), false};   // every other output comes from the fp32 pass
+        return {d, d, true};   // fp32 state with fp32 ranking, or fp64 state through the generic / validation kernels
+    }
+    // the batched drivers: with fp32 ranking the lists come from the dosage pass itself
+    if (d == KIND_F64_DOS && want_lists && !pn->rank_fp64) d = KIND_F64_FULL;
+    // fp64 ranking passes beside the dosage passes (fp32 state, or the fp64 dosage kernels); with the generic fp64 kernels,
+    // or fp32 ranking, one pass yields both
+    if (rank64 && d != KIND_F64_FULL) return {d, rank_kind(pn), false};
+    if (who == FOR_READS_BATCH) return {d, pn->rank_fp64 ? rank_kind(pn) : KIND_F32, true};
+    // (list-only passes of the fp64-dosage mode still take the faster ranking kernels)
+    return {d, rank64 && pick_geometry(pn->K, rank_kind(pn)).NT ? rank_kind(pn) : d, true};
+}
+
 struct BatchOut {
     double *dosage = nullptr;        // [P][T] (row p, or dosage_rows[p] when given)
     const int32_t *dosage_rows = nullptr;
@@ -1008,8 +1038,8 @@ struct BatchOut {
     // truncating drivers: the device arrays as they are, [P][n_thin][top_cap], instead of `lists`
     std::vector<int32_t> *flat_idx = nullptr;
     std::vector<double> *flat_val = nullptr;
-    bool order_by_value = false;
-    std::vector<int32_t> *true_counts = nullptr;   // untruncated list lengths  // lists ordered as everything_per_hap_rejig_haps wants (else ascending k)
+    bool order_by_value = false;   // lists ordered as everything_per_hap_rejig_haps wants (else ascending k)
+    std::vector<int32_t> *true_counts = nullptr;   // untruncated list lengths
     // hla_run: gamma_t_col of grid gamma_grid for every pass (fp64 dosage or validation passes), K doubles to row gamma_rows[p]
     // (p when null) of gamma_col
     double *gamma_col = nullptr;
@@ -1017,23 +1047,29 @@ struct BatchOut {
     const int32_t *gamma_rows = nullptr;
 };
 
-// runs P passes; flags per pass as in PassParams
-int run_passes(qa_panel *pn, int P, const double *gl, const int32_t *h_flags, const int32_t *thin_col_h,
-               int K_top, int normalize_emissions, const BatchOut &out, PassKind kind = KIND_F32,
-               int always_normalize = 0, double norm_threshold = 1e-100) {
-    if (K_top > kMaxTop) {
-        qa::set_error("K_top_matches = %d > %d not supported", K_top, kMaxTop);
-        return QA_ERR_UNSUPPORTED;
-    }
-    const Geometry geo = pick_geometry(pn->K, kind);
-    if (geo.NT == 0) {
-        qa::set_error("K = %d exceeds the on-chip capacity of the %s full-pass kernels", pn->K,
-                      kind == KIND_F32 ? "fp32" : kind == KIND_F64_RANK ? "fp64 ranking" : kind == KIND_F64_DOS ? "fp64 dosage" :
-                      kind == KIND_F64_REF ? "reference-order validation" : "generic fp64");
-        return QA_ERR_UNSUPPORTED;
-    }
-    const bool f64 = geo.f64();
-    const size_t es = f64 ? 8 : 4;
+// ---- run_passes, stage by stage.  What the stages of one call share:
+struct PassRun {
+    qa_panel *pn;
+    qa_panel::Scratch &S;
+    hipStream_t st;
+    int P;
+    const int32_t *h_flags, *thin_col_h;   // per pass as in PassParams::flags; per grid
+    const BatchOut &out;
+    Geometry geo;
+    PassLayout L;
+    int n_thin;
+    bool any_top;   // lists wanted
+    bool fused;     // ... and the fp64 ranking kernels pick them themselves: only the ordered head of each list is wanted (the driver)
+    int top_cap;
+    PassParams prm;
+    bool dosage_direct = false;   // k_dosage writes the caller's rows itself
+    std::vector<int32_t> cnt;     // [P][n_thin] list lengths
+    int n_handed_over = 0;        // fused: lists left to k_topk
+    size_t es() const { return L.es; }
+};
+
+// the request against what the kind can yield
+void check_request(const qa_panel *pn, PassKind kind, int P, const int32_t *h_flags, int K_top, const BatchOut &out) {
     if (kind == KIND_F64_RANK)
         for (int p = 0; p < P; p++)
             if (h_flags[p] & 15) throw std::runtime_error("fp64 ranking passes carry no dosage / gamma / beta outputs");
@@ -1048,172 +1084,193 @@ int run_passes(qa_panel *pn, int P, const double *gl, const int32_t *h_flags, co
             if (!(h_flags[p] & 1) || (h_flags[p] & 12)) throw std::runtime_error("fp64 dosage passes yield the dosage (and c) only");
         if (K_top > 0) throw std::runtime_error("fp64 dosage passes carry no best-haplotype lists (the ranking passes do)");
     }
-    QA_HIP(hipSetDevice(pn->device));
-    if (!pn->scratch) pn->scratch = new qa_panel::Scratch(&pn->A());
-    auto &S = *pn->scratch;
-    hipStream_t st = pn->pass_stream ? pn->pass_stream : pn->stream;
-    for (auto &e : S.ev) if (!e) QA_HIP(hipEventCreate(&e));
-    const int G = pn->G, T = pn->T, K = pn->K;
-    const int Kq = geo.NT * geo.NCH * 16;
-    int n_thin = 0;
-    for (int g = 0; g < G; g++) if (thin_col_h[g] >= 0) n_thin = std::max(n_thin, thin_col_h[g] + 1);
+}
 
-    // alpha checkpoint slots: all grids for dosage / gamma / beta passes, thinned grids otherwise
+// alpha checkpoint slots [P][G]: all grids for dosage / gamma / beta passes, thinned grids otherwise (the column counts:
+// PassLayout::alpha_cols)
+std::vector<int32_t> plan_alpha_slots(const PassRun &r) {
+    const int P = r.P, G = r.pn->G;
     std::vector<int32_t> slot((size_t)P * G, -1);
-    size_t max_cols = 0;
-    bool any_gamma = false, any_beta = false;
     for (int p = 0; p < P; p++) {
-        const int f = h_flags[p];
-        size_t cols;
-        if ((f & 15) && kind == KIND_F64_DOS) {   // every second column: k_bwd64d re-forms the odd grids' (PassParams::fw_add)
-            for (int g = 0; g < G; g += 2) slot[(size_t)p * G + g] = g / 2;
-            cols = (G + 1) / 2;
-        } else if (f & 15) {
-            for (int g = 0; g < G; g++) slot[(size_t)p * G + g] = g;
-            cols = G;
+        int32_t *sl = slot.data() + (size_t)p * G;
+        if ((r.h_flags[p] & 15) && r.geo.kind == KIND_F64_DOS) {   // every second column: k_bwd64d re-forms the odd grids' (PassParams::fw_add)
+            for (int g = 0; g < G; g += 2) sl[g] = g / 2;
+        } else if (r.h_flags[p] & 15) {
+            for (int g = 0; g < G; g++) sl[g] = g;
         } else {
             int n = 0;
-            for (int g = 0; g < G; g++) if (thin_col_h[g] >= 0) slot[(size_t)p * G + g] = n++;
-            cols = std::max(n, 1);
+            for (int g = 0; g < G; g++) if (r.thin_col_h[g] >= 0) sl[g] = n++;
         }
-        max_cols = std::max(max_cols, cols);
-        any_gamma |= (f & 4) != 0;
-        any_beta |= (f & 8) != 0;
     }
-    const bool any_top = n_thin > 0 && K_top > 0;
-    // the fp64 ranking kernels pick the lists themselves when only the ordered head of each list is wanted (the driver)
-    const bool fused = any_top && kind == KIND_F64_RANK && out.truncate_lists && out.top_cap <= 64;
-    const size_t alpha_col = kind == KIND_F64_DOS ? qa::fb64_alpha_col_elems(K) : (size_t)Kq;
-    const size_t alpha_stride = max_cols * alpha_col;
-    const bool lazy = kind == KIND_F64_RANK || kind == KIND_F64_DOS || kind == KIND_F64_REF;
-    const size_t esp_stride = (size_t)pn->n_special + (lazy ? 16 * (size_t)pn->n_sp_grids : 0) + 16;
+    return slot;
+}
 
-    if (gl) {   // host gl; otherwise the caller has filled S.gl on the device already (k_make_gl)
-        S.gl.ensure((size_t)P * T * 2);
-        S.gl.upload(gl, (size_t)P * T * 2, st);
-    }
-    S.thin_col.ensure(G);
-    S.thin_col.upload(thin_col_h, G, st);
-    S.flags.ensure(P);
-    S.flags.upload(h_flags, P, st);
-    S.alpha_slot.ensure((size_t)P * G);
-    S.alpha_slot.upload(slot.data(), (size_t)P * G, st);
-    S.emat.ensure((size_t)P * G * kMaxRow * es);
-    S.escale0.ensure(P);
-    S.emin.ensure((size_t)P * G);
-    S.emin_b1.ensure(P);
-    S.esp.ensure((size_t)P * esp_stride * es);
-    S.gsp.ensure(std::max<size_t>((size_t)P * pn->n_special, 1) * es);
-    S.alpha.ensure((size_t)P * alpha_stride * es + ((size_t)1 << 20));   // (slack: k_bwd64d's idle lanes fetch a fixed line past a short column)
-    S.c.ensure((size_t)P * G);
-    if (kind == KIND_F64_DOS) { S.fw_add.ensure((size_t)P * G); S.fw_xs.ensure((size_t)P * G); }
-    S.mg.ensure((size_t)P * G * kMaxRow * (f64 ? 8 : 4));
-    S.dosage.ensure((size_t)P * T);
-    if (any_gamma) S.gamma.ensure((size_t)P * G * Kq * es);
-    if (any_beta) S.beta.ensure((size_t)P * G * Kq * es);
-    if (any_top) S.beta_thin.ensure((size_t)P * n_thin * Kq * es);
-    if (out.gamma_col) S.gamma_col.ensure((size_t)P * Kq);
-    int top_cap = out.top_cap;
-    S.top_cnt.ensure(std::max<size_t>((size_t)P * std::max(n_thin, 1), 1));
-    const size_t spill_stride = kind == KIND_F64_REF ? qa::fb_ref_state_doubles(Kq)   // the validation kernels' state (when not in LDS)
-                                : lazy ? (size_t)qa::fb64_spill_rows(K) * 8192 : 0;   // doubles per pass: chunk rows streamed through HBM
-    if (spill_stride) S.spill.ensure((size_t)P * spill_stride);
+// the only way a Scratch buffer gets its memory: buffer b of the layout, for P passes
+template <typename T>
+void carve(qa::ABuf<T> &buf, const PassLayout &L, PassLayout::Buf b, int P) { buf.ensure(L.bytes(b, P) / sizeof(T)); }
 
-    PassParams prm{};
+// every buffer of the layout in its order (a buffer the launch set does not use has no elements and stays null); gl: only
+// for a host gl, else the caller has carved and filled S.gl on the device already (k_make_gl)
+void carve_scratch(qa_panel::Scratch &S, const PassLayout &L, int P, bool gl) {
+    using B = PassLayout;
+    if (gl) carve(S.gl, L, B::GL, P);
+    carve(S.thin_col, L, B::THIN_COL, P);
+    carve(S.flags, L, B::FLAGS, P);
+    carve(S.alpha_slot, L, B::ALPHA_SLOT, P);
+    carve(S.emat, L, B::EMAT, P);
+    carve(S.escale0, L, B::ESCALE0, P);
+    carve(S.emin, L, B::EMIN, P);
+    carve(S.emin_b1, L, B::EMIN_B1, P);
+    carve(S.esp, L, B::ESP, P);
+    carve(S.gsp, L, B::GSP, P);
+    carve(S.alpha, L, B::ALPHA, P);
+    carve(S.c, L, B::C, P);
+    carve(S.fw_add, L, B::FW_ADD, P);
+    carve(S.fw_xs, L, B::FW_XS, P);
+    carve(S.mg, L, B::MG, P);
+    carve(S.dosage, L, B::DOSAGE, P);
+    carve(S.gamma, L, B::GAMMA, P);
+    carve(S.beta, L, B::BETA, P);
+    carve(S.beta_thin, L, B::BETA_THIN, P);
+    carve(S.gamma_col, L, B::GAMMA_COL, P);
+    carve(S.top_cnt, L, B::TOP_CNT, P);
+    carve(S.spill, L, B::SPILL, P);
+    carve(S.top_idx, L, B::TOP_IDX, P);
+    carve(S.top_val, L, B::TOP_VAL, P);
+}
+
+void fill_params(PassRun &r, int K_top, int normalize_emissions, int always_normalize, double norm_threshold) {
+    const qa_panel *pn = r.pn;
+    const auto &S = r.S;
+    const PassLayout &L = r.L;
+    const PassKind kind = r.geo.kind;
+    PassParams &prm = r.prm;
+    prm = PassParams{};
     prm.hm = pn->hm.p; prm.B = pn->B.p; prm.sp_off = pn->sp_off.p; prm.sp_k = pn->sp_k.p;
     prm.sp_word = pn->sp_word.p; prm.sp_gidx = pn->sp_gidx.p; prm.sp_chunk_at = pn->sp_chunk_at.p;
     prm.sigma = pn->sigma.p; prm.tm1 = pn->tm1.p; prm.IE = pn->ie_derived ? nullptr : pn->IE.p;
-    prm.K = K; prm.Kp = pn->Kp; prm.G = G; prm.T = T; prm.nMaxDH = pn->nMaxDH; prm.nrow = pn->nrow;
+    prm.K = pn->K; prm.Kp = pn->Kp; prm.G = pn->G; prm.T = pn->T; prm.nMaxDH = pn->nMaxDH; prm.nrow = pn->nrow;
     prm.n_special = pn->n_special; prm.ref_error = pn->ref_error;
-    prm.P = P; prm.gl = S.gl.p; prm.thin_col = S.thin_col.p; prm.n_thin = n_thin; prm.flags = S.flags.p;
+    prm.P = r.P; prm.gl = S.gl.p; prm.thin_col = S.thin_col.p; prm.n_thin = r.n_thin; prm.flags = S.flags.p;
     prm.normalize_emissions = normalize_emissions;
-    prm.lazy = lazy ? 1 : 0; prm.always_normalize = always_normalize; prm.norm_threshold = norm_threshold;
+    prm.lazy = qa::lazy_kind(kind) ? 1 : 0; prm.always_normalize = always_normalize; prm.norm_threshold = norm_threshold;
     prm.grid0_left_to_right = pn->sum_order_grid0_ltr ? 1 : 0;
-    prm.emin = S.emin.p; prm.emin_b1 = S.emin_b1.p; prm.esp_stride = (int)esp_stride;
+    prm.emin = S.emin.p; prm.emin_b1 = S.emin_b1.p; prm.esp_stride = (int)L.esp_stride;
 
-    prm.spill = spill_stride ? S.spill.p : nullptr; prm.spill_pass_stride = spill_stride;
-    prm.fw_add = kind == KIND_F64_DOS ? S.fw_add.p : nullptr; prm.fw_xs = kind == KIND_F64_DOS ? S.fw_xs.p : nullptr;
+    // (a buffer the layout gave no elements is null)
+    prm.spill = S.spill.p; prm.spill_pass_stride = L.spill_stride;
+    prm.fw_add = S.fw_add.p; prm.fw_xs = S.fw_xs.p;
     prm.emat = S.emat.p; prm.esp = S.esp.p; prm.escale0 = S.escale0.p; prm.alpha = S.alpha.p; prm.alpha_slot = S.alpha_slot.p;
-    prm.alpha_pass_stride = alpha_stride; prm.Kq = Kq; prm.alpha_col_elems = alpha_col;
+    prm.alpha_pass_stride = L.alpha_cols * L.alpha_col_elems; prm.Kq = (int)L.Kq; prm.alpha_col_elems = L.alpha_col_elems;
     prm.hist_unit = kind == KIND_F64_DOS ? 1.0 / 2251799813685248.0 /* 2^-51: k_bwd64d */ : 1.0 / kHistScale64; prm.c = S.c.p; prm.mg = S.mg.p; prm.gsp = S.gsp.p;
-    prm.gamma_out = any_gamma ? S.gamma.p : nullptr; prm.beta_out = any_beta ? S.beta.p : nullptr;
-    prm.gamma_col = out.gamma_col ? S.gamma_col.p : nullptr; prm.gamma_grid = out.gamma_col ? out.gamma_grid : -1;
-    // Dosage rows that go to consecutive rows of a qa_host_alloc buffer are written there by k_dosage itself (every element
-    // once, 4 KiB of consecutive bytes per workgroup): the transfer rides under the kernel instead of following it.
-    bool dosage_direct = false;
+    prm.gamma_out = S.gamma.p; prm.beta_out = S.beta.p;
+    prm.gamma_col = S.gamma_col.p; prm.gamma_grid = r.out.gamma_col ? r.out.gamma_grid : -1;
+    prm.K_top = r.any_top ? K_top : 0;
+    prm.beta_thin = S.beta_thin.p;
+    prm.fused_topk = r.fused ? 1 : 0;
+    prm.top_cap = r.top_cap;
+    prm.truncate_lists = r.out.truncate_lists ? 1 : 0;
+    if (r.any_top) { prm.top_cnt = S.top_cnt.p; prm.top_idx = S.top_idx.p; prm.top_val = S.top_val.p; }
+}
+
+// Dosage rows that go to consecutive rows of a qa_host_alloc buffer are written there by k_dosage itself (every element
+// once, 4 KiB of consecutive bytes per workgroup): the transfer rides under the kernel instead of following it.  Else
+// the staging rows of the scratch.
+void choose_dosage_destination(PassRun &r) {
+    const BatchOut &out = r.out;
+    const int P = r.P, T = r.pn->T;
+    bool direct = false;
     if (out.dosage && P > 0) {
         const size_t r0 = out.dosage_rows ? (size_t)out.dosage_rows[0] : 0;
-        dosage_direct = true;
-        for (int p = 0; p < P && dosage_direct; p++)
-            dosage_direct = (h_flags[p] & 1) && (out.dosage_rows ? (size_t)out.dosage_rows[p] : (size_t)p) == r0 + (size_t)p;
-        dosage_direct = dosage_direct && qa::pinned_registry().covers(out.dosage + r0 * T, sizeof(double) * (size_t)P * T);
-        if (dosage_direct) prm.dosage = out.dosage + r0 * T;
+        direct = true;
+        for (int p = 0; p < P && direct; p++)
+            direct = (r.h_flags[p] & 1) && (out.dosage_rows ? (size_t)out.dosage_rows[p] : (size_t)p) == r0 + (size_t)p;
+        direct = direct && qa::pinned_registry().covers(out.dosage + r0 * T, sizeof(double) * (size_t)P * T);
+        if (direct) r.prm.dosage = out.dosage + r0 * T;
     }
-    if (!dosage_direct) prm.dosage = S.dosage.p;
-    prm.K_top = any_top ? K_top : 0;
-    prm.beta_thin = any_top ? S.beta_thin.p : nullptr;
-    prm.fused_topk = fused ? 1 : 0;
-    prm.top_cap = top_cap;
-    prm.truncate_lists = out.truncate_lists ? 1 : 0;
-    if (any_top) {
-        S.top_idx.ensure((size_t)P * n_thin * top_cap);
-        S.top_val.ensure((size_t)P * n_thin * top_cap * es);
-        prm.top_cnt = S.top_cnt.p; prm.top_idx = S.top_idx.p; prm.top_val = S.top_val.p;
-    }
+    if (!direct) r.prm.dosage = r.S.dosage.p;
+    r.dosage_direct = direct;
+}
 
+// emission tables, forward / backward, dosage: events 0 .. 4 around them
+void launch_passes(PassRun &r) {
+    auto &S = r.S;
+    const PassParams &prm = r.prm;
+    const int P = r.P, G = r.pn->G;
+    const bool f64 = r.geo.f64();
+    hipStream_t st = r.st;
     QA_HIP(hipEventRecord(S.ev[0], st));
     if (f64) hipLaunchKernelGGL(k_emat<double>, dim3(G, P), dim3(256), 0, st, prm);
     else hipLaunchKernelGGL(k_emat<float>, dim3(G, P), dim3(256), 0, st, prm);
     QA_HIP(hipGetLastError());
     QA_HIP(hipEventRecord(S.ev[1], st));
-    launch_fb_any(geo, prm, st, S.ev[2]);
+    launch_fb_any(r.geo, prm, st, S.ev[2]);
     QA_HIP(hipEventRecord(S.ev[3], st));
     const dim3 dgrid((G + kDosageGridsPerBlock - 1) / kDosageGridsPerBlock, P);
-    if (kind == KIND_F64_REF) { /* the validation backward kernel wrote the dosage itself, sums in the reference's order */ }
+    if (r.geo.kind == KIND_F64_REF) { /* the validation backward kernel wrote the dosage itself, sums in the reference's order */ }
     else if (f64) hipLaunchKernelGGL(k_dosage<double>, dgrid, dim3(256), 0, st, prm);
     else hipLaunchKernelGGL(k_dosage<float>, dgrid, dim3(256), 0, st, prm);
     QA_HIP(hipGetLastError());
     QA_HIP(hipEventRecord(S.ev[4], st));
-    std::vector<int32_t> cnt;
-    int n_handed_over = 0;
-    if (fused) {
-        // the backward kernel wrote the lists; the grids whose candidates overflowed its LDS list (top_cnt = -1: ties)
-        // left their beta column for k_topk
-        cnt.resize((size_t)P * n_thin);
-        S.top_cnt.download(cnt.data(), cnt.size(), st);
-        std::vector<int32_t> todo;
-        for (size_t i = 0; i < cnt.size(); i++)
-            if (cnt[i] < 0) { todo.push_back((int32_t)(i / n_thin)); todo.push_back((int32_t)(i % n_thin)); }
-        n_handed_over = (int)todo.size() / 2;
-        if (n_handed_over) {
-            S.todo.ensure(todo.size());
-            S.todo.upload(todo.data(), todo.size(), st);
-            prm.topk_todo = S.todo.p;
-            hipLaunchKernelGGL(k_topk<double>, dim3(n_handed_over), dim3(256), 0, st, prm, geo.NT);
-            QA_HIP(hipGetLastError());
-            S.top_cnt.download(cnt.data(), cnt.size(), st);
-            QA_HIP(hipStreamSynchronize(st));
-            prm.topk_todo = nullptr;
+}
+
+// fused: the backward kernel wrote the lists; the grids whose candidates overflowed its LDS list (top_cnt = -1: ties)
+// left their beta column for k_topk
+void finish_fused_lists(PassRun &r) {
+    auto &S = r.S;
+    PassParams &prm = r.prm;
+    hipStream_t st = r.st;
+    const int n_thin = r.n_thin;
+    r.cnt.resize((size_t)r.P * n_thin);
+    S.top_cnt.download(r.cnt.data(), r.cnt.size(), st);
+    std::vector<int32_t> todo;
+    for (size_t i = 0; i < r.cnt.size(); i++)
+        if (r.cnt[i] < 0) { todo.push_back((int32_t)(i / n_thin)); todo.push_back((int32_t)(i % n_thin)); }
+    r.n_handed_over = (int)todo.size() / 2;
+    if (!r.n_handed_over) return;
+    S.todo.ensure(todo.size());
+    S.todo.upload(todo.data(), todo.size(), st);
+    prm.topk_todo = S.todo.p;
+    hipLaunchKernelGGL(k_topk<double>, dim3(r.n_handed_over), dim3(256), 0, st, prm, r.geo.NT);
+    QA_HIP(hipGetLastError());
+    S.top_cnt.download(r.cnt.data(), r.cnt.size(), st);
+    QA_HIP(hipStreamSynchronize(st));
+    prm.topk_todo = nullptr;
+}
+
+// the separate picker over every (thinned column, pass); not truncating: once more with room for the longest list
+void pick_lists_separately(PassRun &r) {
+    auto &S = r.S;
+    PassParams &prm = r.prm;
+    hipStream_t st = r.st;
+    const int P = r.P, n_thin = r.n_thin;
+    for (int attempt = 0; attempt < 2; attempt++) {
+        if (attempt) {   // (outside the per-pass plan: pass_layout.hpp)
+            r.L.set_top_cap(r.top_cap, n_thin);
+            carve(S.top_idx, r.L, PassLayout::TOP_IDX, P);
+            carve(S.top_val, r.L, PassLayout::TOP_VAL, P);
         }
-    }
-    for (int attempt = 0; any_top && !fused && attempt < 2; attempt++) {
-        prm.top_cap = top_cap;
-        S.top_idx.ensure((size_t)P * n_thin * top_cap);
-        S.top_val.ensure((size_t)P * n_thin * top_cap * es);
+        prm.top_cap = r.top_cap;
         prm.top_cnt = S.top_cnt.p; prm.top_idx = S.top_idx.p; prm.top_val = S.top_val.p;
-        if (f64) hipLaunchKernelGGL(k_topk<double>, dim3(n_thin, P), dim3(256), 0, st, prm, geo.NT);
-        else hipLaunchKernelGGL(k_topk<float>, dim3(n_thin, P), dim3(256), 0, st, prm, geo.NT);
+        if (r.geo.f64()) hipLaunchKernelGGL(k_topk<double>, dim3(n_thin, P), dim3(256), 0, st, prm, r.geo.NT);
+        else hipLaunchKernelGGL(k_topk<float>, dim3(n_thin, P), dim3(256), 0, st, prm, r.geo.NT);
         QA_HIP(hipGetLastError());
-        cnt.resize((size_t)P * n_thin);
-        S.top_cnt.download(cnt.data(), cnt.size(), st);
+        r.cnt.resize((size_t)P * n_thin);
+        S.top_cnt.download(r.cnt.data(), r.cnt.size(), st);
         QA_HIP(hipStreamSynchronize(st));
         int mx = 0;
-        for (int32_t v : cnt) mx = std::max(mx, v);
-        if (mx <= top_cap || out.truncate_lists) break;
-        top_cap = mx;  // pathological ties (e.g. a label without reads): redo with room for all
+        for (int32_t v : r.cnt) mx = std::max(mx, v);
+        if (mx <= r.top_cap || r.out.truncate_lists) break;
+        r.top_cap = mx;  // pathological ties (e.g. a label without reads): redo with room for all
     }
-    QA_HIP(hipEventRecord(S.ev[5], st));
-    QA_HIP(hipStreamSynchronize(st));
+}
+
+// event times into g_timing, and the launch set's rows of the kernel profile
+void add_profile_rows(const PassRun &r) {
+    const auto &S = r.S;
+    const int P = r.P, G = r.pn->G, T = r.pn->T, K = r.pn->K, n_thin = r.n_thin;
+    const size_t es = r.es();
+    const PassKind kind = r.geo.kind;
     float ms;
     for (int i = 0; i < 5; i++) {
         QA_HIP(hipEventElapsedTime(&ms, S.ev[i], S.ev[i + 1]));
@@ -1221,146 +1278,216 @@ int run_passes(qa_panel *pn, int P, const double *gl, const int32_t *h_flags, co
     }
     QA_HIP(hipEventElapsedTime(&ms, S.ev[0], S.ev[5]));
     g_timing[5] = ms;
-    {
-        // algorithmic HBM bytes of this launch set: per cell 1 B code + one state element
-        // (4 B, or 8 B with fp64 state) on every stored column, forward (alpha) and backward (alpha re-read) alike;
-        // the separate top-K picker re-reads alpha and beta at the thinned grids twice (outside the SURVEY contract:
-        // it is what the fused picker of the fp64 ranking kernels removes); k_dosage reads the code histograms
-        double cells_all = 0, cells_thin = 0, n_dos = 0;
-        for (int p = 0; p < P; p++) {
-            if (h_flags[p] & 15) cells_all += (double)K * G; else cells_thin += (double)K * G;
-            if (h_flags[p] & 1) n_dos += 1;
-        }
-        const double frac = G > 0 ? (double)n_thin / G : 0;
-        const double per_dir = cells_all * (1.0 + es) + cells_thin * (1.0 + es * frac);
-        const double topk_bytes = (any_top && !fused) ? (double)P * n_thin * K * es * 4.0
-                                                      : (double)n_handed_over * K * es * 4.0;
-        const double t_e = qa::profile_clock_ms(S.ev[0]);
-        double at = t_e;
-        qa::profile_add(qa::PK_EMAT, g_timing[0], (double)P * T * 16.0 + (double)P * G * kMaxRow * es, at); at += g_timing[0];
-        const int pk_f = kind == KIND_F32 ? qa::PK_FWD : kind == KIND_F64_RANK ? qa::PK_FWD64 : kind == KIND_F64_DOS ? qa::PK_FWD64D : qa::PK_FWD64G;
-        const int pk_b = kind == KIND_F32 ? qa::PK_BWD : kind == KIND_F64_RANK ? qa::PK_BWD64 : kind == KIND_F64_DOS ? qa::PK_BWD64D : qa::PK_BWD64G;
-        // (the fp64 dosage forward stores every second column: half of the state bytes; its backward reads each stored column twice)
-        const double per_dir_fwd = kind == KIND_F64_DOS ? cells_all * (1.0 + es * 0.5) : per_dir;
-        qa::profile_add(pk_f, g_timing[1], per_dir_fwd, at); at += g_timing[1];
-        qa::profile_add(pk_b, g_timing[2], per_dir, at); at += g_timing[2];
-        if (n_dos > 0) qa::profile_add(qa::PK_DOSAGE, g_timing[3], n_dos * G * kMaxRow * (f64 ? 8.0 : 4.0) + n_dos * T * 8.0, at);
-        at += g_timing[3];
-        if (topk_bytes > 0) qa::profile_add(qa::PK_TOPK, g_timing[4], topk_bytes, at);
+    // algorithmic HBM bytes of this launch set: per cell 1 B code + one state element
+    // (4 B, or 8 B with fp64 state) on every stored column, forward (alpha) and backward (alpha re-read) alike;
+    // the separate top-K picker re-reads alpha and beta at the thinned grids twice (outside the SURVEY contract:
+    // it is what the fused picker of the fp64 ranking kernels removes); k_dosage reads the code histograms
+    double cells_all = 0, cells_thin = 0, n_dos = 0;
+    for (int p = 0; p < P; p++) {
+        if (r.h_flags[p] & 15) cells_all += (double)K * G; else cells_thin += (double)K * G;
+        if (r.h_flags[p] & 1) n_dos += 1;
     }
+    const double frac = G > 0 ? (double)n_thin / G : 0;
+    const double per_dir = cells_all * (1.0 + es) + cells_thin * (1.0 + es * frac);
+    const double topk_bytes = (r.any_top && !r.fused) ? (double)P * n_thin * K * es * 4.0
+                                                      : (double)r.n_handed_over * K * es * 4.0;
+    const double t_e = qa::profile_clock_ms(S.ev[0]);
+    double at = t_e;
+    qa::profile_add(qa::PK_EMAT, g_timing[0], (double)P * T * 16.0 + (double)P * G * kMaxRow * es, at); at += g_timing[0];
+    // (the fp64 dosage forward stores every second column: half of the state bytes; its backward reads each stored column twice)
+    const double per_dir_fwd = kind == KIND_F64_DOS ? cells_all * (1.0 + es * 0.5) : per_dir;
+    qa::profile_add(kKindInfo[kind].pk_fwd, g_timing[1], per_dir_fwd, at); at += g_timing[1];
+    qa::profile_add(kKindInfo[kind].pk_bwd, g_timing[2], per_dir, at); at += g_timing[2];
+    if (n_dos > 0) qa::profile_add(qa::PK_DOSAGE, g_timing[3], n_dos * G * kMaxRow * (r.geo.f64() ? 8.0 : 4.0) + n_dos * T * 8.0, at);
+    at += g_timing[3];
+    if (topk_bytes > 0) qa::profile_add(qa::PK_TOPK, g_timing[4], topk_bytes, at);
+}
+
+// rows of Kq (the kernels' 16-byte stores) -> rows of K: one 2-D copy per run of consecutive destination rows
+void download_gamma_column(const PassRun &r) {
+    const BatchOut &out = r.out;
+    const int P = r.P, K = r.pn->K;
+    const size_t Kq = r.L.Kq;
+    auto row_of = [&](int p) { return (size_t)(out.gamma_rows ? out.gamma_rows[p] : p); };
+    for (int p = 0; p < P;) {
+        int n = 1;
+        while (p + n < P && row_of(p + n) == row_of(p) + (size_t)n) n++;
+        QA_HIP(hipMemcpy2DAsync(out.gamma_col + row_of(p) * K, sizeof(double) * K, r.S.gamma_col.p + (size_t)p * Kq, sizeof(double) * Kq,
+                                sizeof(double) * K, n, hipMemcpyDeviceToHost, r.st));
+        p += n;
+    }
+    QA_HIP(hipStreamSynchronize(r.st));
+}
+
+// the staged dosage rows: runs of consecutive dosage passes come back in one staged transfer each, then scatter to their rows
+// (a run whose destination rows are consecutive too -- the batch calls' layout -- lands in the caller's buffer
+// directly: one transfer, staged piecewise or, for a qa_host_alloc buffer, written by the copy kernel itself)
+void download_dosage_rows(const PassRun &r) {
+    const BatchOut &out = r.out;
+    const int P = r.P, T = r.pn->T;
+    const int32_t *h_flags = r.h_flags;
+    const int max_rows = std::max<int>(1, (int)(qa::kStagePiece / (sizeof(double) * T)));
+    auto row_of = [&](int p) { return (size_t)(out.dosage_rows ? out.dosage_rows[p] : p); };
+    std::vector<double> tmp;
+    for (int p = 0; p < P;) {
+        if (!(h_flags[p] & 1)) { p++; continue; }
+        int n = 1;
+        while (p + n < P && (h_flags[p + n] & 1) && row_of(p + n) == row_of(p) + (size_t)n) n++;
+        if (n > 1 || max_rows == 1) {
+            qa::staged_download(out.dosage + row_of(p) * T, r.S.dosage.p + (size_t)p * T, sizeof(double) * T * n, r.st);
+            p += n;
+            continue;
+        }
+        while (p + n < P && n < max_rows && (h_flags[p + n] & 1)) n++;
+        tmp.resize((size_t)n * T);
+        qa::staged_download(tmp.data(), r.S.dosage.p + (size_t)p * T, sizeof(double) * T * n, r.st);
+        for (int i = 0; i < n; i++)
+            memcpy(out.dosage + row_of(p + i) * T, tmp.data() + (size_t)i * T, sizeof(double) * T);
+        p += n;
+    }
+}
+
+// single-pass entry: the K x nGrids matrices, un-permuted on the device through one staging buffer (K x G doubles: outside
+// the per-pass plan, pass_layout.hpp) that every matrix re-uses -- each transfer is complete before the next starts
+void download_matrices(PassRun &r, const std::vector<int32_t> &slot) {
+    const BatchOut &out = r.out;
+    if (!out.alphaHat_t && !out.gamma_t && !out.betaHat_t && !out.gammaSmall_t) return;
+    auto &S = r.S;
+    const qa_panel *pn = r.pn;
+    const int G = pn->G, K = pn->K, Kq = (int)r.L.Kq;
+    const bool any_gamma = S.gamma.p != nullptr, any_beta = S.beta.p != nullptr;
+    S.unperm.ensure((size_t)K * G);
+    auto unpermute_to_host = [&](const char *base, size_t elem_off, int cols, double *dst) {
+        if (r.geo.f64())
+            hipLaunchKernelGGL(k_unpermute<double>, dim3((K + 255) / 256, cols), dim3(256), 0, r.st,
+                               reinterpret_cast<const double *>(base) + elem_off, S.unperm.p, K, Kq, r.geo.NT, cols, (size_t)K);
+        else
+            hipLaunchKernelGGL(k_unpermute<float>, dim3((K + 255) / 256, cols), dim3(256), 0, r.st,
+                               reinterpret_cast<const float *>(base) + elem_off, S.unperm.p, K, Kq, r.geo.NT, cols, (size_t)K);
+        QA_HIP(hipGetLastError());
+        S.unperm.download(dst, (size_t)K * cols, r.st);
+        QA_HIP(hipStreamSynchronize(r.st));
+    };
+    if (out.alphaHat_t) {
+        if (r.h_flags[0] & 15) {
+            unpermute_to_host(S.alpha.p, 0, G, out.alphaHat_t);
+        } else {
+            // only column 0 and the thinned columns exist (reference-single.cpp:2264-2268)
+            std::vector<double> col(K);
+            for (int g = 0; g < G; g++) {
+                const int sl = slot[g];
+                if (sl < 0) continue;
+                unpermute_to_host(S.alpha.p, (size_t)sl * Kq, 1, col.data());
+                memcpy(out.alphaHat_t + (size_t)g * K, col.data(), sizeof(double) * K);
+            }
+        }
+    }
+    if (out.gamma_t && any_gamma) unpermute_to_host(S.gamma.p, 0, G, out.gamma_t);
+    if (out.betaHat_t && any_beta) unpermute_to_host(S.beta.p, 0, G, out.betaHat_t);
+    if (out.gammaSmall_t && any_gamma) {
+        std::vector<double> col(K);
+        for (int g = 0; g < G; g++) {
+            if (r.thin_col_h[g] < 0) continue;
+            unpermute_to_host(S.gamma.p, (size_t)g * Kq, 1, col.data());
+            if (out.gamma_small_unscaled && g < G - 1)
+                for (int k = 0; k < K; k++) col[k] /= pn->h_sigma[g];
+            memcpy(out.gammaSmall_t + (size_t)r.thin_col_h[g] * K, col.data(), sizeof(double) * K);
+        }
+    }
+}
+
+// the lists to the caller: the device arrays as they are (flat_idx / flat_val) and / or list by list
+void collect_lists(const PassRun &r) {
+    const BatchOut &out = r.out;
+    const int top_cap = r.top_cap;
+    if (out.true_counts) *out.true_counts = r.cnt;
+    if (!out.lists && !out.flat_idx) return;
+    const size_t n = (size_t)r.P * r.n_thin;
+    std::vector<int32_t> idx_local;
+    std::vector<double> val_local;
+    std::vector<int32_t> &idx = out.flat_idx ? *out.flat_idx : idx_local;
+    std::vector<double> &val = out.flat_val ? *out.flat_val : val_local;
+    idx.resize(n * top_cap);
+    val.resize(n * top_cap);
+    r.S.top_idx.download(idx.data(), idx.size(), r.st);
+    if (r.geo.f64()) {
+        qa::staged_download(val.data(), r.S.top_val.p, val.size() * 8, r.st);
+    } else {
+        std::vector<float> v32(val.size());
+        qa::staged_download(v32.data(), r.S.top_val.p, v32.size() * 4, r.st);
+        for (size_t i = 0; i < val.size(); i++) val[i] = v32[i];
+    }
+    for (size_t i = 0; out.lists && i < n; i++) {
+        std::vector<std::pair<int32_t, double>> tmp;
+        const int nq = std::min<int>(r.cnt[i], top_cap);
+        tmp.reserve(nq);
+        for (int q = 0; q < nq; q++) tmp.emplace_back(idx[i * top_cap + q], val[i * top_cap + q]);
+        if (!out.order_by_value) {
+            std::sort(tmp.begin(), tmp.end());  // ascending k, the reference's emission order
+        } else if (nq > 64) {                    // (k_topk orders lists of up to 64 entries itself)
+            std::sort(tmp.begin(), tmp.end(), [](const std::pair<int32_t, double> &a, const std::pair<int32_t, double> &b) {
+                return a.second > b.second || (a.second == b.second && a.first < b.first);
+            });
+        }
+        out.lists->push_back(std::move(tmp));
+    }
+}
+
+// runs P passes; flags per pass as in PassParams
+int run_passes(qa_panel *pn, int P, const double *gl, const int32_t *h_flags, const int32_t *thin_col_h,
+               int K_top, int normalize_emissions, const BatchOut &out, PassKind kind = KIND_F32,
+               int always_normalize = 0, double norm_threshold = 1e-100) {
+    if (K_top > kMaxTop) {
+        qa::set_error("K_top_matches = %d > %d not supported", K_top, kMaxTop);
+        return QA_ERR_UNSUPPORTED;
+    }
+    const Geometry geo = pick_geometry(pn->K, kind);
+    if (geo.NT == 0) {
+        qa::set_error("K = %d exceeds the on-chip capacity of the %s full-pass kernels", pn->K, kKindInfo[kind].name);
+        return QA_ERR_UNSUPPORTED;
+    }
+    check_request(pn, kind, P, h_flags, K_top, out);
+    QA_HIP(hipSetDevice(pn->device));
+    if (!pn->scratch) pn->scratch = new qa_panel::Scratch(&pn->A());
+    auto &S = *pn->scratch;
+    hipStream_t st = pn->pass_stream ? pn->pass_stream : pn->stream;
+    for (auto &e : S.ev) if (!e) QA_HIP(hipEventCreate(&e));
+    const int G = pn->G, T = pn->T;
+    const Thin thin = qa::count_thin(thin_col_h, G);
+    const bool any_top = thin.n_thin > 0 && K_top > 0;
+    PassRun r{pn, S, st, P, h_flags, thin_col_h, out, geo,
+              PassLayout(dims_of(pn), geo, qa::make_request(h_flags, P, thin, K_top, out.top_cap, out.gamma_col != nullptr)),
+              thin.n_thin, any_top,
+              /* fused */ any_top && kind == KIND_F64_RANK && out.truncate_lists && out.top_cap <= 64,
+              out.top_cap, PassParams{}};
+
+    const std::vector<int32_t> slot = plan_alpha_slots(r);
+    carve_scratch(S, r.L, P, gl != nullptr);
+    if (gl) S.gl.upload(gl, (size_t)P * T * 2, st);
+    S.thin_col.upload(thin_col_h, G, st);
+    S.flags.upload(h_flags, P, st);
+    S.alpha_slot.upload(slot.data(), (size_t)P * G, st);
+    fill_params(r, K_top, normalize_emissions, always_normalize, norm_threshold);
+    choose_dosage_destination(r);
+
+    launch_passes(r);
+    if (r.fused) finish_fused_lists(r);
+    else if (any_top) pick_lists_separately(r);
+    QA_HIP(hipEventRecord(S.ev[5], st));
+    QA_HIP(hipStreamSynchronize(st));
+    add_profile_rows(r);
 
     // ---- copy results back
     if (out.c) S.c.download(out.c, (size_t)P * G, st);
-    if (out.gamma_col) {   // rows of Kq (the kernels' 16-byte stores) -> rows of K: one 2-D copy per run of consecutive destination rows
-        auto row_of = [&](int p) { return (size_t)(out.gamma_rows ? out.gamma_rows[p] : p); };
-        for (int p = 0; p < P;) {
-            int n = 1;
-            while (p + n < P && row_of(p + n) == row_of(p) + (size_t)n) n++;
-            QA_HIP(hipMemcpy2DAsync(out.gamma_col + row_of(p) * K, sizeof(double) * K, S.gamma_col.p + (size_t)p * Kq, sizeof(double) * Kq,
-                                    sizeof(double) * K, n, hipMemcpyDeviceToHost, st));
-            p += n;
-        }
-        QA_HIP(hipStreamSynchronize(st));
-    }
-    if (out.dosage && !dosage_direct) {
-        // runs of consecutive dosage passes come back in one staged transfer each, then scatter to their rows
-        // (a run whose destination rows are consecutive too -- the batch calls' layout -- lands in the caller's buffer
-        // directly: one transfer, staged piecewise or, for a qa_host_alloc buffer, written by the copy kernel itself)
-        const int max_rows = std::max<int>(1, (int)(qa::kStagePiece / (sizeof(double) * T)));
-        auto row_of = [&](int p) { return (size_t)(out.dosage_rows ? out.dosage_rows[p] : p); };
-        std::vector<double> tmp;
-        for (int p = 0; p < P;) {
-            if (!(h_flags[p] & 1)) { p++; continue; }
-            int n = 1;
-            while (p + n < P && (h_flags[p + n] & 1) && row_of(p + n) == row_of(p) + (size_t)n) n++;
-            if (n > 1 || max_rows == 1) {
-                qa::staged_download(out.dosage + row_of(p) * T, S.dosage.p + (size_t)p * T, sizeof(double) * T * n, st);
-                p += n;
-                continue;
-            }
-            while (p + n < P && n < max_rows && (h_flags[p + n] & 1)) n++;
-            tmp.resize((size_t)n * T);
-            qa::staged_download(tmp.data(), S.dosage.p + (size_t)p * T, sizeof(double) * T * n, st);
-            for (int i = 0; i < n; i++)
-                memcpy(out.dosage + row_of(p + i) * T, tmp.data() + (size_t)i * T, sizeof(double) * T);
-            p += n;
-        }
-    }
-    auto unpermute_to_host = [&](const char *base, size_t elem_off, int cols, double *dst) {
-        S.unperm.ensure((size_t)K * cols);
-        if (f64)
-            hipLaunchKernelGGL(k_unpermute<double>, dim3((K + 255) / 256, cols), dim3(256), 0, st,
-                               reinterpret_cast<const double *>(base) + elem_off, S.unperm.p, K, Kq, geo.NT, cols, (size_t)K);
-        else
-            hipLaunchKernelGGL(k_unpermute<float>, dim3((K + 255) / 256, cols), dim3(256), 0, st,
-                               reinterpret_cast<const float *>(base) + elem_off, S.unperm.p, K, Kq, geo.NT, cols, (size_t)K);
-        QA_HIP(hipGetLastError());
-        S.unperm.download(dst, (size_t)K * cols, st);
-        QA_HIP(hipStreamSynchronize(st));
-    };
-    if (P == 1) {
-        if (out.alphaHat_t) {
-            if (h_flags[0] & 15) {
-                unpermute_to_host(S.alpha.p, 0, G, out.alphaHat_t);
-            } else {
-                // only column 0 and the thinned columns exist (reference-single.cpp:2264-2268)
-                std::vector<double> col(K);
-                for (int g = 0; g < G; g++) {
-                    const int sl = slot[g];
-                    if (sl < 0) continue;
-                    unpermute_to_host(S.alpha.p, (size_t)sl * Kq, 1, col.data());
-                    memcpy(out.alphaHat_t + (size_t)g * K, col.data(), sizeof(double) * K);
-                }
-            }
-        }
-        if (out.gamma_t && any_gamma) unpermute_to_host(S.gamma.p, 0, G, out.gamma_t);
-        if (out.betaHat_t && any_beta) unpermute_to_host(S.beta.p, 0, G, out.betaHat_t);
-        if (out.gammaSmall_t && any_gamma) {
-            std::vector<double> col(K);
-            for (int g = 0; g < G; g++) {
-                if (thin_col_h[g] < 0) continue;
-                unpermute_to_host(S.gamma.p, (size_t)g * Kq, 1, col.data());
-                if (out.gamma_small_unscaled && g < G - 1)
-                    for (int k = 0; k < K; k++) col[k] /= pn->h_sigma[g];
-                memcpy(out.gammaSmall_t + (size_t)thin_col_h[g] * K, col.data(), sizeof(double) * K);
-            }
-        }
-    }
-    int status = QA_OK;
-    if (any_top && out.true_counts) *out.true_counts = cnt;
-    if (any_top && (out.lists || out.flat_idx)) {
-        const size_t n = (size_t)P * n_thin;
-        std::vector<int32_t> idx_local;
-        std::vector<double> val_local;
-        std::vector<int32_t> &idx = out.flat_idx ? *out.flat_idx : idx_local;
-        std::vector<double> &val = out.flat_val ? *out.flat_val : val_local;
-        idx.resize(n * top_cap);
-        val.resize(n * top_cap);
-        S.top_idx.download(idx.data(), idx.size(), st);
-        if (f64) {
-            qa::staged_download(val.data(), S.top_val.p, val.size() * 8, st);
-        } else {
-            std::vector<float> v32(val.size());
-            qa::staged_download(v32.data(), S.top_val.p, v32.size() * 4, st);
-            for (size_t i = 0; i < val.size(); i++) val[i] = v32[i];
-        }
-        for (size_t i = 0; out.lists && i < n; i++) {
-            std::vector<std::pair<int32_t, double>> tmp;
-            const int nq = std::min<int>(cnt[i], top_cap);
-            tmp.reserve(nq);
-            for (int q = 0; q < nq; q++) tmp.emplace_back(idx[i * top_cap + q], val[i * top_cap + q]);
-            if (!out.order_by_value) {
-                std::sort(tmp.begin(), tmp.end());  // ascending k, the reference's emission order
-            } else if (nq > 64) {                    // (k_topk orders lists of up to 64 entries itself)
-                std::sort(tmp.begin(), tmp.end(), [](const std::pair<int32_t, double> &a, const std::pair<int32_t, double> &b) {
-                    return a.second > b.second || (a.second == b.second && a.first < b.first);
-                });
-            }
-            out.lists->push_back(std::move(tmp));
-        }
-    }
+    if (out.gamma_col) download_gamma_column(r);
+    if (out.dosage && !r.dosage_direct) download_dosage_rows(r);
+    if (P == 1) download_matrices(r, slot);
+    if (any_top) collect_lists(r);
     QA_HIP(hipStreamSynchronize(st));
-    return status;
+    g_last_plan.P = P;
+    g_last_plan.kind = kind;
+    g_last_plan.carved = (int64_t)S.gl.arena->off;
+    return QA_OK;
 }
 
 }  // namespace
@@ -1414,6 +1541,13 @@ static int pack_lists(const std::vector<std::vector<std::pair<int32_t, double>>>
     return QA_OK;
 }
 
+int qa_fullpass_last_plan(int64_t out[6]) {
+    if (!out) return QA_ERR_INVALID;
+    out[0] = g_last_plan.P; out[1] = g_last_plan.per_pass; out[2] = g_last_plan.fixed; out[3] = g_last_plan.carved;
+    out[4] = PassLayout::N_BUF; out[5] = g_last_plan.kind;
+    return QA_OK;
+}
+
 int qa_Rcpp_haploid_dosage_versus_refs(
     qa_panel_t *panel, const double *gl, const int32_t *gammaSmall_cols_to_get,
     const qa_fullpass_opts_t *o, double *alphaHat_t, double *betaHat_t, double *c, double *gamma_t,
@@ -1452,24 +1586,23 @@ int qa_Rcpp_haploid_dosage_versus_refs(
         out.gamma_small_unscaled = !o->return_gamma_t;
         std::vector<std::vector<std::pair<int32_t, double>>> lists;
         QA_HIP(hipSetDevice(panel->device));
-        int nt = 0;
-        for (int g = 0; g < G; g++) nt = std::max(nt, thin[g] + 1);
+        const Thin thin_dims = qa::count_thin(thin.data(), G);
         const bool want_lists = o->get_best_haps_from_thinned_sites != 0;
         const int K_top = want_lists ? o->K_top_matches : 0;
-        auto plan = [&](PassKind kind, int32_t flags) {
+        // one pass of `kind` with flags `flags`, thinned grids `th` and K_top `kt`, planned with the un-permute staging
+        // (K x nGrids doubles) in the fixed term
+        auto plan = [&](PassKind kind, int32_t flags, const Thin &th, int kt) {
             const Geometry geo1 = pick_geometry(panel->K, kind);
             if (geo1.NT == 0) throw std::runtime_error("K exceeds the on-chip capacity of the full-pass kernels");
-            const size_t need = pass_bytes(panel, geo1, nt, (flags & 15) != 0, (flags & 4) != 0, (flags & 8) != 0, false) +
-                                (size_t)panel->K * G * 8 /* un-permute staging */;
-            plan_chunk(panel, need, 1);
+            plan_chunk(panel, plan_pass_bytes(panel, geo1, flags, th, kt), 1, (size_t)panel->K * G * 8);
         };
         // fp64 dosage: the tuned kernels yield dosage and c; a call that also wants alpha / beta / gamma matrices takes the
         // generic fp64 kernels
         const bool matrices = alphaHat_t || o->return_betaHat_t || o->return_gamma_t || o->return_gammaSmall_t;
-        const bool f32_fits = pick_geometry(panel->K, KIND_F32).NT != 0;
-        const PassKind main_kind = panel->sum_order_ref ? KIND_F64_REF   // validation mode: one pass of the reference-order kernels yields everything
-                                   : (!panel->dosage_fp64 && f32_fits) ? KIND_F32 : (matrices || !o->return_dosage) ? KIND_F64_FULL : dosage_kind(panel);
-        if (pick_geometry(panel->K, main_kind).NT == 0 && !(want_lists && panel->rank_fp64 && only_thin)) {
+        const KindChoice kinds = choose_kinds(panel, FOR_SINGLE_PASS, o->return_dosage != 0, want_lists, matrices);
+        const PassKind main_kind = kinds.dosage;
+        const bool lists_alone = want_lists && panel->rank_fp64 && only_thin;
+        if (pick_geometry(panel->K, main_kind).NT == 0 && !lists_alone) {
             // K x nGrids outputs (alphaHat_t / betaHat_t / gamma_t / gammaSmall_t) come from kernels that keep the whole state
             // on chip; the dosage and the best-haplotype lists (what the driver path asks for) have no such limit
             qa::set_error("K = %d: alphaHat_t / betaHat_t / gamma_t / gammaSmall_t outputs are limited to K <= 57 344 haplotypes (state on "
@@ -1480,41 +1613,40 @@ int qa_Rcpp_haploid_dosage_versus_refs(
         if (main_kind == KIND_F64_DOS) {
             std::vector<int32_t> no_thin(G, -1);
             const int32_t f1 = 1;
-            plan(KIND_F64_DOS, f1);
+            plan(KIND_F64_DOS, f1, Thin{}, 0);
             st = run_passes(panel, 1, gl, &f1, no_thin.data(), 0, o->normalize_emissions, out, KIND_F64_DOS,
                             o->always_normalize, norm_threshold);
             if (st == QA_OK && want_lists) {
                 BatchOut out2;
                 out2.lists = &lists;
                 const int32_t f0 = 0;
-                const PassKind rk = panel->rank_fp64 ? rank_kind(panel) : KIND_F32;
-                plan(rk, 0);
-                st = run_passes(panel, 1, gl, &f0, thin.data(), K_top, o->normalize_emissions, out2, rk,
+                plan(kinds.lists, f0, thin_dims, K_top);
+                st = run_passes(panel, 1, gl, &f0, thin.data(), K_top, o->normalize_emissions, out2, kinds.lists,
                                 o->always_normalize, norm_threshold);
             }
-        } else if (want_lists && panel->rank_fp64 && only_thin) {
+        } else if (lists_alone) {
             // only the lists (and alpha at the thinned grids, c): the fp64 ranking pass, which follows the reference's
             // normalisation schedule (always_normalize / min_emission_prob_normalization_threshold honoured)
             out.lists = &lists;
-            plan(rank_kind(panel), 0);
+            plan(rank_kind(panel), f, thin_dims, K_top);
             st = run_passes(panel, 1, gl, &f, thin.data(), K_top, o->normalize_emissions, out, rank_kind(panel),
                             o->always_normalize, norm_threshold);
-        } else if (want_lists && panel->rank_fp64 && main_kind == KIND_F32) {
+        } else if (want_lists && !kinds.one_pass) {
             // the best-haplotype lists come from a pass with fp64 state, so that their membership and order are
             // the reference's; every other output comes from the fp32 pass
-            plan(KIND_F32, f);
+            plan(KIND_F32, f, thin_dims, 0);
             st = run_passes(panel, 1, gl, &f, thin.data(), 0, o->normalize_emissions, out, KIND_F32);
             if (st != QA_OK) return st;
             BatchOut out2;
             out2.lists = &lists;
             const int32_t f0 = 0;
-            plan(rank_kind(panel), 0);
-            st = run_passes(panel, 1, gl, &f0, thin.data(), K_top, o->normalize_emissions, out2, rank_kind(panel),
+            plan(kinds.lists, f0, thin_dims, K_top);
+            st = run_passes(panel, 1, gl, &f0, thin.data(), K_top, o->normalize_emissions, out2, kinds.lists,
                             o->always_normalize, norm_threshold);
         } else {
             // one pass yields everything: fp32 state with fp32 ranking, or fp64 state (qa_panel_set_dosage_precision(64))
             if (want_lists) out.lists = &lists;
-            plan(main_kind, f);
+            plan(main_kind, f, thin_dims, K_top);
             st = run_passes(panel, 1, gl, &f, thin.data(), K_top, o->normalize_emissions, out, main_kind,
                             o->always_normalize, norm_threshold);
         }
@@ -1539,17 +1671,14 @@ int qa_fullpass_batch(qa_panel_t *panel, int32_t n_pass, const double *gl, const
         // chunk the passes so that the alpha checkpoints fit in HBM (K = 50 000, G = 2 000: 0.4 GB per dosage
         // pass, 0.08 GB per thin pass); chunks are homogeneous so that every pass of a chunk has the same footprint
         QA_HIP(hipSetDevice(panel->device));
-        PassKind main_kind = dosage_kind(panel);
-        if (main_kind == KIND_F64_DOS && !panel->rank_fp64 && K_top_matches > 0) main_kind = KIND_F64_FULL;   // (lists from the dosage pass itself)
-        // fp64 ranking passes beside the dosage passes (fp32 state, or the fp64 dosage kernels); with the generic fp64 kernels,
-        // or fp32 ranking, one pass yields both
-        const bool exact = panel->rank_fp64 && K_top_matches > 0 && main_kind != KIND_F64_FULL;
+        const KindChoice kinds = choose_kinds(panel, FOR_GL_BATCH, true, K_top_matches > 0, false);
+        const PassKind main_kind = kinds.dosage;
+        const bool exact = !kinds.one_pass;   // fp64 ranking passes for the lists beside the dosage passes
         const Geometry geo = pick_geometry(panel->K, main_kind), geo64 = pick_geometry(panel->K, rank_kind(panel));
         if (geo.NT == 0 || (exact && geo64.NT == 0))
             throw std::runtime_error("K exceeds the on-chip capacity of the full-pass kernels");
         const int G = panel->G, T = panel->T;
-        int n_thin = 0;
-        for (int g = 0; g < G; g++) n_thin = std::max(n_thin, gammaSmall_cols_to_get[g] + 1);
+        const Thin thin = qa::count_thin(gammaSmall_cols_to_get, G);
         std::vector<std::vector<std::pair<int32_t, double>>> lists;
         std::vector<int32_t> zeros(n_pass, 0);
         int done = 0;
@@ -1559,27 +1688,27 @@ int qa_fullpass_batch(qa_panel_t *panel, int32_t n_pass, const double *gl, const
             int run = 0;
             while (done + run < n_pass && (f[done + run] != 0) == dos) run++;
             if (!exact) {
-                // (thin passes of the fp64-dosage mode still take the faster ranking kernels)
-                const bool rank = !dos && panel->rank_fp64 && K_top_matches > 0 && geo64.NT != 0;
-                const int n = plan_chunk(panel, pass_bytes(panel, rank ? geo64 : geo, n_thin, dos, false, false, false), run);
+                const PassKind kind = dos ? main_kind : kinds.lists;
+                const int n = plan_chunk(panel, plan_pass_bytes(panel, pick_geometry(panel->K, kind), f[done], thin, K_top_matches), run);
                 BatchOut out;
                 out.dosage = dosage ? dosage + (size_t)done * T : nullptr;
                 out.lists = &lists;
                 status = run_passes(panel, n, gl + (size_t)done * T * 2, f.data() + done, gammaSmall_cols_to_get,
-                                    K_top_matches, 1, out, rank ? rank_kind(panel) : main_kind);
+                                    K_top_matches, 1, out, kind);
                 done += n;
                 continue;
             }
             // fp64-state ranking passes for the lists; dosage passes separately
-            int n = plan_chunk(panel, pass_bytes(panel, geo64, n_thin, false, false, false, false), run);
-            if (dos) n = std::min(n, plan_chunk(panel, pass_bytes(panel, geo, 0, true, false, false, false), run));
+            const size_t rank_bytes = plan_pass_bytes(panel, geo64, 0, thin, K_top_matches);
+            int n = plan_chunk(panel, rank_bytes, run);
+            if (dos) n = std::min(n, plan_chunk(panel, plan_pass_bytes(panel, geo, 1, Thin{}, 0), run));
             if (dos) {
                 BatchOut out;
                 out.dosage = dosage ? dosage + (size_t)done * T : nullptr;
                 std::vector<int32_t> no_thin(G, -1);
                 status = run_passes(panel, n, gl + (size_t)done * T * 2, f.data() + done, no_thin.data(), 0, 1, out, main_kind);
                 if (status != QA_OK) break;
-                plan_chunk(panel, pass_bytes(panel, geo64, n_thin, false, false, false, false), n);
+                plan_chunk(panel, rank_bytes, n);
             }
             BatchOut out2;
             out2.lists = &lists;
@@ -1592,6 +1721,9 @@ int qa_fullpass_batch(qa_panel_t *panel, int32_t n_pass, const double *gl, const
     });
 }
 
+}  // extern "C"
+
+namespace {
 
 // selection arguments of qa_fullpass_reads_select_batch (nullptr: plain qa_fullpass_reads_batch)
 struct SelectArgs {
@@ -1601,33 +1733,301 @@ struct SelectArgs {
     int32_t *which_next, *status;
 };
 
-static int fullpass_reads_impl(qa_panel_t *panel, int32_t n_chain, int32_t n_label, int32_t n_sample,
-                               const int32_t *chain_sample, const int32_t *read_off, const int32_t *read_ptr,
-                               const int32_t *u, const int32_t *bq, const int32_t *H, const int32_t *want_dosage,
-                               const int32_t *want_top, const int32_t *gammaSmall_cols_to_get, int32_t K_top_matches,
-                               double minGLValue, double *dosage, int32_t top_width, int32_t *top_idx, float *top_val,
-                               int32_t *top_cnt, const SelectArgs *sel, int32_t gamma_grid = -1, double *gamma_col = nullptr) {
+// the arguments of the qa_fullpass_reads_*batch entry points (include/quilt_amd.h has their meaning)
+struct ReadsCall {
+    qa_panel_t *panel;
+    int32_t n_chain, n_label, n_sample;
+    const int32_t *chain_sample, *read_off, *read_ptr, *u, *bq, *H, *want_dosage, *want_top, *gammaSmall_cols_to_get;
+    int32_t K_top_matches;
+    double minGLValue;
+    double *dosage;
+    int32_t top_width;
+    int32_t *top_idx;
+    float *top_val;
+    int32_t *top_cnt;
+    const SelectArgs *sel = nullptr;
+    int32_t gamma_grid = -1;
+    double *gamma_col = nullptr;
+    bool wants_lists(int c) const { return K_top_matches > 0 && (!want_top || want_top[c] != 0); }
+};
+
+// per-sample SNP-major index of the bases (input marshalling, O(bases))
+struct BaseIndex { std::vector<int32_t> snp_ptr, ent_off, ent_read, ent_bq; };
+BaseIndex index_bases(const ReadsCall &c) {
+    const int n_sample = c.n_sample, T = c.panel->T;
+    const int32_t *read_off = c.read_off, *read_ptr = c.read_ptr, *u = c.u, *bq = c.bq;
+    BaseIndex ix;
+    std::vector<int32_t> base_off(n_sample + 1, 0);
+    ix.snp_ptr.assign((size_t)n_sample * (T + 1), 0);
+    ix.ent_off.assign(n_sample, 0);
+    for (int s = 0; s < n_sample; s++) {
+        const int R = read_off[s + 1] - read_off[s];
+        base_off[s + 1] = base_off[s] + (read_ptr + read_off[s] + s)[R];
+    }
+    const int totB = base_off[n_sample];
+    ix.ent_read.resize(std::max(totB, 1));
+    ix.ent_bq.resize(std::max(totB, 1));
+    // a counting sort per sample, samples independent: spread over host threads (0.3 s on one thread for 256 samples of
+    // 50 000 bases -- in front of every full-panel launch set, and uncovered whenever one host thread has the device to itself)
+    // (one task per thread, each taking every n_thr-th sample: `fill` is allocated once per thread, not once per sample)
+    const int n_thr = std::max(1, std::min<int>(qa::host_threads(), n_sample));
+    qa::parallel_for((size_t)n_thr, n_thr, [&](size_t tid) {
+        std::vector<int32_t> fill;
+        for (int s = (int)tid; s < n_sample; s += n_thr) {
+            const int R = read_off[s + 1] - read_off[s];
+            const int32_t *rp = read_ptr + read_off[s] + s;
+            const int32_t *su = u + base_off[s], *sb = bq + base_off[s];
+            int32_t *sp = ix.snp_ptr.data() + (size_t)s * (T + 1);
+            ix.ent_off[s] = base_off[s];
+            for (int i = 0; i < rp[R]; i++) {
+                if (su[i] < 0 || su[i] >= T) throw std::runtime_error("SNP index out of range");
+                if (sb[i] > 255 || sb[i] < -255) throw std::runtime_error("|base quality| > 255");
+                sp[su[i] + 1]++;
+            }
+            for (int t = 0; t < T; t++) sp[t + 1] += sp[t];
+            fill.assign(sp, sp + T);
+            for (int r = 0; r < R; r++)
+                for (int i = rp[r]; i < rp[r + 1]; i++) {
+                    const int at = fill[su[i]]++;
+                    ix.ent_read[(size_t)base_off[s] + at] = r;
+                    ix.ent_bq[(size_t)base_off[s] + at] = sb[i];
+                }
+        }
+    });
+    return ix;
+}
+
+// chain -> offset of its labels in H (chains are laid out back to back, each with its sample's R)
+std::vector<int32_t> label_offsets(const ReadsCall &c) {
+    std::vector<int32_t> hoff(c.n_chain + 1, 0);
+    for (int i = 0; i < c.n_chain; i++) {
+        const int s = c.chain_sample[i];
+        if (s < 0 || s >= c.n_sample) throw std::runtime_error("chain_sample out of range");
+        hoff[i + 1] = hoff[i] + (c.read_off[s + 1] - c.read_off[s]);
+    }
+    return hoff;
+}
+
+// Work groups of passes (pass = chain x label).  With fp64 ranking (the default) the dosage comes from a pass
+// with fp32 state and the best-haplotype lists from a pass with fp64 state; a chain that wants both runs both.
+struct Group { std::vector<int32_t> ids; int32_t flag; int K_top; PassKind kind; };
+std::vector<Group> form_groups(const ReadsCall &c) {
+    const KindChoice kinds = choose_kinds(c.panel, FOR_READS_BATCH, true, true, false);
+    Group gd{{}, 1, 0, kinds.dosage}, gdt{{}, 1, c.K_top_matches, kinds.dosage}, gt{{}, 0, c.K_top_matches, kinds.lists};
+    for (int i = 0; i < c.n_chain; i++) {
+        const bool dos = c.want_dosage[i] != 0, top = c.wants_lists(i);
+        for (int l = 0; l < c.n_label; l++) {
+            const int id = i * c.n_label + l;
+            if (!kinds.one_pass) {
+                if (dos) gd.ids.push_back(id);
+                if (top) gt.ids.push_back(id);
+            } else {
+                if (dos && top) gdt.ids.push_back(id);
+                else if (dos) gd.ids.push_back(id);
+                else if (top) gt.ids.push_back(id);
+            }
+        }
+    }
+    std::vector<Group> groups;
+    for (Group *g : {&gd, &gdt, &gt}) if (!g->ids.empty()) groups.push_back(std::move(*g));
+    return groups;
+}
+
+// eps tables from the host libm (convertScaledBQtoProbs, as copied-from-stitch.cpp:166-175)
+std::vector<double> quality_tables() {
+    std::vector<double> tabs(4 * 256);
+    for (int q = 0; q < 256; q++) {
+        const double e = std::pow(10, -(double)q / 10);
+        tabs[q] = 1 - e; tabs[256 + q] = e / 3; tabs[512 + q] = e / 3; tabs[768 + q] = 1 - e;
+    }
+    return tabs;
+}
+
+// Per-call device buffers, carved from the handle's grow-only side arena (no hipMalloc / hipFree per call).  ONE list of
+// (buffer, count) gives both the arena's required size and the carves.
+struct ReadsAux {
+    qa::ABuf<int32_t> ps, pl, ph;        // [P] per pass of the group in hand: sample, label, offset of the chain's labels
+    qa::ABuf<int32_t> sp, eo, er, eb, H; // the base index and the labels
+    qa::ABuf<double> tabs;
+    // with the device-side selection: the call-wide list table [chain * n_label + label][thinned grid][top_width], its
+    // counts, the rows of the launch set in hand, and the selection's own arrays
+    qa::ABuf<int32_t> top_all, cnt_all, rows, which, next, stat, want;
+    qa::ABuf<uint64_t> seed;
+};
+struct AuxItem { size_t bytes; std::function<void()> carve; };
+template <typename T>
+AuxItem aux_item(qa::ABuf<T> &b, qa::Arena *arena, size_t n) {
+    n = std::max<size_t>(n, 1);
+    return {n * sizeof(T), [&b, arena, n] { b.arena = arena; b.ensure(n); }};
+}
+void carve_aux(const ReadsCall &c, ReadsAux &a, const BaseIndex &ix, size_t n_labels, size_t n_tabs, int n_thin) {
+    qa::Arena *A = &c.panel->aux;
+    const size_t P = (size_t)c.n_chain * c.n_label, n_out = P * n_thin, n_chain = c.n_chain;
+    std::vector<AuxItem> items = {aux_item(a.ps, A, P), aux_item(a.pl, A, P), aux_item(a.ph, A, P), aux_item(a.sp, A, ix.snp_ptr.size()),
+                                  aux_item(a.eo, A, c.n_sample), aux_item(a.er, A, ix.ent_read.size()),
+                                  aux_item(a.eb, A, ix.ent_bq.size()), aux_item(a.H, A, n_labels), aux_item(a.tabs, A, n_tabs)};
+    if (c.sel)
+        for (const AuxItem &i : {aux_item(a.top_all, A, n_out * c.top_width), aux_item(a.cnt_all, A, n_out), aux_item(a.rows, A, P),
+                            aux_item(a.which, A, n_chain * c.sel->Ksubset), aux_item(a.next, A, n_chain * c.sel->Ksubset),
+                            aux_item(a.stat, A, n_chain), aux_item(a.want, A, n_chain), aux_item(a.seed, A, n_chain)})
+            items.push_back(i);
+    size_t need = 0;
+    for (const AuxItem &i : items) need += (i.bytes + qa::Arena::kCarveAlign - 1) / qa::Arena::kCarveAlign * qa::Arena::kCarveAlign;
+    if (need > A->cap) A->require(need + need / 4);
+    A->reset();
+    for (const AuxItem &i : items) i.carve();
+}
+
+// what the stages of one call share
+struct ReadsWork {
+    qa_panel::Scratch &S;
+    hipStream_t st;
+    Thin thin;
+    std::vector<int32_t> hoff, no_thin;
+    ReadsAux aux;
+    bool lists_to_host;
+    int status = QA_OK;
+    double t_kern = 0, t_run = 0;
+};
+double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+// one group: its passes' likelihoods (k_make_gl), the passes, their lists to the call-wide device table and to the caller --
+// launch set by launch set
+void run_group(const ReadsCall &c, const Group &grp, ReadsWork &w) {
+    qa_panel *panel = c.panel;
+    auto &S = w.S;
+    ReadsAux &a = w.aux;
+    hipStream_t st = w.st;
+    const int T = panel->T, n_label = c.n_label, n_thin = w.thin.n_thin, top_width = c.top_width;
+    const Geometry geo = pick_geometry(panel->K, grp.kind);
+    if (geo.NT == 0) throw std::runtime_error("K exceeds the on-chip capacity of the full-pass kernels");
+    const int n_grp = (int)grp.ids.size();
+    std::vector<int32_t> ps(n_grp), pl(n_grp), ph(n_grp), flags(n_grp, grp.flag);
+    for (int i = 0; i < n_grp; i++) {
+        const int ch = grp.ids[i] / n_label, l = grp.ids[i] % n_label;
+        ps[i] = c.chain_sample[ch]; pl[i] = l + 1; ph[i] = w.hoff[ch];
+    }
+    QA_HIP(hipStreamSynchronize(st));   // the previous group's launches read ps / pl / ph
+    a.ps.upload(ps.data(), n_grp, st); a.pl.upload(pl.data(), n_grp, st); a.ph.upload(ph.data(), n_grp, st);
+    const bool gc = c.gamma_col && grp.flag != 0;
+    const int32_t *thin_col = grp.K_top > 0 ? c.gammaSmall_cols_to_get : w.no_thin.data();
+    // the layout run_passes will build for passes like these: the plan, and the carve of the likelihoods k_make_gl writes
+    const PassLayout L(dims_of(panel), geo, qa::make_request(&grp.flag, 1, grp.K_top > 0 ? w.thin : Thin{}, grp.K_top, top_width, gc));
+    int done = 0;
+    while (done < n_grp && w.status == QA_OK) {
+        const int n = plan_chunk(panel, L.pass_bytes(qa::Arena::kCarveAlign), n_grp - done);
+        carve(S.gl, L, PassLayout::GL, n);
+        GlParams gp{};
+        gp.P = n; gp.T = T; gp.pass_sample = a.ps.p + done; gp.pass_label = a.pl.p + done; gp.pass_hoff = a.ph.p + done;
+        gp.snp_ptr = a.sp.p; gp.ent_off = a.eo.p; gp.ent_read = a.er.p; gp.ent_bq = a.eb.p; gp.H = a.H.p;
+        gp.pR_tab = a.tabs.p; gp.pA_tab = a.tabs.p + 512; gp.minGLValue = c.minGLValue; gp.gl = S.gl.p;
+        hipLaunchKernelGGL(k_make_gl, dim3((T + 255) / 256, n), dim3(256), 0, st, gp);
+        QA_HIP(hipGetLastError());
+        BatchOut out;
+        out.dosage = grp.flag ? c.dosage : nullptr;
+        out.dosage_rows = grp.ids.data() + done;
+        if (gc) {
+            out.gamma_col = c.gamma_col;
+            out.gamma_grid = c.gamma_grid;
+            out.gamma_rows = grp.ids.data() + done;
+        }
+        std::vector<int32_t> fidx;
+        std::vector<double> fval;
+        if (w.lists_to_host) {   // with the selection on the device the lists need not cross PCIe
+            out.flat_idx = &fidx;
+            out.flat_val = &fval;
+        }
+        out.top_cap = top_width;      // k_topk keeps the ordered head of each list: all the driver reads
+        out.order_by_value = true;
+        out.truncate_lists = true;
+        std::vector<int32_t> true_cnt;
+        out.true_counts = &true_cnt;
+        const double tr = now_s();
+        w.status = run_passes(panel, n, nullptr, flags.data() + done, thin_col, grp.K_top, 1, out, grp.kind);
+        w.t_run += now_s() - tr;
+        w.t_kern += g_timing[5] / 1e3;
+        if (w.status != QA_OK) break;
+        // compact, already ordered lists: the first top_width entries of every (pass, thinned grid)
+        if (grp.K_top > 0 && c.sel) {   // this launch set's lists to their rows of the call-wide device table
+            a.rows.upload(grp.ids.data() + done, n, st);
+            qa::launch_scatter_lists(S.top_idx.p, S.top_cnt.p, a.rows.p, n, n_thin, top_width, a.top_all.p, a.cnt_all.p, st);
+            QA_HIP(hipStreamSynchronize(st));   // rows is re-used by the next launch set
+        }
+        if (grp.K_top > 0) {
+            for (int i = 0; i < n * n_thin; i++) {
+                const size_t o = (size_t)grp.ids[done + i / n_thin] * n_thin + (i % n_thin);
+                const int len = w.lists_to_host ? std::min<int>(true_cnt[i], top_width) : 0;
+                if (c.top_cnt) c.top_cnt[o] = true_cnt[i];
+                for (int q = 0; q < len; q++) {
+                    if (c.top_idx) c.top_idx[o * top_width + q] = fidx[(size_t)i * top_width + q];
+                    if (c.top_val) c.top_val[o * top_width + q] = (float)fval[(size_t)i * top_width + q];
+                }
+            }
+        }
+        done += n;
+    }
+}
+
+// everything_select_good_haps for every chain that asked for lists (select.hip), on the lists still on the device
+void select_on_device(const ReadsCall &c, ReadsWork &w) {
+    const SelectArgs *sel = c.sel;
+    ReadsAux &a = w.aux;
+    hipStream_t st = w.st;
+    const int n_chain = c.n_chain, n_thin = w.thin.n_thin;
+    const size_t n_out = (size_t)n_chain * c.n_label * n_thin;
+    std::vector<int32_t> want(n_chain);
+    for (int i = 0; i < n_chain; i++) want[i] = c.wants_lists(i);
+    a.which.upload(sel->which, (size_t)n_chain * sel->Ksubset, st);
+    a.seed.upload(sel->seed, n_chain, st);
+    a.want.upload(want.data(), n_chain, st);
+    qa::SelectParams sp{};
+    sp.n_label = c.n_label; sp.n_thin = n_thin; sp.top_width = c.top_width; sp.K_top_matches = c.K_top_matches; sp.K = c.panel->K;
+    sp.Ksubset = sel->Ksubset; sp.Knew = sel->Knew; sp.top = a.top_all.p; sp.which = a.which.p; sp.seed = a.seed.p;
+    sp.want = a.want.p; sp.out = a.next.p; sp.status = a.stat.p;
+    hipEvent_t e0, e1;
+    QA_HIP(hipEventCreate(&e0)); QA_HIP(hipEventCreate(&e1));
+    QA_HIP(hipEventRecord(e0, st));
+    const bool launched = qa::launch_select(sp, n_chain, st);
+    QA_HIP(hipEventRecord(e1, st));
+    if (launched) {
+        a.next.download(sel->which_next, (size_t)n_chain * sel->Ksubset, st);
+        a.stat.download(sel->status, n_chain, st);
+    } else {   // tables beyond the LDS: every chain is left to the caller's host path
+        for (int i = 0; i < n_chain; i++) sel->status[i] = want[i] ? 1 : -1;
+    }
+    QA_HIP(hipStreamSynchronize(st));
+    float ms = 0;
+    QA_HIP(hipEventElapsedTime(&ms, e0, e1));
+    qa::profile_add(qa::PK_SELECT, ms, (double)n_out * c.top_width * 4.0 + (double)n_chain * sel->Ksubset * 8.0,
+                    qa::profile_clock_ms(e0), n_chain);
+    QA_HIP(hipEventDestroy(e0)); QA_HIP(hipEventDestroy(e1));
+    // a truncated list only matters to the exhausted branch, which the device leaves to the host (status 1)
+}
+
+int fullpass_reads_impl(const ReadsCall &c) {
+    qa_panel_t *panel = c.panel;
+    const SelectArgs *sel = c.sel;
     if (!qa::device_ready()) return QA_ERR_NO_DEVICE;
-    if (!panel || n_chain <= 0 || n_label < 1 || n_label > 3 || n_sample <= 0 || !chain_sample || !read_off || !read_ptr ||
-        !u || !bq || !H || !want_dosage || !gammaSmall_cols_to_get || top_width < K_top_matches || top_width > 64) {
+    if (!panel || c.n_chain <= 0 || c.n_label < 1 || c.n_label > 3 || c.n_sample <= 0 || !c.chain_sample || !c.read_off || !c.read_ptr ||
+        !c.u || !c.bq || !c.H || !c.want_dosage || !c.gammaSmall_cols_to_get || c.top_width < c.K_top_matches || c.top_width > 64) {
         qa::set_error("qa_fullpass_reads_batch: bad argument");
         return QA_ERR_INVALID;
     }
     if (sel && (sel->Ksubset < 1 || sel->Ksubset > panel->K || sel->Knew < 0 || sel->Knew > sel->Ksubset || !sel->which ||
-                !sel->seed || !sel->which_next || !sel->status || K_top_matches < 1)) {
+                !sel->seed || !sel->which_next || !sel->status || c.K_top_matches < 1)) {
         qa::set_error("qa_fullpass_reads_select_batch: bad selection argument");
         return QA_ERR_INVALID;
     }
-    if (gamma_col) {
-        if (gamma_grid < 0 || gamma_grid >= panel->G) {
-            qa::set_error("qa_fullpass_reads_select_gamma_batch: gamma_grid = %d outside [0, nGrids = %d)", gamma_grid, panel->G);
+    if (c.gamma_col) {
+        if (c.gamma_grid < 0 || c.gamma_grid >= panel->G) {
+            qa::set_error("qa_fullpass_reads_select_gamma_batch: gamma_grid = %d outside [0, nGrids = %d)", c.gamma_grid, panel->G);
             return QA_ERR_INVALID;
         }
         const int st = qa::gamma_column_check(panel, "qa_fullpass_reads_select_gamma_batch");
         if (st != QA_OK) return st;
     }
     if (sel)
-        for (size_t i = 0; i < (size_t)n_chain * sel->Ksubset; i++)
+        for (size_t i = 0; i < (size_t)c.n_chain * sel->Ksubset; i++)
             if (sel->which[i] < 1 || sel->which[i] > panel->K) {
                 qa::set_error("qa_fullpass_reads_select_batch: which_haps_to_use out of range");
                 return QA_ERR_INVALID;
@@ -1635,254 +2035,55 @@ static int fullpass_reads_impl(qa_panel_t *panel, int32_t n_chain, int32_t n_lab
     return qa::guarded([&] {
         QA_HIP(hipSetDevice(panel->device));
         if (!panel->scratch) panel->scratch = new qa_panel::Scratch(&panel->A());
-        auto &S = *panel->scratch;
-        hipStream_t st = panel->pass_stream ? panel->pass_stream : panel->stream;
-        const int G = panel->G, T = panel->T;
-        int n_thin = 0;
-        for (int g = 0; g < G; g++) n_thin = std::max(n_thin, gammaSmall_cols_to_get[g] + 1);
+        const int P = c.n_chain * c.n_label;
         const bool tmg = getenv("QA_TIMING") != nullptr;
-        auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-        const double T0 = now();
-        double t_kern = 0, t_run = 0;
-        // ---- per-sample SNP-major index of the bases (input marshalling, O(bases))
-        std::vector<int32_t> base_off(n_sample + 1, 0), snp_ptr((size_t)n_sample * (T + 1), 0), ent_off(n_sample, 0);
-        for (int s = 0; s < n_sample; s++) {
-            const int R = read_off[s + 1] - read_off[s];
-            base_off[s + 1] = base_off[s] + (read_ptr + read_off[s] + s)[R];
-        }
-        const int totB = base_off[n_sample];
-        std::vector<int32_t> ent_read(std::max(totB, 1)), ent_bq(std::max(totB, 1));
-        {
-            // a counting sort per sample, samples independent: spread over host threads (0.3 s on one thread for 256 samples of
-            // 50 000 bases -- in front of every full-panel launch set, and uncovered whenever one host thread has the device to itself)
-            // (one task per thread, each taking every n_thr-th sample: `fill` is allocated once per thread, not once per sample)
-            const int n_thr = std::max(1, std::min<int>(qa::host_threads(), n_sample));
-            qa::parallel_for((size_t)n_thr, n_thr, [&](size_t tid) {
-                std::vector<int32_t> fill;
-                for (int s = (int)tid; s < n_sample; s += n_thr) {
-                    const int R = read_off[s + 1] - read_off[s];
-                    const int32_t *rp = read_ptr + read_off[s] + s;
-                    const int32_t *su = u + base_off[s], *sb = bq + base_off[s];
-                    int32_t *sp = snp_ptr.data() + (size_t)s * (T + 1);
-                    ent_off[s] = base_off[s];
-                    for (int i = 0; i < rp[R]; i++) {
-                        if (su[i] < 0 || su[i] >= T) throw std::runtime_error("SNP index out of range");
-                        if (sb[i] > 255 || sb[i] < -255) throw std::runtime_error("|base quality| > 255");
-                        sp[su[i] + 1]++;
-                    }
-                    for (int t = 0; t < T; t++) sp[t + 1] += sp[t];
-                    fill.assign(sp, sp + T);
-                    for (int r = 0; r < R; r++)
-                        for (int i = rp[r]; i < rp[r + 1]; i++) {
-                            const int at = fill[su[i]]++;
-                            ent_read[(size_t)base_off[s] + at] = r;
-                            ent_bq[(size_t)base_off[s] + at] = sb[i];
-                        }
-                }
-            });
-        }
-        // chain -> offset of its labels in H (chains are laid out back to back, each with its sample's R)
-        std::vector<int32_t> hoff(n_chain + 1, 0);
-        for (int c = 0; c < n_chain; c++) {
-            const int s = chain_sample[c];
-            if (s < 0 || s >= n_sample) throw std::runtime_error("chain_sample out of range");
-            hoff[c + 1] = hoff[c] + (read_off[s + 1] - read_off[s]);
-        }
-        const int P = n_chain * n_label;
-        // Work groups of passes (pass = chain x label).  With fp64 ranking (the default) the dosage comes from a pass
-        // with fp32 state and the best-haplotype lists from a pass with fp64 state; a chain that wants both runs both.
-        struct Group { std::vector<int32_t> ids; int32_t flag; int K_top; PassKind kind; };
-        std::vector<Group> groups;
-        {
-            PassKind main_kind = dosage_kind(panel);
-            if (main_kind == KIND_F64_DOS && !panel->rank_fp64) main_kind = KIND_F64_FULL;   // (lists from the dosage pass itself)
-            const bool exact = panel->rank_fp64 && main_kind != KIND_F64_FULL;   // else one pass yields dosage and lists
-            Group gd{{}, 1, 0, main_kind}, gdt{{}, 1, K_top_matches, main_kind},
-                gt{{}, 0, K_top_matches, panel->rank_fp64 ? rank_kind(panel) : KIND_F32};
-            for (int c = 0; c < n_chain; c++) {
-                const bool dos = want_dosage[c] != 0, top = K_top_matches > 0 && (!want_top || want_top[c] != 0);
-                for (int l = 0; l < n_label; l++) {
-                    const int id = c * n_label + l;
-                    if (exact) {
-                        if (dos) gd.ids.push_back(id);
-                        if (top) gt.ids.push_back(id);
-                    } else {
-                        if (dos && top) gdt.ids.push_back(id);
-                        else if (dos) gd.ids.push_back(id);
-                        else if (top) gt.ids.push_back(id);
-                    }
-                }
-            }
-            for (Group *g : {&gd, &gdt, &gt}) if (!g->ids.empty()) groups.push_back(std::move(*g));
-        }
-        // eps tables from the host libm (convertScaledBQtoProbs, as copied-from-stitch.cpp:166-175)
-        std::vector<double> tabs(4 * 256);
-        for (int q = 0; q < 256; q++) {
-            const double e = std::pow(10, -(double)q / 10);
-            tabs[q] = 1 - e; tabs[256 + q] = e / 3; tabs[512 + q] = e / 3; tabs[768 + q] = 1 - e;
-        }
-        // per-call device buffers, carved from the handle's grow-only side arena (no hipMalloc / hipFree per call)
-        const size_t n_out_all = (size_t)P * n_thin;
-        {
-            auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
-            size_t need = 0;
-            for (size_t b : {(size_t)P * 4, (size_t)P * 4, (size_t)P * 4, snp_ptr.size() * 4, (size_t)n_sample * 4, ent_read.size() * 4,
-                             ent_bq.size() * 4, (size_t)std::max(hoff[n_chain], 1) * 4, tabs.size() * 8})
-                need += pad(b);
-            if (sel)
-                for (size_t b : {std::max<size_t>(n_out_all * top_width, 1) * 4, std::max<size_t>(n_out_all, 1) * 4, (size_t)P * 4,
-                                 (size_t)n_chain * sel->Ksubset * 4, (size_t)n_chain * sel->Ksubset * 4, (size_t)n_chain * 4,
-                                 (size_t)n_chain * 4, (size_t)n_chain * 8})
-                    need += pad(b);
-            if (need > panel->aux.cap) panel->aux.require(need + need / 4);
-            panel->aux.reset();
-        }
-        auto carve_i32 = [&](size_t n) { qa::ABuf<int32_t> b; b.arena = &panel->aux; b.ensure(std::max<size_t>(n, 1)); return b; };
-        qa::ABuf<int32_t> d_ps = carve_i32(P), d_pl = carve_i32(P), d_ph = carve_i32(P), d_sp = carve_i32(snp_ptr.size()),
-                          d_eo = carve_i32(n_sample), d_er = carve_i32(ent_read.size()), d_eb = carve_i32(ent_bq.size()),
-                          d_H = carve_i32(std::max(hoff[n_chain], 1));
-        qa::ABuf<double> d_tabs;
-        d_tabs.arena = &panel->aux;
-        d_tabs.ensure(tabs.size());
-        d_sp.upload(snp_ptr.data(), snp_ptr.size(), st); d_eo.upload(ent_off.data(), n_sample, st);
-        d_er.upload(ent_read.data(), ent_read.size(), st); d_eb.upload(ent_bq.data(), ent_bq.size(), st);
-        d_H.upload(H, hoff[n_chain], st); d_tabs.upload(tabs.data(), tabs.size(), st);
+        const double T0 = now_s();
+        ReadsWork w{*panel->scratch, panel->pass_stream ? panel->pass_stream : panel->stream,
+                    qa::count_thin(c.gammaSmall_cols_to_get, panel->G)};
+        hipStream_t st = w.st;
+        const BaseIndex ix = index_bases(c);
+        w.hoff = label_offsets(c);
+        const std::vector<Group> groups = form_groups(c);
+        const std::vector<double> tabs = quality_tables();
+        const int n_labels = w.hoff[c.n_chain];
+        ReadsAux &a = w.aux;
+        carve_aux(c, a, ix, n_labels, tabs.size(), w.thin.n_thin);
+        a.sp.upload(ix.snp_ptr.data(), ix.snp_ptr.size(), st); a.eo.upload(ix.ent_off.data(), c.n_sample, st);
+        a.er.upload(ix.ent_read.data(), ix.ent_read.size(), st); a.eb.upload(ix.ent_bq.data(), ix.ent_bq.size(), st);
+        a.H.upload(c.H, n_labels, st); a.tabs.upload(tabs.data(), tabs.size(), st);
 
-        const size_t n_out = (size_t)P * n_thin;
-        if (top_cnt) std::fill(top_cnt, top_cnt + n_out, 0);
-        if (top_idx) std::fill(top_idx, top_idx + n_out * top_width, -1);
-        if (top_val) std::fill(top_val, top_val + n_out * top_width, 0.f);
-
-        int status = QA_OK;
-        std::vector<int32_t> no_thin(G, -1);
-        // call-wide list table for the device-side selection: [chain * n_label + label][thinned grid][top_width]
-        qa::ABuf<int32_t> d_top_all, d_cnt_all, d_rows;
-        if (sel) {
-            d_top_all = carve_i32(n_out * top_width);
-            d_cnt_all = carve_i32(n_out);
-            d_rows = carve_i32(P);
-        }
-        // (no memset: the scatter kernel writes every entry of every row of a chain that wants lists, -1 past the list's
-        // end, and the selection reads no other rows; the runtime's fill is a blit with 512-thread workgroups, which waits
-        // for a compute unit free of the other host thread's Gibbs waves -- half a second per occurrence in the r02 trace)
-        const bool lists_to_host = top_idx || top_val;
+        const size_t n_out = (size_t)P * w.thin.n_thin;
+        if (c.top_cnt) std::fill(c.top_cnt, c.top_cnt + n_out, 0);
+        if (c.top_idx) std::fill(c.top_idx, c.top_idx + n_out * c.top_width, -1);
+        if (c.top_val) std::fill(c.top_val, c.top_val + n_out * c.top_width, 0.f);
+        w.no_thin.assign(panel->G, -1);
+        // (no memset of the call-wide list table: the scatter kernel writes every entry of every row of a chain that wants
+        // lists, -1 past the list's end, and the selection reads no other rows; the runtime's fill is a blit with 512-thread
+        // workgroups, which waits for a compute unit free of the other host thread's Gibbs waves -- half a second per
+        // occurrence in the r02 trace)
+        w.lists_to_host = c.top_idx || c.top_val;
         // ---- everything above is host work and uploads into this handle's own buffers; the launch sets below have the
         // device (exclusive phases: queue behind the other handles' launch sets) and the arena
-        const double T1q = now();
+        const double T1q = now_s();
         qa::GateHold hold;
         hold.acquire(panel->gate(), &panel->arena);
-        const double T1 = now();
+        const double T1 = now_s();
         for (const Group &grp : groups) {
-            const Geometry geo = pick_geometry(panel->K, grp.kind);
-            if (geo.NT == 0) throw std::runtime_error("K exceeds the on-chip capacity of the full-pass kernels");
-            const int n_grp = (int)grp.ids.size();
-            std::vector<int32_t> ps(n_grp), pl(n_grp), ph(n_grp), flags(n_grp, grp.flag);
-            for (int i = 0; i < n_grp; i++) {
-                const int c = grp.ids[i] / n_label, l = grp.ids[i] % n_label;
-                ps[i] = chain_sample[c]; pl[i] = l + 1; ph[i] = hoff[c];
-            }
-            QA_HIP(hipStreamSynchronize(st));   // the previous group's launches read d_ps / d_pl / d_ph
-            d_ps.upload(ps.data(), n_grp, st); d_pl.upload(pl.data(), n_grp, st); d_ph.upload(ph.data(), n_grp, st);
-            const int nt_grp = grp.K_top > 0 ? n_thin : 0;
-            int done = 0;
-            while (done < n_grp && status == QA_OK) {
-                const bool gc = gamma_col && grp.flag != 0;
-                const int n = plan_chunk(panel, pass_bytes(panel, geo, nt_grp, grp.flag != 0, false, false, true, gc), n_grp - done);
-                S.gl.ensure((size_t)n * T * 2);
-                GlParams gp{};
-                gp.P = n; gp.T = T; gp.pass_sample = d_ps.p + done; gp.pass_label = d_pl.p + done; gp.pass_hoff = d_ph.p + done;
-                gp.snp_ptr = d_sp.p; gp.ent_off = d_eo.p; gp.ent_read = d_er.p; gp.ent_bq = d_eb.p; gp.H = d_H.p;
-                gp.pR_tab = d_tabs.p; gp.pA_tab = d_tabs.p + 512; gp.minGLValue = minGLValue; gp.gl = S.gl.p;
-                hipLaunchKernelGGL(k_make_gl, dim3((T + 255) / 256, n), dim3(256), 0, st, gp);
-                QA_HIP(hipGetLastError());
-                BatchOut out;
-                out.dosage = grp.flag ? dosage : nullptr;
-                out.dosage_rows = grp.ids.data() + done;
-                if (gc) {
-                    out.gamma_col = gamma_col;
-                    out.gamma_grid = gamma_grid;
-                    out.gamma_rows = grp.ids.data() + done;
-                }
-                std::vector<int32_t> fidx;
-                std::vector<double> fval;
-                if (lists_to_host) {   // with the selection on the device the lists need not cross PCIe
-                    out.flat_idx = &fidx;
-                    out.flat_val = &fval;
-                }
-                out.top_cap = top_width;      // k_topk keeps the ordered head of each list: all the driver reads
-                out.order_by_value = true;
-                out.truncate_lists = true;
-                std::vector<int32_t> true_cnt;
-                out.true_counts = &true_cnt;
-                const double tr = now();
-                status = run_passes(panel, n, nullptr, flags.data() + done, grp.K_top > 0 ? gammaSmall_cols_to_get : no_thin.data(),
-                                    grp.K_top, 1, out, grp.kind);
-                t_run += now() - tr;
-                t_kern += g_timing[5] / 1e3;
-                if (status != QA_OK) break;
-                // compact, already ordered lists: the first top_width entries of every (pass, thinned grid)
-                if (grp.K_top > 0 && sel) {   // this launch set's lists to their rows of the call-wide device table
-                    d_rows.upload(grp.ids.data() + done, n, st);
-                    qa::launch_scatter_lists(S.top_idx.p, S.top_cnt.p, d_rows.p, n, n_thin, top_width, d_top_all.p, d_cnt_all.p, st);
-                    QA_HIP(hipStreamSynchronize(st));   // d_rows is re-used by the next launch set
-                }
-                if (grp.K_top > 0) {
-                    for (int i = 0; i < n * n_thin; i++) {
-                        const size_t o = (size_t)grp.ids[done + i / n_thin] * n_thin + (i % n_thin);
-                        const int len = lists_to_host ? std::min<int>(true_cnt[i], top_width) : 0;
-                        if (top_cnt) top_cnt[o] = true_cnt[i];
-                        for (int q = 0; q < len; q++) {
-                            if (top_idx) top_idx[o * top_width + q] = fidx[(size_t)i * top_width + q];
-                            if (top_val) top_val[o * top_width + q] = (float)fval[(size_t)i * top_width + q];
-                        }
-                    }
-                }
-                done += n;
-            }
-            if (status != QA_OK) break;
+            run_group(c, grp, w);
+            if (w.status != QA_OK) break;
         }
-        if (sel && status == QA_OK) {
-            // everything_select_good_haps for every chain that asked for lists (select.hip), on the lists still on the device
-            qa::ABuf<int32_t> d_which = carve_i32((size_t)n_chain * sel->Ksubset), d_next = carve_i32((size_t)n_chain * sel->Ksubset),
-                              d_stat = carve_i32(n_chain), d_want = carve_i32(n_chain);
-            qa::ABuf<uint64_t> d_seed;
-            d_seed.arena = &panel->aux;
-            d_seed.ensure(n_chain);
-            std::vector<int32_t> want(n_chain);
-            for (int c = 0; c < n_chain; c++) want[c] = K_top_matches > 0 && (!want_top || want_top[c] != 0);
-            d_which.upload(sel->which, (size_t)n_chain * sel->Ksubset, st);
-            d_seed.upload(sel->seed, n_chain, st);
-            d_want.upload(want.data(), n_chain, st);
-            qa::SelectParams sp{};
-            sp.n_label = n_label; sp.n_thin = n_thin; sp.top_width = top_width; sp.K_top_matches = K_top_matches; sp.K = panel->K;
-            sp.Ksubset = sel->Ksubset; sp.Knew = sel->Knew; sp.top = d_top_all.p; sp.which = d_which.p; sp.seed = d_seed.p;
-            sp.want = d_want.p; sp.out = d_next.p; sp.status = d_stat.p;
-            hipEvent_t e0, e1;
-            QA_HIP(hipEventCreate(&e0)); QA_HIP(hipEventCreate(&e1));
-            QA_HIP(hipEventRecord(e0, st));
-            const bool launched = qa::launch_select(sp, n_chain, st);
-            QA_HIP(hipEventRecord(e1, st));
-            if (launched) {
-                d_next.download(sel->which_next, (size_t)n_chain * sel->Ksubset, st);
-                d_stat.download(sel->status, n_chain, st);
-            } else {   // tables beyond the LDS: every chain is left to the caller's host path
-                for (int c = 0; c < n_chain; c++) sel->status[c] = want[c] ? 1 : -1;
-            }
-            QA_HIP(hipStreamSynchronize(st));
-            float ms = 0;
-            QA_HIP(hipEventElapsedTime(&ms, e0, e1));
-            qa::profile_add(qa::PK_SELECT, ms, (double)n_out * top_width * 4.0 + (double)n_chain * sel->Ksubset * 8.0,
-                            qa::profile_clock_ms(e0), n_chain);
-            QA_HIP(hipEventDestroy(e0)); QA_HIP(hipEventDestroy(e1));
-            // a truncated list only matters to the exhausted branch, which the device leaves to the host (status 1)
-        }
+        if (sel && w.status == QA_OK) select_on_device(c, w);
         hold.release();
         if (tmg)
             fprintf(stderr, "[qa_fullpass_reads P=%d] index+uploads %.3f s, queued for the device %.3f s, run_passes %.3f s (device %.3f s), scatter etc %.3f s\n", P,
-                    T1q - T0, T1 - T1q, t_run, t_kern, now() - T1 - t_run);
-        return status;
+                    T1q - T0, T1 - T1q, w.t_run, w.t_kern, now_s() - T1 - w.t_run);
+        return w.status;
     });
 }
+
+}  // namespace
+
+extern "C" {
 
 int qa_fullpass_reads_batch(qa_panel_t *panel, int32_t n_chain, int32_t n_label, int32_t n_sample,
                             const int32_t *chain_sample, const int32_t *read_off, const int32_t *read_ptr,
@@ -1890,9 +2091,9 @@ int qa_fullpass_reads_batch(qa_panel_t *panel, int32_t n_chain, int32_t n_label,
                             const int32_t *want_top, const int32_t *gammaSmall_cols_to_get, int32_t K_top_matches,
                             double minGLValue,
                             double *dosage, int32_t top_width, int32_t *top_idx, float *top_val, int32_t *top_cnt) {
-    return fullpass_reads_impl(panel, n_chain, n_label, n_sample, chain_sample, read_off, read_ptr, u, bq, H, want_dosage,
-                               want_top, gammaSmall_cols_to_get, K_top_matches, minGLValue, dosage, top_width, top_idx,
-                               top_val, top_cnt, nullptr);
+    return fullpass_reads_impl(ReadsCall{panel, n_chain, n_label, n_sample, chain_sample, read_off, read_ptr, u, bq, H, want_dosage,
+                                         want_top, gammaSmall_cols_to_get, K_top_matches, minGLValue, dosage, top_width, top_idx,
+                                         top_val, top_cnt});
 }
 
 int qa_fullpass_reads_select_batch(qa_panel_t *panel, int32_t n_chain, int32_t n_label, int32_t n_sample,
@@ -1903,9 +2104,9 @@ int qa_fullpass_reads_select_batch(qa_panel_t *panel, int32_t n_chain, int32_t n
                                    int32_t *top_cnt, int32_t Ksubset, int32_t Knew, const int32_t *which_haps_to_use,
                                    const uint64_t *seed_select, int32_t *which_next, int32_t *select_status) {
     const SelectArgs sel{Ksubset, Knew, which_haps_to_use, seed_select, which_next, select_status};
-    return fullpass_reads_impl(panel, n_chain, n_label, n_sample, chain_sample, read_off, read_ptr, u, bq, H, want_dosage,
-                               want_top, gammaSmall_cols_to_get, K_top_matches, minGLValue, dosage, top_width, top_idx,
-                               top_val, top_cnt, &sel);
+    return fullpass_reads_impl(ReadsCall{panel, n_chain, n_label, n_sample, chain_sample, read_off, read_ptr, u, bq, H, want_dosage,
+                                         want_top, gammaSmall_cols_to_get, K_top_matches, minGLValue, dosage, top_width, top_idx,
+                                         top_val, top_cnt, &sel});
 }
 
 int qa_fullpass_reads_select_gamma_batch(qa_panel_t *panel, int32_t n_chain, int32_t n_label, int32_t n_sample,
@@ -1922,9 +2123,9 @@ int qa_fullpass_reads_select_gamma_batch(qa_panel_t *panel, int32_t n_chain, int
         return QA_ERR_INVALID;
     }
     const SelectArgs sel{Ksubset, Knew, which_haps_to_use, seed_select, which_next, select_status};
-    return fullpass_reads_impl(panel, n_chain, n_label, n_sample, chain_sample, read_off, read_ptr, u, bq, H, want_dosage,
-                               want_top, gammaSmall_cols_to_get, K_top_matches, minGLValue, dosage, top_width, top_idx,
-                               top_val, top_cnt, &sel, gamma_grid, gamma_col);
+    return fullpass_reads_impl(ReadsCall{panel, n_chain, n_label, n_sample, chain_sample, read_off, read_ptr, u, bq, H, want_dosage,
+                                         want_top, gammaSmall_cols_to_get, K_top_matches, minGLValue, dosage, top_width, top_idx,
+                                         top_val, top_cnt, &sel, gamma_grid, gamma_col});
 }
 
 }  // extern "C"

@@ -174,6 +174,17 @@ int qa_panel_set_dosage_precision(qa_panel_t *panel, int32_t bits);
  * only difference between the two.  K <= 57 344.  0 (default): the production kernels. */
 int qa_panel_set_sum_order(qa_panel_t *panel, int32_t reference_order);
 
+/* The reference-order sums at batch throughput.  on = 1: while qa_panel_set_sum_order is at 1 or 2, every launch set of TWO OR
+ * MORE passes of this handle (the batched entries: qa_fullpass_batch, qa_fullpass_reads_*_batch, qa_impute_*) runs on kernels
+ * that do the same arithmetic in the same order -- and so return the same bits -- laid out for many passes at once: one wave
+ * per pass, the state in the pass's device scratch instead of the compute unit's LDS, so that every SIMD holds several passes
+ * whose dependent add chains interleave (csrc/fullpass_ord.hip).  Single passes (qa_Rcpp_haploid_dosage_versus_refs, a launch
+ * set of one) keep the validation kernels, and with qa_panel_set_sum_order at 0 the switch does nothing.  0 (default): off.
+ * Measured at K = 50 000 x 2 000 grids it is not faster than the validation kernels (0.85x for ranking, 0.67x for dosage passes in
+ * launch sets of up to 1 024: DESIGN.md 3.3), whose state is in device scratch as well at that K; leave it off there.
+ * Other values: QA_ERR_INVALID. */
+int qa_panel_set_sum_order_batched(qa_panel_t *panel, int32_t on);
+
 /* Tell the library that n_sharers panel handles (normally one per host thread, each with its own stream and arena)
  * work on this device at the same time: each then sizes its scratch for 1 / n_sharers of the free memory and its Gibbs
  * launches for 1 / n_sharers of the SIMDs.  Two host threads hide each other's host-side phases (marshalling, the R-level

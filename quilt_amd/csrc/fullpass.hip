@@ -935,7 +935,8 @@ void launch_fb(const PassParams &prm, int NT, hipStream_t s, hipEvent_t e_mid) {
     QA_HIP(hipGetLastError());
 }
 
-void launch_fb_any(const Geometry &geo, const PassParams &prm, hipStream_t st, hipEvent_t e_mid) {
+// ord: reference-order launch sets of two or more passes take the batched kernels (qa_panel_set_sum_order_batched)
+void launch_fb_any(const Geometry &geo, const PassParams &prm, hipStream_t st, hipEvent_t e_mid, bool ord) {
     if (geo.kind == KIND_F64_DOS) {
         qa::launch_fb64_dosage(&prm, st, e_mid);
         return;
@@ -945,7 +946,8 @@ void launch_fb_any(const Geometry &geo, const PassParams &prm, hipStream_t st, h
         return;
     }
     if (geo.kind == KIND_F64_REF) {
-        qa::launch_fb_ref(&prm, geo.NT, st, e_mid);
+        if (ord && prm.P >= 2) qa::launch_fb_ord(&prm, geo.NT, st, e_mid);
+        else qa::launch_fb_ref(&prm, geo.NT, st, e_mid);
         return;
     }
     if (geo.kind == KIND_F64_FULL) {
@@ -1204,7 +1206,7 @@ void launch_passes(PassRun &r) {
     else hipLaunchKernelGGL(k_emat<float>, dim3(G, P), dim3(256), 0, st, prm);
     QA_HIP(hipGetLastError());
     QA_HIP(hipEventRecord(S.ev[1], st));
-    launch_fb_any(r.geo, prm, st, S.ev[2]);
+    launch_fb_any(r.geo, prm, st, S.ev[2], r.pn->sum_order_batched);
     QA_HIP(hipEventRecord(S.ev[3], st));
     const dim3 dgrid((G + kDosageGridsPerBlock - 1) / kDosageGridsPerBlock, P);
     if (r.geo.kind == KIND_F64_REF) { /* the validation backward kernel wrote the dosage itself, sums in the reference's order */ }
@@ -1546,6 +1548,45 @@ int qa_fullpass_last_plan(int64_t out[6]) {
     out[0] = g_last_plan.P; out[1] = g_last_plan.per_pass; out[2] = g_last_plan.fixed; out[3] = g_last_plan.carved;
     out[4] = PassLayout::N_BUF; out[5] = g_last_plan.kind;
     return QA_OK;
+}
+
+int qa_fullpass_launch_set(qa_panel_t *panel, int32_t n_pass, const double *gl, const int32_t *flags,
+                           const int32_t *gammaSmall_cols_to_get, int32_t K_top_matches, int32_t always_normalize,
+                           double *dosage, double *c, int32_t *best_ptr, int32_t *best_idx, double *best_val, int64_t best_cap) {
+    if (!qa::device_ready()) return QA_ERR_NO_DEVICE;
+    if (!panel || !gl || n_pass <= 0 || !flags || !gammaSmall_cols_to_get) {
+        qa::set_error("qa_fullpass_launch_set: bad argument");
+        return QA_ERR_INVALID;
+    }
+    int32_t any = 0;
+    for (int i = 0; i < n_pass; i++) {
+        if (flags[i] != 0 && flags[i] != 1) {
+            qa::set_error("qa_fullpass_launch_set: flags must be 0 or 1");
+            return QA_ERR_INVALID;
+        }
+        any |= flags[i];
+    }
+    return qa::guarded([&] {
+        qa::GateHold hold;
+        hold.acquire(panel->gate(), &panel->arena);
+        QA_HIP(hipSetDevice(panel->device));
+        const PassKind kind = dosage_kind(panel);
+        const Thin thin = qa::count_thin(gammaSmall_cols_to_get, panel->G);
+        // (fixed term: room for the non-truncating top-K retry at full length -- every haplotype of a pass without reads ties)
+        const size_t retry = K_top_matches > 0 ? (size_t)n_pass * thin.n_thin * panel->K * 12 + 2 * qa::Arena::kCarveAlign : 0;
+        if (plan_chunk(panel, plan_pass_bytes(panel, pick_geometry(panel->K, kind), any, thin, K_top_matches), n_pass, retry) < n_pass) {
+            qa::set_error("qa_fullpass_launch_set: %d passes do not fit one launch set", n_pass);
+            return (int)QA_ERR_CAPACITY;
+        }
+        std::vector<std::vector<std::pair<int32_t, double>>> lists;
+        BatchOut out;
+        out.dosage = dosage;
+        out.c = c;
+        out.lists = &lists;
+        const int status = run_passes(panel, n_pass, gl, flags, gammaSmall_cols_to_get, K_top_matches, 1, out, kind, always_normalize);
+        if (status != QA_OK) return status;
+        return pack_lists(lists, best_ptr, best_idx, best_val, best_cap);
+    });
 }
 
 int qa_Rcpp_haploid_dosage_versus_refs(

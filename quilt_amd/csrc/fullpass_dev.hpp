@@ -204,6 +204,9 @@ void launch_fb64_dosage(const void *pass_params, hipStream_t st, hipEvent_t e_mi
 // fullpass_ref.hip: the VALIDATION kernels (qa_panel_set_sum_order): every K-wide sum in the reference's order
 size_t fb_ref_state_doubles(int Kq);
 void launch_fb_ref(const void *pass_params, int NT, hipStream_t st, hipEvent_t e_mid);
+// fullpass_ord.hip: the same arithmetic and bits from kernels laid out for a launch set of many passes (one wave per pass, state in
+// PassParams::spill): qa_panel_set_sum_order_batched
+void launch_fb_ord(const void *pass_params, int NT, hipStream_t st, hipEvent_t e_mid);
 
 // select.hip: everything_select_good_haps on the device (one wave per chain)
 struct SelectParams {

@@ -25,30 +25,11 @@
 // Layout: one workgroup of 256 threads per pass; state (alpha resp. beta, and the gamma column) in plain k order, in LDS
 // when 2 K doubles fit, else in the pass's HBM scratch (PassParams::spill); checkpoints / outputs in the lane-interleaved
 // layout of the generic kernels (geometry NT = 256) so that k_topk / k_unpermute and the host side read them unchanged.
-#include "fullpass_dev.hpp"
+#include "fullpass_ref_dev.hpp"   // perm_index, add_lanes_in_order, GridEm: shared with fullpass_ord.hip
 
 namespace {
 
 constexpr int kRT = 256;   // threads per pass == kMaxRow (one emission-table row per thread)
-
-// position of haplotype k in a lane-interleaved column (fullpass_dev.hpp: alpha_vec_index)
-__device__ __forceinline__ size_t perm_index(int k, int NT) {
-    const int chunk = k >> 4, e = k & 15;
-    const int j = chunk / NT, t = chunk % NT;
-    return alpha_vec_index<8>(j, e >> 1, NT, t) * 2 + (e & 1);
-}
-
-template <int I>
-__device__ __forceinline__ double lane_value(double x) {
-    const int lo = __builtin_amdgcn_readlane(__double2loint(x), I);
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(x), I);
-    return __hiloint2double(hi, lo);
-}
-// s <- ((s + x[lane 0]) + x[lane 1]) + ... + x[lane 63]
-__device__ __forceinline__ double add_lanes_in_order(double s, double x) {
-    static_for<64>([&](auto ic) { s += lane_value<decltype(ic)::value>(x); });
-    return s;
-}
 
 // wave 0, all 64 lanes: s + v[0] + v[1] + ... + v[K-1], left to right.  SKIP0: haplotypes with code 0 contribute an exact
 // zero (the reference adds alphaHat_t_col(k) = (..) * eMatDH_col(0) = 0 for them).  Lanes past K add +0.0: x + 0.0 == x.
@@ -88,22 +69,6 @@ __device__ double serial_gather_sum(const double *v, const int32_t *list, int n,
         s = add_lanes_in_order(s, x);
     }
     return s;
-}
-
-struct GridEm {
-    const double *et;        // the grid's emission table (LDS)
-    const double *esp_g;     // the grid's special emissions, list order
-    const int32_t *sp_k;     // the grid's special list
-    int sn;
-    __device__ __forceinline__ double at(int k, uint32_t code) const {
-        if (code) return et[code];
-        const int i = special_lower_bound(sp_k, 0, sn, k);
-        return esp_g[i];
-    }
-};
-__device__ __forceinline__ GridEm grid_em(const PassParams &prm, const double *et, const double *esp_pass, int g) {
-    const int so = prm.sp_off[g], sn = prm.sp_off[g + 1] - so;
-    return GridEm{et, esp_pass + so + (sn > 0 ? 16 * prm.sp_gidx[g] : 0), prm.sp_k + so, sn};   // (k_emat, lazy layout)
 }
 
 struct Smem {
@@ -311,6 +276,10 @@ __global__ __launch_bounds__(kRT) void k_bwd_ro(PassParams prm, int NT, int stat
                 }
                 prm.dosage[(size_t)p * T + s + t] = d;
             }
+            // the special haplotypes' gamma is read above from gam: hold the other waves back from the next grid's gam.  Below a
+            // grid without a variant there is no other barrier on the way (a label without reads raced here and took the next
+            // grid's gamma for its specials' terms)
+            __syncthreads();
         }
         // beta *= c_g * sigma_g (:2165-2166)
         const double x = c_g * not_jump_prob;

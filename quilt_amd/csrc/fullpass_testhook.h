@@ -7,6 +7,7 @@
 #ifndef QA_FULLPASS_TESTHOOK_H
 #define QA_FULLPASS_TESTHOOK_H
 #include <stdint.h>
+#include "../../include/quilt_amd.h"
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -15,6 +16,15 @@ extern "C" {
  * out[3] = arena bytes carved when the launch set returned, out[4] = buffers in the layout, out[5] = the kind of kernels
  * that ran it (PassKind, pass_layout.hpp).  All 0 before the thread's first launch set. */
 int qa_fullpass_last_plan(int64_t out[6]);
+
+/* ONE launch set of n_pass passes on the kernels behind the handle's dosage passes, with what the batched entries of the public
+ * ABI do not let a caller choose or see: the per-pass flags in one launch set (flags[i] = 1: a dosage pass, 0: a pass for its
+ * best-haplotype lists only; with K_top_matches > 0 every pass yields lists), always_normalize, and c (n_pass x nGrids).
+ * gl, dosage, best_* as qa_fullpass_batch.  QA_ERR_CAPACITY when the passes do not fit one launch set.
+ * tests/test_sum_order_batched_gpu.py holds the two forms of the reference-order kernels against each other through it. */
+int qa_fullpass_launch_set(qa_panel_t *panel, int32_t n_pass, const double *gl, const int32_t *flags,
+                           const int32_t *gammaSmall_cols_to_get, int32_t K_top_matches, int32_t always_normalize,
+                           double *dosage, double *c, int32_t *best_ptr, int32_t *best_idx, double *best_val, int64_t best_cap);
 
 #ifdef __cplusplus
 }

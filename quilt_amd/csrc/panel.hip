@@ -565,6 +565,15 @@ int qa_panel_set_sum_order(qa_panel_t *panel, int32_t reference_order) {
     return QA_OK;
 }
 
+int qa_panel_set_sum_order_batched(qa_panel_t *panel, int32_t on) {
+    if (!panel || (on != 0 && on != 1)) {
+        qa::set_error("qa_panel_set_sum_order_batched: on must be 0 or 1");
+        return QA_ERR_INVALID;
+    }
+    panel->sum_order_batched = on != 0;
+    return QA_OK;
+}
+
 int qa_panel_get_dims(const qa_panel_t *panel, int32_t *K, int32_t *nGrids, int32_t *nSNPs) {
     if (!panel) {
         qa::set_error("qa_panel_get_dims: null handle");

@@ -122,7 +122,7 @@ def lib() -> C.CDLL:
                      "qa_Rcpp_haploid_dosage_versus_refs", "qa_Rcpp_make_gl_bound", "qa_fullpass_batch",
                      "qa_last_fullpass_timing_ms", "qa_panel_set_ranking_precision", "qa_panel_set_device_share", "qa_profile_get_busy", "qa_panel_create_from_rhb",
                      "qa_panel_export_tables", "qa_rcpp_make_eMatRead_t_nsnps", "qa_rare_common_create", "qa_profile_count",
-                     "qa_profile_get_work", "qa_panel_set_dosage_precision", "qa_panel_set_sum_order",
+                     "qa_profile_get_work", "qa_panel_set_dosage_precision", "qa_panel_set_sum_order", "qa_panel_set_sum_order_batched",
                      "qa_gibbs_batch_rare_common", "qa_nipt_block_table", "qa_panel_set_cu_partition"):
             getattr(L, name).restype = C.c_int
         L.qa_profile_name.restype = C.c_char_p
@@ -250,6 +250,13 @@ class DevicePanel:
         right as well (the library's order before round 6; include/quilt_amd.h says how a maintainer with R decides between
         the two).  ``False`` / 0 (default): the production kernels."""
         check(lib().qa_panel_set_sum_order(self.handle, C.c_int32(int(reference_order))))
+
+    def set_sum_order_batched(self, on):
+        """With ``set_sum_order(1 | 2)``: launch sets of two or more passes take the one-wave-per-pass form of the
+        reference-order kernels (fullpass_ord.hip) -- the same sums in the same order, hence the same bits, with several passes
+        resident per SIMD.  Single passes, and everything while the sum order is 0, are unchanged.  Not faster at K = 50 000.
+        ``False`` / 0 (default): off."""
+        check(lib().qa_panel_set_sum_order_batched(self.handle, C.c_int32(int(on))))
 
     def set_device_share(self, n_sharers: int):
         """This handle is one of ``n_sharers`` working on the device concurrently (one per host thread)."""

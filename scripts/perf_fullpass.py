@@ -20,7 +20,16 @@ ap.add_argument("--reps", type=int, default=3)
 ap.add_argument("--ktop", type=int, default=5)
 ap.add_argument("--fp64", action="store_true", help="dosage passes with fp64 state (k_fwd64 + k_bwd64d)")
 ap.add_argument("--driver", action="store_true", help="time the driver path (qa_fullpass_reads_batch: fused top-K)")
+ap.add_argument("--sum-order-batched", action="store_true",
+                help="reference-order sums (qa_panel_set_sum_order 1): alternate the validation kernels and the batched ones "
+                     "(qa_panel_set_sum_order_batched) in this process on the same inputs, for launch sets of --sets passes with "
+                     "dosage and with ranking flags; passes/s of each, written to --json")
+ap.add_argument("--sets", type=int, nargs="+", default=[256, 1024])
+ap.add_argument("--json", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                               "sum_order_batched.json"))
 a = ap.parse_args()
+if a.sum_order_batched:
+    a.P = max(a.sets)
 
 t0 = time.time()
 panel = make_synthetic_panel(K=a.K, nSNPs=a.T, seed=4916, keep_rhb_t=True)
@@ -48,7 +57,53 @@ bptr = np.zeros(a.P * n_thin + 1, dtype=np.int32)
 cap = a.P * n_thin * 64
 bidx = np.zeros(cap, dtype=np.int32)
 bval = np.zeros(cap)
+
+
+def sum_order_batched():
+    """Old and new form of the reference-order kernels in turn, same process, same inputs, outputs compared."""
+    import json
+    dev.set_dosage_precision(64)
+    dev.set_sum_order(1)
+    lib().qa_panel_set_sum_order_batched.restype = C.c_int
+    rows = []
+    for n in a.sets:
+        for what, flag in (("ranking", 0), ("dosage", 1)):
+            wd = np.full(n, flag, dtype=np.int32)
+            row = dict(K=panel.K, nGrids=G, passes=n, flags=what)
+            outs = {}
+            for r in range(a.reps):
+                for form, on in (("validation", 0), ("batched", 1)):
+                    check(lib().qa_panel_set_sum_order_batched(dev.handle, C.c_int32(on)))
+                    t0 = time.time()
+                    check(lib().qa_fullpass_batch(dev.handle, C.c_int32(n), ptr(gl), ptr(wd), ptr(cols), C.c_int32(a.ktop),
+                                                  ptr(dosage), ptr(bptr), ptr(bidx), ptr(bval), C.c_int64(cap)))
+                    wall = time.time() - t0
+                    tm = last_fullpass_timing_ms()
+                    outs[form] = (dosage[:n].copy() if flag else None, bptr[:n * n_thin + 1].copy(), bidx[:bptr[n * n_thin]].copy(),
+                                  bval[:bptr[n * n_thin]].copy())
+                    best = row.get(form + "_wall_s")
+                    if best is None or wall < best:
+                        row[form + "_wall_s"] = wall
+                        row[form + "_passes_per_s"] = n / wall
+                        row[form + "_last_launch_set_fwd_bwd_ms"] = [tm["forward"], tm["backward"]]
+                    print(f"P={n} {what} rep {r} {form}: wall {wall:.3f}s = {n / wall:.1f} passes/s  (last launch set: forward "
+                          f"{tm['forward']:.1f} ms, backward {tm['backward']:.1f} ms)", flush=True)
+            row["outputs_identical"] = all(x is None or np.array_equal(x, y) for x, y in zip(outs["validation"], outs["batched"]))
+            row["speedup"] = row["validation_wall_s"] / row["batched_wall_s"]
+            rows.append(row)
+            print(row, flush=True)
+    os.makedirs(os.path.dirname(a.json), exist_ok=True)
+    with open(a.json, "w") as f:
+        json.dump(dict(what="reference-order full-panel passes: validation kernels (fullpass_ref.hip) against the batched form "
+                            "(fullpass_ord.hip), qa_fullpass_batch wall time, best of reps, same process and inputs",
+                       reps=a.reps, rows=rows), f, indent=1)
+        f.write("\n")
+
+
 lib().qa_profile_name.restype = C.c_char_p
+if a.sum_order_batched:
+    sum_order_batched()
+    sys.exit(0)
 NAMES = [lib().qa_profile_name(C.c_int32(k)).decode() for k in range(lib().qa_profile_count())]
 for r in range(a.reps):
     t0 = time.time()

@@ -30,8 +30,17 @@ if os.environ.get("QA_VALIDATION", "0") != "0":
     t = time.perf_counter()
     v = impute_samples([dev], s, prm)
     tv = time.perf_counter() - t
-    print(json.dumps({"workload": "one 1x sample (20 000 reads), K = 50 000 x 64 000 SNPs, QUILT defaults, qa_impute_samples, fp64 dosage passes",
-                      "production_mode_s": round(tp, 3), "validation_mode_s": round(tv, 3),
-                      "labels_identical_to_production_mode": bool(np.array_equal(v[0].read_labels, r[0].read_labels)),
-                      "max_abs_dosage_diff_vs_production_mode": float(np.abs(v[0].dosage - r[0].dosage).max())}))
+    row = {"workload": "one 1x sample (20 000 reads), K = 50 000 x 64 000 SNPs, QUILT defaults, qa_impute_samples, fp64 dosage passes",
+           "production_mode_s": round(tp, 3), "validation_mode_s": round(tv, 3),
+           "labels_identical_to_production_mode": bool(np.array_equal(v[0].read_labels, r[0].read_labels)),
+           "max_abs_dosage_diff_vs_production_mode": float(np.abs(v[0].dosage - r[0].dosage).max())}
+    if os.environ["QA_VALIDATION"] == "2":
+        # ... and with the same sums from the batched kernels (qa_panel_set_sum_order_batched, fullpass_ord.hip): the same bits
+        dev.set_sum_order_batched(1)
+        t = time.perf_counter()   # (no warm-up run of its own: the arena and the streams are the validation run's)
+        b = impute_samples([dev], s, prm)
+        row["validation_mode_batched_s"] = round(time.perf_counter() - t, 3)
+        row["batched_identical_to_validation_mode"] = bool(np.array_equal(b[0].read_labels, v[0].read_labels)
+                                                           and np.array_equal(b[0].dosage, v[0].dosage))
+    print(json.dumps(row), flush=True)
 dev.close()

@@ -130,6 +130,7 @@ quilt_amd_impute_sample_range <- function(
     w <- sampleRange[1]:sampleRange[2]
     n <- length(w)
     sum_order <- as.integer(Sys.getenv("QUILT_AMD_SUM_ORDER", "0"))
+    sum_order_batched <- as.integer(Sys.getenv("QUILT_AMD_SUM_ORDER_BATCHED", "0"))   ## with sum_order 1 or 2: the batched kernels, same bits
     panel_objects <- list(
         hapMatcherR = hapMatcherR, distinctHapsB = distinctHapsB, distinctHapsIE = distinctHapsIE,
         eMatDH_special_matrix_helper = eMatDH_special_matrix_helper, eMatDH_special_matrix = eMatDH_special_matrix,
@@ -144,7 +145,7 @@ quilt_amd_impute_sample_range <- function(
         maxDifferenceBetweenReads = maxDifferenceBetweenReads, minGLValue = minGLValue, Jmax = 10000,   ## functions.R:688
         seed = if (is.na(seed)) 1 else as.numeric(seed),
         device = as.numeric(device),   ## 0-based, modulo the number of GPUs: mclapply's iCore - 1 (one R worker per GPU: nCores = GPUs)
-        sum_order = sum_order
+        sum_order = sum_order, sum_order_batched = sum_order_batched
     )
     if (!is.na(n_burn_in_seek_its)) params[["n_burn_in_seek_its"]] <- n_burn_in_seek_its
     if (hla_run) {

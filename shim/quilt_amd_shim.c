@@ -729,6 +729,8 @@ static void range_validate(SEXP panelSEXP, SEXP paramsSEXP, const char *who) {
         Rf_error("quilt_amd: %s: params$seed must be a non-negative whole number below 2^53", who);
     const double so = num_or(paramsSEXP, "sum_order", 0);
     if (!(so == 0 || so == 1 || so == 2)) Rf_error("quilt_amd: %s: params$sum_order must be 0, 1 or 2 (include/quilt_amd.h: qa_panel_set_sum_order)", who);
+    const double sob = num_or(paramsSEXP, "sum_order_batched", 0);
+    if (!(sob == 0 || sob == 1)) Rf_error("quilt_amd: %s: params$sum_order_batched must be 0 or 1 (include/quilt_amd.h: qa_panel_set_sum_order_batched)", who);
     SEXP blocks = list_get(paramsSEXP, "small_ref_panel_block_gibbs_iterations");
     if (blocks != R_NilValue && TYPEOF(blocks) != INTSXP)
         Rf_error("quilt_amd: %s: params$small_ref_panel_block_gibbs_iterations must be an integer vector (0-based sweeps)", who);
@@ -789,6 +791,9 @@ static int range_setup(range_ctx_t *cx, SEXP panelSEXP, SEXP paramsSEXP, int n_h
      * sum of the full-panel passes in the order the reference's code adds it (bit-identical to the CPU package's lists, 20-50x
      * slower passes); 2 = the same with grid 0's Armadillo sum read left to right (include/quilt_amd.h) */
     const int sum_order = (int)num_or(paramsSEXP, "sum_order", 0);
+    /* params$sum_order_batched (QUILT_AMD_SUM_ORDER_BATCHED) beside a sum_order of 1 or 2: the same sums, hence the same bits, from
+     * the kernels laid out for many passes at once (qa_panel_set_sum_order_batched) */
+    const int sum_order_batched = sum_order ? (int)num_or(paramsSEXP, "sum_order_batched", 0) : 0;
     int st = QA_OK;
     for (; cx->made < n_handles && st == QA_OK; cx->made++) {
         cx->handles[cx->made] = NULL;
@@ -797,6 +802,7 @@ static int range_setup(range_ctx_t *cx, SEXP panelSEXP, SEXP paramsSEXP, int n_h
         if (st == QA_OK && n_handles > 1) st = qa_panel_set_exclusive(cx->handles[cx->made], 1);
         if (st == QA_OK) st = qa_panel_set_dosage_precision(cx->handles[cx->made], 64);   /* the reference computes in double */
         if (st == QA_OK && sum_order) st = qa_panel_set_sum_order(cx->handles[cx->made], sum_order);
+        if (st == QA_OK && sum_order_batched) st = qa_panel_set_sum_order_batched(cx->handles[cx->made], 1);
     }
     free(which);
     if (st != QA_OK) {

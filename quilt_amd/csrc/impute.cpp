@@ -215,15 +215,12 @@ struct Ctx {
     int T_out = 0;
     // outputs
     double *dosage = nullptr, *gp_t = nullptr, *phasing_haps = nullptr;
-    int32_t *read_labels = nullptr, *nDosage = nullptr;
-    const int32_t *read_off = nullptr;
+    int32_t *nDosage = nullptr;
     // params->sample_source: reads[s] / reads_all[s] / label_dst[s] are filled when the set holding s is taken (Worker::new_batch)
     const qa_sample_source_t *source = nullptr;
     std::vector<int32_t *> label_dst;   // where sample s's consensus read labels go
     std::atomic<int64_t> n_underflow_retries{0}, n_full_list_refetches{0}, n_device_selections{0}, n_gibbs_chain_calls{0},
         n_gibbs_launches{0};
-    std::mutex stat_mu;
-    double t_gibbs = 0, t_fullpass = 0, t_host = 0, t_consensus = 0, t_finish = 0, t_accumulate = 0;
     Tail tail;
     bool use_tail = false;
     // hla_run (qa_impute_samples_hla): the last seek iteration's passes go through select_gamma, which also returns the gamma
@@ -353,9 +350,6 @@ void recast_nipt_haps(double *hap1, double *hap2, double *hap3, const double *mg
     }
 }
 
-// ---------------------------------------------------------------------------------------------------------------------------
-// one host thread: its handle, its buffers, its stream of launch sets
-// ---------------------------------------------------------------------------------------------------------------------------
 // get_initial_read_labels for method = "nipt" (rare_common.R:104-105 with get_read_groupings_given_fetal_fraction_and_cov and
 // sample_H_for_NIPT_given_groupings, gibbs-nipt.R:1655-1777, :1796-1849; the statement in quilt_amd/driver.py): e = the all-SNP
 // reads' rescaled likelihoods against (hap1, hap2, hap3), [read][3].  A read is grouped by which haplotypes it fits (> 0.5);
@@ -411,6 +405,10 @@ struct WorkerBuffers {
     std::vector<int32_t> g_which, g_read_off, g_read_ptr, g_u, g_bq, g_wif, g_first, g_H, g_uf, g_words;
     std::vector<uint64_t> g_sr, g_ss, seed_sel;
     std::vector<int32_t> f_cs, f_read_off, f_read_ptr, f_u, f_bq, f_H, f_wd, f_wt, f_cnt, f_next, f_status;
+    // what a round's draw stage leaves for its Gibbs call, one entry per chain of the round
+    std::vector<int32_t> first_reads;
+    std::vector<uint64_t> seed_reads, seed_shards;
+    std::vector<double> eh;       // eHapsCurrent_tc of get_initial_read_labels, host-spread: [chain][all SNPs][label]
     HostBuf<double> dos;          // the round's haploid dosages [chain][label][T]
     HostBuf<double> conf;         // read confidence [reads][K]
     HostBuf<double> dos_all;      // impute_rare_common: the all-SNP round's haploid dosages [chain][2][all SNPs]
@@ -425,6 +423,80 @@ std::map<void *, std::unique_ptr<WorkerBuffers>> &bufs() {
     return *m;
 }
 
+// the reads of one sample as the caller describes them (the flat arrays or the sample source); `what`: "" or "all-SNP "
+void check_reads(const Reads &r, int s, const char *what) {
+    const char *dropped = what[0] ? "" : " (the reference drops such samples before imputing, functions.R:300-310)";
+    if (r.R < 1) throw Failure(QA_ERR_INVALID, "sample " + std::to_string(s) + " has no " + what + "reads" + dropped);
+    if (!r.read_ptr || !r.u || !r.bq || !r.wif) throw Failure(QA_ERR_INVALID, std::string("sample ") + std::to_string(s) + ": missing " + what + "read arrays");
+    if (r.read_ptr[0] != 0) throw Failure(QA_ERR_INVALID, std::string(what) + "read_ptr of sample " + std::to_string(s) + " does not start at 0");
+}
+
+// ---- reads of many samples packed into one call's arrays
+std::vector<int32_t> samples_of(const std::vector<Chain *> &ch) {
+    std::vector<int32_t> s(ch.size());
+    for (size_t i = 0; i < ch.size(); i++) s[i] = ch[i]->sample;
+    return s;
+}
+
+// The distinct samples of a chain list in order of first appearance, each chain's index into them, and for each chain the
+// first chain of the same sample.
+struct DistinctSamples { std::vector<int32_t> samples, index, first; };
+DistinctSamples distinct_samples(const std::vector<int32_t> &chain_sample) {
+    DistinctSamples d;
+    d.index.resize(chain_sample.size());
+    d.first.resize(chain_sample.size());
+    std::map<int32_t, int32_t> at;   // sample -> its place in d.samples
+    std::vector<int32_t> first_chain;
+    for (size_t i = 0; i < chain_sample.size(); i++) {
+        auto it = at.find(chain_sample[i]);
+        if (it == at.end()) {
+            it = at.emplace(chain_sample[i], (int32_t)d.samples.size()).first;
+            d.samples.push_back(chain_sample[i]);
+            first_chain.push_back((int32_t)i);
+        }
+        d.index[i] = it->second;
+        d.first[i] = first_chain[(size_t)it->second];
+    }
+    return d;
+}
+
+// The reads of a list of samples in the layout every batched entry point takes: entry a's R + 1 read_ptr values at
+// read_off[a] + a, its per-read values at read_off[a], its bases at base_off[a].  The destinations are the caller's (kept)
+// vectors; the copies run on n_thr threads.
+struct PackedReads {
+    std::vector<int32_t> &read_off, &read_ptr, &u, &bq;
+    std::vector<int32_t> *wif;        // null: the call takes none
+    std::vector<int64_t> base_off;
+    int64_t n_reads() const { return read_off.back(); }
+
+    // same_as (optional): the bases travel only for entry a where same_as[a] == a (qa_gibbs_opts_t.reads_same_as)
+    void fill(const std::vector<int32_t> &samples, const std::vector<Reads> &reads, int n_thr, const int32_t *same_as = nullptr) {
+        const size_t n = samples.size();
+        read_off.assign(n + 1, 0);
+        base_off.assign(n + 1, 0);
+        for (size_t a = 0; a < n; a++) {
+            const Reads &r = reads[(size_t)samples[a]];
+            read_off[a + 1] = read_off[a] + r.R;
+            base_off[a + 1] = base_off[a] + r.nb;
+        }
+        read_ptr.resize((size_t)read_off[n] + n);
+        if (wif) wif->resize((size_t)read_off[n]);
+        u.resize((size_t)base_off[n]);
+        bq.resize((size_t)base_off[n]);
+        parallel_for(n, n_thr, [&](size_t a) {
+            const Reads &r = reads[(size_t)samples[a]];
+            std::memcpy(&read_ptr[(size_t)read_off[a] + a], r.read_ptr, sizeof(int32_t) * ((size_t)r.R + 1));
+            if (wif) std::memcpy(&(*wif)[(size_t)read_off[a]], r.wif, sizeof(int32_t) * (size_t)r.R);
+            if (same_as && same_as[a] != (int32_t)a) return;   // (its bases are another entry's)
+            std::memcpy(&u[(size_t)base_off[a]], r.u, sizeof(int32_t) * (size_t)r.nb);
+            std::memcpy(&bq[(size_t)base_off[a]], r.bq, sizeof(int32_t) * (size_t)r.nb);
+        });
+    }
+};
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// one host thread: its handle, its buffers, its stream of launch sets
+// ---------------------------------------------------------------------------------------------------------------------------
 struct Worker {
     Ctx &cx;
     void *handle;
@@ -433,10 +505,7 @@ struct Worker {
     int n_draw;   // threads for per-chain arithmetic (the copies' n_help is bounded by memory bandwidth, this by cores)
     std::unique_ptr<WorkerBuffers> own;   // a caller-supplied table of entry points: buffers of this call only
     WorkerBuffers &B;
-    std::vector<int32_t> &g_which, &g_read_off, &g_read_ptr, &g_u, &g_bq, &g_wif, &g_first, &g_H, &g_uf, &g_words;
-    std::vector<uint64_t> &g_sr, &g_ss, &seed_sel;
-    std::vector<int32_t> &f_cs, &f_read_off, &f_read_ptr, &f_u, &f_bq, &f_H, &f_wd, &f_wt, &f_cnt, &f_next, &f_status;
-    HostBuf<double> &dos, &conf, &dos_all, &gcol;
+    const void *rc_handle = nullptr;   // this thread's qa_rare_common_t (impute_rare_common)
     std::function<void()> on_first_launch;
     double t_gibbs = 0, t_fullpass = 0, t_host = 0, t_consensus = 0, t_finish = 0, t_accumulate = 0;
 
@@ -450,16 +519,34 @@ struct Worker {
         if (!slot) slot.reset(new WorkerBuffers(c.be));
         return *slot;
     }
-    const void *rc_handle = nullptr;   // this thread's qa_rare_common_t (impute_rare_common)
-    std::vector<double> eh;            // eHapsCurrent_tc of get_initial_read_labels: [chain][all SNPs][2]
     Worker(Ctx &c, void *h, int wi, bool keep)
-        : cx(c), handle(h), w(wi), n_help(qa::host_threads(8)), n_draw(qa::host_threads(24)), B(buffers_for(c, h, keep, own)), g_which(B.g_which),
-          g_read_off(B.g_read_off), g_read_ptr(B.g_read_ptr), g_u(B.g_u), g_bq(B.g_bq), g_wif(B.g_wif), g_first(B.g_first), g_H(B.g_H),
-          g_uf(B.g_uf), g_words(B.g_words), g_sr(B.g_sr), g_ss(B.g_ss), seed_sel(B.seed_sel), f_cs(B.f_cs), f_read_off(B.f_read_off),
-          f_read_ptr(B.f_read_ptr), f_u(B.f_u), f_bq(B.f_bq), f_H(B.f_H), f_wd(B.f_wd), f_wt(B.f_wt), f_cnt(B.f_cnt), f_next(B.f_next),
-          f_status(B.f_status), dos(B.dos), conf(B.conf), dos_all(B.dos_all), gcol(B.gcol) {}
+        : cx(c), handle(h), w(wi), n_help(qa::host_threads(8)), n_draw(qa::host_threads(24)), B(buffers_for(c, h, keep, own)) {}
 
-    // ---- the Gibbs call of a round with impute_one_sample's underflow retry (functions.R:2612-2716)
+    // what of qa_gibbs_opts_t is the same for every Gibbs call of a round
+    qa_gibbs_opts_t gibbs_opts(bool any_first, bool rare) const {
+        const auto &P = cx.P;
+        qa_gibbs_opts_t o{};
+        o.Ks = P.Ksubset;
+        o.sample_is_diploid = cx.nipt ? 0 : 1;
+        o.Jmax = P.Jmax;
+        o.rescale_eMatRead_t = 1;
+        o.n_gibbs_burn_in_its = P.small_ref_panel_gibbs_iterations;
+        o.n_gibbs_sample_its = P.n_gibbs_sample_its;
+        o.block_gibbs_iterations = cx.blocks.data();
+        o.n_block_gibbs_iterations = (int32_t)cx.blocks.size();
+        o.perform_block_gibbs = 1;
+        o.do_shard_block_gibbs = cx.nipt ? 0 : 1;   // (functions.R:2552-2556: no shard pass for ff > 0)
+        o.gibbs_initialize_iteratively = any_first ? 1 : 0;
+        o.disable_read_category_usage = rare ? 1 : 0;
+        o.class_sum_cutoff = 0.06;
+        o.L_grid = cx.nipt ? (rare ? cx.rc->L_grid_all : cx.nipt->L_grid) : nullptr;
+        o.shuffle_bin_radius = cx.nipt ? cx.nipt->shuffle_bin_radius : 5000;
+        o.block_gibbs_quantile_prob = 0.95;
+        return o;
+    }
+
+    // ---- the Gibbs call of a round with impute_one_sample's underflow retry (functions.R:2612-2716); first reads and seeds are
+    // the draw stage's (B.first_reads, B.seed_reads, B.seed_shards), as the starting labels `starts` are.
     // rare: the all-SNP call (qa_gibbs_batch_rare_common on the samples' all-SNP reads, labels given, read categories off:
     // impute_one_sample's defaults for it, functions.R:2385-2409); hap_out then [chain][2][all SNPs]
     void gibbs_with_retry(std::vector<Chain *> &ch, const std::vector<std::vector<int32_t>> &starts, bool any_first, bool want_words,
@@ -472,7 +559,9 @@ struct Worker {
         std::vector<int> pending((size_t)C);
         for (int i = 0; i < C; i++) pending[(size_t)i] = i;
         std::vector<double> maxdiff((size_t)C, P.maxDifferenceBetweenReads);
-        if (want_words) g_words.assign((size_t)C * 3 * G, 0);
+        if (want_words) B.g_words.assign((size_t)C * 3 * G, 0);
+        const qa_gibbs_opts_t round_opts = gibbs_opts(any_first, rare);
+        PackedReads pk{B.g_read_off, B.g_read_ptr, B.g_u, B.g_bq, &B.g_wif, {}};
         int n_try = 0;
         while (!pending.empty()) {
             std::vector<std::pair<double, std::vector<int>>> groups;   // by maxDifferenceBetweenReads, in order of appearance
@@ -486,84 +575,44 @@ struct Worker {
                 const std::vector<int> &idx = grp.second;
                 const int n = (int)idx.size();
                 const bool whole = (n == C && n_try == 0);   // the round's first call writes straight into the round's buffers
-                g_read_off.assign((size_t)n + 1, 0);
-                std::vector<int64_t> base_off((size_t)n + 1, 0);
-                for (int a = 0; a < n; a++) {
-                    const Reads &r = RD[(size_t)ch[(size_t)idx[(size_t)a]]->sample];
-                    g_read_off[(size_t)a + 1] = g_read_off[(size_t)a] + r.R;
-                    base_off[(size_t)a + 1] = base_off[(size_t)a] + r.nb;
-                }
-                const int64_t totR = g_read_off[(size_t)n], totB = base_off[(size_t)n];
-                g_which.resize((size_t)n * P.Ksubset);
-                g_read_ptr.resize((size_t)totR + n);
-                g_wif.resize((size_t)totR);
-                g_H.resize((size_t)totR);
-                g_u.resize((size_t)totB);
-                g_bq.resize((size_t)totB);
-                g_first.resize((size_t)n);
-                g_sr.resize((size_t)n);
-                g_ss.resize((size_t)n);
-                g_uf.assign((size_t)n, 0);
+                std::vector<int32_t> samples((size_t)n);
+                for (int a = 0; a < n; a++) samples[(size_t)a] = ch[(size_t)idx[(size_t)a]]->sample;
                 // the chains of one sample share its reads: on the library's own entry points the bases travel once per sample
                 // (qa_gibbs_opts_t.reads_same_as); a caller-supplied table of entry points gets every chain's copy
                 std::vector<int32_t> same_as;
-                if (cx.product) {
-                    same_as.resize((size_t)n);
-                    std::map<int, int> first_of;
-                    for (int a = 0; a < n; a++) {
-                        const int sm = ch[(size_t)idx[(size_t)a]]->sample;
-                        auto it = first_of.find(sm);
-                        if (it == first_of.end()) it = first_of.emplace(sm, a).first;
-                        same_as[(size_t)a] = it->second;
-                    }
-                }
+                if (cx.product) same_as = distinct_samples(samples).first;
+                pk.fill(samples, RD, n_help, same_as.empty() ? nullptr : same_as.data());
+                B.g_which.resize((size_t)n * P.Ksubset);
+                B.g_H.resize((size_t)pk.n_reads());
+                B.g_first.resize((size_t)n);
+                B.g_sr.resize((size_t)n);
+                B.g_ss.resize((size_t)n);
+                B.g_uf.assign((size_t)n, 0);
                 parallel_for((size_t)n, n_help, [&](size_t a) {
                     const int i = idx[a];
-                    const Chain &c = *ch[(size_t)i];
-                    const Reads &r = RD[(size_t)c.sample];
-                    std::memcpy(&g_which[a * P.Ksubset], c.which.data(), sizeof(int32_t) * (size_t)P.Ksubset);
-                    std::memcpy(&g_read_ptr[(size_t)g_read_off[a] + a], r.read_ptr, sizeof(int32_t) * ((size_t)r.R + 1));
-                    std::memcpy(&g_wif[(size_t)g_read_off[a]], r.wif, sizeof(int32_t) * (size_t)r.R);
-                    std::memcpy(&g_H[(size_t)g_read_off[a]], starts[(size_t)i].data(), sizeof(int32_t) * (size_t)r.R);
-                    if (!same_as.empty() && same_as[a] != (int32_t)a) return;   // (its bases are another chain's)
-                    std::memcpy(&g_u[(size_t)base_off[a]], r.u, sizeof(int32_t) * (size_t)r.nb);
-                    std::memcpy(&g_bq[(size_t)base_off[a]], r.bq, sizeof(int32_t) * (size_t)r.nb);
+                    std::memcpy(&B.g_which[a * P.Ksubset], ch[(size_t)i]->which.data(), sizeof(int32_t) * (size_t)P.Ksubset);
+                    std::memcpy(&B.g_H[(size_t)B.g_read_off[a]], starts[(size_t)i].data(), sizeof(int32_t) * (size_t)RD[(size_t)samples[a]].R);
                 });
                 for (int a = 0; a < n; a++) {
-                    g_first[(size_t)a] = first_reads[(size_t)idx[(size_t)a]];
-                    g_sr[(size_t)a] = seed_reads[(size_t)idx[(size_t)a]];
-                    g_ss[(size_t)a] = seed_shards[(size_t)idx[(size_t)a]];
+                    B.g_first[(size_t)a] = B.first_reads[(size_t)idx[(size_t)a]];
+                    B.g_sr[(size_t)a] = B.seed_reads[(size_t)idx[(size_t)a]];
+                    B.g_ss[(size_t)a] = B.seed_shards[(size_t)idx[(size_t)a]];
                 }
-                qa_gibbs_opts_t o{};
-                o.Ks = P.Ksubset;
+                // what depends on the group: its maxDifferenceBetweenReads, whose bases travel, the fetal fractions, the outputs
+                qa_gibbs_opts_t o = round_opts;
+                o.maxDifferenceBetweenReads = grp.first;
                 o.reads_same_as = same_as.empty() ? nullptr : same_as.data();
                 std::vector<double> ffc;
                 if (cx.nipt) {   // every chain carries its sample's fetal fraction (functions.R:128)
                     ffc.resize((size_t)n);
-                    for (int a = 0; a < n; a++) ffc[(size_t)a] = cx.nipt->ff[ch[(size_t)idx[(size_t)a]]->sample];
+                    for (int a = 0; a < n; a++) ffc[(size_t)a] = cx.nipt->ff[samples[(size_t)a]];
+                    o.ff = ffc[0];
+                    o.ff_chain = ffc.data();
                 }
-                o.ff = cx.nipt ? ffc[0] : 0.0;
-                o.ff_chain = cx.nipt ? ffc.data() : nullptr;
-                o.sample_is_diploid = cx.nipt ? 0 : 1;
-                o.Jmax = P.Jmax;
-                o.maxDifferenceBetweenReads = grp.first;
-                o.rescale_eMatRead_t = 1;
-                o.n_gibbs_burn_in_its = P.small_ref_panel_gibbs_iterations;
-                o.n_gibbs_sample_its = P.n_gibbs_sample_its;
-                o.block_gibbs_iterations = cx.blocks.data();
-                o.n_block_gibbs_iterations = (int32_t)cx.blocks.size();
-                o.perform_block_gibbs = 1;
-                o.do_shard_block_gibbs = cx.nipt ? 0 : 1;   // (functions.R:2552-2556: no shard pass for ff > 0)
-                o.gibbs_initialize_iteratively = any_first ? 1 : 0;
-                o.disable_read_category_usage = rare ? 1 : 0;
-                o.class_sum_cutoff = 0.06;
-                o.L_grid = cx.nipt ? (rare ? cx.rc->L_grid_all : cx.nipt->L_grid) : nullptr;
-                o.shuffle_bin_radius = cx.nipt ? cx.nipt->shuffle_bin_radius : 5000;
-                o.block_gibbs_quantile_prob = 0.95;
                 std::vector<int32_t> words_tmp;
                 std::vector<double> hap_tmp;
                 if (want_words) {
-                    if (whole) o.hap_words_out = g_words.data();
+                    if (whole) o.hap_words_out = B.g_words.data();
                     else { words_tmp.assign((size_t)n * 3 * G, 0); o.hap_words_out = words_tmp.data(); }
                 }
                 if (hap_out) {
@@ -576,17 +625,18 @@ struct Worker {
                 cx.n_gibbs_launches += 1;
                 CallSpan span_g(rare ? "gibbs_rc" : "gibbs", w, n);
                 const int st = rare
-                    ? cx.be->gibbs_batch_rare_common(handle, rc_handle, &o, n, g_which.data(), g_read_off.data(), g_read_ptr.data(),
-                                                     g_u.data(), g_bq.data(), g_wif.data(), nullptr, g_first.data(), nullptr, g_H.data(),
-                                                     nullptr, nullptr, nullptr, nullptr, g_uf.data(), nullptr, g_sr.data(), g_ss.data())
-                    : cx.be->gibbs_batch(handle, &o, n, g_which.data(), g_read_off.data(), g_read_ptr.data(), g_u.data(),
-                                         g_bq.data(), g_wif.data(), nullptr, g_first.data(), nullptr, g_H.data(), nullptr,
-                                         nullptr, nullptr, nullptr, g_uf.data(), nullptr, g_sr.data(), g_ss.data());
+                    ? cx.be->gibbs_batch_rare_common(handle, rc_handle, &o, n, B.g_which.data(), B.g_read_off.data(), B.g_read_ptr.data(),
+                                                     B.g_u.data(), B.g_bq.data(), B.g_wif.data(), nullptr, B.g_first.data(), nullptr,
+                                                     B.g_H.data(), nullptr, nullptr, nullptr, nullptr, B.g_uf.data(), nullptr,
+                                                     B.g_sr.data(), B.g_ss.data())
+                    : cx.be->gibbs_batch(handle, &o, n, B.g_which.data(), B.g_read_off.data(), B.g_read_ptr.data(), B.g_u.data(),
+                                         B.g_bq.data(), B.g_wif.data(), nullptr, B.g_first.data(), nullptr, B.g_H.data(), nullptr,
+                                         nullptr, nullptr, nullptr, B.g_uf.data(), nullptr, B.g_sr.data(), B.g_ss.data());
                 span_g.end();
                 if (st != QA_OK && st != QA_UNDERFLOW) check(st, rare ? "qa_gibbs_batch_rare_common" : "qa_gibbs_batch");
                 for (int a = 0; a < n; a++) {
                     const int i = idx[(size_t)a];
-                    if (g_uf[(size_t)a]) {
+                    if (B.g_uf[(size_t)a]) {
                         maxdiff[(size_t)i] = std::max(1.0, maxdiff[(size_t)i] / 10);   // functions.R:2704-2715
                         nxt.push_back(i);
                         cx.n_underflow_retries += 1;
@@ -596,9 +646,9 @@ struct Worker {
                     const int R = RD[(size_t)c.sample].R;
                     // (the all-SNP call's ending labels are not carried on: the next Gibbs sample starts afresh, the phasing
                     // iteration's result is its haplotypes)
-                    if (!rare) c.labels.assign(g_H.begin() + g_read_off[(size_t)a], g_H.begin() + g_read_off[(size_t)a] + R);
+                    if (!rare) c.labels.assign(B.g_H.begin() + B.g_read_off[(size_t)a], B.g_H.begin() + B.g_read_off[(size_t)a] + R);
                     if (!whole) {
-                        if (want_words) std::memcpy(&g_words[(size_t)i * 3 * G], &words_tmp[(size_t)a * 3 * G], sizeof(int32_t) * 3 * (size_t)G);
+                        if (want_words) std::memcpy(&B.g_words[(size_t)i * 3 * G], &words_tmp[(size_t)a * 3 * G], sizeof(int32_t) * 3 * (size_t)G);
                         if (hap_out) std::memcpy(hap_out + (size_t)i * nLh * T, &hap_tmp[(size_t)a * nLh * T], sizeof(double) * nLh * (size_t)T);
                     }
                 }
@@ -609,9 +659,6 @@ struct Worker {
                 throw Failure(QA_ERR_INVALID, "There were consecutive underflow problems (functions.R:2710)");
         }
     }
-
-    std::vector<int32_t> first_reads;
-    std::vector<uint64_t> seed_reads, seed_shards;
 
     // ---- complete best-haplotype lists of one chain (the reference's lists hold every haplotype at or above the threshold;
     // the batched call keeps their first top_width entries): make_gl_from_u_bq (reference-single.R:19-42) per label, a thin
@@ -669,30 +716,37 @@ struct Worker {
         return top;
     }
 
-    // ---- one [Gibbs -> full-panel pass per label -> new small panel] round over a set of chains at the same seek iteration.
-    // The first n_cur chains are the current launch set's main chains (their dosages are accumulated); the rest are phasing chains.
-    bool round(std::vector<Chain *> &ch, int i_it, Batch *cur) {
+    // ---- the stages of a round
+    // whether a chain's round ends with a new small panel: not the last seek iteration's, except where another Gibbs sample (or
+    // the all-SNP call) starts from it
+    bool wants_new_haps(const Chain &c, int i_it) const {
+        return i_it < cx.P.n_seek_its || cx.rc || (!c.phasing && c.i_chain == cx.P.nGibbsSamples);
+    }
+
+    // ---- draw: what each chain takes from its stream before the Gibbs call -- in a set's first round the small panel and one
+    // label per read, then the call's seeds -- into starts, B.first_reads, B.seed_reads, B.seed_shards; returns whether any
+    // chain is in its first round
+    bool draw(std::vector<Chain *> &ch, int i_it, std::vector<std::vector<int32_t>> &starts) {
         const auto &P = cx.P;
-        const int C = (int)ch.size(), K = cx.K, T = cx.T, G = cx.G, nL = cx.nL;
-        const double t0 = now_s();
+        const size_t C = ch.size();
         bool any_first = false;
-        std::vector<std::vector<int32_t>> starts((size_t)C);
-        first_reads.assign((size_t)C, 0);
-        seed_reads.assign((size_t)C, 0);
-        seed_shards.assign((size_t)C, 0);
-        for (int i = 0; i < C; i++) {
-            if (cx.reads[(size_t)ch[(size_t)i]->sample].R < 1)
+        starts.assign(C, {});
+        B.first_reads.assign(C, 0);
+        B.seed_reads.assign(C, 0);
+        B.seed_shards.assign(C, 0);
+        for (const Chain *c : ch) {
+            if (cx.reads[(size_t)c->sample].R < 1)
                 throw Failure(QA_ERR_INVALID, "a sample without reads cannot be imputed (no read intersects a SNP of the region)");
-            any_first |= (i_it == 1) && !ch[(size_t)i]->phasing;
+            any_first |= (i_it == 1) && !c->phasing;
         }
         // (every chain draws from its own stream: the chains' draws -- a keyed subset of the K haplotypes and one label per read
         // in a set's first round, 0.5 ms a chain at K = 50 000 -- are made side by side)
-        parallel_for((size_t)C, n_draw, [&](size_t i) {
+        parallel_for(C, n_draw, [&](size_t i) {
             Chain &c = *ch[i];
             const int R = cx.reads[(size_t)c.sample].R;
             const bool first = (i_it == 1) && !c.phasing;
             if (first) {   // functions.R:579-585
-                c.which = c.rng.choice_without_replacement(K, P.Ksubset);
+                c.which = c.rng.choice_without_replacement(cx.K, P.Ksubset);
                 std::sort(c.which.begin(), c.which.end());
                 for (auto &v : c.which) v += 1;
                 starts[i].resize((size_t)R);
@@ -706,162 +760,183 @@ struct Worker {
             } else {
                 starts[i] = c.labels;
             }
-            seed_reads[i] = (uint64_t)c.rng.integers(0, 9223372036854775808.0);
+            B.seed_reads[i] = (uint64_t)c.rng.integers(0, 9223372036854775808.0);
             const int32_t fr = (int32_t)c.rng.integers(0, (double)R);
-            first_reads[i] = first ? fr : -1;
-            seed_shards[i] = (uint64_t)c.rng.integers(0, 9223372036854775808.0);
+            B.first_reads[i] = first ? fr : -1;
+            B.seed_shards[i] = (uint64_t)c.rng.integers(0, 9223372036854775808.0);
         });
-        if (!any_first) std::fill(first_reads.begin(), first_reads.end(), 0);
+        if (!any_first) std::fill(B.first_reads.begin(), B.first_reads.end(), 0);
+        return any_first;
+    }
+
+    // ---- use_mspbwt = TRUE (functions.R:784-893): the next small panel from the long matches of the Gibbs call's rounded
+    // haploid dosages (B.g_words)
+    void select_by_mspbwt(std::vector<Chain *> &ch, int i_it) {
+        const auto &P = cx.P;
+        const int G = cx.G, nL = cx.nL;
+        const double t0 = now_s();
+        std::vector<int> idx;
+        for (int i = 0; i < (int)ch.size(); i++)
+            if (wants_new_haps(*ch[(size_t)i], i_it)) idx.push_back(i);
+        if (!idx.empty()) {
+            std::vector<uint64_t> seeds(idx.size());
+            std::vector<int32_t> Zs(idx.size() * nL * (size_t)G), out(idx.size() * (size_t)P.Knew);
+            for (size_t a = 0; a < idx.size(); a++) {
+                seeds[a] = (uint64_t)ch[(size_t)idx[a]]->rng.integers(0, 9223372036854775808.0);
+                std::memcpy(&Zs[a * nL * G], &B.g_words[(size_t)idx[a] * 3 * G], sizeof(int32_t) * nL * (size_t)G);
+            }
+            check(cx.be->mspbwt_select_new_haps(P.mspbwt_index, (int32_t)idx.size(), nL, Zs.data(), P.mspbwtL, P.mspbwtM, P.Knew,
+                                                seeds.data(), out.data()), "qa_mspbwt_select_new_haps");
+            for (size_t a = 0; a < idx.size(); a++)
+                ch[(size_t)idx[a]]->which.assign(out.begin() + a * P.Knew, out.begin() + (a + 1) * P.Knew);
+        }
+        t_fullpass += now_s() - t0;
+    }
+
+    // ---- use_mspbwt = FALSE: impute_using_everything for every chain, selection behind it
+    void fullpass_select(std::vector<Chain *> &ch, int i_it, double *hap, const Batch *cur) {
+        const int C = (int)ch.size();
+        const double t0 = now_s();
+        const int nS = marshal_fullpass(ch, i_it, hap != nullptr);
+        const double t1 = now_s();
+        t_host += t1 - t0;
+        // hla_run: the last seek iteration's passes also return gammaMT_t / gammaMU_t at the grid (functions.R:713-724)
+        const bool hla_it = cx.hla && i_it == cx.P.n_seek_its;
+        call_fullpass(C, nS, hap, hla_it);
+        const double t2 = now_s();
+        t_fullpass += t2 - t1;
+        if (hla_it) scatter_gammas(ch, cur);
+        if (hap) check_dosage_range(hap, C);
+        adopt_selections(ch);
+        t_host += now_s() - t2;
+    }
+
+    // the call's arrays: the distinct samples' reads once (B.f_*), per chain its sample, labels, flags, selection seed and
+    // small panel; returns the number of distinct samples
+    int marshal_fullpass(std::vector<Chain *> &ch, int i_it, bool return_dosage) {
+        const auto &P = cx.P;
+        const size_t C = ch.size();
+        const DistinctSamples ds = distinct_samples(samples_of(ch));
+        B.f_cs = ds.index;
+        PackedReads pk{B.f_read_off, B.f_read_ptr, B.f_u, B.f_bq, nullptr, {}};
+        pk.fill(ds.samples, cx.reads, n_help);
+        size_t totH = 0;
+        for (const Chain *c : ch) totH += c->labels.size();
+        B.f_H.resize(totH);
+        size_t at = 0;
+        for (const Chain *c : ch) {
+            std::memcpy(&B.f_H[at], c->labels.data(), sizeof(int32_t) * c->labels.size());
+            at += c->labels.size();
+        }
+        B.f_wd.assign(C, return_dosage ? 1 : 0);
+        B.f_wt.resize(C);
+        for (size_t i = 0; i < C; i++) B.f_wt[i] = wants_new_haps(*ch[i], i_it) ? 1 : 0;
+        B.seed_sel.resize(C);
+        for (size_t i = 0; i < C; i++) B.seed_sel[i] = (uint64_t)ch[i]->rng.integers(0, 9223372036854775808.0);
+        B.g_which.resize(C * P.Ksubset);
+        for (size_t i = 0; i < C; i++) std::memcpy(&B.g_which[i * P.Ksubset], ch[i]->which.data(), sizeof(int32_t) * (size_t)P.Ksubset);
+        B.f_cnt.assign(C * cx.nL * cx.n_thin, 0);
+        B.f_next.assign(C * P.Ksubset, 0);
+        B.f_status.assign(C, -1);
+        return (int)ds.samples.size();
+    }
+
+    void call_fullpass(int C, int nS, double *hap, bool hla_it) {
+        const auto &P = cx.P;
+        const int nL = cx.nL;
+        CallSpan span_f("fullpass_select", w, C);
+        if (hla_it) {
+            double *gc = B.gcol.get((size_t)C * nL * cx.K);
+            check(cx.select_gamma(handle, C, nL, nS, B.f_cs.data(), B.f_read_off.data(), B.f_read_ptr.data(), B.f_u.data(), B.f_bq.data(),
+                                  B.f_H.data(), B.f_wd.data(), B.f_wt.data(), cx.cols.data(), P.K_top_matches, P.minGLValue, hap,
+                                  cx.top_width, nullptr, nullptr, B.f_cnt.data(), P.Ksubset, P.Knew, B.g_which.data(), B.seed_sel.data(),
+                                  B.f_next.data(), B.f_status.data(), cx.hla->grid, gc),
+                  "qa_fullpass_reads_select_gamma_batch");
+        } else {
+            check(cx.be->fullpass_reads_select_batch(handle, C, nL, nS, B.f_cs.data(), B.f_read_off.data(), B.f_read_ptr.data(),
+                                                     B.f_u.data(), B.f_bq.data(), B.f_H.data(), B.f_wd.data(), B.f_wt.data(), cx.cols.data(),
+                                                     P.K_top_matches, P.minGLValue, hap, cx.top_width, nullptr, nullptr, B.f_cnt.data(),
+                                                     P.Ksubset, P.Knew, B.g_which.data(), B.seed_sel.data(), B.f_next.data(),
+                                                     B.f_status.data()),
+                  "qa_fullpass_reads_select_batch");
+        }
+    }
+
+    void check_dosage_range(const double *hap, int C) {   // functions.R:2072-2075
+        const size_t row = (size_t)cx.nL * cx.T;
+        std::atomic<bool> bad{false};
+        parallel_for((size_t)C, n_help, [&](size_t i) {
+            const double *d = hap + i * row;
+            for (size_t t = 0; t < row; t++)
+                if (!(d[t] >= -1e-5 && d[t] <= 1 + 1e-5)) { bad = true; break; }
+        });
+        if (bad) throw Failure(QA_ERR_INVALID, "Dosage observed outside of range of 0 to 1 on forward-backward full iteration");
+    }
+
+    // the device's selections become the chains' small panels; where the ranks up to K_top_matches did not yield Knew new
+    // haplotypes, every entry of the complete lists, then a random draw from the rest of the panel (functions.R:2278-2300)
+    void adopt_selections(std::vector<Chain *> &ch) {
+        const auto &P = cx.P;
+        for (size_t i = 0; i < ch.size(); i++) {
+            if (!B.f_wt[i]) continue;
+            Chain &c = *ch[i];
+            if (B.f_status[i] == 0) {
+                c.which.assign(B.f_next.begin() + i * P.Ksubset, B.f_next.begin() + (i + 1) * P.Ksubset);
+                cx.n_device_selections += 1;
+                continue;
+            }
+            std::vector<int32_t> prev;
+            for (int32_t j : keyed_subset(B.seed_sel[i], P.Ksubset, P.Ksubset - P.Knew, SELECT_OFFSET_PREV)) prev.push_back(c.which[(size_t)j]);
+            cx.n_full_list_refetches += 1;
+            int width = 1;
+            std::vector<int64_t> top = full_lists(c, width);
+            std::vector<int32_t> sel = select_good_haps_dense(P.Knew, P.K_top_matches, top, cx.nL, cx.n_thin, width, prev, cx.K, B.seed_sel[i]);
+            c.which = prev;
+            c.which.insert(c.which.end(), sel.begin(), sel.end());
+        }
+    }
+
+    // ---- the phasing chains' haploid dosages are their samples' phased haplotypes (functions.R:1207-1217, before recast_haps)
+    void keep_phasing_haps(const std::vector<Chain *> &ch, const double *hap, int T) {
+        const size_t row = (size_t)cx.nL * T;
+        for (size_t i = 0; i < ch.size(); i++)
+            if (ch[i]->phasing) std::memcpy(cx.phasing_haps + (size_t)ch[i]->sample * row, hap + i * row, sizeof(double) * row);
+    }
+
+    // ---- the current launch set's main chains (the first rows of hap) into their samples' accumulators (functions.R:999-1006,
+    // :1099-1123; :1009-1016: the fetus = maternal transmitted + paternal transmitted)
+    void accumulate(const Batch *cur, const double *hap, int T) {
+        if (!cur || cur->chains.empty()) return;
+        const double t0 = now_s();
+        const int n_cur = (int)cur->chains.size();
+        const size_t lo = (size_t)cur->lo;
+        std::vector<int32_t> cs((size_t)n_cur);
+        for (int i = 0; i < n_cur; i++) cs[(size_t)i] = cur->chains[(size_t)i].sample - cur->lo;
+        check(cx.be->accumulate_dosage(n_cur, cx.nL, T, hap, cs.data(), cur->hi - cur->lo, cx.dosage + lo * T, cx.gp_t + lo * 3 * T,
+                                       cx.nipt ? cx.nipt->fet_dosage + lo * T : nullptr, cx.nipt ? cx.nipt->fet_gp_t + lo * 3 * T : nullptr),
+              "qa_accumulate_dosage");
+        for (int i = 0; i < n_cur; i++) cx.nDosage[cur->chains[(size_t)i].sample] += 1;
+        t_accumulate += now_s() - t0;
+    }
+
+    // ---- one [Gibbs -> full-panel pass per label -> new small panel] round over a set of chains at the same seek iteration.
+    // The first chains are the current launch set's main chains (their dosages are accumulated); the rest are phasing chains.
+    bool round(std::vector<Chain *> &ch, int i_it, Batch *cur) {
+        const bool mspbwt = cx.P.use_mspbwt;
+        const double t0 = now_s();
+        std::vector<std::vector<int32_t>> starts;
+        const bool any_first = draw(ch, i_it, starts);
         const double t1 = now_s();
         t_host += t1 - t0;
         const bool return_dosage = i_it > cx.n_burn;
-        double *hap = nullptr;
-        if (return_dosage) hap = dos.get((size_t)C * nL * T);
-        if (P.use_mspbwt) {
-            gibbs_with_retry(ch, starts, any_first, true, return_dosage ? hap : nullptr);
-            const double t2 = now_s();
-            t_gibbs += t2 - t1;
-            // functions.R:784-893: the next small panel from the long matches of the call's rounded haploid dosages
-            std::vector<int> idx;
-            for (int i = 0; i < C; i++)
-                if (i_it < P.n_seek_its || cx.rc || (!ch[(size_t)i]->phasing && ch[(size_t)i]->i_chain == P.nGibbsSamples)) idx.push_back(i);
-            if (!idx.empty()) {
-                std::vector<uint64_t> seeds(idx.size());
-                std::vector<int32_t> Zs(idx.size() * nL * (size_t)G), out(idx.size() * (size_t)P.Knew);
-                for (size_t a = 0; a < idx.size(); a++) {
-                    seeds[a] = (uint64_t)ch[(size_t)idx[a]]->rng.integers(0, 9223372036854775808.0);
-                    std::memcpy(&Zs[a * nL * G], &g_words[(size_t)idx[a] * 3 * G], sizeof(int32_t) * nL * (size_t)G);
-                }
-                check(cx.be->mspbwt_select_new_haps(P.mspbwt_index, (int32_t)idx.size(), nL, Zs.data(), P.mspbwtL, P.mspbwtM, P.Knew,
-                                                    seeds.data(), out.data()), "qa_mspbwt_select_new_haps");
-                for (size_t a = 0; a < idx.size(); a++)
-                    ch[(size_t)idx[a]]->which.assign(out.begin() + a * P.Knew, out.begin() + (a + 1) * P.Knew);
-            }
-            t_fullpass += now_s() - t2;
-        } else {
-            gibbs_with_retry(ch, starts, any_first, false, nullptr);
-            const double t2 = now_s();
-            t_gibbs += t2 - t1;
-            // ---- impute_using_everything for every chain, selection behind it
-            std::map<int, int> uniq;
-            std::vector<int> sample_list;
-            f_cs.resize((size_t)C);
-            for (int i = 0; i < C; i++) {
-                auto it = uniq.find(ch[(size_t)i]->sample);
-                if (it == uniq.end()) { it = uniq.emplace(ch[(size_t)i]->sample, (int)sample_list.size()).first; sample_list.push_back(ch[(size_t)i]->sample); }
-                f_cs[(size_t)i] = it->second;
-            }
-            const int nS = (int)sample_list.size();
-            f_read_off.assign((size_t)nS + 1, 0);
-            std::vector<int64_t> boff((size_t)nS + 1, 0);
-            for (int s = 0; s < nS; s++) {
-                const Reads &r = cx.reads[(size_t)sample_list[(size_t)s]];
-                f_read_off[(size_t)s + 1] = f_read_off[(size_t)s] + r.R;
-                boff[(size_t)s + 1] = boff[(size_t)s] + r.nb;
-            }
-            f_read_ptr.resize((size_t)f_read_off[(size_t)nS] + nS);
-            f_u.resize((size_t)boff[(size_t)nS]);
-            f_bq.resize((size_t)boff[(size_t)nS]);
-            for (int s = 0; s < nS; s++) {
-                const Reads &r = cx.reads[(size_t)sample_list[(size_t)s]];
-                std::memcpy(&f_read_ptr[(size_t)f_read_off[(size_t)s] + s], r.read_ptr, sizeof(int32_t) * ((size_t)r.R + 1));
-                std::memcpy(&f_u[(size_t)boff[(size_t)s]], r.u, sizeof(int32_t) * (size_t)r.nb);
-                std::memcpy(&f_bq[(size_t)boff[(size_t)s]], r.bq, sizeof(int32_t) * (size_t)r.nb);
-            }
-            size_t totH = 0;
-            for (int i = 0; i < C; i++) totH += ch[(size_t)i]->labels.size();
-            f_H.resize(totH);
-            {
-                size_t at = 0;
-                for (int i = 0; i < C; i++) {
-                    std::memcpy(&f_H[at], ch[(size_t)i]->labels.data(), sizeof(int32_t) * ch[(size_t)i]->labels.size());
-                    at += ch[(size_t)i]->labels.size();
-                }
-            }
-            f_wd.assign((size_t)C, return_dosage ? 1 : 0);
-            f_wt.resize((size_t)C);
-            bool any_top = false;
-            for (int i = 0; i < C; i++) {
-                f_wt[(size_t)i] = (i_it < P.n_seek_its || cx.rc || (!ch[(size_t)i]->phasing && ch[(size_t)i]->i_chain == P.nGibbsSamples)) ? 1 : 0;
-                any_top |= f_wt[(size_t)i] != 0;
-            }
-            seed_sel.resize((size_t)C);
-            for (int i = 0; i < C; i++) seed_sel[(size_t)i] = (uint64_t)ch[(size_t)i]->rng.integers(0, 9223372036854775808.0);
-            g_which.resize((size_t)C * P.Ksubset);
-            for (int i = 0; i < C; i++) std::memcpy(&g_which[(size_t)i * P.Ksubset], ch[(size_t)i]->which.data(), sizeof(int32_t) * (size_t)P.Ksubset);
-            f_cnt.assign((size_t)C * nL * cx.n_thin, 0);
-            f_next.assign((size_t)C * P.Ksubset, 0);
-            f_status.assign((size_t)C, -1);
-            const double t3 = now_s();
-            t_host += t3 - t2;
-            CallSpan span_f("fullpass_select", w, C);
-            // hla_run: the last seek iteration's passes also return gammaMT_t / gammaMU_t at the grid (functions.R:713-724)
-            const bool hla_it = cx.hla && i_it == P.n_seek_its;
-            if (hla_it) {
-                double *gc = gcol.get((size_t)C * nL * K);
-                check(cx.select_gamma(handle, C, nL, nS, f_cs.data(), f_read_off.data(), f_read_ptr.data(), f_u.data(), f_bq.data(),
-                                      f_H.data(), f_wd.data(), f_wt.data(), cx.cols.data(), P.K_top_matches, P.minGLValue, hap,
-                                      cx.top_width, nullptr, nullptr, f_cnt.data(), P.Ksubset, P.Knew, g_which.data(), seed_sel.data(),
-                                      f_next.data(), f_status.data(), cx.hla->grid, gc),
-                      "qa_fullpass_reads_select_gamma_batch");
-            } else {
-                check(cx.be->fullpass_reads_select_batch(handle, C, nL, nS, f_cs.data(), f_read_off.data(), f_read_ptr.data(), f_u.data(),
-                                                         f_bq.data(), f_H.data(), f_wd.data(), f_wt.data(), cx.cols.data(), P.K_top_matches,
-                                                         P.minGLValue, hap, cx.top_width, nullptr, nullptr, f_cnt.data(), P.Ksubset, P.Knew,
-                                                         g_which.data(), seed_sel.data(), f_next.data(), f_status.data()),
-                      "qa_fullpass_reads_select_batch");
-            }
-            span_f.end();
-            const double t4 = now_s();
-            t_fullpass += t4 - t3;
-            if (hla_it) scatter_gammas(ch, cur);
-            if (return_dosage) {   // functions.R:2072-2075
-                std::atomic<bool> bad{false};
-                parallel_for((size_t)C, n_help, [&](size_t i) {
-                    const double *d = hap + i * nL * T;
-                    for (size_t t = 0; t < (size_t)nL * T; t++)
-                        if (!(d[t] >= -1e-5 && d[t] <= 1 + 1e-5)) { bad = true; break; }
-                });
-                if (bad) throw Failure(QA_ERR_INVALID, "Dosage observed outside of range of 0 to 1 on forward-backward full iteration");
-            }
-            (void)any_top;
-            for (int i = 0; i < C; i++) {
-                if (!f_wt[(size_t)i]) continue;
-                Chain &c = *ch[(size_t)i];
-                if (f_status[(size_t)i] == 0) {
-                    c.which.assign(f_next.begin() + (size_t)i * P.Ksubset, f_next.begin() + (size_t)(i + 1) * P.Ksubset);
-                    cx.n_device_selections += 1;
-                    continue;
-                }
-                // the ranks up to K_top_matches did not yield Knew new haplotypes: every entry of the complete lists, then a
-                // random draw from the rest of the panel (functions.R:2278-2300)
-                std::vector<int32_t> prev;
-                for (int32_t j : keyed_subset(seed_sel[(size_t)i], P.Ksubset, P.Ksubset - P.Knew, SELECT_OFFSET_PREV)) prev.push_back(c.which[(size_t)j]);
-                cx.n_full_list_refetches += 1;
-                int width = 1;
-                std::vector<int64_t> top = full_lists(c, width);
-                std::vector<int32_t> sel = select_good_haps_dense(P.Knew, P.K_top_matches, top, nL, cx.n_thin, width, prev, K, seed_sel[(size_t)i]);
-                c.which = prev;
-                c.which.insert(c.which.end(), sel.begin(), sel.end());
-            }
-            t_host += now_s() - t4;
-        }
-        // the phasing chains' haploid dosages are their samples' phased haplotypes (functions.R:1207-1217, before recast_haps)
-        if (return_dosage && !cx.rc)
-            for (int i = 0; i < C; i++)
-                if (ch[(size_t)i]->phasing)
-                    std::memcpy(cx.phasing_haps + (size_t)ch[(size_t)i]->sample * nL * T, hap + (size_t)i * nL * T, sizeof(double) * nL * (size_t)T);
-        if (return_dosage && cur && !cur->chains.empty() && !cx.rc) {   // functions.R:999-1006 (rare + common: the all-SNP round counts)
-            const double ta = now_s();
-            const int n_cur = (int)cur->chains.size();
-            std::vector<int32_t> cs((size_t)n_cur);
-            for (int i = 0; i < n_cur; i++) cs[(size_t)i] = cur->chains[(size_t)i].sample - cur->lo;
-            // (functions.R:1009-1016: the fetus = maternal transmitted + paternal transmitted)
-            check(cx.be->accumulate_dosage(n_cur, nL, T, hap, cs.data(), cur->hi - cur->lo, cx.dosage + (size_t)cur->lo * T,
-                                           cx.gp_t + (size_t)cur->lo * 3 * T, cx.nipt ? cx.nipt->fet_dosage + (size_t)cur->lo * T : nullptr,
-                                           cx.nipt ? cx.nipt->fet_gp_t + (size_t)cur->lo * 3 * T : nullptr), "qa_accumulate_dosage");
-            for (int i = 0; i < n_cur; i++) cx.nDosage[cur->chains[(size_t)i].sample] += 1;
-            t_accumulate += now_s() - ta;
+        double *hap = return_dosage ? B.dos.get(ch.size() * cx.nL * cx.T) : nullptr;
+        gibbs_with_retry(ch, starts, any_first, mspbwt, mspbwt ? hap : nullptr);   // (msPBWT: the dosages are the Gibbs call's)
+        t_gibbs += now_s() - t1;
+        if (mspbwt) select_by_mspbwt(ch, i_it);
+        else fullpass_select(ch, i_it, hap, cur);
+        if (return_dosage && !cx.rc) {   // (rare + common: the all-SNP round counts)
+            keep_phasing_haps(ch, hap, cx.T);
+            accumulate(cur, hap, cx.T);
         }
         return return_dosage;
     }
@@ -872,7 +947,7 @@ struct Worker {
     void scatter_gammas(const std::vector<Chain *> &ch, const Batch *cur) {
         const qa_impute_hla_t &h = *cx.hla;
         const size_t K = (size_t)cx.K, nG = (size_t)cx.P.nGibbsSamples;
-        const double *gc = gcol.p;
+        const double *gc = B.gcol.p;
         parallel_for(ch.size(), n_help, [&](size_t i) {
             const Chain &c = *ch[i];
             const double *g = gc + i * 2 * K;
@@ -895,123 +970,89 @@ struct Worker {
         });
     }
 
-    // impute_final_gibbs_with_rare_common (rare_common.R:109-420), once per Gibbs sample after its seek iterations
+    // ---- impute_final_gibbs_with_rare_common (rare_common.R:109-420), once per Gibbs sample after its seek iterations
     // (functions.R:1042-1098): starting labels from the all-SNP reads against the latest (hap1, hap2) spread over all SNPs
     // (get_initial_read_labels, rare_common.R:61-107: 0.5 at the rare SNPs), then one Gibbs call over ALL SNPs with the
-    // haplotypes selected last.  `ch`: the chains of the last round in its order (their dosages are rows of `dos`).
-    void rare_common_round(std::vector<Chain *> &ch, Batch *cur) {
-        const auto &P = cx.P;
+    // haplotypes selected last.
+    // the all-SNP reads' likelihoods against the last seek iteration's dosages `last` [chain][label][T], into lik [read][label].
+    // The device spreads the haplotypes over all SNPs itself (0.5 at the rare ones) and reads a sample's all-SNP reads once for
+    // all of its chains: no 2.75 GB expansion, no seven copies of the reads (per launch set of 896 chains)
+    void initial_likelihoods_device_spread(const std::vector<Chain *> &ch, const double *last, double *lik) {
+        const DistinctSamples ds = distinct_samples(samples_of(ch));
+        std::vector<int32_t> s_off;
+        PackedReads pk{s_off, B.g_read_ptr, B.g_u, B.g_bq, nullptr, {}};
+        pk.fill(ds.samples, cx.reads_all, n_help);
+        check(cx.be->make_eMatRead_t_rare_common(handle, rc_handle, (int32_t)ch.size(), (int32_t)ds.samples.size(), ds.index.data(), cx.nL,
+                                                 last, s_off.data(), B.g_read_ptr.data(), B.g_u.data(), B.g_bq.data(),
+                                                 cx.P.maxDifferenceBetweenReads, 100, 1, lik),
+              "qa_rcpp_make_eMatRead_t_rare_common");
+    }
+
+    // the same with the haplotypes spread here and every chain's copy of its sample's reads: rcpp_make_eMatRead_t as
+    // get_initial_read_labels calls it (rare_common.R:82-98): rescaled, Jmax = 100
+    void initial_likelihoods_host_spread(const std::vector<Chain *> &ch, const double *last, double *lik, std::vector<int32_t> &read_off) {
         const int C = (int)ch.size(), T = cx.T, Ta = cx.T_out, nL = cx.nL;
-        const double t0 = now_s();
-        const double *last = dos.p;   // [chain][label][T] of the last seek iteration
-        std::vector<int32_t> read_off((size_t)C + 1, 0);
-        for (int i = 0; i < C; i++) read_off[(size_t)i + 1] = read_off[(size_t)i] + cx.reads_all[(size_t)ch[(size_t)i]->sample].R;
-        double *lik = conf.get((size_t)read_off[(size_t)C] * nL);
-        if (cx.be->make_eMatRead_t_rare_common) {
-            // the device spreads the haplotypes over all SNPs itself (0.5 at the rare ones) and reads a sample's all-SNP reads
-            // once for all of its chains: no 2.75 GB expansion, no seven copies of the reads (per launch set of 896 chains)
-            std::vector<int32_t> samples_of;            // the distinct samples of the chains, in order of first appearance
-            std::vector<int32_t> chain_sample((size_t)C);
-            {
-                std::map<int, int> at;
-                for (int i = 0; i < C; i++) {
-                    const int sm = ch[(size_t)i]->sample;
-                    auto it = at.find(sm);
-                    if (it == at.end()) { it = at.emplace(sm, (int)samples_of.size()).first; samples_of.push_back(sm); }
-                    chain_sample[(size_t)i] = it->second;
-                }
+        B.eh.resize((size_t)C * Ta * nL);
+        parallel_for((size_t)C, n_help, [&](size_t c) {
+            double *e = &B.eh[c * Ta * nL];
+            for (size_t t = 0; t < (size_t)Ta * nL; t++) e[t] = 0.5;
+            for (int l = 0; l < nL; l++) {
+                const double *h = last + (c * nL + l) * T;
+                for (int j = 0; j < T; j++) e[(size_t)cx.common_at[(size_t)j] * nL + l] = h[j];
             }
-            const int NS = (int)samples_of.size();
-            std::vector<int32_t> s_off((size_t)NS + 1, 0);
-            std::vector<int64_t> s_boff((size_t)NS + 1, 0);
-            for (int i = 0; i < NS; i++) {
-                const Reads &r = cx.reads_all[(size_t)samples_of[(size_t)i]];
-                s_off[(size_t)i + 1] = s_off[(size_t)i] + r.R;
-                s_boff[(size_t)i + 1] = s_boff[(size_t)i] + r.nb;
-            }
-            g_read_ptr.resize((size_t)s_off[(size_t)NS] + NS);
-            g_u.resize((size_t)s_boff[(size_t)NS]);
-            g_bq.resize((size_t)s_boff[(size_t)NS]);
-            parallel_for((size_t)NS, n_help, [&](size_t i) {
-                const Reads &r = cx.reads_all[(size_t)samples_of[i]];
-                std::memcpy(&g_read_ptr[(size_t)s_off[i] + i], r.read_ptr, sizeof(int32_t) * ((size_t)r.R + 1));
-                std::memcpy(&g_u[(size_t)s_boff[i]], r.u, sizeof(int32_t) * (size_t)r.nb);
-                std::memcpy(&g_bq[(size_t)s_boff[i]], r.bq, sizeof(int32_t) * (size_t)r.nb);
-            });
-            check(cx.be->make_eMatRead_t_rare_common(handle, rc_handle, C, NS, chain_sample.data(), nL, last, s_off.data(), g_read_ptr.data(),
-                                                     g_u.data(), g_bq.data(), P.maxDifferenceBetweenReads, 100, 1, lik),
-                  "qa_rcpp_make_eMatRead_t_rare_common");
-        } else {
-            eh.resize((size_t)C * Ta * nL);
-            parallel_for((size_t)C, n_help, [&](size_t c) {
-                double *e = &eh[c * Ta * nL];
-                for (size_t t = 0; t < (size_t)Ta * nL; t++) e[t] = 0.5;
-                for (int l = 0; l < nL; l++) {
-                    const double *h = last + (c * nL + l) * T;
-                    for (int j = 0; j < T; j++) e[(size_t)cx.common_at[(size_t)j] * nL + l] = h[j];
-                }
-            });
-            std::vector<int64_t> boff((size_t)C + 1, 0);
-            for (int i = 0; i < C; i++) boff[(size_t)i + 1] = boff[(size_t)i] + cx.reads_all[(size_t)ch[(size_t)i]->sample].nb;
-            g_read_ptr.resize((size_t)read_off[(size_t)C] + C);
-            g_u.resize((size_t)boff[(size_t)C]);
-            g_bq.resize((size_t)boff[(size_t)C]);
-            parallel_for((size_t)C, n_help, [&](size_t i) {
-                const Reads &r = cx.reads_all[(size_t)ch[i]->sample];
-                std::memcpy(&g_read_ptr[(size_t)read_off[i] + i], r.read_ptr, sizeof(int32_t) * ((size_t)r.R + 1));
-                std::memcpy(&g_u[(size_t)boff[i]], r.u, sizeof(int32_t) * (size_t)r.nb);
-                std::memcpy(&g_bq[(size_t)boff[i]], r.bq, sizeof(int32_t) * (size_t)r.nb);
-            });
-            // rcpp_make_eMatRead_t as get_initial_read_labels calls it (rare_common.R:82-98): rescaled, Jmax = 100
-            check(cx.be->make_eMatRead_t_nsnps(handle, Ta, C, nL, eh.data(), read_off.data(), g_read_ptr.data(), g_u.data(), g_bq.data(),
-                                               P.maxDifferenceBetweenReads, 100, 1, lik), "qa_rcpp_make_eMatRead_t_nsnps");
-        }
-        std::vector<std::vector<int32_t>> starts((size_t)C);
-        first_reads.assign((size_t)C, 0);
-        seed_reads.assign((size_t)C, 0);
-        seed_shards.assign((size_t)C, 0);
-        parallel_for((size_t)C, n_draw, [&](size_t i) {   // (every chain draws from its own stream: order between chains is free)
-            Chain &c = *ch[(size_t)i];
+        });
+        PackedReads pk{read_off, B.g_read_ptr, B.g_u, B.g_bq, nullptr, {}};   // (read_off: the round's, filled again with the same values)
+        pk.fill(samples_of(ch), cx.reads_all, n_help);
+        check(cx.be->make_eMatRead_t_nsnps(handle, Ta, C, nL, B.eh.data(), read_off.data(), B.g_read_ptr.data(), B.g_u.data(), B.g_bq.data(),
+                                           cx.P.maxDifferenceBetweenReads, 100, 1, lik), "qa_rcpp_make_eMatRead_t_nsnps");
+    }
+
+    // draw: each chain's starting labels from its reads' likelihoods (chain i's at lik + read_off[i] * nL), then the call's seeds
+    void draw_rare_common(std::vector<Chain *> &ch, const double *lik, const std::vector<int32_t> &read_off,
+                          std::vector<std::vector<int32_t>> &starts) {
+        const size_t C = ch.size();
+        starts.assign(C, {});
+        B.first_reads.assign(C, 0);
+        B.seed_reads.assign(C, 0);
+        B.seed_shards.assign(C, 0);
+        parallel_for(C, n_draw, [&](size_t i) {   // (every chain draws from its own stream: order between chains is free)
+            Chain &c = *ch[i];
             const int R = cx.reads_all[(size_t)c.sample].R;
-            const double *e = lik + (size_t)read_off[(size_t)i] * nL;
-            starts[(size_t)i].resize((size_t)R);
+            const double *e = lik + (size_t)read_off[i] * cx.nL;
+            starts[i].resize((size_t)R);
             if (cx.nipt) {
-                initial_read_labels_nipt(e, R, cx.nipt->ff[c.sample], c.rng, starts[(size_t)i]);
+                initial_read_labels_nipt(e, R, cx.nipt->ff[c.sample], c.rng, starts[i]);
             } else {
                 for (int r = 0; r < R; r++)   // H <- as.integer(runif(nReads) < e[1, ] / colSums(e)) + 1
-                    starts[(size_t)i][(size_t)r] = (c.rng.uniform() < e[(size_t)r * 2] / (e[(size_t)r * 2] + e[(size_t)r * 2 + 1])) ? 2 : 1;
+                    starts[i][(size_t)r] = (c.rng.uniform() < e[(size_t)r * 2] / (e[(size_t)r * 2] + e[(size_t)r * 2 + 1])) ? 2 : 1;
             }
-            seed_reads[(size_t)i] = (uint64_t)c.rng.integers(0, 9223372036854775808.0);
-            seed_shards[(size_t)i] = (uint64_t)c.rng.integers(0, 9223372036854775808.0);
+            B.seed_reads[i] = (uint64_t)c.rng.integers(0, 9223372036854775808.0);
+            B.seed_shards[i] = (uint64_t)c.rng.integers(0, 9223372036854775808.0);
         });
+    }
+
+    // `ch`: the chains of the last round in its order (their dosages are rows of B.dos)
+    void rare_common_round(std::vector<Chain *> &ch, Batch *cur) {
+        const int C = (int)ch.size(), Ta = cx.T_out, nL = cx.nL;
+        const double t0 = now_s();
+        std::vector<int32_t> read_off((size_t)C + 1, 0);   // all-SNP reads before chain i
+        for (int i = 0; i < C; i++) read_off[(size_t)i + 1] = read_off[(size_t)i] + cx.reads_all[(size_t)ch[(size_t)i]->sample].R;
+        double *lik = B.conf.get((size_t)read_off[(size_t)C] * nL);
+        if (cx.be->make_eMatRead_t_rare_common) initial_likelihoods_device_spread(ch, B.dos.p, lik);
+        else initial_likelihoods_host_spread(ch, B.dos.p, lik, read_off);
+        std::vector<std::vector<int32_t>> starts;
+        draw_rare_common(ch, lik, read_off, starts);
         const double t1 = now_s();
         t_host += t1 - t0;
         if (CallSpan::on()) std::fprintf(stderr, "[impute-trace] rc_prep thr %d n %d %.1f %.1f\n", w, C, t0 * 1e3, t1 * 1e3);
-        double *hall = dos_all.get((size_t)C * nL * Ta);
+        double *hall = B.dos_all.get((size_t)C * nL * Ta);
         gibbs_with_retry(ch, starts, false, false, hall, true);
         const double t2 = now_s();
         t_gibbs += t2 - t1;
-        for (int i = 0; i < C; i++)
-            if (ch[(size_t)i]->phasing)
-                std::memcpy(cx.phasing_haps + (size_t)ch[(size_t)i]->sample * nL * Ta, hall + (size_t)i * nL * Ta, sizeof(double) * nL * (size_t)Ta);
-        if (cur && !cur->chains.empty()) {   // functions.R:1099-1123
-            const int n_cur = (int)cur->chains.size();
-            std::vector<int32_t> cs((size_t)n_cur);
-            for (int i = 0; i < n_cur; i++) cs[(size_t)i] = cur->chains[(size_t)i].sample - cur->lo;
-            check(cx.be->accumulate_dosage(n_cur, nL, Ta, hall, cs.data(), cur->hi - cur->lo, cx.dosage + (size_t)cur->lo * Ta,
-                                           cx.gp_t + (size_t)cur->lo * 3 * Ta, cx.nipt ? cx.nipt->fet_dosage + (size_t)cur->lo * Ta : nullptr,
-                                           cx.nipt ? cx.nipt->fet_gp_t + (size_t)cur->lo * 3 * Ta : nullptr), "qa_accumulate_dosage");
-            for (int i = 0; i < n_cur; i++) cx.nDosage[cur->chains[(size_t)i].sample] += 1;
-        }
+        keep_phasing_haps(ch, hall, Ta);
         t_accumulate += now_s() - t2;
+        accumulate(cur, hall, Ta);   // functions.R:1099-1123
         if (CallSpan::on()) std::fprintf(stderr, "[impute-trace] rc_post thr %d n %d %.1f %.1f\n", w, C, t2 * 1e3, now_s() * 1e3);
-    }
-
-    // the reads of one sample as the caller describes them: the checks of the flat form
-    static void check_reads(const Reads &r, int s, const char *what) {
-        if (r.R < 1) throw Failure(QA_ERR_INVALID, "sample " + std::to_string(s) + " has no " + what + "reads (the reference drops such samples before imputing, functions.R:300-310)");
-        if (!r.read_ptr || !r.u || !r.bq || !r.wif) throw Failure(QA_ERR_INVALID, std::string("sample ") + std::to_string(s) + ": missing " + what + "read arrays");
-        if (r.read_ptr[0] != 0) throw Failure(QA_ERR_INVALID, std::string(what) + "read_ptr of sample " + std::to_string(s) + " does not start at 0");
     }
 
     // params->sample_source: samples [lo, hi) from the caller, in order; returns where the range ends (hi, or the first s the
@@ -1082,26 +1123,14 @@ struct Worker {
     void start_phasing(Batch &b, const double *hap) {
         const auto &P = cx.P;
         const int n = (int)b.chains.size(), T = cx.T, nL = cx.nL;
-        std::vector<int32_t> read_off((size_t)n + 1, 0);
-        std::vector<int64_t> boff((size_t)n + 1, 0);
-        for (int i = 0; i < n; i++) {
-            const Reads &r = cx.reads[(size_t)b.chains[(size_t)i].sample];
-            read_off[(size_t)i + 1] = read_off[(size_t)i] + r.R;
-            boff[(size_t)i + 1] = boff[(size_t)i] + r.nb;
-        }
-        g_read_ptr.resize((size_t)read_off[(size_t)n] + n);
-        g_u.resize((size_t)boff[(size_t)n]);
-        g_bq.resize((size_t)boff[(size_t)n]);
-        parallel_for((size_t)n, n_help, [&](size_t i) {
-            const Reads &r = cx.reads[(size_t)b.chains[i].sample];
-            std::memcpy(&g_read_ptr[(size_t)read_off[i] + i], r.read_ptr, sizeof(int32_t) * ((size_t)r.R + 1));
-            std::memcpy(&g_u[(size_t)boff[i]], r.u, sizeof(int32_t) * (size_t)r.nb);
-            std::memcpy(&g_bq[(size_t)boff[i]], r.bq, sizeof(int32_t) * (size_t)r.nb);
-        });
-        double *e = conf.get((size_t)read_off[(size_t)n] * nL);
+        std::vector<int32_t> chain_sample((size_t)n), read_off;
+        for (int i = 0; i < n; i++) chain_sample[(size_t)i] = b.chains[(size_t)i].sample;
+        PackedReads pk{read_off, B.g_read_ptr, B.g_u, B.g_bq, nullptr, {}};
+        pk.fill(chain_sample, cx.reads, n_help);
+        double *e = B.conf.get((size_t)read_off[(size_t)n] * nL);
         // calculate_eMatRead_t_vs_haplotypes (functions.R:2975-3020): not rescaled, Jmax = 1000
         CallSpan span_e("ematread_conf", w, n);
-        check(cx.be->make_eMatRead_t_hap_major(handle, T, n, nL, hap, read_off.data(), g_read_ptr.data(), g_u.data(), g_bq.data(),
+        check(cx.be->make_eMatRead_t_hap_major(handle, T, n, nL, hap, read_off.data(), B.g_read_ptr.data(), B.g_u.data(), B.g_bq.data(),
                                                P.maxDifferenceBetweenReads, 1000, 0, e), "qa_rcpp_make_eMatRead_t_hap_major");
         span_e.end();
         b.phasing.clear();
@@ -1219,7 +1248,7 @@ struct Worker {
                 const double t0 = now_s();
                 if (prev) finish(*prev);
                 const double t1 = now_s();
-                if (cur) start_phasing(*cur, dos.p);
+                if (cur) start_phasing(*cur, B.dos.p);
                 t_finish += t1 - t0;
                 t_consensus += now_s() - t1;
                 prev = std::move(cur);
@@ -1254,6 +1283,52 @@ std::vector<std::pair<int, int>> sample_ranges(int n, int parts) {
         at += len;
     }
     return out;
+}
+
+// the flat form of a call's reads (read_off n + 1, read_ptr with a leading 0 per sample, u / bq over the bases, wif per read) cut
+// into one view per sample; a sample that fails check_reads ends the call
+int carve_flat_reads(std::vector<Reads> &out, int n_sample, const int32_t *read_off, const int32_t *read_ptr, const int32_t *u,
+                     const int32_t *bq, const int32_t *wif, const char *what) {
+    int64_t base = 0;
+    try {
+        for (int s = 0; s < n_sample; s++) {
+            Reads &r = out[(size_t)s];
+            r.R = read_off[s + 1] - read_off[s];
+            r.read_ptr = read_ptr + read_off[s] + s;
+            r.u = u + base;
+            r.bq = bq + base;
+            r.wif = wif + read_off[s];
+            check_reads(r, s, what);
+            r.nb = r.read_ptr[r.R];
+            base += r.nb;
+        }
+    } catch (const Failure &f) {
+        qa::set_error("qa_impute_samples: %s", f.what());
+        return f.status;
+    }
+    return QA_OK;
+}
+
+// The plan: launch sets of `per_set` samples, whole sets to the W threads in turn.  Sets the thread count leaves over: a Gibbs
+// launch costs nearly the same between 700 and 2 048 chains (a chain's serial time), so a set cut into W parts costs W launches
+// per round where it would cost one -- the left-over sets go WHOLE to the first threads (the others drain, leave their last set's
+// phasing rounds at the meeting point, and the thread that drains last runs all of them together).  Only a call with fewer sets
+// than threads is cut across them (QA_IMPUTE_CUT_LEFTOVERS=1: always, the form of round 3).
+std::vector<std::vector<std::pair<int, int>>> plan_streams(int n_sample, int per_set, int W) {
+    std::vector<std::pair<int, int>> sets;
+    for (int lo = 0; lo < n_sample; lo += per_set) sets.push_back({lo, std::min(n_sample, lo + per_set)});
+    static const bool cut_leftovers = [] { const char *e = std::getenv("QA_IMPUTE_CUT_LEFTOVERS"); return e && e[0] == '1'; }();
+    const size_t n_whole = (cut_leftovers || sets.size() < (size_t)W) ? sets.size() / W * W : sets.size();
+    std::vector<std::vector<std::pair<int, int>>> streams((size_t)W);
+    for (size_t i = 0; i < n_whole; i++) streams[i % W].push_back(sets[i]);
+    if (n_whole < sets.size()) {
+        const int lo = sets[n_whole].first;
+        const auto parts = sample_ranges(n_sample - lo, W);
+        for (int w = 0; w < W; w++)
+            if (parts[(size_t)w].second > parts[(size_t)w].first)
+                streams[(size_t)w].push_back({lo + parts[(size_t)w].first, lo + parts[(size_t)w].second});
+    }
+    return streams;
 }
 
 int impute_impl(bool keep_buffers, const qa_impute_backend_t *be, void *const *handles, int32_t n_handles, int32_t K, int32_t G, int32_t T,
@@ -1328,29 +1403,14 @@ int impute_impl(bool keep_buffers, const qa_impute_backend_t *be, void *const *h
     cx.top_width = std::max(8, P.K_top_matches);
     cx.sample_offset = sample_offset;
     cx.sample_index = P.sample_index;
-    cx.dosage = dosage; cx.gp_t = gp_t; cx.phasing_haps = phasing_haps; cx.read_labels = read_labels; cx.nDosage = nDosage;
-    cx.read_off = read_off;
+    cx.dosage = dosage; cx.gp_t = gp_t; cx.phasing_haps = phasing_haps; cx.nDosage = nDosage;
     cx.source = P.sample_source;
     cx.reads.resize((size_t)n_sample);
     cx.label_dst.assign((size_t)n_sample, nullptr);
     if (flat) {
-        int64_t base = 0;
-        for (int s = 0; s < n_sample; s++) {
-            cx.label_dst[(size_t)s] = read_labels + read_off[s];
-            Reads &r = cx.reads[(size_t)s];
-            r.R = read_off[s + 1] - read_off[s];
-            if (r.R < 1) {
-                qa::set_error("qa_impute_samples: sample %d has no reads (the reference drops such samples before imputing, functions.R:300-310)", s);
-                return QA_ERR_INVALID;
-            }
-            r.read_ptr = read_ptr + read_off[s] + s;
-            if (r.read_ptr[0] != 0) { qa::set_error("qa_impute_samples: read_ptr of sample %d does not start at 0", s); return QA_ERR_INVALID; }
-            r.nb = r.read_ptr[r.R];
-            r.u = u + base;
-            r.bq = bq + base;
-            r.wif = wif + read_off[s];
-            base += r.nb;
-        }
+        for (int s = 0; s < n_sample; s++) cx.label_dst[(size_t)s] = read_labels + read_off[s];
+        const int st = carve_flat_reads(cx.reads, n_sample, read_off, read_ptr, u, bq, wif, "");
+        if (st != QA_OK) return st;
     }
     cx.T_out = T;
     if (P.nipt) {
@@ -1385,43 +1445,13 @@ int impute_impl(bool keep_buffers, const qa_impute_backend_t *be, void *const *h
             return QA_ERR_INVALID;
         }
         cx.reads_all.resize((size_t)n_sample);
-        int64_t base = 0;
-        for (int s = 0; flat && s < n_sample; s++) {
-            Reads &r = cx.reads_all[(size_t)s];
-            r.R = rc.read_off[s + 1] - rc.read_off[s];
-            if (r.R < 1) { qa::set_error("qa_impute_samples: sample %d has no all-SNP reads", s); return QA_ERR_INVALID; }
-            r.read_ptr = rc.read_ptr + rc.read_off[s] + s;
-            if (r.read_ptr[0] != 0) { qa::set_error("qa_impute_samples: all-SNP read_ptr of sample %d does not start at 0", s); return QA_ERR_INVALID; }
-            r.nb = r.read_ptr[r.R];
-            r.u = rc.u + base;
-            r.bq = rc.bq + base;
-            r.wif = rc.wif + rc.read_off[s];
-            base += r.nb;
-        }
+        const int st = flat ? carve_flat_reads(cx.reads_all, n_sample, rc.read_off, rc.read_ptr, rc.u, rc.bq, rc.wif, "all-SNP ") : QA_OK;
+        if (st != QA_OK) return st;
     }
     if (n_sample == 0) return QA_OK;   // (the accumulators are zeroed set by set: Worker::new_batch)
 
-    // ---- the plan: launch sets of `per_set` samples; whole sets to the threads in turn, the left-overs cut across them
-    const int per_set = P.samples_per_launch_set > 0 ? P.samples_per_launch_set : 256;
-    std::vector<std::pair<int, int>> sets;
-    for (int lo = 0; lo < n_sample; lo += per_set) sets.push_back({lo, std::min(n_sample, lo + per_set)});
     const int W = n_handles;
-    // Sets the thread count leaves over: a Gibbs launch costs nearly the same between 700 and 2 048 chains (a chain's serial
-    // time), so a set cut into W parts costs W launches per round where it would cost one -- the left-over sets go WHOLE to the
-    // first threads (the others drain, leave their last set's phasing rounds at the meeting point, and the thread that drains
-    // last runs all of them together).  Only a call with fewer sets than threads is cut across them (QA_IMPUTE_CUT_LEFTOVERS=1:
-    // always, the form of round 3).
-    static const bool cut_leftovers = [] { const char *e = std::getenv("QA_IMPUTE_CUT_LEFTOVERS"); return e && e[0] == '1'; }();
-    size_t n_whole = (cut_leftovers || sets.size() < (size_t)W) ? sets.size() / W * W : sets.size();
-    std::vector<std::vector<std::pair<int, int>>> streams((size_t)W);
-    for (size_t i = 0; i < n_whole; i++) streams[i % W].push_back(sets[i]);
-    if (n_whole < sets.size()) {
-        const int lo = sets[n_whole].first, hi = n_sample;
-        auto parts = sample_ranges(hi - lo, W);
-        for (int w2 = 0; w2 < W; w2++)
-            if (parts[(size_t)w2].second > parts[(size_t)w2].first)
-                streams[(size_t)w2].push_back({lo + parts[(size_t)w2].first, lo + parts[(size_t)w2].second});
-    }
+    const auto streams = plan_streams(n_sample, P.samples_per_launch_set > 0 ? P.samples_per_launch_set : 256, W);
     cx.use_tail = W > 1 && !P.no_fused_tails;
     cx.tail.n_active = W;
 
@@ -1438,13 +1468,17 @@ int impute_impl(bool keep_buffers, const qa_impute_backend_t *be, void *const *h
         started[(size_t)w2].set = true;
         started[(size_t)w2].cv.notify_all();
     };
-    std::vector<std::exception_ptr> errs((size_t)W);
     std::vector<std::string> err_text((size_t)W);
     std::vector<int> err_status((size_t)W, 0);
     std::vector<int> err_order((size_t)W, -1);   // the order in which the threads failed: the report names the FIRST failure
     std::atomic<int> n_failed{0};
     std::atomic<bool> stagger_timed_out{false};
     auto body = [&](int w2) {
+        auto record = [&](int status, const char *text) {
+            err_order[(size_t)w2] = n_failed.fetch_add(1);
+            err_text[(size_t)w2] = text;
+            err_status[(size_t)w2] = status;
+        };
         try {
             if (w2 > 0) {
                 std::unique_lock<std::mutex> lk(started[(size_t)w2 - 1].mu);
@@ -1460,20 +1494,11 @@ int impute_impl(bool keep_buffers, const qa_impute_backend_t *be, void *const *h
             if (be->bind_thread) be->bind_thread(handles[w2]);
             workers[(size_t)w2]->run_stream(streams[(size_t)w2]);
         } catch (const Failure &f) {
-            errs[(size_t)w2] = std::current_exception();
-            err_order[(size_t)w2] = n_failed.fetch_add(1);
-            err_text[(size_t)w2] = f.what();
-            err_status[(size_t)w2] = f.status;
+            record(f.status, f.what());
         } catch (const std::exception &e) {
-            errs[(size_t)w2] = std::current_exception();
-            err_order[(size_t)w2] = n_failed.fetch_add(1);
-            err_text[(size_t)w2] = e.what();
-            err_status[(size_t)w2] = QA_ERR_HIP;
+            record(QA_ERR_HIP, e.what());
         } catch (...) {
-            errs[(size_t)w2] = std::current_exception();
-            err_order[(size_t)w2] = n_failed.fetch_add(1);
-            err_text[(size_t)w2] = "unknown failure";
-            err_status[(size_t)w2] = QA_ERR_HIP;
+            record(QA_ERR_HIP, "unknown failure");
         }
         signal(w2);
     };
@@ -1494,16 +1519,14 @@ int impute_impl(bool keep_buffers, const qa_impute_backend_t *be, void *const *h
     }
     if (stagger_timed_out.load() && std::getenv("QA_TIMING"))
         std::fprintf(stderr, "[qa_impute_samples] a host thread's first launch took more than 5 s: the staggered start was skipped for its successor\n");
-    {
-        // the failure that happened FIRST (a thread that only rethrows a failed tail's exception carries that same exception:
-        // text and status are the originator's either way)
-        int first = -1;
-        for (int w2 = 0; w2 < W; w2++)
-            if (errs[(size_t)w2] && (first < 0 || err_order[(size_t)w2] < err_order[(size_t)first])) first = w2;
-        if (first >= 0) {
-            qa::set_error("qa_impute_samples: %s", err_text[(size_t)first].c_str());
-            return err_status[(size_t)first] ? err_status[(size_t)first] : QA_ERR_HIP;
-        }
+    // the failure that happened FIRST (a thread that only rethrows a failed tail's exception carries that same exception: text
+    // and status are the originator's either way)
+    int first = -1;
+    for (int w2 = 0; w2 < W; w2++)
+        if (err_order[(size_t)w2] >= 0 && (first < 0 || err_order[(size_t)w2] < err_order[(size_t)first])) first = w2;
+    if (first >= 0) {
+        qa::set_error("qa_impute_samples: %s", err_text[(size_t)first].c_str());
+        return err_status[(size_t)first] ? err_status[(size_t)first] : QA_ERR_HIP;
     }
     return QA_OK;
 }

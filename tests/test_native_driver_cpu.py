@@ -171,6 +171,66 @@ def test_native_loop_nipt_rare_common(n_threads):
     assert len({tuple(np.unique(a.read_labels)) for a in got} & {(1, 2, 3)}) == 1
 
 
+@pytest.mark.parametrize("retry", [False, True], ids=["no-retry", "retry-groups"])
+def test_native_loop_packs_uneven_samples(twin_panel, retry):
+    """Samples of very different read counts (1, 37 and 260 reads, one read covering a single SNP) in launch sets of two, seek
+    iterations with Knew < Ksubset: every packed call -- the Gibbs call's per-chain copies (the table gets no reads_same_as: every
+    chain's copy travels), the full-panel call's per-sample reads, the read-confidence call -- carries pieces of very different
+    lengths.  retry-groups: the middle sample is tests/util.py::underflowing_sample, whose chains the oracle reports as
+    underflowing at maxDifferenceBetweenReads = 1e10 while the other samples' chains do not: the retry groups are strict subsets
+    of the round's chains (the packer runs over a non-identity idx, results come back through the scatter of the group's
+    buffers).  Equal to quilt_amd/driver.py on the oracle."""
+    from quilt_amd.driver import Driver, DriverParams
+    from quilt_amd.synth import make_synthetic_sample
+    from tests.native_driver_backend import impute_samples_on_oracle
+    from tests.util import underflowing_sample
+    panel = twin_panel
+    samples = [make_synthetic_sample(panel, seed=610 + i, n_reads=n) for i, n in enumerate((1, 37, 260))]
+    assert [s.nReads for s in samples] == [1, 37, 260] and min(int(np.diff(s.read_ptr).min()) for s in samples) == 1
+    if retry:
+        samples[1] = underflowing_sample(panel, n_reads=37)
+    P = DriverParams(nGibbsSamples=3, n_seek_its=3, Ksubset=64, Knew=24, small_ref_panel_gibbs_iterations=5,
+                     small_ref_panel_block_gibbs_iterations=(2,), seed=13)
+    drv = Driver(panel, OracleBackend(panel), P)
+    want = drv.run(samples, sample_offset=4)
+    got, stats, tab = impute_samples_on_oracle(panel, samples, P, sample_offset=4, samples_per_launch_set=2, n_threads=2)
+    for a, b in zip(got, want):
+        _same(a, b)
+    first_calls = len(samples) * (P.nGibbsSamples + 1) * P.n_seek_its
+    print("underflow_retries", stats["underflow_retries"], "gibbs_chain_calls", stats["gibbs_chain_calls"], "launches", stats["gibbs_launches"])
+    assert stats["gibbs_chain_calls"] == first_calls + stats["underflow_retries"]
+    if retry:
+        assert 0 < stats["underflow_retries"] < stats["gibbs_chain_calls"]
+        assert stats["underflow_retries"] == drv.n_underflow_retries
+    else:
+        assert stats["underflow_retries"] == 0
+
+
+def test_native_loop_nipt_rare_common_host_spread_uneven():
+    """method = "nipt" with impute_rare_common where the table has no make_eMatRead_t_rare_common (the oracle table offers none):
+    the loop spreads the haplotypes over all SNPs itself and packs every chain's copy of its sample's all-SNP reads -- samples of
+    very different read counts, two launch sets, so the phasing chains of the first share the calls of the second."""
+    from quilt_amd.driver import Driver, DriverParams
+    from quilt_amd.synth import make_rare_common, make_synthetic_panel, make_synthetic_sample_rare_common
+    from tests.native_driver_backend import impute_samples_on_oracle
+    panel = make_synthetic_panel(K=300, nSNPs=640, seed=5)
+    rc = make_rare_common(panel, 3)
+    samples = []
+    for i, n in enumerate((3, 41, 230)):
+        s = make_synthetic_sample_rare_common(panel, rc, 90 + i, n_reads=n)[0]
+        s.ff = 0.12 + 0.06 * i
+        samples.append(s)
+    assert len({s.nReads for s in samples}) == 3 and len({s.all_snp.nReads for s in samples}) == 3
+    P = DriverParams(nGibbsSamples=2, n_seek_its=2, Ksubset=64, Knew=40, seed=17, method="nipt", impute_rare_common=True,
+                     small_ref_panel_gibbs_iterations=4, small_ref_panel_block_gibbs_iterations=(2,))
+    want = Driver(panel, OracleBackend(panel, rc), P, rare_common=rc).run(samples, sample_offset=2)
+    got, stats, tab = impute_samples_on_oracle(panel, samples, P, sample_offset=2, samples_per_launch_set=2, n_threads=2, rare_common=rc)
+    assert not tab.table.make_eMatRead_t_rare_common and tab.calls["emat_all"] == tab.calls["gibbs_rc"] > 0
+    for a, b in zip(got, want):
+        _same(a, b)
+        assert np.array_equal(a.fet_dosage, b.fet_dosage) and np.array_equal(a.fet_gp_t, b.fet_gp_t)
+
+
 @pytest.mark.parametrize("n_threads,per_set", [(1, 256), (2, 1)])
 def test_native_loop_nipt(twin_panel, n_threads, per_set):
     """method = "nipt" in the native loop: three read labels drawn with the sample's fetal fraction (functions.R:586), one ff per

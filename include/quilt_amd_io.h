@@ -69,12 +69,47 @@ void qa_bam_opts_default(qa_bam_opts_t *opts);
 int qa_bam_load_sample_reads(const char *bam_path, const char *chr, int32_t nSNPs, const int32_t *L, const char *ref,
                              const char *alt, const int32_t *grid, const qa_bam_opts_t *opts, qa_sample_reads_t **out);
 
+/* Linked reads: the loader with the BX barcode tag (use_bx_tag / bxTagUpperLimit, QUILT/R/quilt.R:46-47; haplotagging and
+ * 10x-style `BX:Z:` files).  use_bx_tag = 0 is qa_bam_load_sample_reads, code path and bytes; with use_bx_tag != 0 the alignments
+ * of one MOLECULE enter the sampler as one read.  The reference's rule lives in STITCH::loadBamAndConvert, which is not in the
+ * reference tree: the rule below is stated here from the documentation of the two arguments and is UNPINNED against STITCH, like
+ * the rules above.  No further STITCH behaviour is guessed: in particular no validity rule is applied to a barcode's contents --
+ * haplotagging's convention that a `00` segment marks an invalid barcode is NOT applied; every non-empty BX:Z value is a barcode.
+ *   tag         the value of an alignment's auxiliary field BX of type Z.  No such field, a BX field of another type (BX:i, ...) or
+ *               an empty string: untagged (the first field named BX decides).  The auxiliary fields are walked once per used alignment (the same walk finds the
+ *               long-CIGAR array CG:B,I), over every type of SAM spec 4.2.4 (A c C s S i I f Z H B); the walk stops at the first
+ *               field it cannot size or that runs past the record, and never reads past the record.
+ *   who         only alignments that are (part of) a read without the tag take part: past the flag, mapping-quality, insert-size
+ *               and window filters and with at least one site after the base filters.  Mates merge by query name first, exactly as
+ *               without the tag: the result is a FRAGMENT, spanning [smallest alignment start, largest aligned end] of its
+ *               alignments in the loader's 1-based coordinates (used soft clips included), tagged as its first alignment in file
+ *               order is.
+ *   chaining    tagged fragments in order of (span start, first appearance in the file) -- so a file's sort order does not change
+ *               the molecules.  Per tag ONE molecule is open, with end = the largest span end so far; the tag's next fragment joins
+ *               it when start - end <= bxTagUpperLimit (an overlap is a negative gap: joins), and otherwise closes it and opens a
+ *               new one.  An untagged fragment is a molecule of its own.
+ *   one read    a molecule's calls are all calls of all its alignments in site order, resolved ONCE over the whole molecule: where
+ *               every call at a site shows the same allele the call with the highest quality is kept (the earliest alignment's on
+ *               a tie), where any two disagree the site is dropped -- for two alignments the mate rule above, so untagged input
+ *               gives the bytes it gives without the tag.  A molecule left without a site is not a read (stats[7], once).  The
+ *               molecule takes the slot of the first of its fragments in the loader's read list and the absorbed fragments leave
+ *               dead slots: every other read keeps its coverage-cap stream key and its place in the ordering by grid; the central
+ *               site, wif, the cap and the ordering treat the molecule like any read.
+ * bxTagUpperLimit < 0: QA_ERR_INVALID before the file is opened. */
+int qa_bam_load_sample_reads_bx(const char *bam_path, const char *chr, int32_t nSNPs, const int32_t *L, const char *ref,
+                                const char *alt, const int32_t *grid, const qa_bam_opts_t *opts, int32_t use_bx_tag,
+                                int32_t bxTagUpperLimit, qa_sample_reads_t **out);
+
 int32_t qa_sample_reads_n_reads(const qa_sample_reads_t *s);
 int64_t qa_sample_reads_n_bases(const qa_sample_reads_t *s);
 /* counts for the log lines of functions.R:289-290 and the loader's filters: [0] alignments seen on chr, [1] used,
  * [2] dropped by mapping quality, [3] by insert size, [4] by flags, [5] reads removed by the coverage cap,
  * [6] mate pairs merged, [7] alignments without a site */
 void qa_sample_reads_stats(const qa_sample_reads_t *s, int64_t stats[8]);
+/* the BX rule's counters (all 0 without use_bx_tag): [0] site-carrying alignments with a usable tag, [1] molecules made of two
+ * or more fragments, [2] fragments absorbed into another fragment's read, [3] times a tag opened a new molecule because the gap
+ * exceeded bxTagUpperLimit */
+void qa_sample_reads_bx_stats(const qa_sample_reads_t *s, int64_t out[4]);
 /* read_ptr[n_reads + 1], u / bq [n_bases] (0-based site, signed quality), wif [n_reads] (0-based grid of the central SNP),
  * central [n_reads] (0-based central site); any pointer may be NULL */
 int qa_sample_reads_export(const qa_sample_reads_t *s, int32_t *read_ptr, int32_t *u, int32_t *bq, int32_t *wif,
@@ -182,6 +217,15 @@ typedef struct qa_bam_range_result qa_bam_range_result_t;   /* opaque; owned by 
 int qa_impute_bam_range(qa_panel_t *const *panels, int32_t n_panels, const qa_impute_params_t *params, const qa_bam_range_io_t *io,
                         int32_t n_sample, const char *const *bam_paths, const int64_t *sample_index, const double *ff,
                         qa_bam_range_result_t **out);
+
+/* The same call with the loader's BX rule (qa_bam_load_sample_reads_bx): qa_impute_bam_range is this with use_bx_tag = 0.  With
+ * impute_rare_common both pile-ups of a file (common sites, all sites) apply the rule independently, as they use the same loader.
+ * bxTagUpperLimit < 0: QA_ERR_INVALID before any file is opened. */
+int qa_impute_bam_range_bx(qa_panel_t *const *panels, int32_t n_panels, const qa_impute_params_t *params, const qa_bam_range_io_t *io,
+                           int32_t use_bx_tag, int32_t bxTagUpperLimit, int32_t n_sample, const char *const *bam_paths,
+                           const int64_t *sample_index, const double *ff, qa_bam_range_result_t **out);
+/* qa_sample_reads_bx_stats summed over the files (their common-site pile-ups, like load_stats below) */
+void qa_bam_range_bx_stats(const qa_bam_range_result_t *r, int64_t out[4]);
 
 int32_t qa_bam_range_n_samples(const qa_bam_range_result_t *r);
 int32_t qa_bam_range_n_snps(const qa_bam_range_result_t *r);              /* all SNPs with impute_rare_common */

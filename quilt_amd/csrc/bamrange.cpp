@@ -69,6 +69,7 @@ struct qa_bam_range_result {
     double format_busy_s = 0;            // thread-seconds spent formatting (most of them inside seconds[1])
     int64_t stats[11] = {0};
     int64_t load_stats[8] = {0};         // the loader's counters summed over the files (qa_sample_reads_stats)
+    int64_t bx_stats[4] = {0};           // the BX rule's counters summed over the files (qa_sample_reads_bx_stats)
 };
 
 namespace {
@@ -117,9 +118,10 @@ struct Loaded {
 };
 
 int load_one(const char *path, const char *chr, int32_t T, const int32_t *L, const char *ref, const char *alt, const int32_t *grid,
-             const qa_bam_opts_t *o, Loaded &out, int64_t stats[8], std::string &err) {
+             const qa_bam_opts_t *o, int32_t use_bx_tag, int32_t bxTagUpperLimit, Loaded &out, int64_t stats[8], int64_t bx_stats[4],
+             std::string &err) {
     qa_sample_reads_t *h = nullptr;
-    const int st = qa_bam_load_sample_reads(path, chr, T, L, ref, alt, grid, o, &h);
+    const int st = qa_bam_load_sample_reads_bx(path, chr, T, L, ref, alt, grid, o, use_bx_tag, bxTagUpperLimit, &h);
     if (st != QA_OK) {
         err = std::string("cannot load ") + path + ": " + qa_last_error();
         return st;
@@ -134,6 +136,7 @@ int load_one(const char *path, const char *chr, int32_t T, const int32_t *L, con
     const int st2 = qa_sample_reads_export(h, out.read_ptr.data(), nb ? out.u.data() : &dummy, nb ? out.bq.data() : &dummy,
                                            out.R ? out.wif.data() : &dummy, nullptr);
     if (stats) qa_sample_reads_stats(h, stats);
+    if (bx_stats) qa_sample_reads_bx_stats(h, bx_stats);
     qa_sample_reads_destroy(h);
     if (st2 != QA_OK) err = std::string("cannot export the reads of ") + path;
     return st2;
@@ -143,9 +146,14 @@ int load_one(const char *path, const char *chr, int32_t T, const int32_t *L, con
 using ImputeFn = std::function<int(const qa_impute_params_t *, int32_t, const int32_t *, const int32_t *, const int32_t *, const int32_t *,
                                    const int32_t *, double *, double *, double *, int32_t *, int32_t *, int64_t *)>;
 
-int bam_range_impl(const ImputeFn &impute, const qa_impute_params_t *params, const qa_bam_range_io_t *io, int32_t n_sample,
-                   const char *const *bam_paths, const int64_t *sample_index, const double *ff, qa_bam_range_result_t **out) {
+int bam_range_impl(const ImputeFn &impute, const qa_impute_params_t *params, const qa_bam_range_io_t *io, int32_t use_bx_tag,
+                   int32_t bxTagUpperLimit, int32_t n_sample, const char *const *bam_paths, const int64_t *sample_index, const double *ff,
+                   qa_bam_range_result_t **out) {
     if (out) *out = nullptr;
+    if (bxTagUpperLimit < 0) {
+        qa::set_error("qa_impute_bam_range: bxTagUpperLimit = %d is negative", (int)bxTagUpperLimit);
+        return QA_ERR_INVALID;
+    }
     if (!params || !io || n_sample < 0 || (n_sample > 0 && (!bam_paths || !sample_index)) || !out ||
         !io->chr || io->nSNPs < 1 || !io->L || !io->ref || !io->alt || !io->grid) {
         qa::set_error("qa_impute_bam_range: missing argument");
@@ -192,6 +200,7 @@ int bam_range_impl(const ImputeFn &impute, const qa_impute_params_t *params, con
     double tr_setup = 0, tr_call = 0, tr_drain = 0, tr_sums = 0;
     std::vector<Loaded> common((size_t)n_sample), all_snps(rare ? (size_t)n_sample : 0);
     std::vector<std::array<int64_t, 8>> lstats((size_t)n_sample);
+    std::vector<std::array<int64_t, 4>> lbx((size_t)n_sample);
     std::vector<int64_t> index((size_t)std::max(n_sample, 1));     // per kept sample, filled as the files are settled
     std::vector<double> ffk((size_t)std::max(n_sample, 1));
     R->kept.assign((size_t)n_sample, -1);                          // (entry j is written before kept sample j is handed to anyone; cut to n_kept at the end)
@@ -216,11 +225,12 @@ int bam_range_impl(const ImputeFn &impute, const qa_impute_params_t *params, con
             std::string e;
             int s1;
             try {
-                s1 = load_one(bam_paths[i], io->chr, T, io->L, io->ref, io->alt, io->grid, &io->bam, common[(size_t)i], lstats[(size_t)i].data(), e);
+                s1 = load_one(bam_paths[i], io->chr, T, io->L, io->ref, io->alt, io->grid, &io->bam, use_bx_tag, bxTagUpperLimit,
+                              common[(size_t)i], lstats[(size_t)i].data(), lbx[(size_t)i].data(), e);
                 // (the all-SNP pile-up only for samples that will be imputed: the minimum test is on the common-SNP reads, functions.R:274)
                 if (s1 == QA_OK && rare && common[(size_t)i].R >= min_reads)
                     s1 = load_one(bam_paths[i], io->chr, io->nSNPs_all, io->L_all, io->ref_all, io->alt_all, io->grid_all, &io->bam,
-                                  all_snps[(size_t)i], nullptr, e);
+                                  use_bx_tag, bxTagUpperLimit, all_snps[(size_t)i], nullptr, nullptr, e);
             } catch (const std::exception &ex) {
                 s1 = QA_ERR_INVALID;
                 e = ex.what();
@@ -237,6 +247,7 @@ int bam_range_impl(const ImputeFn &impute, const qa_impute_params_t *params, con
                 const int f = ld.settled;
                 R->n_reads[(size_t)f] = common[(size_t)f].R;
                 for (int q = 0; q < 8; q++) R->load_stats[q] += lstats[(size_t)f][(size_t)q];
+                for (int q = 0; q < 4; q++) R->bx_stats[q] += lbx[(size_t)f][(size_t)q];
                 bool keep = common[(size_t)f].R >= min_reads;
                 if (keep && rare && all_snps[(size_t)f].R < 1) keep = false;   // (cannot happen: every common SNP is among the all-SNP sites)
                 if (keep) {
@@ -515,6 +526,12 @@ extern "C" {
 int qa_impute_bam_range(qa_panel_t *const *panels, int32_t n_panels, const qa_impute_params_t *params, const qa_bam_range_io_t *io,
                         int32_t n_sample, const char *const *bam_paths, const int64_t *sample_index, const double *ff,
                         qa_bam_range_result_t **out) {
+    return qa_impute_bam_range_bx(panels, n_panels, params, io, 0, 0, n_sample, bam_paths, sample_index, ff, out);
+}
+
+int qa_impute_bam_range_bx(qa_panel_t *const *panels, int32_t n_panels, const qa_impute_params_t *params, const qa_bam_range_io_t *io,
+                           int32_t use_bx_tag, int32_t bxTagUpperLimit, int32_t n_sample, const char *const *bam_paths,
+                           const int64_t *sample_index, const double *ff, qa_bam_range_result_t **out) {
     if (!panels || n_panels < 1 || !panels[0]) {
         if (out) *out = nullptr;
         qa::set_error("qa_impute_bam_range: no panel handle");
@@ -525,7 +542,7 @@ int qa_impute_bam_range(qa_panel_t *const *panels, int32_t n_panels, const qa_im
             double *dosage, double *gp_t, double *haps, int32_t *labels, int32_t *nDosage, int64_t *stats) {
             return qa_impute_samples(panels, n_panels, P, n, 0, ro, rp, u, bq, wif, dosage, gp_t, haps, labels, nDosage, stats);
         },
-        params, io, n_sample, bam_paths, sample_index, ff, out);
+        params, io, use_bx_tag, bxTagUpperLimit, n_sample, bam_paths, sample_index, ff, out);
 }
 
 // test hook (impute_testhook.h): the same host code -- loader, kept-sample bookkeeping, formatting, counts -- with the imputation
@@ -533,6 +550,13 @@ int qa_impute_bam_range(qa_panel_t *const *panels, int32_t n_panels, const qa_im
 int qa_impute_bam_range_backend(const qa_impute_backend_t *backend, void *const *handles, int32_t n_handles, int32_t K, int32_t nGrids,
                                 const qa_impute_params_t *params, const qa_bam_range_io_t *io, int32_t n_sample, const char *const *bam_paths,
                                 const int64_t *sample_index, const double *ff, qa_bam_range_result_t **out) {
+    return qa_impute_bam_range_backend_bx(backend, handles, n_handles, K, nGrids, params, io, 0, 0, n_sample, bam_paths, sample_index, ff, out);
+}
+
+int qa_impute_bam_range_backend_bx(const qa_impute_backend_t *backend, void *const *handles, int32_t n_handles, int32_t K, int32_t nGrids,
+                                   const qa_impute_params_t *params, const qa_bam_range_io_t *io, int32_t use_bx_tag,
+                                   int32_t bxTagUpperLimit, int32_t n_sample, const char *const *bam_paths, const int64_t *sample_index,
+                                   const double *ff, qa_bam_range_result_t **out) {
     if (!backend || !handles || !io) {
         if (out) *out = nullptr;
         qa::set_error("qa_impute_bam_range_backend: missing argument");
@@ -545,7 +569,7 @@ int qa_impute_bam_range_backend(const qa_impute_backend_t *backend, void *const 
             return qa_impute_samples_backend(backend, handles, n_handles, K, nGrids, T, P, n, 0, ro, rp, u, bq, wif, dosage, gp_t, haps, labels,
                                              nDosage, stats);
         },
-        params, io, n_sample, bam_paths, sample_index, ff, out);
+        params, io, use_bx_tag, bxTagUpperLimit, n_sample, bam_paths, sample_index, ff, out);
 }
 
 int32_t qa_bam_range_n_samples(const qa_bam_range_result_t *r) { return r ? r->n : 0; }
@@ -592,6 +616,10 @@ void qa_bam_range_timings(const qa_bam_range_result_t *r, double seconds[4], int
     if (seconds) std::memcpy(seconds, r->seconds, sizeof r->seconds);
     if (impute_stats) std::memcpy(impute_stats, r->stats, sizeof r->stats);
     if (load_stats) std::memcpy(load_stats, r->load_stats, sizeof r->load_stats);
+}
+
+void qa_bam_range_bx_stats(const qa_bam_range_result_t *r, int64_t out[4]) {
+    if (r && out) std::memcpy(out, r->bx_stats, sizeof r->bx_stats);
 }
 
 void qa_bam_range_destroy(qa_bam_range_result_t *r) { delete r; }

@@ -231,12 +231,80 @@ uint64_t bai_start_offset(const char *bam_path, int32_t ref, int32_t beg0, int32
 
 struct Base { int32_t u, bq; };
 struct Read { std::vector<Base> b; bool alive = true; };
+// with the BX rule, beside every Read: the span of its alignments, its tag (empty: untagged) and how many alignments it holds
+struct Frag { int64_t start = 0, end = 0; std::string tag; int32_t n_aln = 1; };
+
+// The calls of several alignments of one molecule (mates; with the BX rule every alignment of a barcode's molecule), appended
+// alignment after alignment: into site order, one call per site.  A site several alignments cover is ONE observation of the
+// molecule: calls that agree keep the call with the highest quality (the earliest alignment's on a tie), calls that disagree
+// drop the site (rule stated in include/quilt_amd_io.h; unpinned vs STITCH)
+void resolve_calls(std::vector<Base> &dst) {
+    std::stable_sort(dst.begin(), dst.end(), [](const Base &a, const Base &b) { return a.u < b.u; });
+    size_t w = 0;
+    for (size_t i = 0; i < dst.size();) {
+        size_t j = i + 1;
+        Base keep = dst[i];
+        bool conflict = false;
+        for (; j < dst.size() && dst[j].u == dst[i].u; j++) {
+            if ((dst[j].bq < 0) != (keep.bq < 0)) conflict = true;
+            else if (std::abs(dst[j].bq) > std::abs(keep.bq)) keep = dst[j];
+        }
+        if (!conflict) dst[w++] = keep;
+        i = j;
+    }
+    dst.resize(w);
+}
+
+// One walk over an alignment's auxiliary fields [a, end): tag[2] type value, the types of SAM spec 4.2.4 (A c C s S i I f Z H B).
+// It serves both look-ups the loader has: the real CIGAR of a long read, CG:B,I (want_cg), and the barcode BX:Z (want_bx; the
+// first field named BX decides: of another type, or empty, the alignment is untagged).  The walk ends when everything wanted is
+// found, at the first field it cannot size (an unknown type) or that runs past the record; nothing past `end` is read.
+struct AuxFields {
+    bool want_cg = false, want_bx = false;
+    const uint8_t *cg = nullptr;   // the CG array's operations, cg_n of them
+    int64_t cg_n = 0;
+    const uint8_t *bx = nullptr;   // the BX string (not NUL-terminated here), bx_len bytes
+    size_t bx_len = 0;
+};
+void walk_aux(const uint8_t *a, const uint8_t *end, AuxFields &x) {
+    bool cg_open = x.want_cg, bx_open = x.want_bx;
+    while ((cg_open || bx_open) && end - a >= 3) {
+        const char t0 = (char)a[0], t1 = (char)a[1], ty = (char)a[2];
+        a += 3;
+        const size_t left = (size_t)(end - a);
+        size_t len = 0;
+        if (ty == 'A' || ty == 'c' || ty == 'C') len = 1;
+        else if (ty == 's' || ty == 'S') len = 2;
+        else if (ty == 'i' || ty == 'I' || ty == 'f') len = 4;
+        else if (ty == 'Z' || ty == 'H') { while (len < left && a[len]) len++; len++; }   // (> left: no terminator inside the record)
+        else if (ty == 'B') {
+            if (left < 5) break;
+            const char sub = (char)a[0];
+            uint32_t cnt;
+            memcpy(&cnt, a + 1, 4);
+            const size_t es = (sub == 'c' || sub == 'C') ? 1 : (sub == 's' || sub == 'S') ? 2 : 4;
+            len = 5 + es * (size_t)cnt;
+            if (cg_open && t0 == 'C' && t1 == 'G' && sub == 'I' && len <= left) {
+                x.cg = a + 5;
+                x.cg_n = cnt;
+                cg_open = false;
+            }
+        } else break;   // unknown type: stop looking
+        if (len > left) break;
+        if (bx_open && t0 == 'B' && t1 == 'X') {
+            if (ty == 'Z' && len > 1) { x.bx = a; x.bx_len = len - 1; }
+            bx_open = false;
+        }
+        a += len;
+    }
+}
 
 }  // namespace
 
 struct qa_sample_reads {
     std::vector<int32_t> read_ptr, u, bq, wif, central;
     int64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    int64_t bx_stats[4] = {0, 0, 0, 0};
 };
 
 extern "C" {
@@ -254,7 +322,18 @@ void qa_bam_opts_default(qa_bam_opts_t *o) {
 
 int qa_bam_load_sample_reads(const char *bam_path, const char *chr, int32_t nSNPs, const int32_t *L, const char *ref,
                              const char *alt, const int32_t *grid, const qa_bam_opts_t *opts, qa_sample_reads_t **out) {
+    return qa_bam_load_sample_reads_bx(bam_path, chr, nSNPs, L, ref, alt, grid, opts, 0, 0, out);
+}
+
+int qa_bam_load_sample_reads_bx(const char *bam_path, const char *chr, int32_t nSNPs, const int32_t *L, const char *ref,
+                                const char *alt, const int32_t *grid, const qa_bam_opts_t *opts, int32_t use_bx_tag,
+                                int32_t bxTagUpperLimit, qa_sample_reads_t **out) {
     if (out) *out = nullptr;
+    if (bxTagUpperLimit < 0) {
+        qa::set_error("qa_bam_load_sample_reads: bxTagUpperLimit = %d is negative", (int)bxTagUpperLimit);
+        return QA_ERR_INVALID;
+    }
+    const bool use_bx = use_bx_tag != 0;
     if (!bam_path || !chr || nSNPs < 1 || !L || !ref || !alt || !grid || !out) {
         qa::set_error("qa_bam_load_sample_reads: missing argument");
         return QA_ERR_INVALID;
@@ -311,6 +390,7 @@ int qa_bam_load_sample_reads(const char *bam_path, const char *chr, int32_t nSNP
 
     auto *S = new qa_sample_reads;
     std::vector<Read> reads;
+    std::vector<Frag> frags;   // (use_bx: one per entry of reads)
     std::unordered_map<std::string, size_t> by_name;
     const int32_t lo_bp = o.chrStart > 0 ? o.chrStart : 1, hi_bp = o.chrEnd > 0 ? o.chrEnd : INT32_MAX;
     std::vector<uint8_t> rec;
@@ -348,37 +428,17 @@ int qa_bam_load_sample_reads(const char *bam_path, const char *chr, int32_t nSNP
         // A CIGAR of more than 65 535 operations (long reads) does not fit n_cigar_op: the record then carries the placeholder
         // <l_seq>S<reference length>N and the real CIGAR as the auxiliary array CG:B,I (SAM spec 4.2.2).
         int64_t n_ops = n_cigar;
+        AuxFields aux;
+        aux.want_bx = use_bx;
         if (n_cigar == 2) {
             uint32_t c0, c1;
             memcpy(&c0, cig, 4);
             memcpy(&c1, cig + 4, 4);
-            if ((c0 & 15) == 4 && (int64_t)(c0 >> 4) == l_seq && (c1 & 15) == 3) {
-                const uint8_t *a = qual + l_seq, *end = rec.data() + rec.size();
-                while (a + 3 <= end) {   // walk the auxiliary fields: tag[2] type value
-                    const char t0 = (char)a[0], t1 = (char)a[1], ty = (char)a[2];
-                    a += 3;
-                    size_t len = 0;
-                    if (ty == 'A' || ty == 'c' || ty == 'C') len = 1;
-                    else if (ty == 's' || ty == 'S') len = 2;
-                    else if (ty == 'i' || ty == 'I' || ty == 'f') len = 4;
-                    else if (ty == 'Z' || ty == 'H') { while (a + len < end && a[len]) len++; len++; }
-                    else if (ty == 'B') {
-                        if (a + 5 > end) break;
-                        const char sub = (char)a[0];
-                        uint32_t cnt;
-                        memcpy(&cnt, a + 1, 4);
-                        const size_t es = (sub == 'c' || sub == 'C') ? 1 : (sub == 's' || sub == 'S') ? 2 : 4;
-                        if (t0 == 'C' && t1 == 'G' && sub == 'I' && a + 5 + 4 * (size_t)cnt <= end) {
-                            cig = a + 5;
-                            n_ops = cnt;
-                            break;
-                        }
-                        len = 5 + es * (size_t)cnt;
-                    } else break;   // unknown type: stop looking (the placeholder then stands: no base is used)
-                    if (a + len > end) break;
-                    a += len;
-                }
-            }
+            aux.want_cg = (c0 & 15) == 4 && (int64_t)(c0 >> 4) == l_seq && (c1 & 15) == 3;
+        }
+        if (aux.want_cg || aux.want_bx) {
+            walk_aux(qual + l_seq, rec.data() + rec.size(), aux);
+            if (aux.cg) { cig = aux.cg; n_ops = aux.cg_n; }   // (not found: the placeholder stands, no base is used)
         }
         // walk the CIGAR; a soft clip is laid out left of / right of the aligned part when its bases are to be used
         int64_t rpos = (int64_t)pos0 + 1;   // 1-based reference coordinate of the next reference-consuming base
@@ -428,29 +488,22 @@ int qa_bam_load_sample_reads(const char *bam_path, const char *chr, int32_t nSNP
         if (rpos - 1 < lo_bp || aln_start > hi_bp) continue;   // outside the window
         S->stats[1]++;
         if (bases.empty()) { S->stats[7]++; continue; }
+        if (use_bx && aux.bx) S->bx_stats[0]++;
         if (o.merge_mates && (flag & 0x1)) {
             std::string name(reinterpret_cast<const char *>(&rec[32]), (size_t)std::max(0, l_read_name - 1));
             auto it = by_name.find(name);
             if (it != by_name.end()) {
                 auto &dst = reads[it->second].b;
                 dst.insert(dst.end(), bases.begin(), bases.end());
-                std::stable_sort(dst.begin(), dst.end(), [](const Base &a, const Base &b) { return a.u < b.u; });
-                // A site both mates cover is ONE observation of the molecule, not two: mates that agree keep the call with the
-                // higher quality, mates that disagree drop the site (rule stated in include/quilt_amd_io.h; unpinned vs STITCH)
-                size_t w = 0;
-                for (size_t i = 0; i < dst.size();) {
-                    size_t j = i + 1;
-                    Base keep = dst[i];
-                    bool conflict = false;
-                    for (; j < dst.size() && dst[j].u == dst[i].u; j++) {
-                        if ((dst[j].bq < 0) != (keep.bq < 0)) conflict = true;
-                        else if (std::abs(dst[j].bq) > std::abs(keep.bq)) keep = dst[j];
-                    }
-                    if (!conflict) dst[w++] = keep;
-                    i = j;
+                if (use_bx) {   // (resolved once the molecule is whole, below)
+                    Frag &f = frags[it->second];
+                    f.start = std::min(f.start, aln_start);
+                    f.end = std::max(f.end, rpos - 1);
+                    f.n_aln++;
+                } else {
+                    resolve_calls(dst);
+                    if (dst.empty()) { reads[it->second].alive = false; S->stats[7]++; }
                 }
-                dst.resize(w);
-                if (dst.empty()) { reads[it->second].alive = false; S->stats[7]++; }
                 by_name.erase(it);
                 S->stats[6]++;
                 continue;
@@ -459,8 +512,55 @@ int qa_bam_load_sample_reads(const char *bam_path, const char *chr, int32_t nSNP
         }
         reads.emplace_back();
         reads.back().b = std::move(bases);
+        if (use_bx) {
+            frags.emplace_back();
+            frags.back().start = aln_start;
+            frags.back().end = rpos - 1;
+            if (aux.bx) frags.back().tag.assign(reinterpret_cast<const char *>(aux.bx), aux.bx_len);
+        }
     }
     if (bz.bad) { delete S; return refuse("damaged or cut short (a BGZF block or an alignment record does not decode)"); }
+
+    // the BX rule (include/quilt_amd_io.h): tagged fragments in order of (span start, first appearance) chain into molecules, one
+    // open molecule per tag; a molecule lives in the slot of the first of its fragments in `reads`, the others leave dead slots
+    if (use_bx) {
+        std::vector<uint32_t> tagged;
+        for (size_t r = 0; r < reads.size(); r++) if (!frags[r].tag.empty()) tagged.push_back((uint32_t)r);
+        std::stable_sort(tagged.begin(), tagged.end(), [&](uint32_t a, uint32_t b) { return frags[a].start < frags[b].start; });
+        struct Open { uint32_t slot; int64_t end; int32_t n_frag; };
+        std::unordered_map<std::string, Open> open;
+        auto close = [&](const Open &m) { if (m.n_frag > 1) S->bx_stats[1]++; };
+        for (uint32_t r : tagged) {
+            auto it = open.find(frags[r].tag);
+            if (it != open.end() && frags[r].start - it->second.end <= (int64_t)bxTagUpperLimit) {
+                Open &m = it->second;
+                const uint32_t keep = std::min(m.slot, r), gone = std::max(m.slot, r);
+                auto &dst = reads[keep].b, &src = reads[gone].b;
+                dst.insert(dst.end(), src.begin(), src.end());
+                std::vector<Base>().swap(src);
+                reads[gone].alive = false;
+                frags[keep].n_aln += frags[gone].n_aln;
+                m.slot = keep;
+                m.end = std::max(m.end, frags[r].end);
+                m.n_frag++;
+                S->bx_stats[2]++;
+                continue;
+            }
+            if (it != open.end()) {   // the gap is above the limit: the tag's molecule so far is closed
+                close(it->second);
+                S->bx_stats[3]++;
+                it->second = Open{r, frags[r].end, 1};
+            } else {
+                open.emplace(frags[r].tag, Open{r, frags[r].end, 1});
+            }
+        }
+        for (auto &kv : open) close(kv.second);
+        for (size_t r = 0; r < reads.size(); r++) {
+            if (!reads[r].alive || frags[r].n_aln < 2) continue;
+            resolve_calls(reads[r].b);
+            if (reads[r].b.empty()) { reads[r].alive = false; S->stats[7]++; }
+        }
+    }
 
     // coverage cap (quilt.R:54): sites in ascending order; at a site above the cap the covering reads with the smallest
     // stream keys go, until the site is at the cap
@@ -513,6 +613,9 @@ int32_t qa_sample_reads_n_reads(const qa_sample_reads_t *s) { return s ? (int32_
 int64_t qa_sample_reads_n_bases(const qa_sample_reads_t *s) { return s ? (int64_t)s->u.size() : 0; }
 void qa_sample_reads_stats(const qa_sample_reads_t *s, int64_t stats[8]) {
     if (s && stats) memcpy(stats, s->stats, sizeof s->stats);
+}
+void qa_sample_reads_bx_stats(const qa_sample_reads_t *s, int64_t out[4]) {
+    if (s && out) memcpy(out, s->bx_stats, sizeof s->bx_stats);
 }
 int qa_sample_reads_export(const qa_sample_reads_t *s, int32_t *read_ptr, int32_t *u, int32_t *bq, int32_t *wif,
                            int32_t *central) {

@@ -92,6 +92,11 @@ int qa_impute_samples_backend_hla(const qa_impute_backend_t *backend, qa_fullpas
 int qa_impute_bam_range_backend(const qa_impute_backend_t *backend, void *const *handles, int32_t n_handles, int32_t K, int32_t nGrids,
                                 const qa_impute_params_t *params, const qa_bam_range_io_t *io, int32_t n_sample, const char *const *bam_paths,
                                 const int64_t *sample_index, const double *ff, qa_bam_range_result_t **out);
+/* qa_impute_bam_range_bx in the same way (qa_impute_bam_range_backend is this with use_bx_tag = 0) */
+int qa_impute_bam_range_backend_bx(const qa_impute_backend_t *backend, void *const *handles, int32_t n_handles, int32_t K, int32_t nGrids,
+                                   const qa_impute_params_t *params, const qa_bam_range_io_t *io, int32_t use_bx_tag,
+                                   int32_t bxTagUpperLimit, int32_t n_sample, const char *const *bam_paths, const int64_t *sample_index,
+                                   const double *ff, qa_bam_range_result_t **out);
 
 #ifdef __cplusplus
 }

@@ -272,7 +272,7 @@ def impute_bam_range(devs: Sequence, bam_files: Sequence[str], chr: str, ref, al
                      samples_per_launch_set: int = 256, fuse_tails: bool = True, drcs: Sequence = (), all_sites=None,
                      bqFilter: int = 17, iSizeUpperLimit: float = 1e6, useSoftClippedBases: bool = False, downsampleToCov: int = 30,
                      chrStart: int = 0, chrEnd: int = 0, merge_mates: bool = True, seed: int = 1, copy_out: Optional[Sequence[int]] = None,
-                     discard_sample_arrays: bool = False, _entry=None) -> dict:
+                     discard_sample_arrays: bool = False, use_bx_tag: bool = False, bxTagUpperLimit: int = 50000, _entry=None) -> dict:
     """The body of QUILT()'s loop over a core's sample range (quilt.R:832-982) as ONE native call: the BAM files are loaded on
     host threads, the samples with enough reads imputed together on the device, their VCF columns formatted on host threads and
     the four per-SNP count arrays summed over the range.  ``sample_index``: the files' global 0-based sample indices (default
@@ -281,8 +281,10 @@ def impute_bam_range(devs: Sequence, bam_files: Sequence[str], chr: str, ref, al
     that only wants the counts or a few samples saves the copies -- 2.5 MB of text and 4 MB of numbers per sample).
     ``discard_sample_arrays``: the library gives a sample's dosage / gp_t / phasing_haps rows back to the system once its column is
     formatted (what the R fast path asks for); ``results`` then carry the read labels and ``nDosage`` only.
+    ``use_bx_tag`` / ``bxTagUpperLimit`` (quilt.R:46-47): the loader's linked-read rule (include/quilt_amd_io.h); ``bx_stats``
+    holds its four counters summed over the files.
     Returns dict(imputed, n_reads, columns [VcfColumn or None], results {file index: SampleResult}, counts SummaryCounts,
-    seconds {load, impute, format, total}, stats)."""
+    seconds {load, impute, format, total}, stats, load_stats, bx_stats)."""
     from .io import BamOpts, SummaryCounts, VcfColumn
     panel = devs[0].panel
     P = params or DriverParams()
@@ -290,6 +292,9 @@ def impute_bam_range(devs: Sequence, bam_files: Sequence[str], chr: str, ref, al
         raise ValueError("the panel carries no SNP positions (Panel.L)")
     n = len(bam_files)
     T = panel.nSNPs
+    if int(bxTagUpperLimit) != bxTagUpperLimit or not -2**31 <= bxTagUpperLimit < 2**31:
+        raise ValueError("bxTagUpperLimit must be a whole number")
+    bx = (C.c_int32(int(bool(use_bx_tag))), C.c_int32(int(bxTagUpperLimit)))
     Lc = np.ascontiguousarray(panel.L, dtype=np.int32)
     grid = np.ascontiguousarray(panel.grid if panel.grid is not None else np.arange(T, dtype=np.int32) // 32, dtype=np.int32)
     as_bytes = lambda a: bytes(a) if isinstance(a, (bytes, bytearray)) else "".join(a).encode()
@@ -338,17 +343,23 @@ def impute_bam_range(devs: Sequence, bam_files: Sequence[str], chr: str, ref, al
     ffv = None if ff is None else np.ascontiguousarray(ff, dtype=np.float64)
     handles = (C.c_void_p * len(devs))(*[getattr(d, "handle", None) for d in devs])
     L = lib()
-    for name in ("qa_impute_bam_range", "qa_bam_range_column", "qa_bam_range_sample", "qa_bam_range_counts", "qa_bam_range_imputed",
+    for name in ("qa_impute_bam_range_bx", "qa_bam_range_column", "qa_bam_range_sample", "qa_bam_range_counts", "qa_bam_range_imputed",
                  "qa_bam_range_n_reads", "qa_bam_range_n_snps", "qa_bam_range_n_samples"):
         getattr(L, name).restype = C.c_int
     L.qa_bam_range_destroy.restype = None
     L.qa_bam_range_timings.restype = None
+    L.qa_bam_range_bx_stats.restype = None
     h = C.c_void_p()
     if _entry is not None:   # (tests: the same native host code with its imputation step on a checker -- impute_testhook.h)
-        _entry(q, io, n, paths, sidx, ffv, h)
+        if use_bx_tag:   # (an entry that is given the tag takes the pair; the others keep their seven arguments)
+            _entry(q, io, n, paths, sidx, ffv, h, use_bx_tag=bx[0], bxTagUpperLimit=bx[1])
+        elif bxTagUpperLimit < 0:
+            raise ValueError("bxTagUpperLimit must not be negative")
+        else:
+            _entry(q, io, n, paths, sidx, ffv, h)
     else:
-        check(L.qa_impute_bam_range(handles, C.c_int32(len(devs)), C.byref(q), C.byref(io), C.c_int32(n), paths, ptr(sidx), ptr(ffv),
-                                    C.byref(h)))
+        check(L.qa_impute_bam_range_bx(handles, C.c_int32(len(devs)), C.byref(q), C.byref(io), *bx, C.c_int32(n), paths, ptr(sidx),
+                                       ptr(ffv), C.byref(h)))
     try:
         assert L.qa_bam_range_n_snps(h) == T_out and L.qa_bam_range_n_samples(h) == n
         nL = 3 if P.method == "nipt" else 2
@@ -380,9 +391,11 @@ def impute_bam_range(devs: Sequence, bam_files: Sequence[str], chr: str, ref, al
                                alleleCount=np.ascontiguousarray(ac))
         sec, st, ls = np.zeros(4), np.zeros(11, dtype=np.int64), np.zeros(8, dtype=np.int64)
         L.qa_bam_range_timings(h, ptr(sec), ptr(st), ptr(ls))
+        bxs = np.zeros(4, dtype=np.int64)
+        L.qa_bam_range_bx_stats(h, ptr(bxs))
     finally:
         L.qa_bam_range_destroy(h)
     del keep, keep_q
     return dict(imputed=imputed, n_reads=n_reads, columns=columns, results=results, counts=counts,
                 seconds=dict(zip(("load", "impute", "format", "total"), sec.tolist())), stats=dict(zip(STAT_NAMES, st.tolist())),
-                load_stats=ls.tolist())
+                load_stats=ls.tolist(), bx_stats=bxs.tolist())

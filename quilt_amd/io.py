@@ -30,7 +30,7 @@ class BamOpts(C.Structure):
 def _io_lib():
     L = lib()
     if not getattr(L, "_io_ready", False):
-        for name in ("qa_bam_load_sample_reads", "qa_sample_reads_n_reads", "qa_sample_reads_export", "qa_vcf_column_diploid",
+        for name in ("qa_bam_load_sample_reads", "qa_bam_load_sample_reads_bx", "qa_sample_reads_n_reads", "qa_sample_reads_export", "qa_vcf_column_diploid",
                      "qa_vcf_column_nipt", "qa_vcf_info_column", "qa_vcf_write_body", "qa_vcf_write_text", "qa_hwe_exact",
                      "qa_accumulate_dosage", "qa_consensus_read_labels"):
             getattr(L, name).restype = C.c_int
@@ -38,6 +38,7 @@ def _io_lib():
         L.qa_vcf_missing_entry.restype = C.c_char_p
         L.qa_sample_reads_destroy.restype = None
         L.qa_sample_reads_stats.restype = None
+        L.qa_sample_reads_bx_stats.restype = None
         L.qa_bam_opts_default.restype = None
         L._io_ready = True
     return L
@@ -91,10 +92,14 @@ def consensus_read_labels(labels: np.ndarray, p: np.ndarray, can_hap: int, minrp
 def loadBamAndConvert(bam_file: str, chr: str, L: np.ndarray, ref: Sequence[str], alt: Sequence[str],
                       grid: Optional[np.ndarray] = None, *, bqFilter: int = 17, iSizeUpperLimit: float = 1e6,
                       useSoftClippedBases: bool = False, downsampleToCov: int = 30, chrStart: int = 0, chrEnd: int = 0,
-                      merge_mates: bool = True, seed: int = 1, return_stats: bool = False):
+                      merge_mates: bool = True, seed: int = 1, return_stats: bool = False, use_bx_tag: bool = False,
+                      bxTagUpperLimit: int = 50000, return_bx_stats: bool = False):
     """One sample's reads over the region's SNPs, already snapped to the grid (functions.R:243-298).
     ``L`` 1-based ascending positions, ``ref`` / ``alt`` one character per SNP, ``grid`` 0-based grid per SNP (default
-    ``snp // 32``, STITCH::assign_positions_to_grid with gridWindowSize = 32 SNPs as QUILT uses it)."""
+    ``snp // 32``, STITCH::assign_positions_to_grid with gridWindowSize = 32 SNPs as QUILT uses it).
+    ``use_bx_tag`` / ``bxTagUpperLimit`` (quilt.R:46-47): alignments that share a ``BX:Z`` barcode and lie within the limit of
+    each other enter as ONE read (the rule is stated in include/quilt_amd_io.h); files without the tag load as without the
+    option.  ``return_bx_stats``: the rule's four counters come back as a dict behind the other return values."""
     lb = _io_lib()
     L = np.ascontiguousarray(L, dtype=np.int32)
     T = len(L)
@@ -105,9 +110,12 @@ def loadBamAndConvert(bam_file: str, chr: str, L: np.ndarray, ref: Sequence[str]
         raise ValueError("L, ref, alt and grid must describe the same SNPs (one character per allele)")
     o = BamOpts(int(bqFilter), int(min(iSizeUpperLimit, 2**31 - 1)), int(bool(useSoftClippedBases)), int(downsampleToCov),
                 int(chrStart), int(chrEnd), int(bool(merge_mates)), int(seed))
+    if int(bxTagUpperLimit) != bxTagUpperLimit or not -2**31 <= bxTagUpperLimit < 2**31:
+        raise ValueError("bxTagUpperLimit must be a whole number")
     h = C.c_void_p()
-    _check(lb.qa_bam_load_sample_reads(bam_file.encode(), chr.encode(), C.c_int32(T), ptr(L), refb, altb, ptr(grid),
-                                       C.byref(o), C.byref(h)), f"cannot load {bam_file} ({chr})")
+    _check(lb.qa_bam_load_sample_reads_bx(bam_file.encode(), chr.encode(), C.c_int32(T), ptr(L), refb, altb, ptr(grid),
+                                          C.byref(o), C.c_int32(int(bool(use_bx_tag))), C.c_int32(int(bxTagUpperLimit)), C.byref(h)),
+           f"cannot load {bam_file} ({chr})")
     try:
         R = lb.qa_sample_reads_n_reads(h)
         nb = lb.qa_sample_reads_n_bases(h)
@@ -117,14 +125,22 @@ def loadBamAndConvert(bam_file: str, chr: str, L: np.ndarray, ref: Sequence[str]
         _check(lb.qa_sample_reads_export(h, ptr(read_ptr), ptr(u), ptr(bq), ptr(wif), None), "export")
         stats = np.zeros(8, dtype=np.int64)
         lb.qa_sample_reads_stats(h, ptr(stats))
+        bx = np.zeros(4, dtype=np.int64)
+        lb.qa_sample_reads_bx_stats(h, ptr(bx))
     finally:
         lb.qa_sample_reads_destroy(h)
     s = SampleReads(read_ptr=read_ptr, u=u, bq=bq, wif=wif)
+    ret = [s]
     if return_stats:
         names = ("alignments_on_chr", "used", "low_mapq", "insert_size", "flagged", "removed_by_coverage_cap",
                  "mates_merged", "no_site")
-        return s, dict(zip(names, (int(x) for x in stats)))
-    return s
+        ret.append(dict(zip(names, (int(x) for x in stats))))
+    if return_bx_stats:
+        ret.append(dict(zip(BX_STAT_NAMES, (int(x) for x in bx))))
+    return ret[0] if len(ret) == 1 else tuple(ret)
+
+
+BX_STAT_NAMES = ("tagged_alignments", "molecules_of_several_fragments", "fragments_absorbed", "split_by_limit")
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -330,11 +346,13 @@ def make_and_write_output_file(output_filename: str, sampleNames: Sequence[str],
 def impute_bams_to_vcf(panel, backend, bam_files: Sequence[str], sampleNames: Sequence[str], chr: str, ref: Sequence[str],
                        alt: Sequence[str], output_filename: str, params=None, inRegion2: Optional[np.ndarray] = None,
                        minimum_number_of_sample_reads: int = 2, ff: Optional[Sequence[float]] = None,
-                       output_gt_phased_genotypes: bool = True, **bam_opts):
+                       output_gt_phased_genotypes: bool = True, use_bx_tag: bool = False, bxTagUpperLimit: int = 50000,
+                       **bam_opts):
     """The per-sample path end to end for one region: BAM -> sampleReads (f3) -> the driver loop on `backend` -> VCF
     columns and file (f4).  What get_and_impute_one_sample does between its ``loadBamAndConvert`` call and its return
     value, plus the writer (functions.R:243-298, 1408-1477; writers.R).  Samples with fewer than
-    ``minimum_number_of_sample_reads`` reads are written as missing and left out of the counts (functions.R:274-287)."""
+    ``minimum_number_of_sample_reads`` reads are written as missing and left out of the counts (functions.R:274-287).
+    ``use_bx_tag`` / ``bxTagUpperLimit``: the loader's linked-read rule (:func:`loadBamAndConvert`)."""
     from .driver import Driver, DriverParams
     params = params or DriverParams()
     if panel.L is None:
@@ -342,7 +360,7 @@ def impute_bams_to_vcf(panel, backend, bam_files: Sequence[str], sampleNames: Se
     grid = panel.grid if panel.grid is not None else np.arange(panel.nSNPs, dtype=np.int32) // 32
     samples, imputed = [], []
     for i, path in enumerate(bam_files):
-        s = loadBamAndConvert(path, chr, panel.L, ref, alt, grid, **bam_opts)
+        s = loadBamAndConvert(path, chr, panel.L, ref, alt, grid, use_bx_tag=use_bx_tag, bxTagUpperLimit=bxTagUpperLimit, **bam_opts)
         if ff is not None:
             s.ff = float(ff[i])
         if s.nReads < minimum_number_of_sample_reads:

@@ -14,7 +14,10 @@
 ##           count arrays natively -- the loop body of quilt.R:832-982 with get_and_impute_one_sample's own I/O
 ##           (functions.R:243-298, :1380-1463) in one call.  R's serial loader and formatter handle about one sample per second;
 ##           the device imputes about forty.
-##       (b) R I/O (the fallback: CRAM input, bx tags, QUILT_AMD_NATIVE_IO=0): per sample the reference's own loader
+##           use_bx_tag (TRUE by default in QUILT(), quilt.R:139) is the native loader's own rule (include/quilt_amd_io.h;
+##           unpinned against STITCH): files without BX tags load exactly as with use_bx_tag = FALSE, so a run with default
+##           arguments takes this form.
+##       (b) R I/O (the fallback: CRAM input, hla_run, QUILT_AMD_NATIVE_IO=0): per sample the reference's own loader
 ##           (functions.R:132-172, :251-298), then `.Call("qa_impute_sample_range", ...)`, then per sample what
 ##           get_and_impute_one_sample returns (functions.R:1380-1463) by the reference's own functions.
 ## Nothing in this FILE computes a probability.
@@ -76,12 +79,13 @@ quilt_amd_hla_iGrid <- function(gamma_physically_closest_to, L, grid, nGrids) {
 
 
 ## may the range's I/O run natively?  Everything the native loader does not implement keeps the reference's R loader.
+## (use_bx_tag stays an argument for the callers that pass it; it no longer decides: the native loader has the BX rule)
 quilt_amd_native_io_is_covered <- function(bam_files, cram_files, use_bx_tag, pos, pos_all, impute_rare_common) {
     if (Sys.getenv("QUILT_AMD_NATIVE_IO", "1") == "0") return(FALSE)
     if (!is.loaded("qa_impute_bam_range", PACKAGE = "QUILT")) return(FALSE)
     one_letter <- function(p) all(nchar(as.character(p[, 3])) == 1) && all(nchar(as.character(p[, 4])) == 1)
     ok <- length(cram_files) == 0 || all(cram_files == "") || all(is.na(cram_files))   ## CRAM: not decoded natively
-    ok <- ok && length(bam_files) > 0 && !any(is.na(bam_files)) && !isTRUE(use_bx_tag) ## bx tags: STITCH's loader only
+    ok <- ok && length(bam_files) > 0 && !any(is.na(bam_files))
     ok <- ok && one_letter(pos) && (!impute_rare_common || one_letter(pos_all))        ## biallelic SNPs, single letters
     return(isTRUE(ok))
 }
@@ -176,7 +180,8 @@ quilt_amd_impute_sample_range <- function(
             bqFilter = bqFilter, iSizeUpperLimit = iSizeUpperLimit, useSoftClippedBases = useSoftClippedBases,
             downsampleToCov = downsampleToCov, chrStart = chrStart, chrEnd = chrEnd,
             minimum_number_of_sample_reads = minimum_number_of_sample_reads,
-            output_gt_phased_genotypes = output_gt_phased_genotypes
+            output_gt_phased_genotypes = output_gt_phased_genotypes,
+            use_bx_tag = isTRUE(use_bx_tag), bxTagUpperLimit = bxTagUpperLimit
         )
         if (impute_rare_common) {
             sites <- c(sites, list(
@@ -188,6 +193,10 @@ quilt_amd_impute_sample_range <- function(
         print_message(paste0("Imputing samples ", w[1], " to ", w[n], " on the GPU from their BAM files (", n, " samples in one call)"))
         out <- .Call("qa_impute_bam_range", as.character(bam_files[w]), sites, panel_objects, params, as.numeric(w - 1L),
                      as.integer(n_handles), PACKAGE = "QUILT")
+        bx <- out[["bx_stats"]]
+        print_message(paste0("Samples ", w[1], " to ", w[n], " were loaded by the native loader (use_bx_tag = ", isTRUE(use_bx_tag),
+                             "): ", bx[1], " tagged alignments, ", bx[2], " molecules of several fragments, ", bx[3],
+                             " fragments absorbed, ", bx[4], " splits at bxTagUpperLimit = ", bxTagUpperLimit))
         results <- as.list(1:n)
         nS <- length(out[["afCount"]])
         ## The loop of quilt.R:955-961 adds eij / fij / max_gen / per_sample_alleleCount of every imputed sample to the core's four
@@ -224,6 +233,8 @@ quilt_amd_impute_sample_range <- function(
         )
     }
     ## ---- 1. reads of every sample of the range (the reference's own loader; functions.R:132-172, :251-298)
+    print_message(paste0("Samples ", w[1], " to ", w[n], " are loaded by the reference's R loader (about a second per sample: CRAM input, ",
+                         "hla_run or QUILT_AMD_NATIVE_IO=0)"))
     loaded <- lapply(w, function(iSample) load1(iSample, L, pos, grid))
     loaded_all <- NULL
     if (impute_rare_common) {

@@ -1037,12 +1037,15 @@ SEXP qa_impute_sample_range(SEXP readsListSEXP, SEXP panelSEXP, SEXP paramsSEXP,
  *   sites           named list: chr; L (pos[, 2]), ref, alt (pos[, 3:4] as character vectors of single letters), grid (0-based);
  *                   impute_rare_common: L_all / ref_all / alt_all / grid_all (pos_all, special_rare_common_objects$grid);
  *                   loader options bqFilter, iSizeUpperLimit, useSoftClippedBases, downsampleToCov, chrStart, chrEnd (the
- *                   window of functions.R:262-263); minimum_number_of_sample_reads, output_gt_phased_genotypes, n_io_threads
+ *                   window of functions.R:262-263); minimum_number_of_sample_reads, output_gt_phased_genotypes, n_io_threads;
+ *                   optional: use_bx_tag (logical) and bxTagUpperLimit (a whole number >= 0; default 50000, quilt.R:47) -- the
+ *                   loader's linked-read rule (include/quilt_amd_io.h: qa_bam_load_sample_reads_bx); absent means off
  *   panel_objects, params, n_handles   as for qa_impute_sample_range (params$ff: one per FILE)
  *   sample_index    0-based global index of every file's sample (iSample - 1)
  * Returns list(sample_was_imputed (logical), n_reads (integer), per_sample_vcf_col (list: character vector per imputed sample,
  * NULL otherwise), read_labels (list), infoCount (nSNPs x 2), afCount, hweCount (nSNPs x 3), alleleCount (nSNPs x 2): the
- * range's sums in sample order as quilt.R:955-961 forms them; seconds (load, impute, format, total), stats).  The loader is
+ * range's sums in sample order as quilt.R:955-961 forms them; seconds (load, impute, format, total), stats, bx_stats (the BX rule's
+ * four counters summed over the files: qa_bam_range_bx_stats; zeros without use_bx_tag)).  The loader is
  * csrc/hostio.cpp's (include/quilt_amd_io.h says where it is unpinned against STITCH: CRAM is refused); quilt-amd.R calls this
  * routine only for the options it implements and falls back to the R loader otherwise. */
 static const char *one_string(SEXP list, const char *name) {
@@ -1076,6 +1079,22 @@ SEXP qa_impute_bam_range_call(SEXP bamFilesSEXP, SEXP sitesSEXP, SEXP panelSEXP,
     if ((TYPEOF(sample_indexSEXP) != REALSXP && TYPEOF(sample_indexSEXP) != INTSXP) || Rf_length(sample_indexSEXP) != n)
         Rf_error("quilt_amd: %s: sample_index must hold one 0-based global index per file", who);
     range_validate(panelSEXP, paramsSEXP, who);
+    /* the BX pair, checked here: before anything is allocated (an R error longjmps out of the routine) */
+    int use_bx_tag = 0, bx_limit = 50000;
+    {
+        SEXP ub = list_get(sitesSEXP, "use_bx_tag"), bl = list_get(sitesSEXP, "bxTagUpperLimit");
+        if (ub != R_NilValue) {
+            if (TYPEOF(ub) != LGLSXP || Rf_length(ub) != 1 || (LOGICAL(ub)[0] != 0 && LOGICAL(ub)[0] != 1))   /* (NA is neither) */
+                Rf_error("quilt_amd: %s: sites$use_bx_tag must be TRUE or FALSE", who);
+            use_bx_tag = LOGICAL(ub)[0] != 0;
+        }
+        if (bl != R_NilValue) {
+            const double v = ((TYPEOF(bl) == INTSXP || TYPEOF(bl) == REALSXP) && Rf_length(bl) == 1) ? Rf_asReal(bl) : -1.0;
+            if (!(v >= 0 && v <= 2147483647.0 && v == (double)(int)v))   /* (NA and NaN fail every comparison) */
+                Rf_error("quilt_amd: %s: sites$bxTagUpperLimit must be one whole number >= 0 (below 2^31)", who);
+            bx_limit = (int)v;
+        }
+    }
     const char *chr = one_string(sitesSEXP, "chr");
     SEXP Lx = list_get(sitesSEXP, "L");
     if (!chr || Lx == R_NilValue) Rf_error("quilt_amd: %s: sites needs chr, L, ref, alt, grid", who);
@@ -1129,7 +1148,7 @@ SEXP qa_impute_bam_range_call(SEXP bamFilesSEXP, SEXP sitesSEXP, SEXP panelSEXP,
         io.output_gt_phased_genotypes = flag(sitesSEXP, "output_gt_phased_genotypes", 1);
         io.n_io_threads = (int)num_or(sitesSEXP, "n_io_threads", 0);
         io.discard_sample_arrays = 1;   /* (columns, labels and counts go back to R: the per-SNP numbers behind them are not kept) */
-        st = qa_impute_bam_range(cx.handles, cx.n_handles, &cx.ip, &io, n, paths, sidx, cx.nipt ? cx.nq.ff : NULL, &res);
+        st = qa_impute_bam_range_bx(cx.handles, cx.n_handles, &cx.ip, &io, use_bx_tag, bx_limit, n, paths, sidx, cx.nipt ? cx.nq.ff : NULL, &res);
         if (st != QA_OK) snprintf(msg, sizeof msg, "%s", qa_last_error());
         range_teardown(&cx);
     }
@@ -1144,8 +1163,8 @@ SEXP qa_impute_bam_range_call(SEXP bamFilesSEXP, SEXP sitesSEXP, SEXP panelSEXP,
     R_RegisterCFinalizerEx(guard, range_result_finalizer, TRUE);
     const int T_out = qa_bam_range_n_snps(res);
     const char *names[] = {"sample_was_imputed", "n_reads", "per_sample_vcf_col", "read_labels", "infoCount", "afCount", "hweCount",
-                           "alleleCount", "seconds", "stats"};
-    SEXP out = PROTECT(named_list(10, names));
+                           "alleleCount", "seconds", "stats", "bx_stats"};
+    SEXP out = PROTECT(named_list(11, names));
     SEXP imputed = PROTECT(Rf_allocVector(LGLSXP, n)), n_reads = PROTECT(Rf_allocVector(INTSXP, n));
     SEXP cols = PROTECT(Rf_allocVector(VECSXP, n)), labs = PROTECT(Rf_allocVector(VECSXP, n));
     SET_VECTOR_ELT(out, 0, imputed); SET_VECTOR_ELT(out, 1, n_reads); SET_VECTOR_ELT(out, 2, cols); SET_VECTOR_ELT(out, 3, labs);
@@ -1177,8 +1196,13 @@ SEXP qa_impute_bam_range_call(SEXP bamFilesSEXP, SEXP sitesSEXP, SEXP panelSEXP,
     qa_bam_range_timings(res, REAL(sec), st64, NULL);
     for (int i = 0; i < 11; i++) REAL(stats)[i] = (double)st64[i];
     SET_VECTOR_ELT(out, 8, sec); SET_VECTOR_ELT(out, 9, stats);
+    SEXP bxs = PROTECT(Rf_allocVector(REALSXP, 4));
+    int64_t bx64[4] = {0};
+    qa_bam_range_bx_stats(res, bx64);
+    for (int i = 0; i < 4; i++) REAL(bxs)[i] = (double)bx64[i];
+    SET_VECTOR_ELT(out, 10, bxs);
     range_result_finalizer(guard);
-    UNPROTECT(12);
+    UNPROTECT(13);
     return out;
 }
 

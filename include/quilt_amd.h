@@ -827,6 +827,30 @@ int qa_impute_samples_hla(qa_panel_t *const *panels, int32_t n_panels, const qa_
                           const int32_t *wif, double *dosage, double *gp_t, double *phasing_haps, int32_t *read_labels,
                           int32_t *nDosage, int64_t *stats, const qa_impute_hla_t *hla);
 
+/*
+ * output_read_label_prob = TRUE (QUILT/R/quilt.R, CHANGELOG v2.0.1; functions.R:1144-1166): per read, the confidence of its label.
+ * The reference keeps assess_reads_out[[2]] of the LAST non-phasing Gibbs sample (each earlier one is overwritten): mp of chain
+ * nGibbsSamples, computed by qa_read_label_confidence (include/quilt_amd_io.h) from the read likelihoods the loop already has for
+ * the consensus labels.  final_read_labels_prob[[3]] are the consensus labels (read_labels of the call).
+ *   read_label_prob   flat reads: OUT, one double per read in read_labels' layout (read_off[n_sample] entries); NULL: not wanted
+ *   dest              params->sample_source: called once per sample, after acquire(s) returned QA_OK, by the same thread;
+ *                     *read_label_prob = where the sample's n_reads doubles go (NULL: not wanted for this sample).  A status < 0
+ *                     fails the call.  With a source read_label_prob above is not read.
+ * Asking for the output changes no other output bit and draws nothing from any stream.
+ */
+typedef struct {
+    double *read_label_prob;
+    int (*dest)(void *ctx, int32_t s, double **read_label_prob);
+    void *ctx;
+} qa_impute_reads_out_t;
+
+/* qa_impute_samples_hla's arguments with hla optional (NULL: qa_impute_samples) and the per-read outputs (NULL: none).  With both
+ * NULL this is qa_impute_samples. */
+int qa_impute_samples_reads(qa_panel_t *const *panels, int32_t n_panels, const qa_impute_params_t *params, int32_t n_sample,
+                            int64_t sample_offset, const int32_t *read_off, const int32_t *read_ptr, const int32_t *u, const int32_t *bq,
+                            const int32_t *wif, double *dosage, double *gp_t, double *phasing_haps, int32_t *read_labels,
+                            int32_t *nDosage, int64_t *stats, const qa_impute_hla_t *hla, const qa_impute_reads_out_t *reads_out);
+
 /* The host threads' marshalling and pinned transfer buffers are kept per panel handle between calls (a launch set of 2 048
  * chains moves ~3.5 GB through them): this frees them all.  Call it when no qa_impute_samples call is running. */
 int qa_impute_release_buffers(void);

@@ -100,6 +100,25 @@ int qa_bam_load_sample_reads_bx(const char *bam_path, const char *chr, int32_t n
                                 const char *alt, const int32_t *grid, const qa_bam_opts_t *opts, int32_t use_bx_tag,
                                 int32_t bxTagUpperLimit, qa_sample_reads_t **out);
 
+/* The loader with one NAME per returned read (output_read_label_prob's final_read_labels_prob[[1]]; people haplotag reads with
+ * it).  keep_names = 0 is qa_bam_load_sample_reads_bx: the code path it runs now, and no name is kept.  The read arrays are the
+ * same bytes with and without the request.  The rule, UNPINNED against STITCH like the loader's other rules:
+ *   a read's name is the query name of the FIRST alignment, in file order, of the fragment that holds the read's slot in the
+ *   loader's read list.  Merged mates share that name by construction (they merge BY name).  A BX molecule takes the name of the
+ *   fragment whose slot it takes (above: the first of its fragments in the read list).  Names follow the reads through the
+ *   coverage cap and through the stable ordering by grid: name r belongs to read r of qa_sample_reads_export's arrays.
+ * Difference from the reference, stated and NOT reproduced: get_and_impute_one_sample takes sampleReadsInfo[, "qname"] BEFORE
+ * snap_sampleReads_to_grid reorders the reads (functions.R:270-298, :319), so where that reordering is not the identity its names
+ * are in the loader's order while its probabilities and labels are in grid order.  Here all three are in the order of the reads. */
+int qa_bam_load_sample_reads_named(const char *bam_path, const char *chr, int32_t nSNPs, const int32_t *L, const char *ref,
+                                   const char *alt, const int32_t *grid, const qa_bam_opts_t *opts, int32_t use_bx_tag,
+                                   int32_t bxTagUpperLimit, int32_t keep_names, qa_sample_reads_t **out);
+/* bytes of all names with their terminators; -1 when the reads were loaded without names */
+int64_t qa_sample_reads_names_bytes(const qa_sample_reads_t *s);
+/* names back to back, NUL-terminated, off[r] = start of name r, off[n_reads] = bytes (the layout of the VCF columns); either
+ * pointer may be NULL; QA_ERR_INVALID when the reads were loaded without names */
+int qa_sample_reads_export_names(const qa_sample_reads_t *s, char *buf, int64_t *off);
+
 int32_t qa_sample_reads_n_reads(const qa_sample_reads_t *s);
 int64_t qa_sample_reads_n_bases(const qa_sample_reads_t *s);
 /* counts for the log lines of functions.R:289-290 and the loader's filters: [0] alignments seen on chr, [1] used,
@@ -224,6 +243,36 @@ int qa_impute_bam_range(qa_panel_t *const *panels, int32_t n_panels, const qa_im
 int qa_impute_bam_range_bx(qa_panel_t *const *panels, int32_t n_panels, const qa_impute_params_t *params, const qa_bam_range_io_t *io,
                            int32_t use_bx_tag, int32_t bxTagUpperLimit, int32_t n_sample, const char *const *bam_paths,
                            const int64_t *sample_index, const double *ff, qa_bam_range_result_t **out);
+
+/* ONE extensible entry for the options of QUILT() that reach the range call: the entries above are calls of it, and a later
+ * option is a field here, not another suffix.  A zeroed struct with hla_grid = -1 is qa_impute_bam_range.
+ *   use_bx_tag, bxTagUpperLimit   as for qa_impute_bam_range_bx
+ *   output_read_label_prob        != 0: per imputed sample the reads' names (qa_bam_load_sample_reads_named), the confidence of
+ *                                 their labels (qa_impute_samples_reads) and, as before, their consensus labels:
+ *                                 qa_bam_range_read_label_prob.  With impute_rare_common these are the COMMON-site reads'.
+ *   hla_grid                      >= 0: hla_run = TRUE, the gamma columns at this 0-based grid (qa_impute_hla_t.grid):
+ *                                 qa_bam_range_hla.  The refusals of qa_impute_samples_hla apply BEFORE any file is opened: a
+ *                                 handle without the gamma column, use_mspbwt, nipt, rare_common, a grid outside the panel, a
+ *                                 last seek iteration that is not a dosage pass.  -1: off (other negative values: QA_ERR_INVALID)
+ * Neither option changes another output bit of the call. */
+typedef struct {
+    int32_t use_bx_tag, bxTagUpperLimit;
+    int32_t output_read_label_prob;
+    int32_t hla_grid;
+} qa_bam_range_extras_t;
+int qa_impute_bam_range_ex(qa_panel_t *const *panels, int32_t n_panels, const qa_impute_params_t *params, const qa_bam_range_io_t *io,
+                           const qa_bam_range_extras_t *ex, int32_t n_sample, const char *const *bam_paths, const int64_t *sample_index,
+                           const double *ff, qa_bam_range_result_t **out);
+/* output_read_label_prob: sample i's names (buf + n + 1 offsets, the layout of qa_sample_reads_export_names), the confidences
+ * (n doubles) and n = its reads; read_labels of qa_bam_range_sample are the third part.  NULL / 0 for a file that was not imputed
+ * or a call without the option; any pointer may be NULL.  discard_sample_arrays does not discard these. */
+int qa_bam_range_read_label_prob(const qa_bam_range_result_t *r, int32_t i, const char **names, const int64_t **names_off,
+                                 const double **prob, int32_t *n);
+/* hla_grid >= 0: sample i's gamma1, gamma2, gamma_total (K each) and list_of_gammas (nGibbsSamples x 2 x K) in qa_impute_hla_t's
+ * layouts, K and nGibbsSamples; NULL / 0 as above.  discard_sample_arrays does not discard these. */
+int qa_bam_range_hla(const qa_bam_range_result_t *r, int32_t i, const double **gamma1, const double **gamma2, const double **gamma_total,
+                     const double **list_of_gammas, int32_t *K, int32_t *nGibbsSamples);
+
 /* qa_sample_reads_bx_stats summed over the files (their common-site pile-ups, like load_stats below) */
 void qa_bam_range_bx_stats(const qa_bam_range_result_t *r, int64_t out[4]);
 
@@ -277,6 +326,12 @@ int qa_select_new_haps_mspbwt(int32_t n_chain, int32_t n_label, int32_t nindices
  * K haplotypes (K = 2, or 3 for NIPT: label 3 is folded into 2 for the consensus and put back); minrp 0.95; can_hap 1-based. */
 int qa_consensus_read_labels(int32_t nReads, int32_t n, const int32_t *labels, const double *p, int32_t K, double minrp,
                              int32_t can_hap, int32_t *out);
+
+/* The confidence of every read's label for ONE Gibbs sample: mp of assess_ability_of_reads_to_be_confident
+ * (functions.R:1635-1658).  p K x nReads as above.  K = 2: p1 / (p1 + p2), NaN (both 0) becomes 0.5, a value below 0.5 becomes
+ * 1 - mp.  K = 3 (NIPT): the largest of the three values normalised by their sum, NaN becomes 1/3.  qa_consensus_read_labels
+ * thresholds exactly this value (mp > minrp), and output_read_label_prob returns it for the last non-phasing Gibbs sample. */
+int qa_read_label_confidence(int32_t nReads, int32_t K, const double *p, double *mp_out);
 
 #ifdef __cplusplus
 }

@@ -1,5 +1,6 @@
 // bamrange.cpp -- qa_impute_bam_range (include/quilt_amd_io.h): a core's sample range from BAM paths to VCF columns in ONE
-// native call.
+// native call.  (The product's three entry points over this code are in csrc/bamrange_entry.cpp; this file names no device entry
+// point, so tests/c can link it with the loop and the loader alone.)
 //
 // What it replaces: per sample of the range, get_and_impute_one_sample's own I/O either side of the imputation
 // (QUILT/R/functions.R:243-298: STITCH::loadBamAndConvert + load() of the per-sample RData temp file +
@@ -41,6 +42,8 @@
 #include "../../include/quilt_amd_io.h"
 #include "impute_testhook.h"   // (qa_impute_bam_range_backend: the same host code over a checker's entry points, for tests/)
 
+#include "bamrange_impl.hpp"
+
 namespace qa { void set_error(const char *fmt, ...); }
 
 // The imputation's result arrays: 48 bytes per sample and SNP (7.9 GB at 2 560 samples x 64 000 SNPs).  qa_impute_samples does not
@@ -70,6 +73,15 @@ struct qa_bam_range_result {
     int64_t stats[11] = {0};
     int64_t load_stats[8] = {0};         // the loader's counters summed over the files (qa_sample_reads_stats)
     int64_t bx_stats[4] = {0};           // the BX rule's counters summed over the files (qa_sample_reads_bx_stats)
+    // output_read_label_prob: per kept sample its reads' names (NUL-terminated, back to back, n + 1 offsets) and label confidences
+    bool with_prob = false;
+    std::vector<std::vector<char>> names_buf;
+    std::vector<std::vector<int64_t>> names_off;
+    std::vector<std::vector<double>> prob_of;
+    // hla_grid >= 0: kept-major gamma1 / gamma2 / gamma_total (K per sample) and list_of_gammas (nG x 2 x K per sample)
+    bool with_hla = false;
+    int K = 0, nG = 0;
+    RawDoubles gamma1, gamma2, gamma_total, list_of_gammas;
 };
 
 namespace {
@@ -115,13 +127,16 @@ int parallel_for(int n, int n_threads, std::string &err, F f) {
 struct Loaded {
     std::vector<int32_t> read_ptr, u, bq, wif;
     int32_t R = 0;
+    std::vector<char> names;          // (keep_names only)
+    std::vector<int64_t> names_off;
 };
 
 int load_one(const char *path, const char *chr, int32_t T, const int32_t *L, const char *ref, const char *alt, const int32_t *grid,
-             const qa_bam_opts_t *o, int32_t use_bx_tag, int32_t bxTagUpperLimit, Loaded &out, int64_t stats[8], int64_t bx_stats[4],
-             std::string &err) {
+             const qa_bam_opts_t *o, int32_t use_bx_tag, int32_t bxTagUpperLimit, bool keep_names, Loaded &out, int64_t stats[8],
+             int64_t bx_stats[4], std::string &err) {
     qa_sample_reads_t *h = nullptr;
-    const int st = qa_bam_load_sample_reads_bx(path, chr, T, L, ref, alt, grid, o, use_bx_tag, bxTagUpperLimit, &h);
+    const int st = keep_names ? qa_bam_load_sample_reads_named(path, chr, T, L, ref, alt, grid, o, use_bx_tag, bxTagUpperLimit, 1, &h)
+                              : qa_bam_load_sample_reads_bx(path, chr, T, L, ref, alt, grid, o, use_bx_tag, bxTagUpperLimit, &h);
     if (st != QA_OK) {
         err = std::string("cannot load ") + path + ": " + qa_last_error();
         return st;
@@ -135,21 +150,37 @@ int load_one(const char *path, const char *chr, int32_t T, const int32_t *L, con
     int32_t dummy = 0;   // (export wants non-null pointers only for what it writes; empty vectors have a null data())
     const int st2 = qa_sample_reads_export(h, out.read_ptr.data(), nb ? out.u.data() : &dummy, nb ? out.bq.data() : &dummy,
                                            out.R ? out.wif.data() : &dummy, nullptr);
+    int st3 = QA_OK;
+    if (keep_names) {
+        out.names.resize((size_t)std::max<int64_t>(qa_sample_reads_names_bytes(h), 0));
+        out.names_off.assign((size_t)out.R + 1, 0);
+        st3 = qa_sample_reads_export_names(h, out.names.data(), out.names_off.data());
+    }
     if (stats) qa_sample_reads_stats(h, stats);
     if (bx_stats) qa_sample_reads_bx_stats(h, bx_stats);
     qa_sample_reads_destroy(h);
+    if (st3 != QA_OK) { err = std::string("cannot export the read names of ") + path; return st3; }
     if (st2 != QA_OK) err = std::string("cannot export the reads of ") + path;
     return st2;
 }
 
-// qa_impute_samples, or the test hook's form of it, on the kept samples
-using ImputeFn = std::function<int(const qa_impute_params_t *, int32_t, const int32_t *, const int32_t *, const int32_t *, const int32_t *,
-                                   const int32_t *, double *, double *, double *, int32_t *, int32_t *, int64_t *)>;
+// K, G: the panel's haplotypes and grids (read with ex->hla_grid >= 0 only)
+using ImputeFn = qa::BamRangeImputeFn;
 
-int bam_range_impl(const ImputeFn &impute, const qa_impute_params_t *params, const qa_bam_range_io_t *io, int32_t use_bx_tag,
-                   int32_t bxTagUpperLimit, int32_t n_sample, const char *const *bam_paths, const int64_t *sample_index, const double *ff,
+int bam_range_impl_(const ImputeFn &impute, const qa_impute_params_t *params, const qa_bam_range_io_t *io, const qa_bam_range_extras_t *ex,
+                   int32_t K, int32_t G, int32_t n_sample, const char *const *bam_paths, const int64_t *sample_index, const double *ff,
                    qa_bam_range_result_t **out) {
     if (out) *out = nullptr;
+    if (!ex) {
+        qa::set_error("qa_impute_bam_range_ex: ex is NULL");
+        return QA_ERR_INVALID;
+    }
+    const int32_t use_bx_tag = ex->use_bx_tag, bxTagUpperLimit = ex->bxTagUpperLimit;
+    const bool want_prob = ex->output_read_label_prob != 0, want_hla = ex->hla_grid >= 0;
+    if (ex->hla_grid < -1) {
+        qa::set_error("qa_impute_bam_range_ex: hla_grid = %d (-1 is off, a grid is 0-based)", (int)ex->hla_grid);
+        return QA_ERR_INVALID;
+    }
     if (bxTagUpperLimit < 0) {
         qa::set_error("qa_impute_bam_range: bxTagUpperLimit = %d is negative", (int)bxTagUpperLimit);
         return QA_ERR_INVALID;
@@ -172,6 +203,21 @@ int bam_range_impl(const ImputeFn &impute, const qa_impute_params_t *params, con
     }
     for (int i = 0; i < n_sample; i++)
         if (!bam_paths[i]) { qa::set_error("qa_impute_bam_range: bam_paths[%d] is null", i); return QA_ERR_INVALID; }
+    if (want_hla) {   // hla_run: qa_impute_samples_hla's refusals, here, before any file is opened
+        int n_seek = params->n_seek_its, n_burn = params->n_burn_in_seek_its < 0 ? params->n_seek_its - 1 : params->n_burn_in_seek_its;
+        if (K < params->Ksubset) { n_seek = 1; n_burn = 0; }   // (quilt.R:453-471, as the loop resets them)
+        const char *why = params->use_mspbwt ? "use_mspbwt = TRUE is not covered (the gamma columns come from the full-panel passes)"
+                          : nipt ? "method = \"nipt\" is not covered (diploid only)"
+                          : rare ? "impute_rare_common = TRUE is not covered"
+                          : ex->hla_grid >= G ? "grid outside [0, nGrids)"
+                          : n_burn >= n_seek ? "the last seek iteration is not a dosage pass (n_burn_in_seek_its >= n_seek_its)"
+                          : params->nGibbsSamples < 1 ? "nGibbsSamples < 1"
+                          : nullptr;
+        if (why) {
+            qa::set_error("qa_impute_bam_range_ex: hla_grid = %d (nGrids = %d): %s", (int)ex->hla_grid, (int)G, why);
+            return QA_ERR_INVALID;
+        }
+    }
     const auto t_all = Clock::now();
     // host threads of the loading and of the formatting (each): 16 by default.  Measured at 2 560 files on a 128-core host, both ends
     // beside the imputation: 16 / 32 / 64 threads -> the last file is in after 3.1 / 2.9 / 3.0 s either way (the loading does not
@@ -203,6 +249,12 @@ int bam_range_impl(const ImputeFn &impute, const qa_impute_params_t *params, con
     std::vector<std::array<int64_t, 4>> lbx((size_t)n_sample);
     std::vector<int64_t> index((size_t)std::max(n_sample, 1));     // per kept sample, filled as the files are settled
     std::vector<double> ffk((size_t)std::max(n_sample, 1));
+    R->with_prob = want_prob;
+    if (want_prob) {
+        R->names_buf.resize((size_t)n_sample);
+        R->names_off.resize((size_t)n_sample);
+        R->prob_of.resize((size_t)n_sample);
+    }
     R->kept.assign((size_t)n_sample, -1);                          // (entry j is written before kept sample j is handed to anyone; cut to n_kept at the end)
     R->labels_of.resize((size_t)n_sample);
     struct Loader {
@@ -225,12 +277,12 @@ int bam_range_impl(const ImputeFn &impute, const qa_impute_params_t *params, con
             std::string e;
             int s1;
             try {
-                s1 = load_one(bam_paths[i], io->chr, T, io->L, io->ref, io->alt, io->grid, &io->bam, use_bx_tag, bxTagUpperLimit,
+                s1 = load_one(bam_paths[i], io->chr, T, io->L, io->ref, io->alt, io->grid, &io->bam, use_bx_tag, bxTagUpperLimit, want_prob,
                               common[(size_t)i], lstats[(size_t)i].data(), lbx[(size_t)i].data(), e);
                 // (the all-SNP pile-up only for samples that will be imputed: the minimum test is on the common-SNP reads, functions.R:274)
                 if (s1 == QA_OK && rare && common[(size_t)i].R >= min_reads)
                     s1 = load_one(bam_paths[i], io->chr, io->nSNPs_all, io->L_all, io->ref_all, io->alt_all, io->grid_all, &io->bam,
-                                  use_bx_tag, bxTagUpperLimit, all_snps[(size_t)i], nullptr, nullptr, e);
+                                  use_bx_tag, bxTagUpperLimit, false, all_snps[(size_t)i], nullptr, nullptr, e);
             } catch (const std::exception &ex) {
                 s1 = QA_ERR_INVALID;
                 e = ex.what();
@@ -255,6 +307,11 @@ int bam_range_impl(const ImputeFn &impute, const qa_impute_params_t *params, con
                     index[j] = sample_index[f];
                     if (nipt) ffk[j] = ff[f];
                     R->labels_of[j].assign((size_t)common[(size_t)f].R, 0);
+                    if (want_prob) {   // (the names leave the loaded reads here: those are released when the column is formatted)
+                        R->names_buf[j] = std::move(common[(size_t)f].names);
+                        R->names_off[j] = std::move(common[(size_t)f].names_off);
+                        R->prob_of[j].assign((size_t)common[(size_t)f].R, 0.0);
+                    }
                     R->slot[(size_t)f] = (int32_t)j;
                     R->imputed[(size_t)f] = 1;
                     R->kept[j] = f;
@@ -294,8 +351,28 @@ int bam_range_impl(const ImputeFn &impute, const qa_impute_params_t *params, con
             }
             return QA_OK;
         }
+        // qa_impute_reads_out_t.dest: asked after acquire(s) returned, so kept sample s is settled
+        static int prob_dest(void *ctx, int32_t s, double **dst) {
+            Source &S = *static_cast<Source *>(ctx);
+            *dst = S.R->prob_of[(size_t)s].data();
+            return QA_OK;
+        }
     } src{&ld, R.get(), &common, &all_snps, n_sample, rare};
     const qa_sample_source_t source{&Source::acquire, &src};
+    const qa_impute_reads_out_t reads_out{nullptr, &Source::prob_dest, &src};
+    qa_impute_hla_t hla{};
+    if (want_hla) {   // (kept-major like the other result arrays; untouched pages of rows that no kept sample takes cost nothing)
+        R->with_hla = true;
+        R->K = K;
+        R->nG = params->nGibbsSamples;
+        R->gamma1.alloc((size_t)n_sample * K);
+        R->gamma2.alloc((size_t)n_sample * K);
+        R->gamma_total.alloc((size_t)n_sample * K);
+        R->list_of_gammas.alloc((size_t)n_sample * R->nG * 2 * K);
+        hla.grid = ex->hla_grid;
+        hla.gamma1 = R->gamma1.data(); hla.gamma2 = R->gamma2.data(); hla.gamma_total = R->gamma_total.data();
+        hla.list_of_gammas = R->list_of_gammas.data();
+    }
     std::vector<std::thread> loaders;
     for (int w = 0; w < std::max(1, std::min(n_io, n_sample)); w++) loaders.emplace_back(loader_body);
     auto join_loaders = [&] {
@@ -492,7 +569,7 @@ int bam_range_impl(const ImputeFn &impute, const qa_impute_params_t *params, con
     std::string err;
     if (n_sample > 0)
         st = impute(&P, n_sample, nullptr, nullptr, nullptr, nullptr, nullptr, R->dosage.data(), R->gp_t.data(), R->haps.data(), nullptr,
-                    R->nDosage.data(), R->stats);
+                    R->nDosage.data(), R->stats, want_hla ? &hla : nullptr, want_prob ? &reads_out : nullptr);
     join_loaders();
     if (ld.status != QA_OK) { close_pool(); qa::set_error("qa_impute_bam_range: %s", ld.err.c_str()); return ld.status; }
     if (st != QA_OK) { close_pool(); return st; }   // (qa_last_error holds qa_impute_samples' text)
@@ -521,55 +598,55 @@ int bam_range_impl(const ImputeFn &impute, const qa_impute_params_t *params, con
 
 }  // namespace
 
+int qa::bam_range_impl(const qa::BamRangeImputeFn &impute, const qa_impute_params_t *params, const qa_bam_range_io_t *io,
+                       const qa_bam_range_extras_t *ex, int32_t K, int32_t G, int32_t n_sample, const char *const *bam_paths,
+                       const int64_t *sample_index, const double *ff, qa_bam_range_result_t **out) {
+    return bam_range_impl_(impute, params, io, ex, K, G, n_sample, bam_paths, sample_index, ff, out);
+}
+
 extern "C" {
-
-int qa_impute_bam_range(qa_panel_t *const *panels, int32_t n_panels, const qa_impute_params_t *params, const qa_bam_range_io_t *io,
-                        int32_t n_sample, const char *const *bam_paths, const int64_t *sample_index, const double *ff,
-                        qa_bam_range_result_t **out) {
-    return qa_impute_bam_range_bx(panels, n_panels, params, io, 0, 0, n_sample, bam_paths, sample_index, ff, out);
-}
-
-int qa_impute_bam_range_bx(qa_panel_t *const *panels, int32_t n_panels, const qa_impute_params_t *params, const qa_bam_range_io_t *io,
-                           int32_t use_bx_tag, int32_t bxTagUpperLimit, int32_t n_sample, const char *const *bam_paths,
-                           const int64_t *sample_index, const double *ff, qa_bam_range_result_t **out) {
-    if (!panels || n_panels < 1 || !panels[0]) {
-        if (out) *out = nullptr;
-        qa::set_error("qa_impute_bam_range: no panel handle");
-        return QA_ERR_INVALID;
-    }
-    return bam_range_impl(
-        [&](const qa_impute_params_t *P, int32_t n, const int32_t *ro, const int32_t *rp, const int32_t *u, const int32_t *bq, const int32_t *wif,
-            double *dosage, double *gp_t, double *haps, int32_t *labels, int32_t *nDosage, int64_t *stats) {
-            return qa_impute_samples(panels, n_panels, P, n, 0, ro, rp, u, bq, wif, dosage, gp_t, haps, labels, nDosage, stats);
-        },
-        params, io, use_bx_tag, bxTagUpperLimit, n_sample, bam_paths, sample_index, ff, out);
-}
 
 // test hook (impute_testhook.h): the same host code -- loader, kept-sample bookkeeping, formatting, counts -- with the imputation
 // running over a checker's entry points instead of the device
 int qa_impute_bam_range_backend(const qa_impute_backend_t *backend, void *const *handles, int32_t n_handles, int32_t K, int32_t nGrids,
                                 const qa_impute_params_t *params, const qa_bam_range_io_t *io, int32_t n_sample, const char *const *bam_paths,
                                 const int64_t *sample_index, const double *ff, qa_bam_range_result_t **out) {
-    return qa_impute_bam_range_backend_bx(backend, handles, n_handles, K, nGrids, params, io, 0, 0, n_sample, bam_paths, sample_index, ff, out);
+    const qa_bam_range_extras_t ex{0, 0, 0, -1};
+    return qa_impute_bam_range_backend_ex(backend, nullptr, handles, n_handles, K, nGrids, params, io, &ex, n_sample, bam_paths, sample_index,
+                                          ff, out);
 }
 
 int qa_impute_bam_range_backend_bx(const qa_impute_backend_t *backend, void *const *handles, int32_t n_handles, int32_t K, int32_t nGrids,
                                    const qa_impute_params_t *params, const qa_bam_range_io_t *io, int32_t use_bx_tag,
                                    int32_t bxTagUpperLimit, int32_t n_sample, const char *const *bam_paths, const int64_t *sample_index,
                                    const double *ff, qa_bam_range_result_t **out) {
-    if (!backend || !handles || !io) {
+    const qa_bam_range_extras_t ex{use_bx_tag, bxTagUpperLimit, 0, -1};
+    return qa_impute_bam_range_backend_ex(backend, nullptr, handles, n_handles, K, nGrids, params, io, &ex, n_sample, bam_paths, sample_index,
+                                          ff, out);
+}
+
+int qa_impute_bam_range_backend_ex(const qa_impute_backend_t *backend, qa_fullpass_select_gamma_fn select_gamma, void *const *handles,
+                                   int32_t n_handles, int32_t K, int32_t nGrids, const qa_impute_params_t *params,
+                                   const qa_bam_range_io_t *io, const qa_bam_range_extras_t *ex, int32_t n_sample,
+                                   const char *const *bam_paths, const int64_t *sample_index, const double *ff,
+                                   qa_bam_range_result_t **out) {
+    if (!backend || !handles || !io || (ex && ex->hla_grid >= 0 && !select_gamma)) {
         if (out) *out = nullptr;
         qa::set_error("qa_impute_bam_range_backend: missing argument");
         return QA_ERR_INVALID;
     }
     const int32_t T = io->nSNPs;
-    return bam_range_impl(
+    return qa::bam_range_impl(
         [&](const qa_impute_params_t *P, int32_t n, const int32_t *ro, const int32_t *rp, const int32_t *u, const int32_t *bq, const int32_t *wif,
-            double *dosage, double *gp_t, double *haps, int32_t *labels, int32_t *nDosage, int64_t *stats) {
-            return qa_impute_samples_backend(backend, handles, n_handles, K, nGrids, T, P, n, 0, ro, rp, u, bq, wif, dosage, gp_t, haps, labels,
-                                             nDosage, stats);
+            double *dosage, double *gp_t, double *haps, int32_t *labels, int32_t *nDosage, int64_t *stats, const qa_impute_hla_t *hla,
+            const qa_impute_reads_out_t *reads_out) {
+            if (!hla && !reads_out)
+                return qa_impute_samples_backend(backend, handles, n_handles, K, nGrids, T, P, n, 0, ro, rp, u, bq, wif, dosage, gp_t, haps,
+                                                 labels, nDosage, stats);
+            return qa_impute_samples_backend_reads(backend, select_gamma, handles, n_handles, K, nGrids, T, P, n, 0, ro, rp, u, bq, wif, dosage,
+                                                   gp_t, haps, labels, nDosage, stats, hla, reads_out);
         },
-        params, io, use_bx_tag, bxTagUpperLimit, n_sample, bam_paths, sample_index, ff, out);
+        params, io, ex, K, nGrids, n_sample, bam_paths, sample_index, ff, out);
 }
 
 int32_t qa_bam_range_n_samples(const qa_bam_range_result_t *r) { return r ? r->n : 0; }
@@ -616,6 +693,31 @@ void qa_bam_range_timings(const qa_bam_range_result_t *r, double seconds[4], int
     if (seconds) std::memcpy(seconds, r->seconds, sizeof r->seconds);
     if (impute_stats) std::memcpy(impute_stats, r->stats, sizeof r->stats);
     if (load_stats) std::memcpy(load_stats, r->load_stats, sizeof r->load_stats);
+}
+
+int qa_bam_range_read_label_prob(const qa_bam_range_result_t *r, int32_t i, const char **names, const int64_t **names_off,
+                                 const double **prob, int32_t *n) {
+    if (!r || i < 0 || i >= r->n) return QA_ERR_INVALID;
+    const int j = r->with_prob ? r->slot[(size_t)i] : -1;
+    if (names) *names = j < 0 ? nullptr : r->names_buf[(size_t)j].data();
+    if (names_off) *names_off = j < 0 ? nullptr : r->names_off[(size_t)j].data();
+    if (prob) *prob = j < 0 ? nullptr : r->prob_of[(size_t)j].data();
+    if (n) *n = j < 0 ? 0 : (int32_t)r->prob_of[(size_t)j].size();
+    return QA_OK;
+}
+
+int qa_bam_range_hla(const qa_bam_range_result_t *r, int32_t i, const double **gamma1, const double **gamma2, const double **gamma_total,
+                     const double **list_of_gammas, int32_t *K, int32_t *nGibbsSamples) {
+    if (!r || i < 0 || i >= r->n) return QA_ERR_INVALID;
+    const int j = r->with_hla ? r->slot[(size_t)i] : -1;
+    const size_t Kk = (size_t)r->K;
+    if (gamma1) *gamma1 = j < 0 ? nullptr : r->gamma1.data() + (size_t)j * Kk;
+    if (gamma2) *gamma2 = j < 0 ? nullptr : r->gamma2.data() + (size_t)j * Kk;
+    if (gamma_total) *gamma_total = j < 0 ? nullptr : r->gamma_total.data() + (size_t)j * Kk;
+    if (list_of_gammas) *list_of_gammas = j < 0 ? nullptr : r->list_of_gammas.data() + (size_t)j * r->nG * 2 * Kk;
+    if (K) *K = j < 0 ? 0 : r->K;
+    if (nGibbsSamples) *nGibbsSamples = j < 0 ? 0 : r->nG;
+    return QA_OK;
 }
 
 void qa_bam_range_bx_stats(const qa_bam_range_result_t *r, int64_t out[4]) {

@@ -305,6 +305,9 @@ struct qa_sample_reads {
     std::vector<int32_t> read_ptr, u, bq, wif, central;
     int64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     int64_t bx_stats[4] = {0, 0, 0, 0};
+    bool named = false;                  // names asked for (qa_bam_load_sample_reads_named)
+    std::vector<char> names;             // then: the reads' names back to back, NUL-terminated, in the order of the reads
+    std::vector<int64_t> names_off;      // n_reads + 1 offsets
 };
 
 extern "C" {
@@ -322,13 +325,20 @@ void qa_bam_opts_default(qa_bam_opts_t *o) {
 
 int qa_bam_load_sample_reads(const char *bam_path, const char *chr, int32_t nSNPs, const int32_t *L, const char *ref,
                              const char *alt, const int32_t *grid, const qa_bam_opts_t *opts, qa_sample_reads_t **out) {
-    return qa_bam_load_sample_reads_bx(bam_path, chr, nSNPs, L, ref, alt, grid, opts, 0, 0, out);
+    return qa_bam_load_sample_reads_named(bam_path, chr, nSNPs, L, ref, alt, grid, opts, 0, 0, 0, out);
 }
 
 int qa_bam_load_sample_reads_bx(const char *bam_path, const char *chr, int32_t nSNPs, const int32_t *L, const char *ref,
                                 const char *alt, const int32_t *grid, const qa_bam_opts_t *opts, int32_t use_bx_tag,
                                 int32_t bxTagUpperLimit, qa_sample_reads_t **out) {
+    return qa_bam_load_sample_reads_named(bam_path, chr, nSNPs, L, ref, alt, grid, opts, use_bx_tag, bxTagUpperLimit, 0, out);
+}
+
+int qa_bam_load_sample_reads_named(const char *bam_path, const char *chr, int32_t nSNPs, const int32_t *L, const char *ref,
+                                   const char *alt, const int32_t *grid, const qa_bam_opts_t *opts, int32_t use_bx_tag,
+                                   int32_t bxTagUpperLimit, int32_t keep_names, qa_sample_reads_t **out) {
     if (out) *out = nullptr;
+    const bool want_names = keep_names != 0;
     if (bxTagUpperLimit < 0) {
         qa::set_error("qa_bam_load_sample_reads: bxTagUpperLimit = %d is negative", (int)bxTagUpperLimit);
         return QA_ERR_INVALID;
@@ -391,6 +401,7 @@ int qa_bam_load_sample_reads_bx(const char *bam_path, const char *chr, int32_t n
     auto *S = new qa_sample_reads;
     std::vector<Read> reads;
     std::vector<Frag> frags;   // (use_bx: one per entry of reads)
+    std::vector<std::string> qnames;   // (want_names: one per entry of reads -- the query name of the alignment that opened the slot)
     std::unordered_map<std::string, size_t> by_name;
     const int32_t lo_bp = o.chrStart > 0 ? o.chrStart : 1, hi_bp = o.chrEnd > 0 ? o.chrEnd : INT32_MAX;
     std::vector<uint8_t> rec;
@@ -512,6 +523,7 @@ int qa_bam_load_sample_reads_bx(const char *bam_path, const char *chr, int32_t n
         }
         reads.emplace_back();
         reads.back().b = std::move(bases);
+        if (want_names) qnames.emplace_back(reinterpret_cast<const char *>(&rec[32]), (size_t)std::max(0, l_read_name - 1));
         if (use_bx) {
             frags.emplace_back();
             frags.back().start = aln_start;
@@ -605,6 +617,15 @@ int qa_bam_load_sample_reads_bx(const char *bam_path, const char *chr, int32_t n
         S->wif.push_back(grid[cen[r]]);
         S->central.push_back(cen[r]);
     }
+    if (want_names) {   // name r belongs to read r of the arrays above: the slots that survived, in their final order
+        S->named = true;
+        S->names_off.push_back(0);
+        for (uint32_t r : order) {
+            const char *nm = qnames[r].c_str();   // (a name ends at its first NUL, as the record's own field does)
+            S->names.insert(S->names.end(), nm, nm + strlen(nm) + 1);
+            S->names_off.push_back((int64_t)S->names.size());
+        }
+    }
     *out = S;
     return QA_OK;
 }
@@ -626,6 +647,13 @@ int qa_sample_reads_export(const qa_sample_reads_t *s, int32_t *read_ptr, int32_
     cp(bq, s->bq);
     cp(wif, s->wif);
     cp(central, s->central);
+    return QA_OK;
+}
+int64_t qa_sample_reads_names_bytes(const qa_sample_reads_t *s) { return (s && s->named) ? (int64_t)s->names.size() : -1; }
+int qa_sample_reads_export_names(const qa_sample_reads_t *s, char *buf, int64_t *off) {
+    if (!s || !s->named) return QA_ERR_INVALID;
+    if (buf && !s->names.empty()) memcpy(buf, s->names.data(), s->names.size());
+    if (off) memcpy(off, s->names_off.data(), sizeof(int64_t) * s->names_off.size());
     return QA_OK;
 }
 void qa_sample_reads_destroy(qa_sample_reads_t *s) { delete s; }
@@ -1030,6 +1058,30 @@ int qa_select_new_haps_mspbwt(int32_t n_chain, int32_t n_label, int32_t nindices
 // the reference's working matrix are kept as flip parities (quilt_amd/driver.py has the numpy text and the line-by-line
 // form this is tested against), including that the final flip starts at the LAST change point counted in the filtered rows.
 //   labels  n x nReads (chain-major) read labels of the n Gibbs samples; p  n x K x nReads likelihoods (K = 2, or 3: NIPT)
+// mp of assess_ability_of_reads_to_be_confident (functions.R:1635-1658) for one Gibbs sample: the ONE place the expression lives --
+// the consensus labels below threshold it, and output_read_label_prob (csrc/impute.cpp) returns it.
+int qa_read_label_confidence(int32_t nReads, int32_t K, const double *p, double *mp_out) {
+    if (nReads < 0 || (K != 2 && K != 3) || (nReads > 0 && (!p || !mp_out))) return QA_ERR_INVALID;
+    const size_t R = (size_t)nReads;
+    for (size_t r = 0; r < R; r++) {
+        double mp;
+        if (K == 2) {
+            mp = p[r] / (p[r] + p[R + r]);
+            if (std::isnan(mp)) mp = 0.5;
+            if (mp < 0.5) mp = 1 - mp;
+        } else {
+            const double sum = p[r] + p[R + r] + p[2 * R + r];
+            const double q0 = p[r] / sum, q1 = p[R + r] / sum, q2 = p[2 * R + r] / sum;
+            mp = q0;
+            if (q1 > q0) mp = q1;
+            if (q2 > mp) mp = q2;
+            if (std::isnan(mp)) mp = 1.0 / 3;
+        }
+        mp_out[r] = mp;
+    }
+    return QA_OK;
+}
+
 int qa_consensus_read_labels(int32_t nReads, int32_t n, const int32_t *labels, const double *p, int32_t K, double minrp,
                              int32_t can_hap, int32_t *out) {
     if (nReads < 0 || n < 1 || !labels || !p || (K != 2 && K != 3) || can_hap < 1 || can_hap > n || !out) return QA_ERR_INVALID;
@@ -1037,24 +1089,12 @@ int qa_consensus_read_labels(int32_t nReads, int32_t n, const int32_t *labels, c
     const size_t R = (size_t)nReads;
     std::vector<int32_t> rl((size_t)n * R);
     std::vector<uint8_t> conf((size_t)n * R);
+    std::vector<double> mp(R);
     for (int32_t c = 0; c < n; c++) {
-        const double *pc = p + (size_t)c * K * R;
+        qa_read_label_confidence(nReads, K, p + (size_t)c * K * R, mp.data());
         for (size_t r = 0; r < R; r++) {
-            double mp;
-            if (!nipt) {
-                mp = pc[r] / (pc[r] + pc[R + r]);
-                if (std::isnan(mp)) mp = 0.5;
-                if (mp < 0.5) mp = 1 - mp;
-            } else {
-                const double sum = pc[r] + pc[R + r] + pc[2 * R + r];
-                const double q0 = pc[r] / sum, q1 = pc[R + r] / sum, q2 = pc[2 * R + r] / sum;
-                mp = q0;
-                if (q1 > q0) mp = q1;
-                if (q2 > mp) mp = q2;
-                if (std::isnan(mp)) mp = 1.0 / 3;
-            }
             int32_t l = labels[(size_t)c * R + r];
-            bool cf = mp > minrp;
+            bool cf = mp[r] > minrp;
             if (nipt && l == 3) { cf = false; l = 2; }   // label 3 folded into 2 and called not confident (:1800-1806)
             rl[(size_t)c * R + r] = l;
             conf[(size_t)c * R + r] = cf;

@@ -52,7 +52,8 @@ __attribute__((visibility("hidden"))) int impute_samples_product(qa_panel_t *con
                                                                 const int32_t *read_ptr, const int32_t *u, const int32_t *bq,
                                                                 const int32_t *wif, double *dosage, double *gp_t, double *phasing_haps,
                                                                 int32_t *read_labels, int32_t *nDosage, int64_t *stats,
-                                                                const qa_impute_hla_t *hla, qa_fullpass_select_gamma_fn select_gamma);
+                                                                const qa_impute_hla_t *hla, qa_fullpass_select_gamma_fn select_gamma,
+                                                                const qa_impute_reads_out_t *reads_out);
 }
 
 namespace {
@@ -219,6 +220,10 @@ struct Ctx {
     // params->sample_source: reads[s] / reads_all[s] / label_dst[s] are filled when the set holding s is taken (Worker::new_batch)
     const qa_sample_source_t *source = nullptr;
     std::vector<int32_t *> label_dst;   // where sample s's consensus read labels go
+    // output_read_label_prob (qa_impute_samples_reads): where sample s's label confidences go (empty: not asked for; an entry may
+    // be null); with a source, asked of reads_out->dest after acquire(s)
+    const qa_impute_reads_out_t *reads_out = nullptr;
+    std::vector<double *> prob_dst;
     std::atomic<int64_t> n_underflow_retries{0}, n_full_list_refetches{0}, n_device_selections{0}, n_gibbs_chain_calls{0},
         n_gibbs_launches{0};
     Tail tail;
@@ -1069,6 +1074,12 @@ struct Worker {
             r.nb = r.read_ptr[r.R];
             if (!v.read_labels) throw Failure(QA_ERR_INVALID, "the sample source gave sample " + std::to_string(s) + " no place for its read labels");
             cx.label_dst[(size_t)s] = v.read_labels;
+            if (cx.reads_out && cx.reads_out->dest) {
+                double *dst = nullptr;
+                const int sd = cx.reads_out->dest(cx.reads_out->ctx, s, &dst);
+                if (sd < 0) throw Failure(sd, "no place for the label confidences of sample " + std::to_string(s));
+                cx.prob_dst[(size_t)s] = dst;
+            }
             if (cx.rc) {
                 Reads &a = cx.reads_all[(size_t)s];
                 a.R = v.n_reads_all; a.read_ptr = v.read_ptr_all; a.u = v.u_all; a.bq = v.bq_all; a.wif = v.wif_all;
@@ -1158,6 +1169,10 @@ struct Worker {
             if (cx.be->consensus_read_labels(R, nG, labels.data(), p.data(), nL, 0.95, nG, ph.labels.data()) != QA_OK)
                 throw Failure(QA_ERR_INVALID, "qa_consensus_read_labels failed");
             std::memcpy(cx.label_dst[(size_t)s], ph.labels.data(), sizeof(int32_t) * (size_t)R);
+            // final_read_labels_prob[[2]] (functions.R:1164-1166): mp of the last non-phasing Gibbs sample, from the p above
+            if (!cx.prob_dst.empty() && cx.prob_dst[(size_t)s] &&
+                qa_read_label_confidence(R, nL, p.data() + (size_t)(nG - 1) * nL * R, cx.prob_dst[(size_t)s]) != QA_OK)
+                throw Failure(QA_ERR_INVALID, "qa_read_label_confidence failed");
             b.phasing[si] = std::move(ph);
         });
         b.chains.clear();
@@ -1335,7 +1350,8 @@ int impute_impl(bool keep_buffers, const qa_impute_backend_t *be, void *const *h
                 const qa_impute_params_t *params, int32_t n_sample, int64_t sample_offset, const int32_t *read_off,
                 const int32_t *read_ptr, const int32_t *u, const int32_t *bq, const int32_t *wif, double *dosage, double *gp_t,
                 double *phasing_haps, int32_t *read_labels, int32_t *nDosage, int64_t *stats,
-                const qa_impute_hla_t *hla = nullptr, qa_fullpass_select_gamma_fn select_gamma = nullptr) {
+                const qa_impute_hla_t *hla = nullptr, qa_fullpass_select_gamma_fn select_gamma = nullptr,
+                const qa_impute_reads_out_t *reads_out = nullptr) {
     const bool flat = !(params && params->sample_source);
     if (!be || !handles || n_handles < 1 || n_handles > 16 || !params || n_sample < 0 ||
         (flat && (!read_off || !read_ptr || !u || !bq || !wif || !read_labels)) || (!flat && !params->sample_source->acquire) ||
@@ -1407,8 +1423,13 @@ int impute_impl(bool keep_buffers, const qa_impute_backend_t *be, void *const *h
     cx.source = P.sample_source;
     cx.reads.resize((size_t)n_sample);
     cx.label_dst.assign((size_t)n_sample, nullptr);
+    if (reads_out && (flat ? reads_out->read_label_prob != nullptr : reads_out->dest != nullptr)) {
+        cx.reads_out = reads_out;
+        cx.prob_dst.assign((size_t)n_sample, nullptr);
+    }
     if (flat) {
         for (int s = 0; s < n_sample; s++) cx.label_dst[(size_t)s] = read_labels + read_off[s];
+        if (cx.reads_out) for (int s = 0; s < n_sample; s++) cx.prob_dst[(size_t)s] = reads_out->read_label_prob + read_off[s];
         const int st = carve_flat_reads(cx.reads, n_sample, read_off, read_ptr, u, bq, wif, "");
         if (st != QA_OK) return st;
     }
@@ -1617,7 +1638,8 @@ int qa_impute_params_default(qa_impute_params_t *p) {
 int qa::impute_samples_product(qa_panel_t *const *panels, int32_t n_panels, const qa_impute_params_t *params, int32_t n_sample,
                               int64_t sample_offset, const int32_t *read_off, const int32_t *read_ptr, const int32_t *u, const int32_t *bq,
                               const int32_t *wif, double *dosage, double *gp_t, double *phasing_haps, int32_t *read_labels,
-                              int32_t *nDosage, int64_t *stats, const qa_impute_hla_t *hla, qa_fullpass_select_gamma_fn select_gamma) {
+                              int32_t *nDosage, int64_t *stats, const qa_impute_hla_t *hla, qa_fullpass_select_gamma_fn select_gamma,
+                              const qa_impute_reads_out_t *reads_out) {
     if (!panels || n_panels < 1 || !panels[0]) {
         qa::set_error("qa_impute_samples: no panel handle");
         return QA_ERR_INVALID;
@@ -1642,7 +1664,7 @@ int qa::impute_samples_product(qa_panel_t *const *panels, int32_t n_panels, cons
                 return QA_ERR_INVALID;
             }
     return impute_impl(true, &kProduct, reinterpret_cast<void *const *>(panels), n_panels, K, G, T, params, n_sample, sample_offset, read_off,
-                       read_ptr, u, bq, wif, dosage, gp_t, phasing_haps, read_labels, nDosage, stats, hla, select_gamma);
+                       read_ptr, u, bq, wif, dosage, gp_t, phasing_haps, read_labels, nDosage, stats, hla, select_gamma, reads_out);
 }
 
 extern "C" {
@@ -1652,7 +1674,7 @@ int qa_impute_samples(qa_panel_t *const *panels, int32_t n_panels, const qa_impu
                       const int32_t *wif, double *dosage, double *gp_t, double *phasing_haps, int32_t *read_labels, int32_t *nDosage,
                       int64_t *stats) {
     return qa::impute_samples_product(panels, n_panels, params, n_sample, sample_offset, read_off, read_ptr, u, bq, wif, dosage, gp_t,
-                                      phasing_haps, read_labels, nDosage, stats, nullptr, nullptr);
+                                      phasing_haps, read_labels, nDosage, stats, nullptr, nullptr, nullptr);
 }
 
 int qa_impute_release_buffers(void) {
@@ -1674,14 +1696,19 @@ extern "C" void qa_impute_drop_handle_buffers(void *handle) {
     bufs().erase(handle);
 }
 
+// is every entry the loop always calls there?
+static bool table_complete(const qa_impute_backend_t *backend) {
+    return backend && backend->gibbs_batch && backend->fullpass_reads_select_batch && backend->fullpass_batch &&
+           backend->make_eMatRead_t_hap_major && backend->mspbwt_select_new_haps && backend->accumulate_dosage &&
+           backend->consensus_read_labels && backend->host_alloc && backend->host_free;
+}
+
 int qa_impute_samples_backend(const qa_impute_backend_t *backend, void *const *handles, int32_t n_handles, int32_t K, int32_t nGrids,
                               int32_t nSNPs, const qa_impute_params_t *params, int32_t n_sample, int64_t sample_offset,
                               const int32_t *read_off, const int32_t *read_ptr, const int32_t *u, const int32_t *bq, const int32_t *wif,
                               double *dosage, double *gp_t, double *phasing_haps, int32_t *read_labels, int32_t *nDosage,
                               int64_t *stats) {
-    if (!backend || !backend->gibbs_batch || !backend->fullpass_reads_select_batch || !backend->fullpass_batch ||
-        !backend->make_eMatRead_t_hap_major || !backend->mspbwt_select_new_haps || !backend->accumulate_dosage ||
-        !backend->consensus_read_labels || !backend->host_alloc || !backend->host_free) {
+    if (!table_complete(backend)) {
         qa::set_error("qa_impute_samples_backend: incomplete table");
         return QA_ERR_INVALID;
     }
@@ -1695,14 +1722,26 @@ int qa_impute_samples_backend_hla(const qa_impute_backend_t *backend, qa_fullpas
                                   const int32_t *u, const int32_t *bq, const int32_t *wif, double *dosage, double *gp_t,
                                   double *phasing_haps, int32_t *read_labels, int32_t *nDosage, int64_t *stats,
                                   const qa_impute_hla_t *hla) {
-    if (!backend || !backend->gibbs_batch || !backend->fullpass_reads_select_batch || !backend->fullpass_batch ||
-        !backend->make_eMatRead_t_hap_major || !backend->mspbwt_select_new_haps || !backend->accumulate_dosage ||
-        !backend->consensus_read_labels || !backend->host_alloc || !backend->host_free || !select_gamma || !hla) {
+    if (!table_complete(backend) || !select_gamma || !hla) {
         qa::set_error("qa_impute_samples_backend_hla: incomplete table");
         return QA_ERR_INVALID;
     }
     return impute_impl(false, backend, handles, n_handles, K, nGrids, nSNPs, params, n_sample, sample_offset, read_off, read_ptr, u, bq, wif,
                        dosage, gp_t, phasing_haps, read_labels, nDosage, stats, hla, select_gamma);
+}
+
+int qa_impute_samples_backend_reads(const qa_impute_backend_t *backend, qa_fullpass_select_gamma_fn select_gamma, void *const *handles,
+                                    int32_t n_handles, int32_t K, int32_t nGrids, int32_t nSNPs, const qa_impute_params_t *params,
+                                    int32_t n_sample, int64_t sample_offset, const int32_t *read_off, const int32_t *read_ptr,
+                                    const int32_t *u, const int32_t *bq, const int32_t *wif, double *dosage, double *gp_t,
+                                    double *phasing_haps, int32_t *read_labels, int32_t *nDosage, int64_t *stats,
+                                    const qa_impute_hla_t *hla, const qa_impute_reads_out_t *reads_out) {
+    if (!table_complete(backend) || (hla && !select_gamma)) {
+        qa::set_error("qa_impute_samples_backend_reads: incomplete table");
+        return QA_ERR_INVALID;
+    }
+    return impute_impl(false, backend, handles, n_handles, K, nGrids, nSNPs, params, n_sample, sample_offset, read_off, read_ptr, u, bq, wif,
+                       dosage, gp_t, phasing_haps, read_labels, nDosage, stats, hla, hla ? select_gamma : nullptr, reads_out);
 }
 
 }   // extern "C"

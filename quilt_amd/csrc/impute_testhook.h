@@ -84,6 +84,13 @@ int qa_impute_samples_backend_hla(const qa_impute_backend_t *backend, qa_fullpas
                                   const int32_t *u, const int32_t *bq, const int32_t *wif, double *dosage, double *gp_t,
                                   double *phasing_haps, int32_t *read_labels, int32_t *nDosage, int64_t *stats,
                                   const qa_impute_hla_t *hla);
+/* qa_impute_samples_reads over the same kind of table: hla may be NULL (select_gamma then too), reads_out may be NULL */
+int qa_impute_samples_backend_reads(const qa_impute_backend_t *backend, qa_fullpass_select_gamma_fn select_gamma, void *const *handles,
+                                    int32_t n_handles, int32_t K, int32_t nGrids, int32_t nSNPs, const qa_impute_params_t *params,
+                                    int32_t n_sample, int64_t sample_offset, const int32_t *read_off, const int32_t *read_ptr,
+                                    const int32_t *u, const int32_t *bq, const int32_t *wif, double *dosage, double *gp_t,
+                                    double *phasing_haps, int32_t *read_labels, int32_t *nDosage, int64_t *stats,
+                                    const qa_impute_hla_t *hla, const qa_impute_reads_out_t *reads_out);
 
 
 /* qa_impute_bam_range (include/quilt_amd_io.h) with its imputation step on a caller's table: the loader, the bookkeeping of
@@ -97,6 +104,13 @@ int qa_impute_bam_range_backend_bx(const qa_impute_backend_t *backend, void *con
                                    const qa_impute_params_t *params, const qa_bam_range_io_t *io, int32_t use_bx_tag,
                                    int32_t bxTagUpperLimit, int32_t n_sample, const char *const *bam_paths, const int64_t *sample_index,
                                    const double *ff, qa_bam_range_result_t **out);
+/* qa_impute_bam_range_ex in the same way (the two above are calls of this); select_gamma stands in for
+ * qa_fullpass_reads_select_gamma_batch and is needed with ex->hla_grid >= 0 only */
+int qa_impute_bam_range_backend_ex(const qa_impute_backend_t *backend, qa_fullpass_select_gamma_fn select_gamma, void *const *handles,
+                                   int32_t n_handles, int32_t K, int32_t nGrids, const qa_impute_params_t *params,
+                                   const qa_bam_range_io_t *io, const qa_bam_range_extras_t *ex, int32_t n_sample,
+                                   const char *const *bam_paths, const int64_t *sample_index, const double *ff,
+                                   qa_bam_range_result_t **out);
 
 #ifdef __cplusplus
 }

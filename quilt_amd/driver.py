@@ -279,24 +279,31 @@ def everything_select_good_haps_dense(Knew: int, K_top_matches: int, top: np.nda
     return to_keep.astype(np.int32)
 
 
-def assess_ability_of_reads_to_be_confident(p: np.ndarray, minrp: float = 0.95) -> np.ndarray:
-    """functions.R:1615-1660: ``p`` = 2 x nReads read likelihoods against (hap1, hap2), or 3 x nReads (NIPT)."""
+def read_label_confidence(p: np.ndarray) -> np.ndarray:
+    """``mp`` of functions.R:1635-1658, the twin of the native qa_read_label_confidence (include/quilt_amd_io.h): ``p`` = 2 x nReads
+    read likelihoods against (hap1, hap2), or 3 x nReads (NIPT).  What ``output_read_label_prob`` returns for the last non-phasing
+    Gibbs sample (functions.R:1164-1166) and what the consensus labels threshold."""
+    p = np.asarray(p, dtype=np.float64)
     if p.shape[0] == 3:
         with np.errstate(invalid="ignore", divide="ignore"):
-            q = p / p.sum(axis=0)
+            q = p / (p[0] + p[1] + p[2])
         mp = q[0].copy()
         w = q[1] > q[0]
         mp[w] = q[1][w]
         w = q[2] > mp
         mp[w] = q[2][w]
         mp[np.isnan(mp)] = 1 / 3
-        return mp > minrp
+        return mp
     p1, p2 = p[0], p[1]
     with np.errstate(invalid="ignore", divide="ignore"):
         mp = p1 / (p1 + p2)
     mp[np.isnan(mp)] = 0.5
-    mp = np.where(mp < 0.5, 1 - mp, mp)
-    return mp > minrp
+    return np.where(mp < 0.5, 1 - mp, mp)
+
+
+def assess_ability_of_reads_to_be_confident(p: np.ndarray, minrp: float = 0.95) -> np.ndarray:
+    """functions.R:1615-1660: ``p`` = 2 x nReads read likelihoods against (hap1, hap2), or 3 x nReads (NIPT)."""
+    return read_label_confidence(p) > minrp
 
 
 def determine_best_read_label_so_far(read_label_matrix_all: np.ndarray, read_label_matrix_conf: np.ndarray,
@@ -501,6 +508,9 @@ class SampleResult:
     gamma2: Optional[np.ndarray] = None
     gamma_total: Optional[np.ndarray] = None
     list_of_gammas: Optional[np.ndarray] = None
+    # output_read_label_prob (functions.R:1164-1166): per read, the confidence of its label in the last non-phasing Gibbs sample
+    # (read_label_confidence); with read_labels and the loader's names, final_read_labels_prob
+    read_label_prob: Optional[np.ndarray] = None
 
 
 def hla_gamma_total(list_of_gammas: np.ndarray) -> np.ndarray:
@@ -522,6 +532,7 @@ class _Batch:
     nDosage: np.ndarray
     phasing: Optional[List[ChainState]] = None
     consensus: Optional[List[np.ndarray]] = None
+    read_label_prob: Optional[List[np.ndarray]] = None
     fet_dosage: Optional[np.ndarray] = None     # method = "nipt": dosage / gp_t hold the mother's
     fet_gp_t: Optional[np.ndarray] = None
     dosage_all: Optional[np.ndarray] = None     # impute_rare_common: the same accumulators over ALL SNPs
@@ -973,6 +984,7 @@ class Driver:
             haps = [ch.hap for ch in b.chains]
         conf = self.backend.read_confidence_batch([ch.sample for ch in b.chains], haps, P.maxDifferenceBetweenReads)
         b.phasing = []
+        b.read_label_prob = []
         from .io import consensus_read_labels
         by_sample: dict = {}
         for k, ch in enumerate(b.chains):
@@ -985,6 +997,7 @@ class Driver:
                                            np.stack([np.asarray(conf[k], dtype=np.float64) for k in mine]),
                                            can_hap=P.nGibbsSamples)
             last = b.chains[mine[-1]]
+            b.read_label_prob.append(read_label_confidence(conf[max(mine, key=lambda k: b.chains[k].i_chain)]))
             b.phasing.append(ChainState(smp, i, P.nGibbsSamples + 1, chain_rng(P.seed, b.offset + i, P.nGibbsSamples + 1),
                                         which_haps_to_use=last.which_haps_to_use.copy(), read_labels=labels, _phasing=True))
         b.consensus = [ph.read_labels.copy() for ph in b.phasing]
@@ -1025,6 +1038,8 @@ class Driver:
                 lg = b.list_of_gammas[i]
                 out[-1].gamma1, out[-1].gamma2 = b.phasing[i].gamma[0], b.phasing[i].gamma[1]
                 out[-1].gamma_total, out[-1].list_of_gammas = hla_gamma_total(lg), lg
+        for r, mp in zip(out, b.read_label_prob or []):
+            r.read_label_prob = mp
         return out
 
     def run_stream(self, batches):

@@ -94,6 +94,14 @@ class ImputeRareCommon(C.Structure):
                 ("L_grid_all", C.c_void_p)]
 
 
+class BamRangeExtras(C.Structure):   # qa_bam_range_extras_t (include/quilt_amd_io.h)
+    _fields_ = [("use_bx_tag", C.c_int32), ("bxTagUpperLimit", C.c_int32), ("output_read_label_prob", C.c_int32), ("hla_grid", C.c_int32)]
+
+
+class ImputeReadsOut(C.Structure):   # qa_impute_reads_out_t
+    _fields_ = [("read_label_prob", C.c_void_p), ("dest", C.c_void_p), ("ctx", C.c_void_p)]
+
+
 class ImputeHla(C.Structure):   # qa_impute_hla_t
     _fields_ = [("grid", C.c_int32), ("gamma1", C.c_void_p), ("gamma2", C.c_void_p), ("gamma_total", C.c_void_p),
                 ("list_of_gammas", C.c_void_p)]
@@ -165,7 +173,7 @@ def make_params(P: DriverParams, samples_per_launch_set: int, mspbwt_index=None,
     return q, (blocks, mspbwt_index, rare_common, nipt)
 
 
-def wrap_results(samples, dosage, gp_t, haps, labels, nDosage, read_off, fet_dosage=None, fet_gp_t=None, hla=None) -> List[SampleResult]:
+def wrap_results(samples, dosage, gp_t, haps, labels, nDosage, read_off, fet_dosage=None, fet_gp_t=None, hla=None, prob=None) -> List[SampleResult]:
     """One SampleResult per sample over the call's output arrays: rows and slices of them, no copies (``phasing_haps`` is the
     nSNPs x n_label transposed VIEW of the library's n_label x nSNPs rows).  ``hla``: make_hla's arrays (hla_run)."""
     out = [SampleResult(dosage[i], gp_t[i], haps[i].T, labels[read_off[i]:read_off[i + 1]],
@@ -174,6 +182,9 @@ def wrap_results(samples, dosage, gp_t, haps, labels, nDosage, read_off, fet_dos
     if hla is not None:
         for i, r in enumerate(out):
             r.gamma1, r.gamma2, r.gamma_total, r.list_of_gammas = hla[0][i], hla[1][i], hla[2][i], hla[3][i]
+    if prob is not None:
+        for i, r in enumerate(out):
+            r.read_label_prob = prob[read_off[i]:read_off[i + 1]]
     return out
 
 
@@ -213,8 +224,9 @@ def prepare_range(devs: Sequence, samples: Sequence, params: Optional[DriverPara
                          K=panel.K)
 
 
-def run_prepared(r: PreparedRange, return_stats: bool = False, one_by_one: bool = False):
-    """``one_by_one``: the samples' reads are handed to the call through a qa_sample_source_t (include/quilt_amd.h: each sample
+def run_prepared(r: PreparedRange, return_stats: bool = False, one_by_one: bool = False, output_read_label_prob: bool = False):
+    """``output_read_label_prob``: the results carry ``read_label_prob`` (qa_impute_samples_reads; flat reads only).
+    ``one_by_one``: the samples' reads are handed to the call through a qa_sample_source_t (include/quilt_amd.h: each sample
     when the launch set holding it is taken) instead of the flat arrays -- same results."""
     n, T = r.n, r.T
     dosage, gp_t, haps = np.empty((n, T)), np.empty((n, 3, T)), np.empty((n, r.nL, T))
@@ -225,7 +237,7 @@ def run_prepared(r: PreparedRange, return_stats: bool = False, one_by_one: bool 
     L.qa_impute_samples.restype = C.c_int
     L.qa_impute_samples_hla.restype = C.c_int
     flat = (ptr(r.read_off), ptr(r.read_ptr), ptr(r.u), ptr(r.bq), ptr(r.wif))
-    hq = hla = None
+    hq = hla = prob = None
     if getattr(r, "hla_grid", None) is not None:   # hla_run: qa_impute_samples_hla with the gamma outputs
         hq, hla = make_hla(r.hla_grid, n, r.nG, r.K)
     keep_s = None
@@ -237,22 +249,31 @@ def run_prepared(r: PreparedRange, return_stats: bool = False, one_by_one: bool 
     try:
         args = (r.handles, C.c_int32(len(r.devs)), C.byref(r.q), C.c_int32(n), C.c_int64(r.sample_offset), *flat,
                 ptr(dosage), ptr(gp_t), ptr(haps), None if one_by_one else ptr(labels), ptr(nDosage), ptr(stats))
-        check(L.qa_impute_samples(*args) if hq is None else L.qa_impute_samples_hla(*args, C.byref(hq)))
+        if output_read_label_prob:
+            if one_by_one:
+                raise ValueError("output_read_label_prob with one_by_one is not wired in this wrapper")
+            prob = np.zeros(int(r.read_off[-1]))
+            ro = ImputeReadsOut(prob.ctypes.data, None, None)
+            L.qa_impute_samples_reads.restype = C.c_int
+            check(L.qa_impute_samples_reads(*args, None if hq is None else C.byref(hq), C.byref(ro)))
+        else:
+            check(L.qa_impute_samples(*args) if hq is None else L.qa_impute_samples_hla(*args, C.byref(hq)))
     finally:
         r.q.sample_source = None
         del keep_s
-    out = wrap_results(r.samples, dosage, gp_t, haps, labels, nDosage, r.read_off, r.fd, r.fg, hla)
+    out = wrap_results(r.samples, dosage, gp_t, haps, labels, nDosage, r.read_off, r.fd, r.fg, hla, prob)
     return (out, dict(zip(STAT_NAMES, stats.tolist()))) if return_stats else out
 
 
 def impute_samples(devs: Sequence, samples: Sequence, params: Optional[DriverParams] = None, sample_offset: int = 0,
                    samples_per_launch_set: int = 256, fuse_tails: bool = True, return_stats: bool = False, drcs: Sequence = (),
-                   one_by_one: bool = False):
+                   one_by_one: bool = False, output_read_label_prob: bool = False):
     """``devs``: one :class:`quilt_amd.native.DevicePanel` per host thread (replicas of one panel on one device; with more
     than one, switch ``set_exclusive`` on).  ``drcs`` (with ``params.impute_rare_common``): one
     :class:`quilt_amd.native.DeviceRareCommon` per entry of ``devs``; every sample then carries its all-SNP reads as
     ``sample.all_snp`` and the results cover all SNPs.  Returns one SampleResult per sample (and the native counters)."""
-    return run_prepared(prepare_range(devs, samples, params, sample_offset, samples_per_launch_set, fuse_tails, drcs), return_stats, one_by_one)
+    return run_prepared(prepare_range(devs, samples, params, sample_offset, samples_per_launch_set, fuse_tails, drcs), return_stats, one_by_one,
+                        output_read_label_prob)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -272,7 +293,8 @@ def impute_bam_range(devs: Sequence, bam_files: Sequence[str], chr: str, ref, al
                      samples_per_launch_set: int = 256, fuse_tails: bool = True, drcs: Sequence = (), all_sites=None,
                      bqFilter: int = 17, iSizeUpperLimit: float = 1e6, useSoftClippedBases: bool = False, downsampleToCov: int = 30,
                      chrStart: int = 0, chrEnd: int = 0, merge_mates: bool = True, seed: int = 1, copy_out: Optional[Sequence[int]] = None,
-                     discard_sample_arrays: bool = False, use_bx_tag: bool = False, bxTagUpperLimit: int = 50000, _entry=None) -> dict:
+                     discard_sample_arrays: bool = False, use_bx_tag: bool = False, bxTagUpperLimit: int = 50000,
+                     output_read_label_prob: bool = False, hla_grid: Optional[int] = None, _entry=None) -> dict:
     """The body of QUILT()'s loop over a core's sample range (quilt.R:832-982) as ONE native call: the BAM files are loaded on
     host threads, the samples with enough reads imputed together on the device, their VCF columns formatted on host threads and
     the four per-SNP count arrays summed over the range.  ``sample_index``: the files' global 0-based sample indices (default
@@ -283,6 +305,9 @@ def impute_bam_range(devs: Sequence, bam_files: Sequence[str], chr: str, ref, al
     formatted (what the R fast path asks for); ``results`` then carry the read labels and ``nDosage`` only.
     ``use_bx_tag`` / ``bxTagUpperLimit`` (quilt.R:46-47): the loader's linked-read rule (include/quilt_amd_io.h); ``bx_stats``
     holds its four counters summed over the files.
+    ``output_read_label_prob``: ``final_read_labels_prob`` {file index: (names, prob, labels)} and ``results[i].read_label_prob``.
+    ``hla_grid`` (0-based; hla_run = TRUE): ``results[i]`` carry gamma1, gamma2, gamma_total and list_of_gammas.  Either option goes
+    through qa_impute_bam_range_ex; neither changes another output.
     Returns dict(imputed, n_reads, columns [VcfColumn or None], results {file index: SampleResult}, counts SummaryCounts,
     seconds {load, impute, format, total}, stats, load_stats, bx_stats)."""
     from .io import BamOpts, SummaryCounts, VcfColumn
@@ -295,6 +320,10 @@ def impute_bam_range(devs: Sequence, bam_files: Sequence[str], chr: str, ref, al
     if int(bxTagUpperLimit) != bxTagUpperLimit or not -2**31 <= bxTagUpperLimit < 2**31:
         raise ValueError("bxTagUpperLimit must be a whole number")
     bx = (C.c_int32(int(bool(use_bx_tag))), C.c_int32(int(bxTagUpperLimit)))
+    extras = bool(output_read_label_prob) or hla_grid is not None
+    ex = BamRangeExtras(int(bool(use_bx_tag)), int(bxTagUpperLimit), int(bool(output_read_label_prob)), -1 if hla_grid is None else int(hla_grid))
+    if hla_grid is not None and int(hla_grid) < 0:
+        raise ValueError("hla_grid is a 0-based grid")
     Lc = np.ascontiguousarray(panel.L, dtype=np.int32)
     grid = np.ascontiguousarray(panel.grid if panel.grid is not None else np.arange(T, dtype=np.int32) // 32, dtype=np.int32)
     as_bytes = lambda a: bytes(a) if isinstance(a, (bytes, bytearray)) else "".join(a).encode()
@@ -343,7 +372,7 @@ def impute_bam_range(devs: Sequence, bam_files: Sequence[str], chr: str, ref, al
     ffv = None if ff is None else np.ascontiguousarray(ff, dtype=np.float64)
     handles = (C.c_void_p * len(devs))(*[getattr(d, "handle", None) for d in devs])
     L = lib()
-    for name in ("qa_impute_bam_range_bx", "qa_bam_range_column", "qa_bam_range_sample", "qa_bam_range_counts", "qa_bam_range_imputed",
+    for name in ("qa_impute_bam_range_bx", "qa_impute_bam_range_ex", "qa_bam_range_read_label_prob", "qa_bam_range_hla", "qa_bam_range_column", "qa_bam_range_sample", "qa_bam_range_counts", "qa_bam_range_imputed",
                  "qa_bam_range_n_reads", "qa_bam_range_n_snps", "qa_bam_range_n_samples"):
         getattr(L, name).restype = C.c_int
     L.qa_bam_range_destroy.restype = None
@@ -351,12 +380,17 @@ def impute_bam_range(devs: Sequence, bam_files: Sequence[str], chr: str, ref, al
     L.qa_bam_range_bx_stats.restype = None
     h = C.c_void_p()
     if _entry is not None:   # (tests: the same native host code with its imputation step on a checker -- impute_testhook.h)
-        if use_bx_tag:   # (an entry that is given the tag takes the pair; the others keep their seven arguments)
+        if extras:   # (an entry over the _ex form takes the whole struct)
+            _entry(q, io, n, paths, sidx, ffv, h, ex=ex)
+        elif use_bx_tag:   # (an entry that is given the tag takes the pair; the others keep their seven arguments)
             _entry(q, io, n, paths, sidx, ffv, h, use_bx_tag=bx[0], bxTagUpperLimit=bx[1])
         elif bxTagUpperLimit < 0:
             raise ValueError("bxTagUpperLimit must not be negative")
         else:
             _entry(q, io, n, paths, sidx, ffv, h)
+    elif extras:
+        check(L.qa_impute_bam_range_ex(handles, C.c_int32(len(devs)), C.byref(q), C.byref(io), C.byref(ex), C.c_int32(n), paths, ptr(sidx),
+                                       ptr(ffv), C.byref(h)))
     else:
         check(L.qa_impute_bam_range_bx(handles, C.c_int32(len(devs)), C.byref(q), C.byref(io), *bx, C.c_int32(n), paths, ptr(sidx),
                                        ptr(ffv), C.byref(h)))
@@ -365,7 +399,7 @@ def impute_bam_range(devs: Sequence, bam_files: Sequence[str], chr: str, ref, al
         nL = 3 if P.method == "nipt" else 2
         imputed = [bool(L.qa_bam_range_imputed(h, C.c_int32(i))) for i in range(n)]
         n_reads = [int(L.qa_bam_range_n_reads(h, C.c_int32(i))) for i in range(n)]
-        columns, results = [None] * n, {}
+        columns, results, frlp = [None] * n, {}, {}
         wanted = set(range(n)) if copy_out is None else set(int(i) for i in copy_out)
         for i in range(n):
             if not imputed[i] or i not in wanted:
@@ -385,6 +419,21 @@ def impute_bam_range(devs: Sequence, bam_files: Sequence[str], chr: str, ref, al
                                       arr(pl, (nl.value,), C.c_int32) if nl.value else np.zeros(0, dtype=np.int32), int(nd.value),
                                       fet_dosage=arr(pfd, (T_out,)) if pfd.value else None,
                                       fet_gp_t=arr(pfg, (3, T_out)) if pfg.value else None)
+            if output_read_label_prob:
+                pn, po, pp, nr = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int32()
+                check(L.qa_bam_range_read_label_prob(h, C.c_int32(i), C.byref(pn), C.byref(po), C.byref(pp), C.byref(nr)))
+                from .io import split_names
+                noff = arr(po, (nr.value + 1,), C.c_int64)
+                nbuf = arr(pn, (max(int(noff[-1]), 1),), C.c_uint8)
+                results[i].read_label_prob = arr(pp, (nr.value,))
+                frlp[i] = (split_names(nbuf, noff), results[i].read_label_prob, results[i].read_labels)
+            if hla_grid is not None:
+                g = [C.c_void_p() for _ in range(4)]
+                kk, ng = C.c_int32(), C.c_int32()
+                check(L.qa_bam_range_hla(h, C.c_int32(i), *[C.byref(x) for x in g], C.byref(kk), C.byref(ng)))
+                r_ = results[i]
+                r_.gamma1, r_.gamma2, r_.gamma_total = (arr(x, (kk.value,)) for x in g[:3])
+                r_.list_of_gammas = arr(g[3], (ng.value, 2, kk.value))
         info, af, hwe, ac = np.zeros((T_out, 2), order="F"), np.zeros(T_out), np.zeros((T_out, 3), order="F"), np.zeros((T_out, 2), order="F")
         check(L.qa_bam_range_counts(h, ptr(info), ptr(af), ptr(hwe), ptr(ac)))
         counts = SummaryCounts(T_out, hweCount=np.ascontiguousarray(hwe), infoCount=np.ascontiguousarray(info), afCount=af,
@@ -396,6 +445,9 @@ def impute_bam_range(devs: Sequence, bam_files: Sequence[str], chr: str, ref, al
     finally:
         L.qa_bam_range_destroy(h)
     del keep, keep_q
-    return dict(imputed=imputed, n_reads=n_reads, columns=columns, results=results, counts=counts,
-                seconds=dict(zip(("load", "impute", "format", "total"), sec.tolist())), stats=dict(zip(STAT_NAMES, st.tolist())),
-                load_stats=ls.tolist(), bx_stats=bxs.tolist())
+    out = dict(imputed=imputed, n_reads=n_reads, columns=columns, results=results, counts=counts,
+               seconds=dict(zip(("load", "impute", "format", "total"), sec.tolist())), stats=dict(zip(STAT_NAMES, st.tolist())),
+               load_stats=ls.tolist(), bx_stats=bxs.tolist())
+    if output_read_label_prob:
+        out["final_read_labels_prob"] = frlp
+    return out

@@ -30,11 +30,13 @@ class BamOpts(C.Structure):
 def _io_lib():
     L = lib()
     if not getattr(L, "_io_ready", False):
-        for name in ("qa_bam_load_sample_reads", "qa_bam_load_sample_reads_bx", "qa_sample_reads_n_reads", "qa_sample_reads_export", "qa_vcf_column_diploid",
+        for name in ("qa_bam_load_sample_reads", "qa_bam_load_sample_reads_bx", "qa_bam_load_sample_reads_named",
+                     "qa_sample_reads_export_names", "qa_read_label_confidence", "qa_sample_reads_n_reads", "qa_sample_reads_export", "qa_vcf_column_diploid",
                      "qa_vcf_column_nipt", "qa_vcf_info_column", "qa_vcf_write_body", "qa_vcf_write_text", "qa_hwe_exact",
                      "qa_accumulate_dosage", "qa_consensus_read_labels"):
             getattr(L, name).restype = C.c_int
         L.qa_sample_reads_n_bases.restype = C.c_int64
+        L.qa_sample_reads_names_bytes.restype = C.c_int64
         L.qa_vcf_missing_entry.restype = C.c_char_p
         L.qa_sample_reads_destroy.restype = None
         L.qa_sample_reads_stats.restype = None
@@ -86,6 +88,22 @@ def consensus_read_labels(labels: np.ndarray, p: np.ndarray, can_hap: int, minrp
     return out
 
 
+def read_label_confidence(p: np.ndarray) -> np.ndarray:
+    """``mp`` of functions.R:1635-1658 for one Gibbs sample, native (qa_read_label_confidence -- the expression the consensus labels
+    threshold and ``output_read_label_prob`` returns): ``p`` [2 or 3, nReads].  numpy twin: quilt_amd/driver.py."""
+    p = np.ascontiguousarray(p, dtype=np.float64)
+    if p.ndim != 2 or p.shape[0] not in (2, 3):
+        raise ValueError("p must be [2 or 3, nReads]")
+    out = np.zeros(p.shape[1])
+    _check(_io_lib().qa_read_label_confidence(C.c_int32(p.shape[1]), C.c_int32(p.shape[0]), ptr(p), ptr(out)), "qa_read_label_confidence")
+    return out
+
+
+def split_names(buf: np.ndarray, off: np.ndarray) -> List[str]:
+    """names back to back, NUL-terminated, with n + 1 offsets (qa_sample_reads_export_names) -> list of str"""
+    return bytes(buf[:int(off[-1])]).decode().split("\0")[:-1] if len(off) > 1 else []
+
+
 # ---------------------------------------------------------------------------------------------------------------------------
 # f3
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -93,13 +111,15 @@ def loadBamAndConvert(bam_file: str, chr: str, L: np.ndarray, ref: Sequence[str]
                       grid: Optional[np.ndarray] = None, *, bqFilter: int = 17, iSizeUpperLimit: float = 1e6,
                       useSoftClippedBases: bool = False, downsampleToCov: int = 30, chrStart: int = 0, chrEnd: int = 0,
                       merge_mates: bool = True, seed: int = 1, return_stats: bool = False, use_bx_tag: bool = False,
-                      bxTagUpperLimit: int = 50000, return_bx_stats: bool = False):
+                      bxTagUpperLimit: int = 50000, return_bx_stats: bool = False, return_names: bool = False):
     """One sample's reads over the region's SNPs, already snapped to the grid (functions.R:243-298).
     ``L`` 1-based ascending positions, ``ref`` / ``alt`` one character per SNP, ``grid`` 0-based grid per SNP (default
     ``snp // 32``, STITCH::assign_positions_to_grid with gridWindowSize = 32 SNPs as QUILT uses it).
     ``use_bx_tag`` / ``bxTagUpperLimit`` (quilt.R:46-47): alignments that share a ``BX:Z`` barcode and lie within the limit of
     each other enter as ONE read (the rule is stated in include/quilt_amd_io.h); files without the tag load as without the
-    option.  ``return_bx_stats``: the rule's four counters come back as a dict behind the other return values."""
+    option.  ``return_bx_stats``: the rule's four counters come back as a dict behind the other return values.
+    ``return_names``: one name per read (the rule is stated in include/quilt_amd_io.h: the query name of the first alignment of the
+    fragment that holds the read's slot), as a list behind the other return values; the read arrays are the same either way."""
     lb = _io_lib()
     L = np.ascontiguousarray(L, dtype=np.int32)
     T = len(L)
@@ -113,9 +133,10 @@ def loadBamAndConvert(bam_file: str, chr: str, L: np.ndarray, ref: Sequence[str]
     if int(bxTagUpperLimit) != bxTagUpperLimit or not -2**31 <= bxTagUpperLimit < 2**31:
         raise ValueError("bxTagUpperLimit must be a whole number")
     h = C.c_void_p()
-    _check(lb.qa_bam_load_sample_reads_bx(bam_file.encode(), chr.encode(), C.c_int32(T), ptr(L), refb, altb, ptr(grid),
-                                          C.byref(o), C.c_int32(int(bool(use_bx_tag))), C.c_int32(int(bxTagUpperLimit)), C.byref(h)),
-           f"cannot load {bam_file} ({chr})")
+    args = (bam_file.encode(), chr.encode(), C.c_int32(T), ptr(L), refb, altb, ptr(grid), C.byref(o), C.c_int32(int(bool(use_bx_tag))),
+            C.c_int32(int(bxTagUpperLimit)))
+    _check(lb.qa_bam_load_sample_reads_named(*args, C.c_int32(1), C.byref(h)) if return_names else
+           lb.qa_bam_load_sample_reads_bx(*args, C.byref(h)), f"cannot load {bam_file} ({chr})")
     try:
         R = lb.qa_sample_reads_n_reads(h)
         nb = lb.qa_sample_reads_n_bases(h)
@@ -127,6 +148,10 @@ def loadBamAndConvert(bam_file: str, chr: str, L: np.ndarray, ref: Sequence[str]
         lb.qa_sample_reads_stats(h, ptr(stats))
         bx = np.zeros(4, dtype=np.int64)
         lb.qa_sample_reads_bx_stats(h, ptr(bx))
+        if return_names:
+            nbuf = np.zeros(max(int(lb.qa_sample_reads_names_bytes(h)), 1), dtype=np.uint8)
+            noff = np.zeros(R + 1, dtype=np.int64)
+            _check(lb.qa_sample_reads_export_names(h, ptr(nbuf), ptr(noff)), "export names")
     finally:
         lb.qa_sample_reads_destroy(h)
     s = SampleReads(read_ptr=read_ptr, u=u, bq=bq, wif=wif)
@@ -137,6 +162,8 @@ def loadBamAndConvert(bam_file: str, chr: str, L: np.ndarray, ref: Sequence[str]
         ret.append(dict(zip(names, (int(x) for x in stats))))
     if return_bx_stats:
         ret.append(dict(zip(BX_STAT_NAMES, (int(x) for x in bx))))
+    if return_names:
+        ret.append(split_names(nbuf, noff))
     return ret[0] if len(ret) == 1 else tuple(ret)
 
 
@@ -347,20 +374,29 @@ def impute_bams_to_vcf(panel, backend, bam_files: Sequence[str], sampleNames: Se
                        alt: Sequence[str], output_filename: str, params=None, inRegion2: Optional[np.ndarray] = None,
                        minimum_number_of_sample_reads: int = 2, ff: Optional[Sequence[float]] = None,
                        output_gt_phased_genotypes: bool = True, use_bx_tag: bool = False, bxTagUpperLimit: int = 50000,
-                       **bam_opts):
+                       output_read_label_prob: bool = False, hla_grid: Optional[int] = None, **bam_opts):
     """The per-sample path end to end for one region: BAM -> sampleReads (f3) -> the driver loop on `backend` -> VCF
     columns and file (f4).  What get_and_impute_one_sample does between its ``loadBamAndConvert`` call and its return
     value, plus the writer (functions.R:243-298, 1408-1477; writers.R).  Samples with fewer than
     ``minimum_number_of_sample_reads`` reads are written as missing and left out of the counts (functions.R:274-287).
-    ``use_bx_tag`` / ``bxTagUpperLimit``: the loader's linked-read rule (:func:`loadBamAndConvert`)."""
-    from .driver import Driver, DriverParams
+    ``use_bx_tag`` / ``bxTagUpperLimit``: the loader's linked-read rule (:func:`loadBamAndConvert`).
+    ``output_read_label_prob``: the record gains ``final_read_labels_prob`` {file index: (names, prob, labels)} (functions.R:318-319,
+    :1164-1166, :1202-1204; names in the order of the reads).  ``hla_grid`` (0-based; hla_run = TRUE): the results carry gamma1,
+    gamma2, gamma_total and list_of_gammas (HlaDriverParams)."""
+    from .driver import Driver, DriverParams, HlaDriverParams
     params = params or DriverParams()
+    if hla_grid is not None and getattr(params, "hla_grid", None) is None:
+        params = HlaDriverParams(**params.__dict__, hla_grid=int(hla_grid))
+    names_of = {}
     if panel.L is None:
         raise ValueError("the panel carries no SNP positions (Panel.L)")
     grid = panel.grid if panel.grid is not None else np.arange(panel.nSNPs, dtype=np.int32) // 32
     samples, imputed = [], []
     for i, path in enumerate(bam_files):
-        s = loadBamAndConvert(path, chr, panel.L, ref, alt, grid, use_bx_tag=use_bx_tag, bxTagUpperLimit=bxTagUpperLimit, **bam_opts)
+        s = loadBamAndConvert(path, chr, panel.L, ref, alt, grid, use_bx_tag=use_bx_tag, bxTagUpperLimit=bxTagUpperLimit,
+                              return_names=bool(output_read_label_prob), **bam_opts)
+        if output_read_label_prob:
+            s, names_of[i] = s
         if ff is not None:
             s.ff = float(ff[i])
         if s.nReads < minimum_number_of_sample_reads:
@@ -378,4 +414,7 @@ def impute_bams_to_vcf(panel, backend, bam_files: Sequence[str], sampleNames: Se
             cols[i] = make_per_sample_vcf_col(r.gp_t, r.phasing_haps, output_gt_phased_genotypes)
     make_and_write_output_file(output_filename, sampleNames, chr, panel.L, ref, alt, cols, counts, inRegion2=inRegion2,
                                method=params.method, output_gt_phased_genotypes=output_gt_phased_genotypes)
-    return dict(results=dict(zip(imputed, results)), columns=cols, counts=counts)
+    rec = dict(results=dict(zip(imputed, results)), columns=cols, counts=counts)
+    if output_read_label_prob:
+        rec["final_read_labels_prob"] = {i: (names_of[i], r.read_label_prob, r.read_labels) for i, r in zip(imputed, results)}
+    return rec

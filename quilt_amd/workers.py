@@ -231,9 +231,10 @@ class NativeWorkers:
     (the batches' samples must be consecutive: they are one sample range).  ``n_workers`` panel handles = host threads."""
 
     def __init__(self, panel, params: Optional[DriverParams] = None, n_workers: int = 3, fp64_dosage: bool = False,
-                 exclusive: bool = True, fuse_tails: bool = True, rare_common=None):
+                 exclusive: bool = True, fuse_tails: bool = True, rare_common=None, output_read_label_prob: bool = False):
         self.n = n_workers
         self.panel = panel
+        self.output_read_label_prob = bool(output_read_label_prob)   # results carry read_label_prob (qa_impute_samples_reads)
         self.params = (params or DriverParams()).resolved(panel.K)
         if self.params.impute_rare_common and rare_common is None:
             raise ValueError("impute_rare_common needs the panel's rare/common tables")
@@ -289,7 +290,7 @@ class NativeWorkers:
         prep = batches if isinstance(batches, PreparedRange) else self.prepare(batches)
         if prep is None:
             return
-        res, st = run_prepared(prep, return_stats=True)
+        res, st = run_prepared(prep, return_stats=True, output_read_label_prob=self.output_read_label_prob)
         batches = [(res[:n], None) for n in prep.batch_sizes]   # (only the sizes are used below)
         self.stats = st
         for k in ("gibbs", "fullpass", "host", "consensus", "finish", "accumulate"):

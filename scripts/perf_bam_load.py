@@ -10,6 +10,10 @@ that exports qa_bam_load_sample_reads, e.g. that commit's libquilt_amd.so), (b) 
 it on (--use-bx-tag; what a QUILT run with default arguments now asks for).  Each round times every file once per way, one
 thread; the result (medians over the rounds, and the spread between rounds) goes to --out as JSON.
     python scripts/perf_bam_load.py --alternate /path/to/parent/libquilt_amd.so --use-bx-tag --out profiles/bx_loader.json
+
+--names: no device.  The same files through this tree's loader with read names kept (qa_bam_load_sample_reads_named, what
+output_read_label_prob asks for) and without, ALTERNATED file by file, one thread; names exported in the timed region.
+    python scripts/perf_bam_load.py --names --out profiles/read_label_names.json
 """
 import argparse, ctypes as C, json, os, sys, tempfile, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -20,11 +24,12 @@ from quilt_amd.synth import make_synthetic_panel, make_synthetic_sample, synthet
 ap = argparse.ArgumentParser()
 ap.add_argument("--use-bx-tag", action="store_true", help="load with use_bx_tag = TRUE (bxTagUpperLimit 50000)")
 ap.add_argument("--alternate", metavar="PARENT_LIB", help="compare with an earlier build's loader, alternated; no device")
+ap.add_argument("--names", action="store_true", help="names on / off, alternated; no device")
 ap.add_argument("--rounds", type=int, default=3)
 ap.add_argument("--out", default=None)
 args = ap.parse_args()
 
-N = int(os.environ.get("N_FILES", "16" if args.alternate else "512"))
+N = int(os.environ.get("N_FILES", "16" if (args.alternate or args.names) else "512"))
 panel = make_synthetic_panel(K=2000, nSNPs=64000, seed=4916)
 ref, alt = synthetic_alleles(panel.nSNPs, 1)
 d = tempfile.mkdtemp(prefix="qa_load_")
@@ -40,6 +45,48 @@ with mp.get_context("fork").Pool(min(32, N, os.cpu_count() or 1)) as pool:
     pool.map(mk, range(N), chunksize=4)
 files = [os.path.join(d, f"s{i}.bam") for i in range(N)]
 print("files", N, "bytes each", os.path.getsize(files[0]))
+
+if args.names:
+    from quilt_amd.io import loadBamAndConvert
+    grid = np.arange(panel.nSNPs, dtype=np.int32) // 32
+    ways = [("names_off", False), ("names_on", True)]
+
+    def load(path, names):
+        t = time.perf_counter()
+        r = loadBamAndConvert(path, "chr20", panel.L, ref, alt, grid, bqFilter=1, downsampleToCov=0, use_bx_tag=args.use_bx_tag,
+                              return_names=names)
+        t = time.perf_counter() - t
+        s_, nm = r if names else (r, None)
+        assert nm is None or len(nm) == s_.nReads
+        return t, s_.nReads
+
+    for _, nm in ways:
+        load(files[0], nm)
+    per_round = {w: [] for w, _ in ways}
+    for r in range(args.rounds):
+        tot = {w: 0.0 for w, _ in ways}
+        for f in files:
+            counts = set()
+            for w, nm in ways:
+                t, n = load(f, nm)
+                tot[w] += t
+                counts.add(n)
+            assert len(counts) == 1
+        for w in tot:
+            per_round[w].append(1e3 * tot[w] / N)
+        print("round", r, {w: round(v[-1], 3) for w, v in per_round.items()})
+    med = {w: float(np.median(v)) for w, v in per_round.items()}
+    res = dict(what="loadBamAndConvert per file with and without read names (qa_bam_load_sample_reads_named), one thread, files of "
+                    "20 000 reads over 64 000 SNPs, export included; ms", n_files=N, rounds=args.rounds, use_bx_tag=bool(args.use_bx_tag),
+               bytes_per_file=os.path.getsize(files[0]), ms_per_file_by_round=per_round, ms_per_file_median=med,
+               spread_between_rounds={w: float((max(v) - min(v)) / np.median(v)) for w, v in per_round.items()},
+               names_on_over_off=med["names_on"] / med["names_off"], cpus=os.cpu_count())
+    print(json.dumps(res))
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+    sys.exit(0)
 
 if args.alternate:
     from quilt_amd.io import BamOpts

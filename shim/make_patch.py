@@ -21,7 +21,7 @@ It also writes shim/QUILT-R.patch: the R side of the FAST path (INTEGRATION.md 4
   * QUILT/R/quilt.R -- inside the mclapply body (:692-990), in front of the loop over a core's samples (:832), the whole range
     goes through ONE `.Call("qa_impute_sample_range", ...)` (quilt_amd_impute_sample_range, new file below) whenever the run
     asks for nothing the range call does not cover (quilt_amd_range_is_covered: no plots, no phasefile / genfile
-    truth, no per-read outputs, ...); the loop then takes each sample's result from that call instead of calling
+    truth, no development switches, ...); the loop then takes each sample's result from that call instead of calling
     get_and_impute_one_sample (:835).  Otherwise -- and always with QUILT_AMD_RANGE=0 -- the unpatched loop runs, through the
     four per-call entries of QUILT-src.patch.
   * QUILT/R/quilt-amd.R -- new: shim/quilt-amd.R (loading by the reference's own loader, the call, the per-sample VCF column
@@ -127,7 +127,8 @@ R_RANGE_CALL = '''        ## libquilt_amd: the whole sample range as ONE call (q
                 chrStart = chrStart, chrEnd = chrEnd, use_bx_tag = use_bx_tag, bxTagUpperLimit = bxTagUpperLimit,
                 minimum_number_of_sample_reads = minimum_number_of_sample_reads,
                 output_gt_phased_genotypes = output_gt_phased_genotypes,
-                hla_run = hla_run, gamma_physically_closest_to = gamma_physically_closest_to
+                hla_run = hla_run, gamma_physically_closest_to = gamma_physically_closest_to,
+                output_read_label_prob = output_read_label_prob
             )
             ## native I/O (quilt-amd.R, form (a)): the range's four count arrays come back summed (in sample order) -- added here
             ## once; the per-sample entries the loop below adds are exact zeros then

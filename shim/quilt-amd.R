@@ -6,7 +6,7 @@
 ## `.Call("qa_impute_sample_range", ...)` (shim/quilt_amd_shim.c; csrc/impute.cpp is get_and_impute_one_sample's loop nest,
 ## functions.R:330-1300, in host C++ over the batched kernels).  This file holds
 ##   quilt_amd_range_is_covered()   -- may this run take the range call?  Anything it does not cover falls back to the
-##                                     unpatched loop (plots, truth haplotypes / genotypes, per-read outputs, ...)
+##                                     unpatched loop (plots, truth haplotypes / genotypes, the development switches, ...)
 ##   quilt_amd_hla_iGrid()          -- hla_run's grid (functions.R:1264-1268), 1-based as the reference forms it
 ##   quilt_amd_impute_sample_range() -- the range's samples through the ONE call.  Two forms:
 ##       (a) NATIVE I/O (the fast one; quilt_amd_native_io_is_covered): `.Call("qa_impute_bam_range", bam_files, ...)` reads the
@@ -16,8 +16,9 @@
 ##           the device imputes about forty.
 ##           use_bx_tag (TRUE by default in QUILT(), quilt.R:139) is the native loader's own rule (include/quilt_amd_io.h;
 ##           unpinned against STITCH): files without BX tags load exactly as with use_bx_tag = FALSE, so a run with default
-##           arguments takes this form.
-##       (b) R I/O (the fallback: CRAM input, hla_run, QUILT_AMD_NATIVE_IO=0): per sample the reference's own loader
+##           arguments takes this form.  hla_run = TRUE (the gamma columns at one grid) and output_read_label_prob = TRUE
+##           (per read: name, confidence, label) take it too: qa_impute_bam_range_ex behind the same `.Call`.
+##       (b) R I/O (the fallback: CRAM input, QUILT_AMD_NATIVE_IO=0): per sample the reference's own loader
 ##           (functions.R:132-172, :251-298), then `.Call("qa_impute_sample_range", ...)`, then per sample what
 ##           get_and_impute_one_sample returns (functions.R:1380-1463) by the reference's own functions.
 ## Nothing in this FILE computes a probability.
@@ -57,7 +58,7 @@ quilt_amd_range_is_covered <- function(
         !make_plots && !make_plots_block_gibbs &&      ## need gamma matrices (return_gamma_t) of every call
         hla_ok &&
         !have_truth_haplotypes && !have_truth_genotypes && ## phasefile / genfile: per-iteration accuracy printing, truth labels
-        !record_interim_dosages && !output_read_label_prob && !record_read_label_usage &&
+        !record_interim_dosages && !record_read_label_usage &&   ## (output_read_label_prob: served by both forms)
         !plot_per_sample_likelihoods && !plot_p1 && !make_heuristic_plot &&
         !estimate_bq_using_truth_read_labels && !addOptimalHapsToVCF &&
         !use_splitreadgl && !small_ref_panel_skip_equally_likely_reads &&
@@ -105,12 +106,14 @@ quilt_amd_load_sample <- function(
         use_bx_tag = use_bx_tag, bxTagUpperLimit = bxTagUpperLimit, default_sample_no_read_behaviour = "return_null"
     )
     load(file_sampleReads(tempdir, iSample, regionName))
+    load(file_sampleReadsInfo(tempdir, iSample, regionName))   ## sampleReadsInfo: the reads' names (functions.R:271, :319)
     removeTmpSamplesFile(tempdir, iSample, regionName, save_sampleReadsInfo = TRUE)
     ungridded <- sampleReads
     if (length(sampleReads) > 0) {
         sampleReads <- snap_sampleReads_to_grid(sampleReads = sampleReads, grid = grid)
     }
-    return(list(sampleReads = sampleReads, ungridded = ungridded))
+    ## the names as the reference takes them: in the loader's order, before snap_sampleReads_to_grid reorders the reads
+    return(list(sampleReads = sampleReads, ungridded = ungridded, qname = sampleReadsInfo[, "qname"]))
 }
 
 
@@ -129,10 +132,31 @@ quilt_amd_impute_sample_range <- function(
     downsampleToCov, tempdir, regionName, chrStart, chrEnd, use_bx_tag, bxTagUpperLimit,
     minimum_number_of_sample_reads, output_gt_phased_genotypes,
     ## hla_run (functions.R:1261-1280, :1489-1494)
-    hla_run = FALSE, gamma_physically_closest_to = NA
+    hla_run = FALSE, gamma_physically_closest_to = NA,
+    ## output_read_label_prob (functions.R:318-319, :1164-1166, :1202-1204)
+    output_read_label_prob = FALSE
 ) {
     w <- sampleRange[1]:sampleRange[2]
     n <- length(w)
+    ## hla_run's four objects of one sample from the call's matrices (functions.R:1489-1494): column j is sample j's
+    hla_objects <- function(out, j) {
+        K <- nrow(hapMatcherR)
+        g <- array(out[["list_of_gammas"]][, j], c(K, 2, nGibbsSamples))
+        list(
+            gamma1 = out[["gamma1"]][, j], gamma2 = out[["gamma2"]][, j], gamma_total = out[["gamma_total"]][, j],
+            list_of_gammas = lapply(1:nGibbsSamples, function(i_gibbs) list(g[, 1, i_gibbs], g[, 2, i_gibbs]))
+        )
+    }
+    ## hla_run on a panel whose dosage passes keep no gamma column (a K the fp64 dosage kernels do not hold): refused by the
+    ## library before any sample is imputed or any file opened -- the range is not covered, the unpatched loop runs (NULL)
+    no_gamma_column <- function(e) {
+        if (hla_run && grepl("keep no gamma column", conditionMessage(e), fixed = TRUE)) return(NULL)
+        stop(e)
+    }
+    no_gamma_message <- function() {
+        print_message(paste0("hla_run: this panel's full-panel passes keep no gamma column on the GPU; samples ", w[1], " to ", w[n],
+                             " take the per-sample loop"))
+    }
     sum_order <- as.integer(Sys.getenv("QUILT_AMD_SUM_ORDER", "0"))
     sum_order_batched <- as.integer(Sys.getenv("QUILT_AMD_SUM_ORDER_BATCHED", "0"))   ## with sum_order 1 or 2: the batched kernels, same bits
     panel_objects <- list(
@@ -173,15 +197,15 @@ quilt_amd_impute_sample_range <- function(
         )
     }
     ## ---- (a) native I/O: BAM paths in, VCF columns and the range's counts out (one call)
-    ## (hla_run: the gammas come back through form (b); native I/O for it is not built)
-    if (!hla_run && quilt_amd_native_io_is_covered(bam_files, cram_files, use_bx_tag, pos, pos_all, impute_rare_common)) {
+    if (quilt_amd_native_io_is_covered(bam_files, cram_files, use_bx_tag, pos, pos_all, impute_rare_common)) {
         sites <- list(
             chr = chr, L = as.integer(L), ref = as.character(pos[, 3]), alt = as.character(pos[, 4]), grid = as.integer(grid),
             bqFilter = bqFilter, iSizeUpperLimit = iSizeUpperLimit, useSoftClippedBases = useSoftClippedBases,
             downsampleToCov = downsampleToCov, chrStart = chrStart, chrEnd = chrEnd,
             minimum_number_of_sample_reads = minimum_number_of_sample_reads,
             output_gt_phased_genotypes = output_gt_phased_genotypes,
-            use_bx_tag = isTRUE(use_bx_tag), bxTagUpperLimit = bxTagUpperLimit
+            use_bx_tag = isTRUE(use_bx_tag), bxTagUpperLimit = bxTagUpperLimit,
+            output_read_label_prob = isTRUE(output_read_label_prob)
         )
         if (impute_rare_common) {
             sites <- c(sites, list(
@@ -191,8 +215,12 @@ quilt_amd_impute_sample_range <- function(
         }
         if (method == "nipt") params[["ff"]] <- as.numeric(ff_values[w])
         print_message(paste0("Imputing samples ", w[1], " to ", w[n], " on the GPU from their BAM files (", n, " samples in one call)"))
-        out <- .Call("qa_impute_bam_range", as.character(bam_files[w]), sites, panel_objects, params, as.numeric(w - 1L),
-                     as.integer(n_handles), PACKAGE = "QUILT")
+        out <- tryCatch(.Call("qa_impute_bam_range", as.character(bam_files[w]), sites, panel_objects, params, as.numeric(w - 1L),
+                              as.integer(n_handles), PACKAGE = "QUILT"), error = no_gamma_column)
+        if (is.null(out)) {
+            no_gamma_message()
+            return(NULL)
+        }
         bx <- out[["bx_stats"]]
         print_message(paste0("Samples ", w[1], " to ", w[n], " were loaded by the native loader (use_bx_tag = ", isTRUE(use_bx_tag),
                              "): ", bx[1], " tagged alignments, ", bx[2], " molecules of several fragments, ", bx[3],
@@ -218,6 +246,10 @@ quilt_amd_impute_sample_range <- function(
                 super_out_hap_dosages = NULL, super_out_read_labels = out[["read_labels"]][[i]],
                 super_out_dosage_matrix = NULL, final_read_labels_prob = as.list(1:3)
             )
+            ## 1: read name; 2: probability; 3: best hap -- all three in the order of the reads (include/quilt_amd_io.h says how
+            ## that differs from the reference's names, which are in the loader's order)
+            if (output_read_label_prob) results[[i]][["final_read_labels_prob"]] <- out[["final_read_labels_prob"]][[i]]
+            if (hla_run) results[[i]] <- c(results[[i]], hla_objects(out, i))
         }
         attr(results, "quilt_amd_counts") <- out[c("infoCount", "afCount", "hweCount", "alleleCount")]
         attr(results, "quilt_amd_seconds") <- out[["seconds"]]
@@ -233,8 +265,8 @@ quilt_amd_impute_sample_range <- function(
         )
     }
     ## ---- 1. reads of every sample of the range (the reference's own loader; functions.R:132-172, :251-298)
-    print_message(paste0("Samples ", w[1], " to ", w[n], " are loaded by the reference's R loader (about a second per sample: CRAM input, ",
-                         "hla_run or QUILT_AMD_NATIVE_IO=0)"))
+    print_message(paste0("Samples ", w[1], " to ", w[n], " are loaded by the reference's R loader (about a second per sample: CRAM input ",
+                         "or QUILT_AMD_NATIVE_IO=0)"))
     loaded <- lapply(w, function(iSample) load1(iSample, L, pos, grid))
     loaded_all <- NULL
     if (impute_rare_common) {
@@ -255,6 +287,7 @@ quilt_amd_impute_sample_range <- function(
     }
     ## ---- 2. the ONE call: every chain of every kept sample of the range, in lock-step on the device
     if (method == "nipt") params[["ff"]] <- as.numeric(ff_values[w[keep]])
+    if (output_read_label_prob) params[["output_read_label_prob"]] <- TRUE
     all_reads <- NULL
     if (impute_rare_common) {
         all_reads <- lapply(loaded_all[keep], "[[", "sampleReads")
@@ -265,15 +298,9 @@ quilt_amd_impute_sample_range <- function(
         as.numeric(w[keep] - 1L),      ## every kept sample's own global index: its streams do not depend on which other samples
                                        ## of the range were skipped
         as.integer(n_handles), all_reads, PACKAGE = "QUILT"
-    ), error = function(e) {
-        ## hla_run on a panel whose dosage passes keep no gamma column (a K the fp64 dosage kernels do not hold): refused by the
-        ## library before any sample is imputed -- the range is not covered, the unpatched loop runs (NULL)
-        if (hla_run && grepl("keep no gamma column", conditionMessage(e), fixed = TRUE)) return(NULL)
-        stop(e)
-    })
+    ), error = no_gamma_column)
     if (is.null(out)) {
-        print_message(paste0("hla_run: this panel's full-panel passes keep no gamma column on the GPU; samples ", w[1], " to ", w[n],
-                             " take the per-sample loop"))
+        no_gamma_message()
         return(NULL)
     }
     ## ---- 3. per sample, what get_and_impute_one_sample returns (functions.R:1304-1463)
@@ -321,15 +348,13 @@ quilt_amd_impute_sample_range <- function(
             super_out_hap_dosages = NULL, super_out_read_labels = out[["read_labels"]][[j]],
             super_out_dosage_matrix = NULL, final_read_labels_prob = as.list(1:3)
         )
-        if (hla_run) {
-            ## functions.R:1489-1494: the phasing iteration's columns, their sum over the Gibbs samples, and every Gibbs sample's pair
-            K <- nrow(hapMatcherR)
-            g <- array(out[["list_of_gammas"]][, j], c(K, 2, nGibbsSamples))
-            results[[i]][["gamma1"]] <- out[["gamma1"]][, j]
-            results[[i]][["gamma2"]] <- out[["gamma2"]][, j]
-            results[[i]][["gamma_total"]] <- out[["gamma_total"]][, j]
-            results[[i]][["list_of_gammas"]] <- lapply(1:nGibbsSamples, function(i_gibbs) list(g[, 1, i_gibbs], g[, 2, i_gibbs]))
+        if (output_read_label_prob) {
+            ## as the reference fills it: names from sampleReadsInfo (functions.R:319), mp of the last Gibbs sample (:1165), the
+            ## consensus labels (:1203)
+            results[[i]][["final_read_labels_prob"]] <- list(loaded[[i]][["qname"]], out[["read_label_prob"]][[j]], out[["read_labels"]][[j]])
         }
+        ## functions.R:1489-1494: the phasing iteration's columns, their sum over the Gibbs samples, and every Gibbs sample's pair
+        if (hla_run) results[[i]] <- c(results[[i]], hla_objects(out, j))
     }
     return(results)
 }

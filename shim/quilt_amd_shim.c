@@ -579,7 +579,8 @@ SEXP qa_QUILT_rcpp_make_eMatRead_t(SEXP eMatRead_tSEXP, SEXP sampleReadsSEXP, SE
  *                         wif on the all-SNP grid); NULL otherwise
  * Returns list(dosage = nSNPs x n, gp_t = 3 nSNPs x n (per sample 3 x nSNPs, row-major as the library writes it),
  * phasing_haps = 2 nSNPs x n (nipt: 3 nSNPs x n), read_labels = list of integer vectors, nDosage, stats[, fet_dosage, fet_gp_t]);
- * nSNPs = all SNPs with impute_rare_common.  With params$hla_grid also gamma1, gamma2, gamma_total (K x n: a sample's column is
+ * nSNPs = all SNPs with impute_rare_common.  With params$output_read_label_prob = TRUE also read_label_prob (list of numeric
+ * vectors: per read the confidence of its label, qa_impute_samples_reads).  With params$hla_grid also gamma1, gamma2, gamma_total (K x n: a sample's column is
  * its vector) and list_of_gammas ((K x 2 x nGibbsSamples) x n: per sample the nGibbsSamples pairs (gamma1, gamma2) of
  * functions.R:1276-1278, each column an R array of dim c(K, 2, nGibbsSamples)).  Draws: the library's counter streams (R's stream cannot be handed to 2 048 chains
  * advancing in lock-step); `seed` plays set.seed's part.  use_mspbwt: the panel's msPBWT indices are built here by
@@ -940,6 +941,8 @@ SEXP qa_impute_sample_range(SEXP readsListSEXP, SEXP panelSEXP, SEXP paramsSEXP,
             Rf_error("quilt_amd: %s: params$hla_grid must be one whole number in [0, nGrids = %d) (iGrid - 1)", who, G);
         hla_grid = (int)hg;
     }
+    /* output_read_label_prob (functions.R:1164-1166): params$output_read_label_prob -> read_label_prob, one vector per sample */
+    const int want_prob = flag(paramsSEXP, "output_read_label_prob", 0);
     range_ctx_t cx;
     int st = range_setup(&cx, panelSEXP, paramsSEXP, Rf_asInteger(n_handlesSEXP), n);
     if (st != QA_OK) Rf_error("quilt_amd: %s: %s", who, cx.msg);
@@ -980,15 +983,22 @@ SEXP qa_impute_sample_range(SEXP readsListSEXP, SEXP panelSEXP, SEXP paramsSEXP,
         hq.gamma1 = REAL(g1); hq.gamma2 = REAL(g2); hq.gamma_total = REAL(gtot); hq.list_of_gammas = REAL(glist);
     }
     int32_t *labels = (int32_t *)malloc(sizeof(int32_t) * (size_t)(totR > 0 ? totR : 1));
+    double *prob = want_prob ? (double *)malloc(sizeof(double) * (size_t)(totR > 0 ? totR : 1)) : NULL;
     int64_t *sidx = sample_index_of(sample_offsetSEXP, n);
     char msg[512];
     msg[0] = 0;
-    if (!labels || (Rf_length(sample_offsetSEXP) == n && n > 1 && !sidx)) { st = QA_ERR_INVALID; snprintf(msg, sizeof msg, "out of memory"); }
+    if (!labels || (want_prob && !prob) || (Rf_length(sample_offsetSEXP) == n && n > 1 && !sidx)) { st = QA_ERR_INVALID; snprintf(msg, sizeof msg, "out of memory"); }
     int64_t st64[11] = {0};
     if (st == QA_OK) {
         cx.ip.sample_index = sidx;
         const int64_t off = sidx ? 0 : (int64_t)Rf_asReal(sample_offsetSEXP);
-        if (hla)
+        if (want_prob) {
+            qa_impute_reads_out_t ro;
+            memset(&ro, 0, sizeof ro);
+            ro.read_label_prob = prob;
+            st = qa_impute_samples_reads(cx.handles, cx.n_handles, &cx.ip, n, off, read_off, fr.read_ptr, fr.u, fr.bq, fr.wif, REAL(dosage),
+                                         REAL(gp_t), REAL(haps), labels, INTEGER(nDosage), st64, hla ? &hq : NULL, &ro);
+        } else if (hla)
             st = qa_impute_samples_hla(cx.handles, cx.n_handles, &cx.ip, n, off, read_off, fr.read_ptr, fr.u, fr.bq, fr.wif, REAL(dosage),
                                        REAL(gp_t), REAL(haps), labels, INTEGER(nDosage), st64, &hq);
         else
@@ -1000,6 +1010,7 @@ SEXP qa_impute_sample_range(SEXP readsListSEXP, SEXP panelSEXP, SEXP paramsSEXP,
     free(sidx);
     if (fa.read_off) flat_reads_free(&fa);
     SEXP lab = PROTECT(Rf_allocVector(VECSXP, n));
+    SEXP probs = PROTECT(want_prob ? Rf_allocVector(VECSXP, n) : R_NilValue);
     if (st == QA_OK)
         for (int i = 0; i < n; i++) {
             const int R = read_off[i + 1] - read_off[i];
@@ -1007,23 +1018,34 @@ SEXP qa_impute_sample_range(SEXP readsListSEXP, SEXP panelSEXP, SEXP paramsSEXP,
             memcpy(INTEGER(v), labels + read_off[i], sizeof(int) * (size_t)R);
             SET_VECTOR_ELT(lab, i, v);
             UNPROTECT(1);
+            if (!want_prob) continue;
+            SEXP pv = PROTECT(Rf_allocVector(REALSXP, R));
+            memcpy(REAL(pv), prob + read_off[i], sizeof(double) * (size_t)R);
+            SET_VECTOR_ELT(probs, i, pv);
+            UNPROTECT(1);
         }
     flat_reads_free(&fr);
     free(labels);
+    free(prob);
     if (st != QA_OK) {
-        UNPROTECT(6 + n_prot);
+        UNPROTECT(7 + n_prot);
         Rf_error("quilt_amd: %s: %s", who, msg);
     }
     for (int i = 0; i < 11; i++) REAL(stats)[i] = (double)st64[i];
     const char *names[] = {"dosage", "gp_t", "phasing_haps", "read_labels", "nDosage", "stats", "fet_dosage", "fet_gp_t"};
     const char *names_hla[] = {"dosage", "gp_t", "phasing_haps", "read_labels", "nDosage", "stats", "gamma1", "gamma2", "gamma_total",
-                               "list_of_gammas"};
-    SEXP out = PROTECT(hla ? named_list(10, names_hla) : named_list(cx.nipt ? 8 : 6, names));
+                               "list_of_gammas", "read_label_prob"};
+    const int n_names = hla ? 10 : cx.nipt ? 8 : 6;   /* (read_label_prob, when asked for, is the entry behind these) */
+    const char *names_all[11];
+    for (int i = 0; i < n_names; i++) names_all[i] = hla ? names_hla[i] : names[i];
+    names_all[n_names] = "read_label_prob";
+    SEXP out = PROTECT(named_list(n_names + (want_prob ? 1 : 0), names_all));
     SET_VECTOR_ELT(out, 0, dosage); SET_VECTOR_ELT(out, 1, gp_t); SET_VECTOR_ELT(out, 2, haps);
     SET_VECTOR_ELT(out, 3, lab); SET_VECTOR_ELT(out, 4, nDosage); SET_VECTOR_ELT(out, 5, stats);
     if (hla) { SET_VECTOR_ELT(out, 6, g1); SET_VECTOR_ELT(out, 7, g2); SET_VECTOR_ELT(out, 8, gtot); SET_VECTOR_ELT(out, 9, glist); }
     else if (cx.nipt) { SET_VECTOR_ELT(out, 6, fet_dosage); SET_VECTOR_ELT(out, 7, fet_gp_t); }
-    UNPROTECT(7 + n_prot);
+    if (want_prob) SET_VECTOR_ELT(out, n_names, probs);
+    UNPROTECT(8 + n_prot);
     return out;
 }
 
@@ -1045,7 +1067,10 @@ SEXP qa_impute_sample_range(SEXP readsListSEXP, SEXP panelSEXP, SEXP paramsSEXP,
  * Returns list(sample_was_imputed (logical), n_reads (integer), per_sample_vcf_col (list: character vector per imputed sample,
  * NULL otherwise), read_labels (list), infoCount (nSNPs x 2), afCount, hweCount (nSNPs x 3), alleleCount (nSNPs x 2): the
  * range's sums in sample order as quilt.R:955-961 forms them; seconds (load, impute, format, total), stats, bx_stats (the BX rule's
- * four counters summed over the files: qa_bam_range_bx_stats; zeros without use_bx_tag)).  The loader is
+ * four counters summed over the files: qa_bam_range_bx_stats; zeros without use_bx_tag)).  With sites$output_read_label_prob = TRUE
+ * also final_read_labels_prob (per file list(names, prob, labels), NULL when not imputed); with params$hla_grid (iGrid - 1) also
+ * gamma1, gamma2, gamma_total (K x n) and list_of_gammas ((K x 2 x nGibbsSamples) x n) as qa_impute_sample_range returns them (NA
+ * columns for files not imputed).  Both go through qa_impute_bam_range_ex (include/quilt_amd_io.h).  The loader is
  * csrc/hostio.cpp's (include/quilt_amd_io.h says where it is unpinned against STITCH: CRAM is refused); quilt-amd.R calls this
  * routine only for the options it implements and falls back to the R loader otherwise. */
 static const char *one_string(SEXP list, const char *name) {
@@ -1093,6 +1118,24 @@ SEXP qa_impute_bam_range_call(SEXP bamFilesSEXP, SEXP sitesSEXP, SEXP panelSEXP,
             if (!(v >= 0 && v <= 2147483647.0 && v == (double)(int)v))   /* (NA and NaN fail every comparison) */
                 Rf_error("quilt_amd: %s: sites$bxTagUpperLimit must be one whole number >= 0 (below 2^31)", who);
             bx_limit = (int)v;
+        }
+    }
+    /* the two options of qa_bam_range_extras_t beyond the tag: sites$output_read_label_prob, params$hla_grid (0-based, as for
+     * qa_impute_sample_range) -- checked here too */
+    int want_prob = 0, hla_grid = -1;
+    {
+        SEXP op = list_get(sitesSEXP, "output_read_label_prob"), hg = list_get(paramsSEXP, "hla_grid");
+        if (op != R_NilValue) {
+            if (TYPEOF(op) != LGLSXP || Rf_length(op) != 1 || (LOGICAL(op)[0] != 0 && LOGICAL(op)[0] != 1))
+                Rf_error("quilt_amd: %s: sites$output_read_label_prob must be TRUE or FALSE", who);
+            want_prob = LOGICAL(op)[0] != 0;
+        }
+        if (hg != R_NilValue) {
+            const double v = Rf_length(hg) == 1 && (TYPEOF(hg) == INTSXP || TYPEOF(hg) == REALSXP) ? Rf_asReal(hg) : -1;
+            const int G = Rf_ncols(list_get(panelSEXP, "hapMatcherR"));
+            if (!(v >= 0 && v < G && v == floor(v)))
+                Rf_error("quilt_amd: %s: params$hla_grid must be one whole number in [0, nGrids = %d) (iGrid - 1)", who, G);
+            hla_grid = (int)v;
         }
     }
     const char *chr = one_string(sitesSEXP, "chr");
@@ -1148,7 +1191,10 @@ SEXP qa_impute_bam_range_call(SEXP bamFilesSEXP, SEXP sitesSEXP, SEXP panelSEXP,
         io.output_gt_phased_genotypes = flag(sitesSEXP, "output_gt_phased_genotypes", 1);
         io.n_io_threads = (int)num_or(sitesSEXP, "n_io_threads", 0);
         io.discard_sample_arrays = 1;   /* (columns, labels and counts go back to R: the per-SNP numbers behind them are not kept) */
-        st = qa_impute_bam_range_bx(cx.handles, cx.n_handles, &cx.ip, &io, use_bx_tag, bx_limit, n, paths, sidx, cx.nipt ? cx.nq.ff : NULL, &res);
+        qa_bam_range_extras_t ex;
+        memset(&ex, 0, sizeof ex);
+        ex.use_bx_tag = use_bx_tag; ex.bxTagUpperLimit = bx_limit; ex.output_read_label_prob = want_prob; ex.hla_grid = hla_grid;
+        st = qa_impute_bam_range_ex(cx.handles, cx.n_handles, &cx.ip, &io, &ex, n, paths, sidx, cx.nipt ? cx.nq.ff : NULL, &res);
         if (st != QA_OK) snprintf(msg, sizeof msg, "%s", qa_last_error());
         range_teardown(&cx);
     }
@@ -1162,9 +1208,14 @@ SEXP qa_impute_bam_range_call(SEXP bamFilesSEXP, SEXP sitesSEXP, SEXP panelSEXP,
     SEXP guard = PROTECT(R_MakeExternalPtr(res, R_NilValue, R_NilValue));
     R_RegisterCFinalizerEx(guard, range_result_finalizer, TRUE);
     const int T_out = qa_bam_range_n_snps(res);
-    const char *names[] = {"sample_was_imputed", "n_reads", "per_sample_vcf_col", "read_labels", "infoCount", "afCount", "hweCount",
-                           "alleleCount", "seconds", "stats", "bx_stats"};
-    SEXP out = PROTECT(named_list(11, names));
+    const char *names[16] = {"sample_was_imputed", "n_reads", "per_sample_vcf_col", "read_labels", "infoCount", "afCount", "hweCount",
+                             "alleleCount", "seconds", "stats", "bx_stats"};
+    int n_names = 11;   /* (the options' entries follow the eleven a call without them returns) */
+    const int at_prob = want_prob ? n_names : -1;
+    if (want_prob) names[n_names++] = "final_read_labels_prob";
+    const int at_hla = hla_grid >= 0 ? n_names : -1;
+    if (hla_grid >= 0) { names[n_names++] = "gamma1"; names[n_names++] = "gamma2"; names[n_names++] = "gamma_total"; names[n_names++] = "list_of_gammas"; }
+    SEXP out = PROTECT(named_list(n_names, names));
     SEXP imputed = PROTECT(Rf_allocVector(LGLSXP, n)), n_reads = PROTECT(Rf_allocVector(INTSXP, n));
     SEXP cols = PROTECT(Rf_allocVector(VECSXP, n)), labs = PROTECT(Rf_allocVector(VECSXP, n));
     SET_VECTOR_ELT(out, 0, imputed); SET_VECTOR_ELT(out, 1, n_reads); SET_VECTOR_ELT(out, 2, cols); SET_VECTOR_ELT(out, 3, labs);
@@ -1201,6 +1252,48 @@ SEXP qa_impute_bam_range_call(SEXP bamFilesSEXP, SEXP sitesSEXP, SEXP panelSEXP,
     qa_bam_range_bx_stats(res, bx64);
     for (int i = 0; i < 4; i++) REAL(bxs)[i] = (double)bx64[i];
     SET_VECTOR_ELT(out, 10, bxs);
+    if (want_prob) {   /* final_read_labels_prob: per sample list(names, prob, labels) (functions.R:318-319, :1165, :1203); NULL when not imputed */
+        SEXP frlp = PROTECT(Rf_allocVector(VECSXP, n));
+        SET_VECTOR_ELT(out, at_prob, frlp);
+        UNPROTECT(1);
+        for (int i = 0; i < n; i++) {
+            const char *nb = NULL;
+            const int64_t *no = NULL;
+            const double *pr = NULL;
+            int32_t nr = 0;
+            qa_bam_range_read_label_prob(res, i, &nb, &no, &pr, &nr);
+            if (!no) continue;
+            SEXP three = PROTECT(Rf_allocVector(VECSXP, 3));
+            SET_VECTOR_ELT(frlp, i, three);
+            UNPROTECT(1);
+            SEXP nm = PROTECT(Rf_allocVector(STRSXP, nr));
+            for (int r = 0; r < nr; r++) SET_STRING_ELT(nm, r, Rf_mkChar(nb + no[r]));
+            SET_VECTOR_ELT(three, 0, nm);
+            UNPROTECT(1);
+            SEXP pv = PROTECT(Rf_allocVector(REALSXP, nr));
+            if (nr > 0) memcpy(REAL(pv), pr, sizeof(double) * (size_t)nr);
+            SET_VECTOR_ELT(three, 1, pv);
+            UNPROTECT(1);
+            SET_VECTOR_ELT(three, 2, VECTOR_ELT(labs, i));
+        }
+    }
+    if (hla_grid >= 0) {   /* the shapes of qa_impute_sample_range: K x n, and (K x 2 x nGibbsSamples) x n; NA for a file not imputed */
+        const int32_t K = cx.K, nG = cx.ip.nGibbsSamples;   /* (plain numbers of the context: they outlive its teardown) */
+        const size_t rows[4] = {(size_t)K, (size_t)K, (size_t)K, (size_t)K * 2 * (size_t)nG};
+        for (int q = 0; q < 4; q++) {
+            SEXP m = PROTECT(Rf_allocMatrix(REALSXP, (int)rows[q], n));
+            SET_VECTOR_ELT(out, at_hla + q, m);
+            UNPROTECT(1);
+            for (int i = 0; i < n; i++) {
+                const double *g[4] = {NULL, NULL, NULL, NULL};
+                int32_t k2 = 0, g2 = 0;
+                qa_bam_range_hla(res, i, &g[0], &g[1], &g[2], &g[3], &k2, &g2);
+                double *dst = REAL(m) + (size_t)i * rows[q];
+                if (g[q] && k2 == K && g2 == nG) memcpy(dst, g[q], sizeof(double) * rows[q]);
+                else for (size_t r = 0; r < rows[q]; r++) dst[r] = NA_REAL;
+            }
+        }
+    }
     range_result_finalizer(guard);
     UNPROTECT(13);
     return out;

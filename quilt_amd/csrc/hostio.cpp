@@ -7,6 +7,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -310,6 +311,355 @@ struct qa_sample_reads {
     std::vector<int64_t> names_off;      // n_reads + 1 offsets
 };
 
+// ---------------------------------------------------------------------------------------------------------------------
+// The loader in stages (qa_bam_load_sample_reads_named below is their sequence).  Each stage says what it reads and what it
+// leaves; the counters are the result's own (stats[8], bx_stats[4]: include/quilt_amd_io.h).
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+
+// One load, as every stage sees it: the file, the sites, the resolved options, the window in 1-based positions and the rules asked for.
+struct LoadRequest {
+    const char *bam_path, *chr;
+    int32_t nSNPs; const int32_t *L; const char *ref, *alt; const int32_t *grid;
+    qa_bam_opts_t o;
+    int32_t lo_bp, hi_bp;
+    bool use_bx; int32_t bxTagUpperLimit; bool want_names;
+};
+
+// every refusal says which file and what about it (qa_impute_bam_range reports it as "cannot load <file>: <this>")
+int refuse(const LoadRequest &rq, const char *what) { qa::set_error("%s: %s", rq.bam_path, what); return (int)QA_ERR_INVALID; }
+template <class... A> int invalid(const char *fmt, A... a) { qa::set_error(fmt, a...); return (int)QA_ERR_INVALID; }   // (a refusal of the arguments)
+
+// Reads the entry's arguments (has_out: the result pointer was given) and the file's first four bytes; leaves the status and text
+// of the first check that fails -- the limit's sign, a missing argument, the sites' order, CRAM -- or QA_OK.
+int check_request(const LoadRequest &rq, bool has_out) {
+    if (rq.bxTagUpperLimit < 0) return invalid("qa_bam_load_sample_reads: bxTagUpperLimit = %d is negative", (int)rq.bxTagUpperLimit);
+    if (!rq.bam_path || !rq.chr || rq.nSNPs < 1 || !rq.L || !rq.ref || !rq.alt || !rq.grid || !has_out)
+        return invalid("qa_bam_load_sample_reads: missing argument");
+    for (int32_t t = 1; t < rq.nSNPs; t++)
+        if (rq.L[t] <= rq.L[t - 1]) return invalid("qa_bam_load_sample_reads: the site positions must ascend (L[%d] <= L[%d])", t, t - 1);
+    // CRAM (cramlist + reference, quilt.R:106-108): not decoded here -- say so, with the way round it
+    FILE *fc = fopen(rq.bam_path, "rb");
+    char m4[4] = {0, 0, 0, 0};
+    const bool cram = fc && fread(m4, 1, 4, fc) == 4 && memcmp(m4, "CRAM", 4) == 0;
+    if (fc) fclose(fc);
+    if (cram) {
+        qa::set_error("%s is a CRAM file: qa_bam_load_sample_reads reads BAM only.  Convert it first -- "
+                      "`samtools view -b -T <reference.fa> -o sample.bam sample.cram && samtools index sample.bam` -- "
+                      "(the reference reads CRAM through STITCH / htslib given `reference`; test-acceptance-cram.R makes its "
+                      "CRAMs with the inverse command)", rq.bam_path);
+        return QA_ERR_UNSUPPORTED;
+    }
+    return QA_OK;
+}
+
+struct OpenBam {   // the reader; rq.chr's index in the reference dictionary; the header says SO:coordinate
+    BgzfReader bz;
+    int32_t target = -1;
+    bool sorted = false;
+};
+
+// Reads the BGZF magic, the header text and the reference dictionary, and for a sorted file the index beside it; leaves the reader
+// at the first alignment the window can need, with `target` and `sorted` -- or a refusal.
+int open_at_window(const LoadRequest &rq, OpenBam &in) {
+    BgzfReader &bz = in.bz;
+    if (bz.bad) return refuse(rq, "cannot be opened");
+    char magic[4];
+    int32_t l_text, n_ref;
+    if (!bz.read(magic, 4) || memcmp(magic, "BAM\1", 4) != 0 || !bz.read(&l_text, 4) || l_text < 0)
+        return refuse(rq, "not a BAM file (no BGZF block with the BAM magic at its start)");
+    std::string text((size_t)l_text, '\0');
+    if (l_text && !bz.read(&text[0], (size_t)l_text)) return refuse(rq, "the header text is cut short");
+    in.sorted = text.find("SO:coordinate") != std::string::npos;
+    if (!bz.read(&n_ref, 4) || n_ref < 0) return refuse(rq, "the reference dictionary is cut short");
+    for (int32_t i = 0; i < n_ref; i++) {
+        int32_t l_name, l_ref;
+        if (!bz.read(&l_name, 4) || l_name < 1 || l_name > 65536) return refuse(rq, "the reference dictionary is damaged");
+        std::string name((size_t)l_name, '\0');
+        if (!bz.read(&name[0], (size_t)l_name) || !bz.read(&l_ref, 4)) return refuse(rq, "the reference dictionary is cut short");
+        if (strcmp(name.c_str(), rq.chr) == 0) in.target = i;
+    }
+    if (in.target < 0) return invalid("%s: no reference sequence named %s", rq.bam_path, rq.chr);
+    // A coordinate-sorted file with a BAI index next to it (<file>.bai or <file without .bam>.bai): start at the linear
+    // index's offset for the window's first 16 kb interval -- the first alignment overlapping it (SAM spec 5.1.3) --, tightened
+    // by the bin index's chunks (bai_start_offset), instead of scanning from the top of a whole-genome file.  Any problem with the index just means the sequential scan.
+    if (in.sorted) {
+        const uint64_t voff = bai_start_offset(rq.bam_path, in.target, rq.o.chrStart > 0 ? rq.o.chrStart - 1 : 0,
+                                               rq.o.chrEnd > 0 ? rq.o.chrEnd : INT32_MAX);
+        if (voff != 0 && !bz.seek_virtual(voff)) return refuse(rq, "the index points outside the file");
+    }
+    return QA_OK;
+}
+
+// The fixed fields of one alignment record (SAM spec 4.2) and where its variable parts lie.
+struct Alignment {
+    int32_t refID, pos0, l_seq, tlen;
+    int l_read_name, mapq;
+    uint16_t n_cigar, flag;
+    bool whole;                  // the lengths the record states fit inside it (false: damaged)
+    const uint8_t *name, *end;   // the variable parts: name, CIGAR, sequence, qualities, auxiliary fields up to end
+    std::string qname() const { return std::string(reinterpret_cast<const char *>(name), (size_t)std::max(0, l_read_name - 1)); }
+};
+
+// Reads the first 32 bytes of `rec` (at least 32 long); leaves the fields and whether the parts they size lie inside the record.
+Alignment decode_alignment(const std::vector<uint8_t> &rec) {
+    Alignment a;
+    memcpy(&a.refID, &rec[0], 4);
+    memcpy(&a.pos0, &rec[4], 4);
+    a.l_read_name = rec[8]; a.mapq = rec[9];
+    memcpy(&a.n_cigar, &rec[12], 2);
+    memcpy(&a.flag, &rec[14], 2);
+    memcpy(&a.l_seq, &rec[16], 4);
+    memcpy(&a.tlen, &rec[28], 4);   // (next_refID and next_pos, bytes 20-27, are not used)
+    const size_t need = 32 + (size_t)a.l_read_name + 4 * (size_t)a.n_cigar + (size_t)((a.l_seq + 1) / 2) + (size_t)a.l_seq;
+    a.whole = a.l_seq >= 0 && need <= rec.size();
+    a.name = rec.data() + 32;
+    a.end = rec.data() + rec.size();
+    return a;
+}
+
+// What one alignment contributes: its calls at the sites, the span it covers (soft clips included when they are used) and its barcode.
+struct PileUp {
+    std::vector<Base> bases;
+    int64_t aln_start = 0, aln_end = 0;   // 1-based, inclusive
+    const uint8_t *bx = nullptr;          // the BX string inside the record (null: untagged, or the rule is off), bx_len bytes
+    size_t bx_len = 0;
+};
+
+// Reads a whole alignment of the target sequence; leaves its calls and span in `p` and says whether it goes on to a slot.  The
+// filters, in this order, each with its counter: flags (stats[4]), mapq (stats[2]), tlen (stats[3]), outside the window (none),
+// no call at any site (stats[7]); stats[0] counts what came in, stats[1] what lies in the window, bx_stats[0] the tagged that go on.
+bool pile_up(const LoadRequest &rq, const Alignment &a, PileUp &p, qa_sample_reads &S) {
+    static const char kNt16[] = "=ACMGRSVTWYHKDBN";
+    const qa_bam_opts_t &o = rq.o;
+    S.stats[0]++;
+    if (a.flag & (0x4 | 0x100 | 0x200 | 0x400 | 0x800)) { S.stats[4]++; return false; }
+    if (a.mapq < o.bqFilter) { S.stats[2]++; return false; }
+    if (std::abs((int64_t)a.tlen) > (int64_t)o.iSizeUpperLimit) { S.stats[3]++; return false; }
+    // A CIGAR of more than 65 535 operations (long reads) does not fit n_cigar_op: the record then carries the placeholder
+    // <l_seq>S<reference length>N and the real CIGAR as the auxiliary array CG:B,I (SAM spec 4.2.2).
+    const uint8_t *cig = a.name + a.l_read_name, *seq = cig + 4 * (size_t)a.n_cigar, *qual = seq + (a.l_seq + 1) / 2;
+    int64_t n_ops = a.n_cigar;
+    AuxFields aux;
+    aux.want_bx = rq.use_bx;
+    if (a.n_cigar == 2) {
+        uint32_t c0, c1;
+        memcpy(&c0, cig, 4);
+        memcpy(&c1, cig + 4, 4);
+        aux.want_cg = (c0 & 15) == 4 && (int64_t)(c0 >> 4) == a.l_seq && (c1 & 15) == 3;
+    }
+    if (aux.want_cg || aux.want_bx) {
+        walk_aux(qual + a.l_seq, a.end, aux);
+        if (aux.cg) { cig = aux.cg; n_ops = aux.cg_n; }   // (not found: the placeholder stands, no base is used)
+    }
+    // walk the CIGAR; a soft clip is laid out left of / right of the aligned part when its bases are to be used
+    int64_t rpos = (int64_t)a.pos0 + 1;   // 1-based reference coordinate of the next reference-consuming base
+    if (o.useSoftClippedBases) {   // the leading soft clip: the first operation that is not a hard clip (2H3S4M)
+        for (int64_t ci = 0; ci < n_ops; ci++) {
+            uint32_t c0;
+            memcpy(&c0, cig + 4 * (size_t)ci, 4);
+            if ((c0 & 15) == 5) continue;
+            if ((c0 & 15) == 4) rpos -= (c0 >> 4);
+            break;
+        }
+    }
+    p.aln_start = rpos;
+    p.bases.clear();
+    const int32_t nSNPs = rq.nSNPs, *L = rq.L;
+    int32_t q = 0;
+    // first site at or after the alignment start
+    int32_t t = (int32_t)(std::lower_bound(L, L + nSNPs, (int32_t)std::max<int64_t>(rpos, INT32_MIN)) - L);
+    for (int64_t ci = 0; ci < n_ops; ci++) {
+        uint32_t c;
+        memcpy(&c, cig + 4 * (size_t)ci, 4);
+        const int op = c & 15;
+        const int32_t len = (int32_t)(c >> 4);
+        const bool clip_used = op == 4 && o.useSoftClippedBases;
+        if (op == 0 || op == 7 || op == 8 || clip_used) {   // M, =, X (and S when used): query and reference advance
+            while (t < nSNPs && L[t] < rpos) t++;
+            while (t < nSNPs && L[t] < rpos + len) {
+                const int32_t qi = q + (int32_t)(L[t] - rpos);
+                if (qi < a.l_seq) {
+                    const char base = kNt16[(seq[qi >> 1] >> ((qi & 1) ? 0 : 4)) & 15];
+                    int32_t bqv = qual[qi] == 0xff ? 0 : qual[qi];
+                    if (bqv > a.mapq) bqv = a.mapq;
+                    if (bqv >= o.bqFilter) {
+                        if (base == rq.ref[t]) p.bases.push_back({t, -bqv});
+                        else if (base == rq.alt[t]) p.bases.push_back({t, bqv});
+                    }
+                }
+                t++;
+            }
+            q += len;
+            rpos += len;
+        } else if (op == 1 || op == 4) {   // I, S (unused): query only
+            q += len;
+        } else if (op == 2 || op == 3) {   // D, N: reference only
+            rpos += len;
+        }                                  // H, P: neither
+    }
+    p.aln_end = rpos - 1;
+    if (p.aln_end < rq.lo_bp || p.aln_start > rq.hi_bp) return false;   // outside the window
+    S.stats[1]++;
+    if (p.bases.empty()) { S.stats[7]++; return false; }
+    p.bx = rq.use_bx ? aux.bx : nullptr;
+    p.bx_len = aux.bx_len;
+    if (p.bx) S.bx_stats[0]++;
+    return true;
+}
+
+// The reads being built, one slot each: the slot's calls, with the BX rule its fragment (span, tag, alignments), with names the
+// query name of the alignment that opened it, and the names of the pairs whose second mate is still to come.  Everything indexed by
+// a slot number grows here and nowhere else.
+struct ReadSlots {
+    const bool merge_mates, use_bx, want_names;
+    std::vector<Read> reads;
+    std::vector<Frag> frags;            // (use_bx: one per slot)
+    std::vector<std::string> qnames;    // (want_names: one per slot)
+    std::unordered_map<std::string, size_t> by_name;
+
+    explicit ReadSlots(const LoadRequest &rq) : merge_mates(rq.o.merge_mates != 0), use_bx(rq.use_bx), want_names(rq.want_names) {}
+
+    // Reads a piled-up alignment (p.bases is taken); leaves it in a slot.  The mate rule: the second alignment of a pair's name joins
+    // the slot the first opened (stats[6]) and the name is forgotten; without the BX rule the slot's calls are resolved at once (all
+    // dropped: stats[7]), with it the fragment grows and the molecule resolves them (join_molecules).  Anything else opens a slot.
+    void add(const Alignment &a, PileUp &p, qa_sample_reads &S) {
+        if (merge_mates && (a.flag & 0x1)) {
+            std::string name = a.qname();
+            auto it = by_name.find(name);
+            if (it != by_name.end()) {
+                auto &dst = reads[it->second].b;
+                dst.insert(dst.end(), p.bases.begin(), p.bases.end());
+                if (use_bx) {
+                    Frag &f = frags[it->second];
+                    f.start = std::min(f.start, p.aln_start);
+                    f.end = std::max(f.end, p.aln_end);
+                    f.n_aln++;
+                } else {
+                    resolve_calls(dst);
+                    if (dst.empty()) { reads[it->second].alive = false; S.stats[7]++; }
+                }
+                by_name.erase(it);
+                S.stats[6]++;
+                return;
+            }
+            by_name.emplace(std::move(name), reads.size());
+        }
+        reads.emplace_back();
+        reads.back().b = std::move(p.bases);
+        if (want_names) qnames.push_back(a.qname());
+        if (use_bx) {
+            frags.emplace_back();
+            frags.back().start = p.aln_start;
+            frags.back().end = p.aln_end;
+            if (p.bx) frags.back().tag.assign(reinterpret_cast<const char *>(p.bx), p.bx_len);
+        }
+    }
+};
+
+// The BX rule (include/quilt_amd_io.h).  Reads every slot's fragment; leaves each molecule in the slot of the first of its fragments
+// (the others dead and empty), its calls resolved, and bx_stats[1..3].  Tagged fragments in order of (span start, first appearance)
+// chain into molecules, one open molecule per tag.
+void join_molecules(ReadSlots &slots, int32_t bxTagUpperLimit, qa_sample_reads &S) {
+    auto &reads = slots.reads;
+    auto &frags = slots.frags;
+    std::vector<uint32_t> tagged;
+    for (size_t r = 0; r < reads.size(); r++) if (!frags[r].tag.empty()) tagged.push_back((uint32_t)r);
+    std::stable_sort(tagged.begin(), tagged.end(), [&](uint32_t a, uint32_t b) { return frags[a].start < frags[b].start; });
+    struct Open { uint32_t slot; int64_t end; int32_t n_frag; };
+    std::unordered_map<std::string, Open> open;
+    auto close = [&](const Open &m) { if (m.n_frag > 1) S.bx_stats[1]++; };
+    for (uint32_t r : tagged) {
+        auto it = open.find(frags[r].tag);
+        if (it != open.end() && frags[r].start - it->second.end <= (int64_t)bxTagUpperLimit) {
+            Open &m = it->second;
+            const uint32_t keep = std::min(m.slot, r), gone = std::max(m.slot, r);
+            auto &dst = reads[keep].b, &src = reads[gone].b;
+            dst.insert(dst.end(), src.begin(), src.end());
+            std::vector<Base>().swap(src);
+            reads[gone].alive = false;
+            frags[keep].n_aln += frags[gone].n_aln;
+            m.slot = keep;
+            m.end = std::max(m.end, frags[r].end);
+            m.n_frag++;
+            S.bx_stats[2]++;
+            continue;
+        }
+        if (it != open.end()) {   // the gap is above the limit: the tag's molecule so far is closed
+            close(it->second);
+            S.bx_stats[3]++;
+            it->second = Open{r, frags[r].end, 1};
+        } else {
+            open.emplace(frags[r].tag, Open{r, frags[r].end, 1});
+        }
+    }
+    for (auto &kv : open) close(kv.second);
+    for (size_t r = 0; r < reads.size(); r++) {
+        if (!reads[r].alive || frags[r].n_aln < 2) continue;
+        resolve_calls(reads[r].b);
+        if (reads[r].b.empty()) { reads[r].alive = false; S.stats[7]++; }
+    }
+}
+
+// The coverage cap (quilt.R:54).  Reads the slots' calls; leaves the reads it removes dead (stats[5]).  Sites in ascending order; at
+// a site above the cap the covering reads with the smallest stream keys go, until the site is at the cap.
+void cap_coverage(const LoadRequest &rq, std::vector<Read> &reads, qa_sample_reads &S) {
+    const int32_t nSNPs = rq.nSNPs, cap = rq.o.downsampleToCov;
+    std::vector<int32_t> depth((size_t)nSNPs, 0);
+    for (auto &r : reads) for (auto &b : r.b) depth[b.u]++;
+    bool any = false;
+    for (int32_t t = 0; t < nSNPs; t++) any |= depth[t] > cap;
+    if (!any) return;
+    std::vector<std::vector<uint32_t>> cover((size_t)nSNPs);
+    for (size_t r = 0; r < reads.size(); r++)
+        for (auto &b : reads[r].b) if (depth[b.u] > cap) cover[b.u].push_back((uint32_t)r);
+    for (int32_t t = 0; t < nSNPs; t++) {
+        if (depth[t] <= cap) continue;
+        std::vector<std::pair<uint64_t, uint32_t>> cand;
+        for (uint32_t r : cover[t]) if (reads[r].alive) cand.push_back({stream_key(rq.o.seed, r), r});
+        std::sort(cand.begin(), cand.end());
+        for (size_t i = 0; i < cand.size() && depth[t] > cap; i++) {
+            Read &rd = reads[cand[i].second];
+            if (!rd.alive) continue;
+            rd.alive = false;
+            S.stats[5]++;
+            for (auto &b : rd.b) depth[b.u]--;
+        }
+    }
+}
+
+// Reads the slots that are alive; leaves the result's flat arrays -- the reads ordered by the grid of their central site (stable) --
+// and, when names are kept, name r of read r in that same order.
+void order_and_flatten(const LoadRequest &rq, const ReadSlots &slots, qa_sample_reads &S) {
+    const auto &reads = slots.reads;
+    const int32_t *grid = rq.grid;
+    std::vector<uint32_t> order;
+    std::vector<int32_t> cen(reads.size());
+    for (size_t r = 0; r < reads.size(); r++) {
+        if (!reads[r].alive) continue;
+        cen[r] = reads[r].b[(reads[r].b.size() - 1) / 2].u;
+        order.push_back((uint32_t)r);
+    }
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return grid[cen[a]] < grid[cen[b]]; });
+    S.read_ptr.push_back(0);
+    for (uint32_t r : order) {
+        for (auto &b : reads[r].b) { S.u.push_back(b.u); S.bq.push_back(b.bq); }
+        S.read_ptr.push_back((int32_t)S.u.size());
+        S.wif.push_back(grid[cen[r]]);
+        S.central.push_back(cen[r]);
+    }
+    if (!rq.want_names) return;
+    S.named = true;
+    S.names_off.push_back(0);
+    for (uint32_t r : order) {
+        const char *nm = slots.qnames[r].c_str();   // (a name ends at its first NUL, as the record's own field does)
+        S.names.insert(S.names.end(), nm, nm + strlen(nm) + 1);
+        S.names_off.push_back((int64_t)S.names.size());
+    }
+}
+
+}  // namespace
+
 extern "C" {
 
 void qa_bam_opts_default(qa_bam_opts_t *o) {
@@ -338,295 +688,40 @@ int qa_bam_load_sample_reads_named(const char *bam_path, const char *chr, int32_
                                    const char *alt, const int32_t *grid, const qa_bam_opts_t *opts, int32_t use_bx_tag,
                                    int32_t bxTagUpperLimit, int32_t keep_names, qa_sample_reads_t **out) {
     if (out) *out = nullptr;
-    const bool want_names = keep_names != 0;
-    if (bxTagUpperLimit < 0) {
-        qa::set_error("qa_bam_load_sample_reads: bxTagUpperLimit = %d is negative", (int)bxTagUpperLimit);
-        return QA_ERR_INVALID;
-    }
-    const bool use_bx = use_bx_tag != 0;
-    if (!bam_path || !chr || nSNPs < 1 || !L || !ref || !alt || !grid || !out) {
-        qa::set_error("qa_bam_load_sample_reads: missing argument");
-        return QA_ERR_INVALID;
-    }
-    for (int32_t t = 1; t < nSNPs; t++)
-        if (L[t] <= L[t - 1]) { qa::set_error("qa_bam_load_sample_reads: the site positions must ascend (L[%d] <= L[%d])", t, t - 1); return QA_ERR_INVALID; }
-    // every refusal says which file and what about it (qa_impute_bam_range reports it as "cannot load <file>: <this>")
-    auto refuse = [&](const char *what) {
-        qa::set_error("%s: %s", bam_path, what);
-        return (int)QA_ERR_INVALID;
-    };
-    qa_bam_opts_t o;
-    if (opts) o = *opts; else qa_bam_opts_default(&o);
-    {   // CRAM (cramlist + reference, quilt.R:106-108): not decoded here -- say so, with the way round it
-        FILE *fc = fopen(bam_path, "rb");
-        char m4[4] = {0, 0, 0, 0};
-        const bool cram = fc && fread(m4, 1, 4, fc) == 4 && memcmp(m4, "CRAM", 4) == 0;
-        if (fc) fclose(fc);
-        if (cram) {
-            qa::set_error("%s is a CRAM file: qa_bam_load_sample_reads reads BAM only.  Convert it first -- "
-                          "`samtools view -b -T <reference.fa> -o sample.bam sample.cram && samtools index sample.bam` -- "
-                          "(the reference reads CRAM through STITCH / htslib given `reference`; test-acceptance-cram.R makes its "
-                          "CRAMs with the inverse command)", bam_path);
-            return QA_ERR_UNSUPPORTED;
-        }
-    }
-    BgzfReader bz(bam_path);
-    if (bz.bad) return refuse("cannot be opened");
-    char magic[4];
-    int32_t l_text, n_ref;
-    if (!bz.read(magic, 4) || memcmp(magic, "BAM\1", 4) != 0 || !bz.read(&l_text, 4) || l_text < 0)
-        return refuse("not a BAM file (no BGZF block with the BAM magic at its start)");
-    std::string text((size_t)l_text, '\0');
-    if (l_text && !bz.read(&text[0], (size_t)l_text)) return refuse("the header text is cut short");
-    const bool sorted = text.find("SO:coordinate") != std::string::npos;
-    if (!bz.read(&n_ref, 4) || n_ref < 0) return refuse("the reference dictionary is cut short");
-    int32_t target = -1;
-    for (int32_t i = 0; i < n_ref; i++) {
-        int32_t l_name, l_ref;
-        if (!bz.read(&l_name, 4) || l_name < 1 || l_name > 65536) return refuse("the reference dictionary is damaged");
-        std::string name((size_t)l_name, '\0');
-        if (!bz.read(&name[0], (size_t)l_name) || !bz.read(&l_ref, 4)) return refuse("the reference dictionary is cut short");
-        if (strcmp(name.c_str(), chr) == 0) target = i;
-    }
-    if (target < 0) { qa::set_error("%s: no reference sequence named %s", bam_path, chr); return QA_ERR_INVALID; }
-    // A coordinate-sorted file with a BAI index next to it (<file>.bai or <file without .bam>.bai): start at the linear
-    // index's offset for the window's first 16 kb interval -- the first alignment overlapping it (SAM spec 5.1.3) --, tightened
-    // by the bin index's chunks (bai_start_offset), instead of scanning from the top of a whole-genome file.  Any problem with the index just means the sequential scan.
-    if (sorted) {
-        const uint64_t voff = bai_start_offset(bam_path, target, o.chrStart > 0 ? o.chrStart - 1 : 0,
-                                               o.chrEnd > 0 ? o.chrEnd : INT32_MAX);
-        if (voff != 0 && !bz.seek_virtual(voff)) return refuse("the index points outside the file");
-    }
+    LoadRequest rq{bam_path, chr, nSNPs, L, ref, alt, grid, {}, 0, 0, use_bx_tag != 0, bxTagUpperLimit, keep_names != 0};
+    if (opts) rq.o = *opts; else qa_bam_opts_default(&rq.o);
+    rq.lo_bp = rq.o.chrStart > 0 ? rq.o.chrStart : 1;
+    rq.hi_bp = rq.o.chrEnd > 0 ? rq.o.chrEnd : INT32_MAX;
+    if (const int st = check_request(rq, out != nullptr)) return st;
+    OpenBam in{BgzfReader(bam_path)};
+    if (const int st = open_at_window(rq, in)) return st;
 
-    auto *S = new qa_sample_reads;
-    std::vector<Read> reads;
-    std::vector<Frag> frags;   // (use_bx: one per entry of reads)
-    std::vector<std::string> qnames;   // (want_names: one per entry of reads -- the query name of the alignment that opened the slot)
-    std::unordered_map<std::string, size_t> by_name;
-    const int32_t lo_bp = o.chrStart > 0 ? o.chrStart : 1, hi_bp = o.chrEnd > 0 ? o.chrEnd : INT32_MAX;
-    std::vector<uint8_t> rec;
-    static const char kNt16[] = "=ACMGRSVTWYHKDBN";
+    std::unique_ptr<qa_sample_reads> S(new qa_sample_reads);
+    ReadSlots slots(rq);
+    std::vector<uint8_t> rec;   // (one buffer and one pile-up for every record)
+    PileUp p;
+    BgzfReader &bz = in.bz;
     for (;;) {
         int32_t block_size;
         if (!bz.read(&block_size, 4)) break;
         if (block_size < 32 || block_size > (1 << 28)) { bz.bad = true; break; }   // (no alignment record is a quarter of a GB: a damaged length)
         rec.resize((size_t)block_size);
         if (!bz.read(rec.data(), rec.size())) { bz.bad = true; break; }
-        int32_t refID, pos0, next_ref, next_pos, tlen, l_seq;
-        memcpy(&refID, &rec[0], 4);
-        memcpy(&pos0, &rec[4], 4);
-        const int l_read_name = rec[8], mapq = rec[9];
-        uint16_t n_cigar, flag;
-        memcpy(&n_cigar, &rec[12], 2);
-        memcpy(&flag, &rec[14], 2);
-        memcpy(&l_seq, &rec[16], 4);
-        memcpy(&next_ref, &rec[20], 4);
-        memcpy(&next_pos, &rec[24], 4);
-        memcpy(&tlen, &rec[28], 4);
-        (void)next_ref; (void)next_pos;
-        if (refID != target) {
-            if (sorted && refID > target) break;
+        const Alignment a = decode_alignment(rec);
+        if (a.refID != in.target) {
+            if (in.sorted && a.refID > in.target) break;
             continue;
         }
-        size_t need = 32 + (size_t)l_read_name + 4 * (size_t)n_cigar + (size_t)((l_seq + 1) / 2) + (size_t)l_seq;
-        if (l_seq < 0 || need > rec.size()) { bz.bad = true; break; }
-        if (sorted && pos0 + 1 > hi_bp) break;
-        S->stats[0]++;
-        if (flag & (0x4 | 0x100 | 0x200 | 0x400 | 0x800)) { S->stats[4]++; continue; }
-        if (mapq < o.bqFilter) { S->stats[2]++; continue; }
-        if (std::abs((int64_t)tlen) > (int64_t)o.iSizeUpperLimit) { S->stats[3]++; continue; }
-        const uint8_t *cig = &rec[32 + l_read_name], *seq = cig + 4 * (size_t)n_cigar, *qual = seq + (l_seq + 1) / 2;
-        // A CIGAR of more than 65 535 operations (long reads) does not fit n_cigar_op: the record then carries the placeholder
-        // <l_seq>S<reference length>N and the real CIGAR as the auxiliary array CG:B,I (SAM spec 4.2.2).
-        int64_t n_ops = n_cigar;
-        AuxFields aux;
-        aux.want_bx = use_bx;
-        if (n_cigar == 2) {
-            uint32_t c0, c1;
-            memcpy(&c0, cig, 4);
-            memcpy(&c1, cig + 4, 4);
-            aux.want_cg = (c0 & 15) == 4 && (int64_t)(c0 >> 4) == l_seq && (c1 & 15) == 3;
-        }
-        if (aux.want_cg || aux.want_bx) {
-            walk_aux(qual + l_seq, rec.data() + rec.size(), aux);
-            if (aux.cg) { cig = aux.cg; n_ops = aux.cg_n; }   // (not found: the placeholder stands, no base is used)
-        }
-        // walk the CIGAR; a soft clip is laid out left of / right of the aligned part when its bases are to be used
-        int64_t rpos = (int64_t)pos0 + 1;   // 1-based reference coordinate of the next reference-consuming base
-        if (o.useSoftClippedBases) {   // the leading soft clip: the first operation that is not a hard clip (2H3S4M)
-            for (int64_t ci = 0; ci < n_ops; ci++) {
-                uint32_t c0;
-                memcpy(&c0, cig + 4 * (size_t)ci, 4);
-                if ((c0 & 15) == 5) continue;
-                if ((c0 & 15) == 4) rpos -= (c0 >> 4);
-                break;
-            }
-        }
-        const int64_t aln_start = rpos;
-        int32_t q = 0;
-        std::vector<Base> bases;
-        // first site at or after the alignment start
-        int32_t t = (int32_t)(std::lower_bound(L, L + nSNPs, (int32_t)std::max<int64_t>(rpos, INT32_MIN)) - L);
-        for (int64_t ci = 0; ci < n_ops; ci++) {
-            uint32_t c;
-            memcpy(&c, cig + 4 * (size_t)ci, 4);
-            const int op = c & 15;
-            const int32_t len = (int32_t)(c >> 4);
-            const bool clip_used = op == 4 && o.useSoftClippedBases;
-            if (op == 0 || op == 7 || op == 8 || clip_used) {   // M, =, X (and S when used): query and reference advance
-                while (t < nSNPs && L[t] < rpos) t++;
-                while (t < nSNPs && L[t] < rpos + len) {
-                    const int32_t qi = q + (int32_t)(L[t] - rpos);
-                    if (qi < l_seq) {
-                        const char base = kNt16[(seq[qi >> 1] >> ((qi & 1) ? 0 : 4)) & 15];
-                        int32_t bqv = qual[qi] == 0xff ? 0 : qual[qi];
-                        if (bqv > mapq) bqv = mapq;
-                        if (bqv >= o.bqFilter) {
-                            if (base == ref[t]) bases.push_back({t, -bqv});
-                            else if (base == alt[t]) bases.push_back({t, bqv});
-                        }
-                    }
-                    t++;
-                }
-                q += len;
-                rpos += len;
-            } else if (op == 1 || op == 4) {   // I, S (unused): query only
-                q += len;
-            } else if (op == 2 || op == 3) {   // D, N: reference only
-                rpos += len;
-            }                                  // H, P: neither
-        }
-        if (rpos - 1 < lo_bp || aln_start > hi_bp) continue;   // outside the window
-        S->stats[1]++;
-        if (bases.empty()) { S->stats[7]++; continue; }
-        if (use_bx && aux.bx) S->bx_stats[0]++;
-        if (o.merge_mates && (flag & 0x1)) {
-            std::string name(reinterpret_cast<const char *>(&rec[32]), (size_t)std::max(0, l_read_name - 1));
-            auto it = by_name.find(name);
-            if (it != by_name.end()) {
-                auto &dst = reads[it->second].b;
-                dst.insert(dst.end(), bases.begin(), bases.end());
-                if (use_bx) {   // (resolved once the molecule is whole, below)
-                    Frag &f = frags[it->second];
-                    f.start = std::min(f.start, aln_start);
-                    f.end = std::max(f.end, rpos - 1);
-                    f.n_aln++;
-                } else {
-                    resolve_calls(dst);
-                    if (dst.empty()) { reads[it->second].alive = false; S->stats[7]++; }
-                }
-                by_name.erase(it);
-                S->stats[6]++;
-                continue;
-            }
-            by_name.emplace(std::move(name), reads.size());
-        }
-        reads.emplace_back();
-        reads.back().b = std::move(bases);
-        if (want_names) qnames.emplace_back(reinterpret_cast<const char *>(&rec[32]), (size_t)std::max(0, l_read_name - 1));
-        if (use_bx) {
-            frags.emplace_back();
-            frags.back().start = aln_start;
-            frags.back().end = rpos - 1;
-            if (aux.bx) frags.back().tag.assign(reinterpret_cast<const char *>(aux.bx), aux.bx_len);
-        }
+        if (!a.whole) { bz.bad = true; break; }
+        if (in.sorted && a.pos0 + 1 > rq.hi_bp) break;
+        if (pile_up(rq, a, p, *S)) slots.add(a, p, *S);
     }
-    if (bz.bad) { delete S; return refuse("damaged or cut short (a BGZF block or an alignment record does not decode)"); }
+    if (bz.bad) return refuse(rq, "damaged or cut short (a BGZF block or an alignment record does not decode)");
 
-    // the BX rule (include/quilt_amd_io.h): tagged fragments in order of (span start, first appearance) chain into molecules, one
-    // open molecule per tag; a molecule lives in the slot of the first of its fragments in `reads`, the others leave dead slots
-    if (use_bx) {
-        std::vector<uint32_t> tagged;
-        for (size_t r = 0; r < reads.size(); r++) if (!frags[r].tag.empty()) tagged.push_back((uint32_t)r);
-        std::stable_sort(tagged.begin(), tagged.end(), [&](uint32_t a, uint32_t b) { return frags[a].start < frags[b].start; });
-        struct Open { uint32_t slot; int64_t end; int32_t n_frag; };
-        std::unordered_map<std::string, Open> open;
-        auto close = [&](const Open &m) { if (m.n_frag > 1) S->bx_stats[1]++; };
-        for (uint32_t r : tagged) {
-            auto it = open.find(frags[r].tag);
-            if (it != open.end() && frags[r].start - it->second.end <= (int64_t)bxTagUpperLimit) {
-                Open &m = it->second;
-                const uint32_t keep = std::min(m.slot, r), gone = std::max(m.slot, r);
-                auto &dst = reads[keep].b, &src = reads[gone].b;
-                dst.insert(dst.end(), src.begin(), src.end());
-                std::vector<Base>().swap(src);
-                reads[gone].alive = false;
-                frags[keep].n_aln += frags[gone].n_aln;
-                m.slot = keep;
-                m.end = std::max(m.end, frags[r].end);
-                m.n_frag++;
-                S->bx_stats[2]++;
-                continue;
-            }
-            if (it != open.end()) {   // the gap is above the limit: the tag's molecule so far is closed
-                close(it->second);
-                S->bx_stats[3]++;
-                it->second = Open{r, frags[r].end, 1};
-            } else {
-                open.emplace(frags[r].tag, Open{r, frags[r].end, 1});
-            }
-        }
-        for (auto &kv : open) close(kv.second);
-        for (size_t r = 0; r < reads.size(); r++) {
-            if (!reads[r].alive || frags[r].n_aln < 2) continue;
-            resolve_calls(reads[r].b);
-            if (reads[r].b.empty()) { reads[r].alive = false; S->stats[7]++; }
-        }
-    }
-
-    // coverage cap (quilt.R:54): sites in ascending order; at a site above the cap the covering reads with the smallest
-    // stream keys go, until the site is at the cap
-    if (o.downsampleToCov > 0) {
-        std::vector<int32_t> depth((size_t)nSNPs, 0);
-        for (auto &r : reads) for (auto &b : r.b) depth[b.u]++;
-        bool any = false;
-        for (int32_t t = 0; t < nSNPs; t++) any |= depth[t] > o.downsampleToCov;
-        if (any) {
-            std::vector<std::vector<uint32_t>> cover((size_t)nSNPs);
-            for (size_t r = 0; r < reads.size(); r++)
-                for (auto &b : reads[r].b) if (depth[b.u] > o.downsampleToCov) cover[b.u].push_back((uint32_t)r);
-            for (int32_t t = 0; t < nSNPs; t++) {
-                if (depth[t] <= o.downsampleToCov) continue;
-                std::vector<std::pair<uint64_t, uint32_t>> cand;
-                for (uint32_t r : cover[t]) if (reads[r].alive) cand.push_back({stream_key(o.seed, r), r});
-                std::sort(cand.begin(), cand.end());
-                for (size_t i = 0; i < cand.size() && depth[t] > o.downsampleToCov; i++) {
-                    Read &rd = reads[cand[i].second];
-                    if (!rd.alive) continue;
-                    rd.alive = false;
-                    S->stats[5]++;
-                    for (auto &b : rd.b) depth[b.u]--;
-                }
-            }
-        }
-    }
-
-    // order by the grid of the central site (stable), flatten
-    std::vector<uint32_t> order;
-    std::vector<int32_t> cen(reads.size());
-    for (size_t r = 0; r < reads.size(); r++) {
-        if (!reads[r].alive) continue;
-        cen[r] = reads[r].b[(reads[r].b.size() - 1) / 2].u;
-        order.push_back((uint32_t)r);
-    }
-    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return grid[cen[a]] < grid[cen[b]]; });
-    S->read_ptr.push_back(0);
-    for (uint32_t r : order) {
-        for (auto &b : reads[r].b) { S->u.push_back(b.u); S->bq.push_back(b.bq); }
-        S->read_ptr.push_back((int32_t)S->u.size());
-        S->wif.push_back(grid[cen[r]]);
-        S->central.push_back(cen[r]);
-    }
-    if (want_names) {   // name r belongs to read r of the arrays above: the slots that survived, in their final order
-        S->named = true;
-        S->names_off.push_back(0);
-        for (uint32_t r : order) {
-            const char *nm = qnames[r].c_str();   // (a name ends at its first NUL, as the record's own field does)
-            S->names.insert(S->names.end(), nm, nm + strlen(nm) + 1);
-            S->names_off.push_back((int64_t)S->names.size());
-        }
-    }
-    *out = S;
+    if (rq.use_bx) join_molecules(slots, rq.bxTagUpperLimit, *S);
+    if (rq.o.downsampleToCov > 0) cap_coverage(rq, slots.reads, *S);
+    order_and_flatten(rq, slots, *S);
+    *out = S.release();
     return QA_OK;
 }
 

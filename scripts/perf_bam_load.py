@@ -7,7 +7,8 @@ load phase only.
 --alternate PARENT_LIB: no device.  The per-file time of qa_bam_load_sample_reads on untagged files of the headline shape (20 000
 reads per file), three ways ALTERNATED in one process: (a) a build of an earlier commit's loader (PARENT_LIB: any shared object
 that exports qa_bam_load_sample_reads, e.g. that commit's libquilt_amd.so), (b) this tree's loader with the BX rule off, (c) with
-it on (--use-bx-tag; what a QUILT run with default arguments now asks for).  Each round times every file once per way, one
+it on (--use-bx-tag; what a QUILT run with default arguments now asks for; a PARENT_LIB that has the rule is timed with it on as
+well).  Each round times every file once per way, one
 thread; the result (medians over the rounds, and the spread between rounds) goes to --out as JSON.
     python scripts/perf_bam_load.py --alternate /path/to/parent/libquilt_amd.so --use-bx-tag --out profiles/bx_loader.json
 
@@ -112,6 +113,8 @@ if args.alternate:
         return t, n
 
     ways = [("parent", parent, None), ("tag_off", here, 0)] + ([("tag_on", here, 1)] if args.use_bx_tag else [])
+    if args.use_bx_tag and hasattr(parent, "qa_bam_load_sample_reads_bx"):   # (a parent that has the rule: its own time with the tag on)
+        ways.insert(1, ("parent_tag_on", parent, 1))
     for _, L_, bx in ways:   # (warm-up: page cache, allocator)
         load(L_, files[0], bx)
     per_round = {w: [] for w, _, _ in ways}
@@ -132,7 +135,8 @@ if args.alternate:
                ms_per_file_median=med,
                spread_between_rounds={w: float((max(v) - min(v)) / np.median(v)) for w, v in per_round.items()},
                tag_off_over_parent=med["tag_off"] / med["parent"],
-               tag_on_over_parent=(med["tag_on"] / med["parent"]) if "tag_on" in med else None, cpus=os.cpu_count())
+               tag_on_over_parent=(med["tag_on"] / med["parent"]) if "tag_on" in med else None,
+               tag_on_over_parent_tag_on=(med["tag_on"] / med["parent_tag_on"]) if "parent_tag_on" in med else None, cpus=os.cpu_count())
     print(json.dumps(res))
     if args.out:
         with open(args.out, "w") as f:

@@ -85,6 +85,21 @@ int f_mspbwt(const qa_mspbwt_t *, int32_t n_chain, int32_t, const int32_t *, int
         for (int j = 0; j < Knew; j++) out[(size_t)a * Knew + j] = 1 + j;
     return QA_OK;
 }
+// the imputation step that fails part-way: from the moment one launch set's worth of samples has passed the consensus step -- the
+// last before a set is reported final and formatted -- every further sampler call fails, i.e. from the second launch set on
+std::atomic<long> n_consensus{0};
+long fail_after_consensus = 0;
+int f_consensus_counted(int32_t R, int32_t nG, const int32_t *labels, const double *p, int32_t nL, double thr, int32_t n_use, int32_t *out) {
+    const int st = qa_consensus_read_labels(R, nG, labels, p, nL, thr, n_use, out);
+    n_consensus++;
+    return st;
+}
+int f_gibbs_failing(void *h, const qa_gibbs_opts_t *o, int32_t n, const int32_t *which, const int32_t *read_off, const int32_t *a5, const int32_t *a6,
+                    const int32_t *a7, const int32_t *a8, const double *a9, const int32_t *a10, const double *a11, int32_t *H, int32_t *a13,
+                    double *a14, double *a15, double *a16, int32_t *uf, double *a18, const uint64_t *a19, const uint64_t *a20) {
+    if (n_consensus.load() >= fail_after_consensus) return QA_ERR_HIP;
+    return f_gibbs(h, o, n, which, read_off, a5, a6, a7, a8, a9, a10, a11, H, a13, a14, a15, a16, uf, a18, a19, a20);
+}
 void *f_alloc(size_t b) { return std::malloc(b ? b : 1); }
 int f_free(void *p) { std::free(p); return QA_OK; }
 
@@ -419,6 +434,24 @@ int main(int argc, char **argv) {
         qa_bam_range_result_t *res = nullptr;
         io.n_io_threads = 4;
         REQUIRE(qa_impute_bam_range_backend(&tab, handles, W, K, G, &P, &io, n, bad.data(), idx.data(), nullptr, &res) != QA_OK && res == nullptr);
+        // the imputation itself fails while files are still being loaded (the list six times over: loading outlasts the first launch
+        // set) and earlier sets are being formatted: its status comes back, nothing else, and every loader and formatter is joined
+        std::vector<const char *> many;
+        for (int rep = 0; rep < 6; rep++) many.insert(many.end(), argv + 2, argv + argc);
+        std::vector<int64_t> idx_many(many.size());
+        for (size_t i = 0; i < many.size(); i++) idx_many[i] = 100 + (int64_t)i;
+        qa_impute_backend_t failing = tab;
+        failing.gibbs_batch = f_gibbs_failing;
+        failing.consensus_read_labels = f_consensus_counted;
+        P.samples_per_launch_set = 2;
+        fail_after_consensus = P.samples_per_launch_set;
+        n_consensus = 0;
+        res = reinterpret_cast<qa_bam_range_result_t *>(0x10);
+        REQUIRE(qa_impute_bam_range_backend(&failing, handles, W, K, G, &P, &io, (int)many.size(), many.data(), idx_many.data(), nullptr, &res) == QA_ERR_HIP);
+        REQUIRE(res == nullptr);
+        REQUIRE(n_consensus.load() >= fail_after_consensus);   // (at least one launch set got as far as being reported)
+        std::printf("tsan harness: imputation failed beside %d files after %ld samples' consensus: status and joins as expected\n", (int)many.size(),
+                    n_consensus.load());
     }
     std::printf("tsan harness: ok (%ld chain calls, %ld full-panel chains)\n", n_gibbs.load(), n_full.load());
     return 0;

@@ -171,7 +171,9 @@ int qa_panel_set_dosage_precision(qa_panel_t *panel, int32_t bits);
  * tree sums, whose last bits differ from either order's).  Its purpose: on panels with many identical or exactly tied haplotypes the last bits of
  * those sums decide which of the tied haplotypes make a best-haplotype list ("ties"); with this mode the
  * device reproduces the CPU path's lists, c, alpha / beta and dosage bit for bit, which proves the order of the sums to be the
- * only difference between the two.  K <= 57 344.  0 (default): the production kernels. */
+ * only difference between the two.  Any K the device's memory holds: beyond what LDS holds a pass keeps its state in its
+ * device scratch (2 x 8 bytes per haplotype), so the K x nGrids outputs of qa_Rcpp_haploid_dosage_versus_refs exist in this
+ * mode for panels of any size.  0 (default): the production kernels. */
 int qa_panel_set_sum_order(qa_panel_t *panel, int32_t reference_order);
 
 /* The reference-order sums at batch throughput.  on = 1: while qa_panel_set_sum_order is at 1 or 2, every launch set of TWO OR
@@ -265,9 +267,12 @@ typedef struct {
  * Panel size: dosage, c and best_haps_stuff_list are available for ANY K (up to K = 57 344 a pass keeps its whole state on
  * one compute unit -- seven chunk rows of 8 192 haplotypes in registers and LDS; beyond that the chunk rows past the seventh
  * stream their state through HBM: K = 65 536 reads and writes one row of eight per grid, K = 131 072 nine of sixteen, the
- * same arithmetic).  The K x nGrids outputs -- alphaHat_t, betaHat_t, gamma_t, gammaSmall_t -- come from kernels that hold
- * the state on chip and are limited to K <= 57 344: QA_ERR_UNSUPPORTED beyond (qa_last_error says so).  The batched entry
- * points below (dosage + lists only) have no limit but the device's memory (QA_ERR_CAPACITY).
+ * same arithmetic).  The K x nGrids outputs -- alphaHat_t, betaHat_t, gamma_t, gammaSmall_t -- depend on the mode:
+ *   production mode (qa_panel_set_sum_order at 0): they come from kernels that hold the state on chip and are limited to
+ *     K <= 57 344: QA_ERR_UNSUPPORTED beyond (qa_last_error says so, and names the other mode);
+ *   validation mode (qa_panel_set_sum_order at 1 or 2): every output, the four matrices included, at any K.
+ * The batched entry points below (dosage + lists only) have no limit but the device's memory in either mode; a launch set
+ * of one pass that the device's memory does not hold is QA_ERR_CAPACITY.
  *   gl                      2 x nSNPs
  *   gammaSmall_cols_to_get  nGrids, -1 or the 0-based thinned column
  *   alphaHat_t              K x nGrids (NULL: not copied back).  Columns are normalised

@@ -41,6 +41,10 @@ double profile_clock_ms(hipEvent_t completed_event);
 struct HipError : std::runtime_error {
     using std::runtime_error::runtime_error;
 };
+// the device's memory does not hold what the call needs: QA_ERR_CAPACITY at the C boundary (guarded)
+struct CapacityError : std::runtime_error {
+    using std::runtime_error::runtime_error;
+};
 
 #define QA_HIP(expr)                                                                         \
     do {                                                                                     \
@@ -497,6 +501,9 @@ template <typename F>
 int guarded(F &&f) {
     try {
         return f();
+    } catch (const CapacityError &e) {
+        set_error("%s", e.what());
+        return QA_ERR_CAPACITY;
     } catch (const HipError &e) {
         set_error("%s", e.what());
         return QA_ERR_HIP;

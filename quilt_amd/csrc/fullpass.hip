@@ -860,7 +860,8 @@ constexpr KindInfo kKindInfo[qa::KIND_COUNT] = {
 // Register-resident geometry: NT threads (multiple of 64) x NCH chunks of 16 haplotypes per lane.  fp32 state:
 // NT <= 512 so that each wave may use 256 VGPRs.  The smallest NCH that covers K gives the most waves; tiny panels
 // still get >= 2 chunks per lane for ILP.  KIND_F64_RANK: 512 threads, chunk rows of 8192 haplotypes (fullpass64.hip).
-// KIND_F64_FULL: 256 threads, NCH = ceil(K / 4096) rounded up to a built variant.
+// KIND_F64_FULL: 256 threads, NCH = ceil(K / 4096) rounded up to a built variant.  KIND_F64_REF: the same up to the largest
+// built variant (so that nothing moves there), NCH = ceil(K / 4096) beyond.
 constexpr int kNchList32[] = {1, 2, 3, 4, 5, 6, 7, 8, 10, 12};
 constexpr int kNchList64[] = {1, 2, 4, 6, 8, 10, 12, 13, 14};
 Geometry pick_geometry(int K, PassKind kind = KIND_F32) {
@@ -873,6 +874,10 @@ Geometry pick_geometry(int K, PassKind kind = KIND_F32) {
     if (kind == KIND_F64_FULL || kind == KIND_F64_REF) {   // (the validation kernels write the generic kernels' layout)
         const int need = (K + 4095) / 4096;
         for (int nch : kNchList64) if (nch >= need) return {256, nch, kind};
+        // The list is the generic kernels' BUILT variants.  The validation kernels take the layout's NT and Kq at run time and keep
+        // a pass's state in HBM (PassParams::spill) once it exceeds LDS, so beyond the list they get the layout of exactly the
+        // chunk rows K needs: any K.
+        if (kind == KIND_F64_REF) return {256, need, kind};
         return {0, 0, kind};
     }
     auto fit = [&](int nch) -> int {
@@ -895,8 +900,8 @@ PanelDims dims_of(const qa_panel *pn) { return {pn->K, pn->G, pn->T, pn->n_speci
 
 // the plan of a launch set of passes that all carry `flag`: bytes per pass
 size_t plan_pass_bytes(const qa_panel *pn, const Geometry &geo, int32_t flag, const Thin &thin, int K_top, int top_cap = 64,
-                       bool gamma_col = false) {
-    return PassLayout(dims_of(pn), geo, qa::make_request(&flag, 1, thin, K_top, top_cap, gamma_col)).pass_bytes(qa::Arena::kCarveAlign);
+                       bool gamma_col = false, bool alpha_grid0 = false) {
+    return PassLayout(dims_of(pn), geo, qa::make_request(&flag, 1, thin, K_top, top_cap, gamma_col, alpha_grid0)).pass_bytes(qa::Arena::kCarveAlign);
 }
 
 // how many homogeneous passes fit, and make the arena big enough for them.  The fixed term pays for what a launch set carves
@@ -917,7 +922,17 @@ int plan_chunk(qa_panel *pn, size_t per_pass, int remaining, size_t extra_fixed 
         return std::max(prop.multiProcessorCount, 1);
     }();
     if (n < remaining && n > n_cu) n = n / n_cu * n_cu;
-    pn->require_scratch(fixed + (size_t)n * per_pass);
+    try {
+        pn->require_scratch(fixed + (size_t)n * per_pass);
+    } catch (const qa::HipError &e) {
+        // not even the smallest launch set (n = 1 when the budget holds no pass) could be allocated: the panel is too large for
+        // this device's memory, which is the only limit of the kinds that keep a pass's state in HBM
+        (void)hipGetLastError();
+        char b[768];
+        snprintf(b, sizeof b, "K = %d, nGrids = %d: a launch set of %ld pass(es) needs %zu bytes of device scratch: %s", pn->K, pn->G, n,
+                 fixed + (size_t)n * per_pass, e.what());
+        throw qa::CapacityError(b);
+    }
     pn->A().reset();
     return (int)n;
 }
@@ -1047,6 +1062,8 @@ struct BatchOut {
     double *gamma_col = nullptr;
     int gamma_grid = -1;
     const int32_t *gamma_rows = nullptr;
+    // single-pass entry, validation mode: alpha at the thinned grids only, and at grid 0 (PassRequest::alpha_grid0)
+    bool alpha_grid0 = false;
 };
 
 // ---- run_passes, stage by stage.  What the stages of one call share:
@@ -1102,6 +1119,7 @@ std::vector<int32_t> plan_alpha_slots(const PassRun &r) {
         } else {
             int n = 0;
             for (int g = 0; g < G; g++) if (r.thin_col_h[g] >= 0) sl[g] = n++;
+            if (r.out.alpha_grid0 && sl[0] < 0) sl[0] = n;   // (the thinned grids keep their slots)
         }
     }
     return slot;
@@ -1458,7 +1476,7 @@ int run_passes(qa_panel *pn, int P, const double *gl, const int32_t *h_flags, co
     const Thin thin = qa::count_thin(thin_col_h, G);
     const bool any_top = thin.n_thin > 0 && K_top > 0;
     PassRun r{pn, S, st, P, h_flags, thin_col_h, out, geo,
-              PassLayout(dims_of(pn), geo, qa::make_request(h_flags, P, thin, K_top, out.top_cap, out.gamma_col != nullptr)),
+              PassLayout(dims_of(pn), geo, qa::make_request(h_flags, P, thin, K_top, out.top_cap, out.gamma_col != nullptr, out.alpha_grid0)),
               thin.n_thin, any_top,
               /* fused */ any_top && kind == KIND_F64_RANK && out.truncate_lists && out.top_cap <= 64,
               out.top_cap, PassParams{}};
@@ -1625,17 +1643,22 @@ int qa_Rcpp_haploid_dosage_versus_refs(
         out.gamma_t = o->return_gamma_t ? gamma_t : nullptr;
         out.gammaSmall_t = o->return_gammaSmall_t ? gammaSmall_t : nullptr;
         out.gamma_small_unscaled = !o->return_gamma_t;
+        // the reference writes alphaHat_t column 0 in its "only thinned outputs" form too (:2347-2354); validation mode, which
+        // yields every output of the call, keeps that column when grid 0 is not among the thinned grids
+        out.alpha_grid0 = panel->sum_order_ref && alphaHat_t && only_thin && thin[0] < 0;
         std::vector<std::vector<std::pair<int32_t, double>>> lists;
         QA_HIP(hipSetDevice(panel->device));
         const Thin thin_dims = qa::count_thin(thin.data(), G);
         const bool want_lists = o->get_best_haps_from_thinned_sites != 0;
         const int K_top = want_lists ? o->K_top_matches : 0;
         // one pass of `kind` with flags `flags`, thinned grids `th` and K_top `kt`, planned with the un-permute staging
-        // (K x nGrids doubles) in the fixed term
+        // (K x nGrids doubles) in the fixed term, and with room for the non-truncating top-K retry at full length (every
+        // haplotype of a label without reads ties: n_thin lists of K entries, beyond the fixed term's 2 MiB on large panels)
         auto plan = [&](PassKind kind, int32_t flags, const Thin &th, int kt) {
             const Geometry geo1 = pick_geometry(panel->K, kind);
             if (geo1.NT == 0) throw std::runtime_error("K exceeds the on-chip capacity of the full-pass kernels");
-            plan_chunk(panel, plan_pass_bytes(panel, geo1, flags, th, kt), 1, (size_t)panel->K * G * 8);
+            const size_t retry = kt > 0 ? (size_t)th.n_thin * panel->K * 12 + 2 * qa::Arena::kCarveAlign : 0;
+            plan_chunk(panel, plan_pass_bytes(panel, geo1, flags, th, kt, 64, false, out.alpha_grid0), 1, (size_t)panel->K * G * 8 + retry);
         };
         // fp64 dosage: the tuned kernels yield dosage and c; a call that also wants alpha / beta / gamma matrices takes the
         // generic fp64 kernels
@@ -1647,7 +1670,8 @@ int qa_Rcpp_haploid_dosage_versus_refs(
             // K x nGrids outputs (alphaHat_t / betaHat_t / gamma_t / gammaSmall_t) come from kernels that keep the whole state
             // on chip; the dosage and the best-haplotype lists (what the driver path asks for) have no such limit
             qa::set_error("K = %d: alphaHat_t / betaHat_t / gamma_t / gammaSmall_t outputs are limited to K <= 57 344 haplotypes (state on "
-                          "chip); dosage, c and best_haps_stuff_list are available for any K", panel->K);
+                          "chip); dosage, c and best_haps_stuff_list are available for any K; validation mode "
+                          "(qa_panel_set_sum_order(panel, 1)) serves these outputs at any K", panel->K);
             return QA_ERR_UNSUPPORTED;
         }
         int st;

@@ -48,11 +48,15 @@ struct PassRequest {
     bool stores_all = false;   // a pass with dosage / alpha / gamma / beta output: alpha at every grid, else at the thinned grids
     bool gamma = false, beta = false, gamma_col = false;
     bool lists = false;        // best-haplotype lists (thinned columns and K_top > 0)
+    bool alpha_grid0 = false;  // a pass that stores alpha at the thinned grids only keeps grid 0's column too, in one more slot
+                               // (the reference writes alphaHat_t column 0 whatever is asked, reference-single.cpp:2347-2354: the
+                               // single-pass entry in validation mode, when grid 0 is not a thinned grid)
     Thin thin;
     int top_cap = 64;          // entries per list
 };
 // flags as in PassParams::flags
-inline PassRequest make_request(const int32_t *flags, int P, const Thin &thin, int K_top, int top_cap, bool gamma_col) {
+inline PassRequest make_request(const int32_t *flags, int P, const Thin &thin, int K_top, int top_cap, bool gamma_col,
+                                bool alpha_grid0 = false) {
     PassRequest r;
     for (int p = 0; p < P; p++) {
         r.stores_all |= (flags[p] & 15) != 0;
@@ -63,6 +67,7 @@ inline PassRequest make_request(const int32_t *flags, int P, const Thin &thin, i
     r.thin = thin;
     r.top_cap = top_cap;
     r.gamma_col = gamma_col;
+    r.alpha_grid0 = alpha_grid0 && !r.stores_all;
     return r;
 }
 
@@ -72,7 +77,8 @@ inline PassRequest make_request(const int32_t *flags, int P, const Thin &thin, i
 //     set: paid by plan_chunk's fixed term;
 //   * the single-pass entry's un-permute staging (Scratch::unperm, K x G doubles): that entry adds it to the fixed term itself;
 //   * TOP_IDX / TOP_VAL carved a second time with a larger top_cap by the non-truncating top-K retry (single passes and
-//     qa_fullpass_batch only: pathological ties): plan_chunk's fixed term.
+//     qa_fullpass_batch only: pathological ties): plan_chunk's fixed term; the single-pass entry and the launch-set hook add
+//     room for lists of all K haplotypes (a label without reads) to it themselves.
 struct PassLayout {
     enum Buf { GL, THIN_COL, FLAGS, ALPHA_SLOT, EMAT, ESCALE0, EMIN, EMIN_B1, ESP, GSP, ALPHA, C, FW_ADD, FW_XS, MG, DOSAGE, GAMMA,
                BETA, BETA_THIN, GAMMA_COL, TOP_CNT, SPILL, TOP_IDX, TOP_VAL, N_BUF };
@@ -89,7 +95,7 @@ struct PassLayout {
         Kq = (size_t)geo.NT * geo.NCH * 16;
         // alpha checkpoints: all grids for dosage / gamma / beta passes (the fp64 dosage kernels: every second one, k_bwd64d
         // re-forms the odd grids'), the thinned grids otherwise
-        alpha_cols = !r.stores_all ? (size_t)std::max(r.thin.n_grids, 1) : kind == KIND_F64_DOS ? (G + 1) / 2 : G;
+        alpha_cols = !r.stores_all ? (size_t)std::max(r.thin.n_grids, 1) + (r.alpha_grid0 ? 1 : 0) : kind == KIND_F64_DOS ? (G + 1) / 2 : G;
         alpha_col_elems = kind == KIND_F64_DOS ? fb64_alpha_col_elems(d.K) : Kq;
         esp_stride = (size_t)d.n_special + (lazy_kind(kind) ? 16 * (size_t)d.n_sp_grids : 0) + 16;
         spill_stride = kind == KIND_F64_REF ? fb_ref_state_doubles((int)Kq)   // the validation kernels' state (when not in LDS)

@@ -24,11 +24,23 @@ ap.add_argument("--sum-order-batched", action="store_true",
                 help="reference-order sums (qa_panel_set_sum_order 1): alternate the validation kernels and the batched ones "
                      "(qa_panel_set_sum_order_batched) in this process on the same inputs, for launch sets of --sets passes with "
                      "dosage and with ranking flags; passes/s of each, written to --json")
-ap.add_argument("--sets", type=int, nargs="+", default=[256, 1024])
-ap.add_argument("--json", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
-                                               "sum_order_batched.json"))
+ap.add_argument("--validation-large-k", action="store_true",
+                help="validation mode beyond 57 344 haplotypes: K = 64 976 x 500 grids (the HRC-sized shape; overrides --K / --T), "
+                     "launch sets of --sets ranking passes and dosage passes in production mode (fp64 dosage), validation mode "
+                     "(qa_panel_set_sum_order 1) and validation mode with the batched form, in this process on the same inputs; "
+                     "passes/s of each, written to --json")
+ap.add_argument("--sets", type=int, nargs="+", default=None, help="default: 256 1024 (--validation-large-k: 256)")
+ap.add_argument("--json", default=None, help="default: profiles/sum_order_batched.json (--validation-large-k: "
+                                             "profiles/validation_large_k.json)")
 a = ap.parse_args()
-if a.sum_order_batched:
+PROFILES = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles")
+if a.validation_large_k:
+    a.K, a.T = 64976, 16000
+    a.sets = a.sets or [256]
+    a.json = a.json or os.path.join(PROFILES, "validation_large_k.json")
+a.sets = a.sets or [256, 1024]
+a.json = a.json or os.path.join(PROFILES, "sum_order_batched.json")
+if a.sum_order_batched or a.validation_large_k:
     a.P = max(a.sets)
 
 t0 = time.time()
@@ -100,9 +112,60 @@ def sum_order_batched():
         f.write("\n")
 
 
+def validation_large_k():
+    """Production mode, validation mode and validation mode's batched form in turn, same process, same inputs; the two validation
+    forms' outputs compared.  A record, not a bar."""
+    import json
+    dev.set_dosage_precision(64)
+    lib().qa_panel_set_sum_order_batched.restype = C.c_int
+    forms = (("production", 0, 0), ("validation", 1, 0), ("validation_batched", 1, 1))
+    rows = []
+    for n in a.sets:
+        for what, flag in (("ranking", 0), ("dosage", 1)):
+            wd = np.full(n, flag, dtype=np.int32)
+            row = dict(K=panel.K, nGrids=G, passes=n, flags=what)
+            outs = {}
+            for r in range(a.reps):
+                for form, order, on in forms:
+                    dev.set_sum_order(order)
+                    check(lib().qa_panel_set_sum_order_batched(dev.handle, C.c_int32(on)))
+                    t0 = time.time()
+                    check(lib().qa_fullpass_batch(dev.handle, C.c_int32(n), ptr(gl), ptr(wd), ptr(cols), C.c_int32(a.ktop),
+                                                  ptr(dosage), ptr(bptr), ptr(bidx), ptr(bval), C.c_int64(cap)))
+                    wall = time.time() - t0
+                    tm = last_fullpass_timing_ms()
+                    outs[form] = (dosage[:n].copy() if flag else None, bptr[:n * n_thin + 1].copy(), bidx[:bptr[n * n_thin]].copy(),
+                                  bval[:bptr[n * n_thin]].copy())
+                    best = row.get(form + "_wall_s")
+                    if best is None or wall < best:
+                        row[form + "_wall_s"] = wall
+                        row[form + "_passes_per_s"] = n / wall
+                        row[form + "_last_launch_set_fwd_bwd_ms"] = [tm["forward"], tm["backward"]]
+                    print(f"P={n} {what} rep {r} {form}: wall {wall:.3f}s = {n / wall:.1f} passes/s  (last launch set: forward "
+                          f"{tm['forward']:.1f} ms, backward {tm['backward']:.1f} ms)", flush=True)
+            row["outputs_identical"] = all(x is None or np.array_equal(x, y)
+                                           for x, y in zip(outs["validation"], outs["validation_batched"]))
+            row["production_over_validation"] = row["validation_wall_s"] / row["production_wall_s"]
+            if flag:
+                row["production_dosage_max_abs_diff"] = float(np.abs(outs["production"][0] - outs["validation"][0]).max())
+            rows.append(row)
+            print(row, flush=True)
+    check(lib().qa_panel_set_sum_order_batched(dev.handle, C.c_int32(0)))
+    os.makedirs(os.path.dirname(a.json), exist_ok=True)
+    with open(a.json, "w") as f:
+        json.dump(dict(what="full-panel passes beyond 57 344 haplotypes: production mode (fp64 dosage and ranking kernels), "
+                            "validation mode (fullpass_ref.hip) and its batched form (fullpass_ord.hip), qa_fullpass_batch wall time, "
+                            "best of reps, same process and inputs; outputs_identical: the two validation forms",
+                       reps=a.reps, rows=rows), f, indent=1)
+        f.write("\n")
+
+
 lib().qa_profile_name.restype = C.c_char_p
 if a.sum_order_batched:
     sum_order_batched()
+    sys.exit(0)
+if a.validation_large_k:
+    validation_large_k()
     sys.exit(0)
 NAMES = [lib().qa_profile_name(C.c_int32(k)).decode() for k in range(lib().qa_profile_count())]
 for r in range(a.reps):

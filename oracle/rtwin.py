@@ -226,6 +226,20 @@ def make_eMatRead_t(panel, sample, which_haps_to_use_1based, maxDifferenceBetwee
         s, e = 32 * g, min(32 * (g + 1), panel.nSNPs)
         bits[:, s:e] = expand_words(panel.rhb_t[which0, g], 32)[:, : e - s]
     eh = np.where(bits == 1, 1 - panel.ref_error, panel.ref_error)
+    return _eMatRead_t_of_allele_probabilities(eh, sample, maxDifferenceBetweenReads, Jmax, rescale)
+
+
+def make_eMatRead_t_dense(haps, sample, maxDifferenceBetweenReads=1e10, Jmax=1000, rescale=False):
+    """The same call with the allele probabilities given directly: calculate_eMatRead_t_vs_haplotypes (functions.R:2975-3020),
+    ``haps`` = K per-SNP dosages."""
+    eh = np.stack([np.asarray(h, dtype=np.float64) for h in haps], axis=0)
+    return _eMatRead_t_of_allele_probabilities(eh, sample, maxDifferenceBetweenReads, Jmax, rescale)
+
+
+def _eMatRead_t_of_allele_probabilities(eh, sample, maxDifferenceBetweenReads, Jmax, rescale):
+    """rcpp_make_eMatRead_t as the R twin calls it.  pR / pA are those of the last base that had a quality: they survive bases
+    with bq == 0, the end of a read, and the bases a read clipped at Jmax never visits."""
+    Ks, R = eh.shape[0], sample.nReads
     out = np.ones((Ks, R))
     probs = bq_to_probs(sample.bq)
     pR_prev, pA_prev = 1.0, 1.0
@@ -239,7 +253,7 @@ def make_eMatRead_t(panel, sample, which_haps_to_use_1based, maxDifferenceBetwee
             col = col * (eh[:, sample.u[j]] * pA_prev + (1 - eh[:, sample.u[j]]) * pR_prev)
         if rescale:
             x = col.max()
-            with np.errstate(divide="ignore"):
+            with np.errstate(divide="ignore", over="ignore"):
                 d1 = 1 / x if x != 0 else np.inf
             if not np.isfinite(x) or x == 0 or not np.isfinite(d1):
                 col[:] = 1.0

@@ -237,3 +237,30 @@ def calculate_eMatRead_t_vs_haplotypes_batch(panel: DevicePanel, samples: Sequen
                  ptr(read_ptr), ptr(u), ptr(bq), C.c_double(maxDifferenceBetweenReads), C.c_int32(Jmax),
                  C.c_int32(int(rescale_eMatRead_t)), ptr(out)))
     return [np.asfortranarray(out[read_off[c]:read_off[c + 1]].T) for c in range(Cn)]
+
+
+def calculate_eMatRead_t_rare_common_batch(panel: DevicePanel, rare_common, samples_all: Sequence, chain_sample: Sequence[int],
+                                           hap_common: np.ndarray, maxDifferenceBetweenReads: float,
+                                           rescale_eMatRead_t: bool = False, Jmax: int = 1000):
+    """``qa_rcpp_make_eMatRead_t_rare_common``: the read likelihoods of get_initial_read_labels (QUILT/R/rare_common.R:61-107) for
+    chains that name their sample.  ``samples_all[i]``: sample i's all-SNP reads; ``chain_sample[c]``: the sample of chain c;
+    ``hap_common``: [chain, haplotype, common SNP] dosages (0.5 at the rare SNPs is supplied by the kernel).  Returns one
+    K x nReads matrix per chain."""
+    lib().qa_rcpp_make_eMatRead_t_rare_common.restype = C.c_int
+    cs = np.ascontiguousarray(chain_sample, dtype=np.int32)
+    e = np.ascontiguousarray(hap_common, dtype=np.float64)
+    Cn, NS, K = len(cs), len(samples_all), e.shape[1]
+    assert e.shape == (Cn, K, panel.panel.nSNPs)
+    read_off = np.zeros(NS + 1, dtype=np.int32)
+    for i, s in enumerate(samples_all):
+        read_off[i + 1] = read_off[i] + s.nReads
+    read_ptr = np.concatenate([np.asarray(s.read_ptr, dtype=np.int32) for s in samples_all])
+    u = np.concatenate([np.asarray(s.u, dtype=np.int32) for s in samples_all])
+    bq = np.concatenate([np.asarray(s.bq, dtype=np.int32) for s in samples_all])
+    n_out = np.r_[0, np.cumsum([samples_all[i].nReads if 0 <= i < NS else 0 for i in cs])]
+    out = np.zeros((int(n_out[-1]), K))
+    with span("device:read_confidence"):
+        check(lib().qa_rcpp_make_eMatRead_t_rare_common(
+            panel.handle, rare_common.handle, C.c_int32(Cn), C.c_int32(NS), ptr(cs), C.c_int32(K), ptr(e), ptr(read_off), ptr(read_ptr),
+            ptr(u), ptr(bq), C.c_double(maxDifferenceBetweenReads), C.c_int32(Jmax), C.c_int32(int(rescale_eMatRead_t)), ptr(out)))
+    return [np.asfortranarray(out[n_out[c]:n_out[c + 1]].T) for c in range(Cn)]

@@ -20,6 +20,9 @@ from a counter-based stream keyed by (seed, sample, chain) -- see :func:`chain_r
 """
 from __future__ import annotations
 
+import time
+from collections import namedtuple
+from contextlib import contextmanager
 from dataclasses import dataclass, field
 from typing import List, Optional, Sequence
 
@@ -635,6 +638,15 @@ class PhasingTail:
                 fut.set_exception(exc)
 
 
+def _draw_seed(ch: ChainState) -> int:
+    """The chain's next draw as the seed of a counter-based stream (quilt_amd/rng.py) that stands in for Rcpp::runif."""
+    return int(ch.rng.integers(0, 2 ** 63))
+
+
+# what Driver._call_fullpass makes of the backend's tuple: entries the call did not return are None
+FullpassOut = namedtuple("FullpassOut", "dosage top count which_next status gamma")
+
+
 class Driver:
     """Runs ``get_and_impute_one_sample`` (quilt.R:688-996, functions.R:420-1259) for batches of samples, all chains of
     a batch in lock-step.
@@ -670,17 +682,59 @@ class Driver:
         self.n_device_selections = 0     # chains whose next small panel was chosen by csrc/select.hip
         self._zero_hap = None
         self.gibbs_gate = None           # workers.PairGate shared by the host threads of a device, or None
+        self._gate_left = False          # this thread has left the gate (workers resets it per stream)
         self.phasing_tail = None         # PhasingTail shared by the host threads of a device, or None
         self.on_first_launch = None      # called once, right before this driver's next Gibbs call (workers: staggered start)
         self._round_dosages = None
         self._round_dosage_chains = []
 
-    # -- one [Gibbs -> full pass -> select] round over a set of chains (main and / or phasing chains, same i_it)
-    def _round(self, chains: List[ChainState], i_it: int):
-        import time
-        P = self.params
-        K, G, T = self.panel.K, self.panel.nGrids, self.panel.nSNPs
+    @contextmanager
+    def _timed(self, key: str, name: Optional[str] = None):
+        """Books the block's wall time to ``timing[key]`` and, with ``name``, records it as a span of the host trace."""
         t0 = time.perf_counter()
+        try:
+            yield
+        finally:
+            t1 = time.perf_counter()
+            self.timing[key] += t1 - t0
+            if name is not None:
+                trace.add(name, t0, t1)
+
+    # -- one [Gibbs -> full pass -> select] round over a set of chains (main and / or phasing chains, same i_it)
+    def _round(self, chains: List[ChainState], i_it: int) -> bool:
+        """The stages are those of csrc/impute.cpp's ``round`` (DESIGN section 5 lists the two side by side).  Returns whether
+        the round's dosages count (``_round_dosages``: run_stream accumulates from them)."""
+        P = self.params
+        return_dosage = i_it > P.n_burn_in_seek_its
+        with self._timed("host", "round:prepare"):
+            starts, seed_reads, first_reads, seed_shards, any_first = self._draw(chains, i_it)
+        with self._timed("gibbs", "round:gibbs_call"):
+            # use_mspbwt: the haplotype search wants the call's rounded, packed haploid dosages (formed on the device); the
+            # dosages themselves only on the rounds that accumulate them (the last round's also feed the read-confidence step)
+            extra = {"return_hap_words": True, "return_hapProbs": return_dosage} if P.use_mspbwt else {}
+            results = self._gibbs_with_retry(chains, [ch.sample for ch in chains], starts, seed_reads, first_reads, seed_shards,
+                                             gibbs_initialize_iteratively=any_first, **extra)
+        if P.use_mspbwt:
+            with self._timed("fullpass"):
+                self._adopt_labels(chains, results)
+                self._keep_round_haps(chains, self._gibbs_dosages(chains, results) if return_dosage else None)
+                self._select_by_mspbwt(chains, results, i_it)
+        else:
+            self._fullpass_select(chains, results, i_it, return_dosage)
+        return return_dosage
+
+    def wants_new_haps(self, ch: ChainState, i_it: int) -> bool:
+        """Whether the chain's round ends with a new small panel.  The reference asks for the best haplotypes on every call
+        (functions.R:738-743), but the selection made from them is read again only by a later round of the same chain or -- the
+        last chain's final selection -- by the phasing rounds (which_haps_to_use carried over): skip the lists nobody reads.
+        (with impute_rare_common every chain's final selection feeds its all-SNP Gibbs call)"""
+        P = self.params
+        return i_it < P.n_seek_its or P.impute_rare_common or (not ch.phasing and ch.i_chain == P.nGibbsSamples)
+
+    def _draw(self, chains: List[ChainState], i_it: int):
+        """What each chain takes from its stream before the Gibbs call -- in a batch's first round the small panel and one label
+        per read, then the call's seeds: (starts, seed_reads, first_reads, seed_shards, any chain in its first round)."""
+        P, K = self.params, self.panel.K
         any_first = False
         starts, seed_reads, first_reads, seed_shards = [], [], [], []
         for ch in chains:
@@ -689,8 +743,7 @@ class Driver:
                 raise ValueError("a sample without reads cannot be imputed (no read intersects a SNP of the region)")
             first = (i_it == 1) and not ch.phasing
             any_first |= first
-            if first:
-                # functions.R:579-585
+            if first:   # functions.R:579-585
                 ch.which_haps_to_use = np.sort(ch.rng.choice(K, size=P.Ksubset, replace=False) + 1).astype(np.int32)
                 if P.method == "nipt":   # functions.R:586
                     ff = ch.sample.ff
@@ -700,97 +753,144 @@ class Driver:
             else:
                 H0 = ch.read_labels
             starts.append(H0)
-            # seeds of the counter-based streams that stand in for Rcpp::runif (quilt_amd/rng.py)
-            seed_reads.append(int(ch.rng.integers(0, 2 ** 63)))
+            seed_reads.append(_draw_seed(ch))
             fr = int(ch.rng.integers(0, R))
             # only first-round chains initialise iteratively (functions.R:2369); in a launch that also carries
             # later-round (phasing) chains a negative first_read marks those (include/quilt_amd.h)
             first_reads.append(fr if first else -1)
-            seed_shards.append(int(ch.rng.integers(0, 2 ** 63)))
+            seed_shards.append(_draw_seed(ch))
         if not any_first:
             first_reads = [0] * len(chains)   # unused without gibbs_initialize_iteratively
-        t1 = time.perf_counter()
-        self.timing["host"] += t1 - t0
-        trace.add("round:prepare", t0, t1)
-        # ---- small-panel Gibbs (impute_one_sample, functions.R:2313-2774), with the underflow retry
-        # use_mspbwt: the haplotype search wants the call's rounded, packed haploid dosages (formed on the device); the
-        # dosages themselves only on the rounds that accumulate them (the last round's also feed the read-confidence step)
-        extra = {"return_hap_words": True, "return_hapProbs": i_it > P.n_burn_in_seek_its} if P.use_mspbwt else {}
-        results = self._gibbs_with_retry(chains, [ch.sample for ch in chains], starts, seed_reads, first_reads, seed_shards,
-                                         gibbs_initialize_iteratively=any_first, **extra)
-        t2 = time.perf_counter()
-        self.timing["gibbs"] += t2 - t1
-        trace.add("round:gibbs_call", t1, t2)
-        # ---- full-panel pass per read label (impute_using_everything, functions.R:1922-2157)
-        return_dosage = i_it > P.n_burn_in_seek_its
+        return starts, seed_reads, first_reads, seed_shards, any_first
+
+    @staticmethod
+    def _adopt_labels(chains: List[ChainState], results):
         for ch, res in zip(chains, results):
             ch.read_labels = res["double_list_of_ending_read_labels"][0][0].astype(np.int32)
-        if P.use_mspbwt:
-            self._round_mspbwt(chains, results, i_it, return_dosage)
-            self.timing["fullpass"] += time.perf_counter() - t2
-            return return_dosage
-        uniq, sample_list = {}, []
-        for ch in chains:
-            if id(ch.sample) not in uniq:
-                uniq[id(ch.sample)] = len(sample_list)
-                sample_list.append(ch.sample)
-        t3 = time.perf_counter()
-        self.timing["host"] += t3 - t2
-        trace.add("round:labels", t2, t3)
-        # The reference asks for the best haplotypes on every call (functions.R:738-743), but the selection made from
-        # them is read again only by a later round of the same chain or -- the last chain's final selection -- by the
-        # phasing rounds (which_haps_to_use carried over): skip the lists nobody reads.
-        # (with impute_rare_common every chain's final selection feeds its all-SNP Gibbs call)
-        want_top = [i_it < P.n_seek_its or P.impute_rare_common or (not ch.phasing and ch.i_chain == P.nGibbsSamples)
-                    for ch in chains]
-        # everything_select_good_haps: one selection stream per chain and round; its draws are keyed (quilt_amd/rng.py), so
-        # the device (csrc/select.hip, behind the full-panel call) and the host make the same choice
-        seed_sel = [int(ch.rng.integers(0, 2 ** 63)) for ch in chains]
-        # hla_run: the last seek iteration's passes also return gammaMT_t / gammaMU_t at the grid (functions.R:713-724)
-        hla_it = P.hla_grid is not None and i_it == P.n_seek_its
-        on_device = bool(getattr(self.backend, "select_on_device", False)) and (any(want_top) or hla_it)
-        select = None
-        if on_device:
-            select = dict(Ksubset=P.Ksubset, Knew=P.Knew, which=[ch.which_haps_to_use for ch in chains], seeds=seed_sel)
-        kw = {"select": select} if on_device else {}
-        if hla_it:
-            kw["gamma_grid"] = int(P.hla_grid)
-        out = self.backend.fullpass_reads_batch(
-            sample_list, [uniq[id(ch.sample)] for ch in chains], [ch.read_labels for ch in chains],
-            [return_dosage] * len(chains), want_top, self.cols, P.K_top_matches, P.minGLValue, self.top_width,
-            n_label=self.n_label, **kw)
-        if hla_it:   # (the gamma columns come last)
-            for ci, ch in enumerate(chains):
-                ch.gamma = np.array(out[-1][ci], dtype=np.float64)
-        dosages, top, top_cnt = out[:3]
-        which_next, sel_status = out[3:5] if on_device else (None, None)
-        t4 = time.perf_counter()
-        self.timing["fullpass"] += t4 - t3
-        trace.add("round:fullpass_call", t3, t4)
-        if return_dosage and (dosages.min() < -1e-5 or dosages.max() > 1 + 1e-5):   # functions.R:2072-2075
-            raise RuntimeError("Dosage observed outside of range of 0 to 1 on forward-backward full iteration")
-        self._round_dosages = dosages if return_dosage else None   # [chain, label, T]: run_stream accumulates from it
-        self._round_dosage_chains = list(chains) if return_dosage else []
+
+    def _gibbs_dosages(self, chains: List[ChainState], results) -> np.ndarray:
+        """use_mspbwt = TRUE (functions.R:784-893): the haploid dosages [chain, label, SNP] are the Gibbs call's hapProbs_t."""
+        T, nL = self.panel.nSNPs, self.n_label
+        allh = results[0].get("hap_major_all")
+        if allh is not None and allh.shape == (len(chains), nL, T) and all(r.get("hap_major_all") is allh for r in results):
+            return allh   # the backend's [chain, label, SNP] buffer itself, in chain order: nothing to copy
+        dosages = np.empty((len(chains), nL, T))
+        for ci, res in enumerate(results):
+            dosages[ci] = np.asarray(res["hapProbs_t"])[:nL]
+        return dosages
+
+    def _keep_round_haps(self, chains: List[ChainState], dosages: Optional[np.ndarray]):
+        """The end of a round on either path: every chain's ``hap`` is its rows of the round's dosages [chain, label, SNP] (or,
+        in a round whose dosages do not count, ``dosages`` None, a shared read-only zero row), and run_stream / _start_phasing
+        find the array and its chain order in ``_round_dosages`` / ``_round_dosage_chains``."""
+        T, nL = self.panel.nSNPs, self.n_label
+        self._round_dosages = dosages
+        self._round_dosage_chains = list(chains) if dosages is not None else []
         if self._zero_hap is None or len(self._zero_hap) != T:
             self._zero_hap = np.zeros(T)
             self._zero_hap.flags.writeable = False
         for ci, ch in enumerate(chains):
+            ch.hap = [dosages[ci][l] for l in range(nL)] if dosages is not None else [self._zero_hap] * nL
+
+    def _select_by_mspbwt(self, chains: List[ChainState], results, i_it: int):
+        """use_mspbwt = TRUE: the next small panel comes from the long matches of the Gibbs call's rounded haploid dosages
+        against the whole panel (select_new_haps_mspbwt_v3, mspbwt.R:225-474) -- searched for all chains and labels at once."""
+        from .mspbwt import int_contract_rows, select_new_haps_mspbwt_batch
+        P, nL = self.params, self.n_label
+        idx = [ci for ci, ch in enumerate(chains) if self.wants_new_haps(ch, i_it)]
+        if not idx:
+            return
+        seed_sel = [_draw_seed(chains[ci]) for ci in idx]
+        # per chain its nL haplotypes, rounded and packed (mspbwt.R:271-272)
+        if "hap_words" in results[idx[0]]:
+            Zs = np.concatenate([np.asarray(results[ci]["hap_words"])[:nL] for ci in idx])
+        else:
+            Zs = int_contract_rows(np.concatenate([np.asarray(results[ci]["hapProbs_t"])[:nL] for ci in idx]))
+        if P.mspbwt_search == "scan":
+            # the reference's query: the neighbour scan of the panel's msPBWT indices, then the selection, natively per chain
+            new = self.backend.mspbwt_select(Zs, nL, P.mspbwt_nindices, P.mspbwtL, P.mspbwtM, P.Knew, seed_sel)
+        else:
+            n_max = P.mspbwt_max_matches or 50 * P.mspbwtL
+            match, n_match = self.backend.find_good_matches(Zs, P.mspbwt_nindices, P.mspbwtM, n_max)
+            new = select_new_haps_mspbwt_batch(match, n_match, nL, P.Knew, self.panel.K, self.panel.nGrids, seed_sel)
+        for a, ci in enumerate(idx):
+            chains[ci].which_haps_to_use = new[a].copy()
+
+    def _fullpass_select(self, chains: List[ChainState], results, i_it: int, return_dosage: bool):
+        """use_mspbwt = FALSE: the full-panel pass per read label (impute_using_everything, functions.R:1922-2157) for every
+        chain, the selection behind it."""
+        P = self.params
+        with self._timed("host", "round:labels"):
+            self._adopt_labels(chains, results)
+            samples, chain_sample = self._marshal_fullpass(chains)
+        with self._timed("fullpass", "round:fullpass_call"):
+            want = [self.wants_new_haps(ch, i_it) for ch in chains]
+            # everything_select_good_haps: one selection stream per chain and round; its draws are keyed (quilt_amd/rng.py), so
+            # the device (csrc/select.hip, behind the full-panel call) and the host make the same choice
+            seed_sel = [_draw_seed(ch) for ch in chains]
+            # hla_run: the last seek iteration's passes also return gammaMT_t / gammaMU_t at the grid (functions.R:713-724)
+            hla_it = P.hla_grid is not None and i_it == P.n_seek_its
+            out = self._call_fullpass(chains, samples, chain_sample, return_dosage, want, seed_sel, hla_it)
+            if hla_it:
+                self._scatter_gammas(chains, out.gamma)
+        with self._timed("host", "round:select"):
             if return_dosage:
-                ch.hap = [dosages[ci][l] for l in range(self.n_label)]
-            else:
-                ch.hap = [self._zero_hap] * self.n_label
-            if not want_top[ci]:
+                self._check_dosage_range(out.dosage)
+            self._keep_round_haps(chains, out.dosage if return_dosage else None)
+            self._adopt_selections(chains, want, seed_sel, out)
+
+    @staticmethod
+    def _marshal_fullpass(chains: List[ChainState]):
+        """The chains' distinct samples in order of first appearance, and each chain's index into them."""
+        samples = list({id(ch.sample): ch.sample for ch in chains}.values())
+        index = {id(s): i for i, s in enumerate(samples)}
+        return samples, [index[id(ch.sample)] for ch in chains]
+
+    def _call_fullpass(self, chains, samples, chain_sample, return_dosage: bool, want, seed_sel, hla_it: bool) -> "FullpassOut":
+        """The backend's full-panel call, with the selection on the device where the backend has it and a list or a gamma
+        column is wanted.  The only place that knows the positional forms of what ``fullpass_reads_batch`` returns:
+        (dosage, top, count), then (which_next, status) with ``select``, then gamma last with ``gamma_grid``."""
+        P = self.params
+        on_device = bool(getattr(self.backend, "select_on_device", False)) and (any(want) or hla_it)
+        kw = {}
+        if on_device:
+            kw["select"] = dict(Ksubset=P.Ksubset, Knew=P.Knew, which=[ch.which_haps_to_use for ch in chains], seeds=seed_sel)
+        if hla_it:
+            kw["gamma_grid"] = int(P.hla_grid)
+        out = self.backend.fullpass_reads_batch(
+            samples, chain_sample, [ch.read_labels for ch in chains], [return_dosage] * len(chains), want, self.cols,
+            P.K_top_matches, P.minGLValue, self.top_width, n_label=self.n_label, **kw)
+        which_next, status = out[3:5] if on_device else (None, None)
+        return FullpassOut(*out[:3], which_next, status, out[-1] if hla_it else None)
+
+    @staticmethod
+    def _scatter_gammas(chains: List[ChainState], gamma):   # functions.R:1261-1280: [chain, label, K], kept per chain
+        for ch, g in zip(chains, gamma):
+            ch.gamma = np.array(g, dtype=np.float64)
+
+    @staticmethod
+    def _check_dosage_range(dosages: np.ndarray):   # functions.R:2072-2075
+        if dosages.min() < -1e-5 or dosages.max() > 1 + 1e-5:
+            raise RuntimeError("Dosage observed outside of range of 0 to 1 on forward-backward full iteration")
+
+    def _adopt_selections(self, chains: List[ChainState], want, seed_sel, out: "FullpassOut"):
+        """The device's selections become the chains' small panels; the host selects where the lists came back instead, and
+        from the complete lists (``_full_lists``) where the ranked candidates ran out."""
+        P, K = self.params, self.panel.K
+        on_device = out.status is not None
+        for ci, ch in enumerate(chains):
+            if not want[ci]:
                 continue
-            if on_device and sel_status[ci] == 0:
-                ch.which_haps_to_use = which_next[ci].astype(np.int32)
+            if on_device and out.status[ci] == 0:
+                ch.which_haps_to_use = out.which_next[ci].astype(np.int32)
                 self.n_device_selections += 1
                 continue
             prev_sel = previously_selected(ch.which_haps_to_use, P.Ksubset - P.Knew, seed_sel[ci])
             try:
                 if on_device:   # the device ran out of ranked candidates (status 1): the lists did not come back
                     raise ListsTruncated()
-                sel = everything_select_good_haps_dense(P.Knew, P.K_top_matches, top[ci].astype(np.int64) + 1, prev_sel, K,
-                                                        seed_sel[ci], truncated=bool((top_cnt[ci] > self.top_width).any()))
+                sel = everything_select_good_haps_dense(P.Knew, P.K_top_matches, out.top[ci].astype(np.int64) + 1, prev_sel, K,
+                                                        seed_sel[ci], truncated=bool((out.count[ci] > self.top_width).any()))
             except ListsTruncated:
                 # the reference's lists hold every haplotype at or above the threshold (reference-single.cpp:129-194); the
                 # batched call returns their first top_width entries.  Ties made a list longer and the selection ran out
@@ -799,60 +899,6 @@ class Driver:
                 new_haps = self._full_lists(ch)
                 sel = everything_select_good_haps(P.Knew, P.K_top_matches, new_haps, prev_sel, K, seed_sel[ci])
             ch.which_haps_to_use = np.concatenate([prev_sel, sel]).astype(np.int32)
-        t5 = time.perf_counter()
-        self.timing["host"] += t5 - t4
-        trace.add("round:select", t4, t5)
-        return return_dosage
-
-    def _round_mspbwt(self, chains: List[ChainState], results, i_it: int, return_dosage: bool):
-        """use_mspbwt = TRUE (functions.R:784-893): the haploid dosages are the Gibbs call's hapProbs_t; the next small panel
-        comes from the long matches of their rounded form against the whole panel (select_new_haps_mspbwt_v3,
-        mspbwt.R:225-474) -- searched on the device for all chains and labels at once."""
-        from .mspbwt import int_contract_rows, select_new_haps_mspbwt_batch
-        P = self.params
-        T, nL = self.panel.nSNPs, self.n_label
-        if return_dosage:
-            allh = results[0].get("hap_major_all")
-            if (allh is not None and allh.shape == (len(chains), nL, T) and
-                    all(r.get("hap_major_all") is allh for r in results)):
-                dosages = allh   # the backend's [chain, label, SNP] buffer itself, in chain order: nothing to copy
-            else:
-                dosages = np.empty((len(chains), nL, T))
-                for ci, res in enumerate(results):
-                    dosages[ci] = np.asarray(res["hapProbs_t"])[:nL]
-            for ci, ch in enumerate(chains):
-                ch.hap = [dosages[ci][l] for l in range(nL)]
-        else:
-            dosages = None
-            if self._zero_hap is None or len(self._zero_hap) != T:
-                self._zero_hap = np.zeros(T)
-                self._zero_hap.flags.writeable = False
-            for ch in chains:
-                ch.hap = [self._zero_hap] * nL
-        self._round_dosages = dosages
-        self._round_dosage_chains = list(chains) if return_dosage else []
-        want = [i_it < P.n_seek_its or P.impute_rare_common or (not ch.phasing and ch.i_chain == P.nGibbsSamples)
-                for ch in chains]
-        idx = [ci for ci, w in enumerate(want) if w]
-        if not idx:
-            return
-        seed_sel = {ci: int(chains[ci].rng.integers(0, 2 ** 63)) for ci in idx}
-        # per chain its nL haplotypes, rounded and packed (mspbwt.R:271-272)
-        if "hap_words" in results[idx[0]]:
-            Zs = np.concatenate([np.asarray(results[ci]["hap_words"])[:nL] for ci in idx])
-        else:
-            Zs = int_contract_rows(np.concatenate([np.asarray(results[ci]["hapProbs_t"])[:nL] for ci in idx]))
-        if P.mspbwt_search == "scan":
-            # the reference's query: the neighbour scan of the panel's msPBWT indices, then the selection, natively per chain
-            new = self.backend.mspbwt_select(Zs, nL, P.mspbwt_nindices, P.mspbwtL, P.mspbwtM, P.Knew,
-                                             [seed_sel[ci] for ci in idx])
-        else:
-            n_max = P.mspbwt_max_matches or 50 * P.mspbwtL
-            match, n_match = self.backend.find_good_matches(Zs, P.mspbwt_nindices, P.mspbwtM, n_max)
-            new = select_new_haps_mspbwt_batch(match, n_match, nL, P.Knew, self.panel.K, self.panel.nGrids,
-                                               [seed_sel[ci] for ci in idx])
-        for a, ci in enumerate(idx):
-            chains[ci].which_haps_to_use = new[a].copy()
 
     def _full_lists(self, ch: ChainState) -> List[List[np.ndarray]]:
         """``new_haps`` of one chain from complete best-haplotype lists: per read label its gl (make_gl_from_u_bq,
@@ -897,13 +943,8 @@ class Driver:
                     n_gibbs_sample_its=P.n_gibbs_sample_its,
                     block_gibbs_iterations=P.small_ref_panel_block_gibbs_iterations,
                     maxDifferenceBetweenReads=md, Jmax_local=P.Jmax, **kw)
-                if len(groups) > 1 or n_try > 0:
-                    # the backend's dosage buffer is reused by its next call: results of a call that is not the round's only
-                    # one keep copies
-                    for o in out:
-                        if o.get("hap_major_all") is not None:
-                            o["hapProbs_t"] = np.array(o["hapProbs_t"])
-                            o["hap_major_all"] = None
+                if len(groups) > 1 or n_try > 0:   # not the round's only call
+                    self._detach_from_backend_buffer(out)
                 for i, o in zip(idx, out):
                     if o["underflow_problem"]:
                         maxdiff[i] = max(1.0, maxdiff[i] / 10)   # functions.R:2704-2715
@@ -911,65 +952,63 @@ class Driver:
                         self.n_underflow_retries += 1
                     else:
                         results[i] = o
-            if nxt:   # another call follows and reuses the backend's dosage buffer: what has been accepted keeps copies
-                for o in results:
-                    if o is not None and o.get("hap_major_all") is not None:
-                        o["hapProbs_t"] = np.array(o["hapProbs_t"])
-                        o["hap_major_all"] = None
+            if nxt:   # another call follows: what has been accepted keeps copies
+                self._detach_from_backend_buffer(results)
             pending = nxt
             n_try += 1
             if n_try > 10 and pending:
                 raise RuntimeError("There were consecutive underflow problems (functions.R:2710)")
         return results
 
+    @staticmethod
+    def _detach_from_backend_buffer(results):
+        """The backend's dosage buffer is reused by its next Gibbs call: results that must outlive one keep copies of their
+        rows and no longer name the buffer (``results`` may hold None for chains still pending)."""
+        for o in results:
+            if o is not None and o.get("hap_major_all") is not None:
+                o["hapProbs_t"] = np.array(o["hapProbs_t"])
+                o["hap_major_all"] = None
+
     def _rare_common_round(self, chains: List[ChainState]):
         """impute_final_gibbs_with_rare_common (rare_common.R:109-420), once per Gibbs sample after its seek
         iterations (functions.R:1042-1098): starting labels from the all-SNP reads against the latest (hap1, hap2)
         (get_initial_read_labels), then one Gibbs call over ALL SNPs with the haplotypes selected last."""
-        import time
         P, rc = self.params, self.rare_common
-        t0 = time.perf_counter()
-        common = rc.snp_is_common == 1
         reads = [ch.sample.all_snp for ch in chains]
         nL = self.n_label
-        # eHapsCurrent_tc of get_initial_read_labels (rare_common.R:76-81) for every chain at once: [chain, SNP, haplotype],
-        # 0.5 at the rare SNPs, the latest full-pass dosages at the common ones
-        haps = np.full((len(chains), rc.nSNPs_all, nL), 0.5)
-        cidx = np.flatnonzero(common)
-        for l in range(nL):
-            haps[:, cidx, l] = np.stack([ch.hap[l] for ch in chains])
-        lik = self.backend.read_likelihood_all_snps_batch(reads, haps, P.maxDifferenceBetweenReads)
-        starts, seed_reads, seed_shards = [], [], []
-        for ch, e in zip(chains, lik):
-            if P.method == "nipt":
-                starts.append(get_initial_read_labels_nipt(e, ch.sample.ff, ch.rng))
-            else:
-                starts.append(get_initial_read_labels(e, ch.rng.random(e.shape[1])))
-            seed_reads.append(int(ch.rng.integers(0, 2 ** 63)))
-            seed_shards.append(int(ch.rng.integers(0, 2 ** 63)))
-        t1 = time.perf_counter()
-        self.timing["host"] += t1 - t0
-        # impute_one_sample's defaults for this call (functions.R:2385-2409): labels given, read categories off
-        results = self._gibbs_with_retry(chains, reads, starts, seed_reads, [0] * len(chains), seed_shards,
-                                         gibbs_initialize_iteratively=False, rare_common=True)
-        for ch, res in zip(chains, results):
-            ch.hap_all = [res["hapProbs_t"][l] for l in range(nL)]
-        self.timing["gibbs"] += time.perf_counter() - t1
+        with self._timed("host"):
+            # eHapsCurrent_tc of get_initial_read_labels (rare_common.R:76-81) for every chain at once: [chain, SNP, haplotype],
+            # 0.5 at the rare SNPs, the latest full-pass dosages at the common ones
+            haps = np.full((len(chains), rc.nSNPs_all, nL), 0.5)
+            cidx = np.flatnonzero(rc.snp_is_common == 1)
+            for l in range(nL):
+                haps[:, cidx, l] = np.stack([ch.hap[l] for ch in chains])
+            lik = self.backend.read_likelihood_all_snps_batch(reads, haps, P.maxDifferenceBetweenReads)
+            starts, seed_reads, seed_shards = [], [], []
+            for ch, e in zip(chains, lik):
+                if P.method == "nipt":
+                    starts.append(get_initial_read_labels_nipt(e, ch.sample.ff, ch.rng))
+                else:
+                    starts.append(get_initial_read_labels(e, ch.rng.random(e.shape[1])))
+                seed_reads.append(_draw_seed(ch))
+                seed_shards.append(_draw_seed(ch))
+        with self._timed("gibbs"):
+            # impute_one_sample's defaults for this call (functions.R:2385-2409): labels given, read categories off
+            results = self._gibbs_with_retry(chains, reads, starts, seed_reads, [0] * len(chains), seed_shards,
+                                             gibbs_initialize_iteratively=False, rare_common=True)
+            for ch, res in zip(chains, results):
+                ch.hap_all = [res["hapProbs_t"][l] for l in range(nL)]
 
     def _new_batch(self, samples, offset: int) -> _Batch:
-        P = self.params
-        T = self.panel.nSNPs
-        N = len(samples)
+        P, T, N = self.params, self.panel.nSNPs, len(samples)
         chains = [ChainState(samples[i], i, c, chain_rng(P.seed, offset + i, c))
                   for i in range(N) for c in range(1, P.nGibbsSamples + 1)]
         b = _Batch(list(samples), offset, chains, np.zeros((N, T)), np.zeros((N, 3, T)), np.zeros(N, dtype=np.int64))
-        if P.method == "nipt" and not P.impute_rare_common:
-            b.fet_dosage, b.fet_gp_t = np.zeros((N, T)), np.zeros((N, 3, T))
+        Ta = self.rare_common.nSNPs_all if P.impute_rare_common else T   # what the results cover
         if P.impute_rare_common:
-            Ta = self.rare_common.nSNPs_all
             b.dosage_all, b.gp_t_all, b.nDosage_all = np.zeros((N, Ta)), np.zeros((N, 3, Ta)), np.zeros(N, dtype=np.int64)
-            if P.method == "nipt":
-                b.fet_dosage, b.fet_gp_t = np.zeros((N, Ta)), np.zeros((N, 3, Ta))
+        if P.method == "nipt":
+            b.fet_dosage, b.fet_gp_t = np.zeros((N, Ta)), np.zeros((N, 3, Ta))
         return b
 
     def _start_phasing(self, b: _Batch):
@@ -1007,34 +1046,19 @@ class Driver:
         b.chains = []   # the main chains are done
 
     def _finish(self, b: _Batch) -> List[SampleResult]:
-        out = []
-        rc = self.params.impute_rare_common
+        P, out = self.params, []
+        # impute_rare_common: the switch-over to all SNPs (functions.R:1232-1252, 1305-1317)
+        dosage, gp_t, nDosage = (b.dosage_all, b.gp_t_all, b.nDosage_all) if P.impute_rare_common else (b.dosage, b.gp_t, b.nDosage)
         for i in range(len(b.samples)):
-            if rc:   # the switch-over to all SNPs (functions.R:1232-1252, 1305-1317)
-                d = b.dosage_all[i] / b.nDosage_all[i]
-                g = b.gp_t_all[i] / b.nDosage_all[i]
-                if self.params.method == "nipt":
-                    fd, fg = b.fet_dosage[i] / b.nDosage_all[i], b.fet_gp_t[i] / b.nDosage_all[i]
-                    ph = b.phasing[i].hap_all
-                    h1, h2, h3 = recast_nipt_haps(ph[0], ph[1], ph[2], g, fg)
-                    out.append(SampleResult(d, g, np.stack([h1, h2, h3], axis=1), b.consensus[i], int(b.nDosage_all[i]),
-                                            fet_dosage=fd, fet_gp_t=fg))
-                    continue
-                h1, h2 = recast_haps(b.phasing[i].hap_all[0], b.phasing[i].hap_all[1], g.T)
-                out.append(SampleResult(d, g, np.stack([h1, h2], axis=1), b.consensus[i], int(b.nDosage_all[i])))
-                continue
-            d = b.dosage[i] / b.nDosage[i]
-            g = b.gp_t[i] / b.nDosage[i]
-            if self.params.method == "nipt":   # functions.R:1218-1231, 1313-1317
-                fd, fg = b.fet_dosage[i] / b.nDosage[i], b.fet_gp_t[i] / b.nDosage[i]
-                ph = b.phasing[i].hap
-                h1, h2, h3 = recast_nipt_haps(ph[0], ph[1], ph[2], g, fg)
-                out.append(SampleResult(d, g, np.stack([h1, h2, h3], axis=1), b.consensus[i], int(b.nDosage[i]),
-                                        fet_dosage=fd, fet_gp_t=fg))
-                continue
-            h1, h2 = recast_haps(b.phasing[i].hap[0], b.phasing[i].hap[1], g.T)   # functions.R:1207-1217
-            out.append(SampleResult(d, g, np.stack([h1, h2], axis=1), b.consensus[i], int(b.nDosage[i])))
-            if self.params.hla_grid is not None:   # functions.R:1489-1494
+            ph = b.phasing[i].hap_all if P.impute_rare_common else b.phasing[i].hap
+            d, g = dosage[i] / nDosage[i], gp_t[i] / nDosage[i]
+            if P.method == "nipt":   # functions.R:1218-1231, 1313-1317
+                fd, fg = b.fet_dosage[i] / nDosage[i], b.fet_gp_t[i] / nDosage[i]
+                haps, fetus = recast_nipt_haps(ph[0], ph[1], ph[2], g, fg), dict(fet_dosage=fd, fet_gp_t=fg)
+            else:
+                haps, fetus = recast_haps(ph[0], ph[1], g.T), {}   # functions.R:1207-1217
+            out.append(SampleResult(d, g, np.stack(haps, axis=1), b.consensus[i], int(nDosage[i]), **fetus))
+            if P.hla_grid is not None:   # functions.R:1489-1494
                 lg = b.list_of_gammas[i]
                 out[-1].gamma1, out[-1].gamma2 = b.phasing[i].gamma[0], b.phasing[i].gamma[1]
                 out[-1].gamma_total, out[-1].list_of_gammas = hla_gamma_total(lg), lg
@@ -1042,84 +1066,86 @@ class Driver:
             r.read_label_prob = mp
         return out
 
+    def _seek_rounds(self, cur: Optional[_Batch], phasing: List[ChainState]):
+        """The ``n_seek_its`` rounds of ``cur``'s main chains (if any) fused with those of ``phasing``, the phasing chains of
+        earlier batches; with impute_rare_common the all-SNP round after them (functions.R:1042-1123)."""
+        chains = (cur.chains if cur else []) + phasing   # cur's first: the first rows of a round's dosages are theirs
+        for i_it in range(1, self.params.n_seek_its + 1):
+            with span("round"):
+                stored = self._round(chains, i_it)
+            if stored and cur:
+                self._accumulate(cur)
+        if self.params.impute_rare_common:
+            self._rare_common_round(chains)
+            if cur:
+                self._accumulate_all_snps(cur)
+
+    def _accumulate(self, cur: _Batch):
+        """functions.R:999-1020 (1009-1016: fetus = maternal transmitted + paternal transmitted) from the round's dosages,
+        natively (io.accumulate_dosage)."""
+        from .io import accumulate_dosage
+        P = self.params
+        with self._timed("accumulate"):
+            fetal = P.method == "nipt" and not P.impute_rare_common
+            accumulate_dosage(np.ascontiguousarray(self._round_dosages[:len(cur.chains)], dtype=np.float64),
+                              [ch.i_sample for ch in cur.chains], cur.dosage, cur.gp_t,
+                              cur.fet_dosage if fetal else None, cur.fet_gp_t if fetal else None)
+            for ch in cur.chains:
+                cur.nDosage[ch.i_sample] += 1
+
+    def _accumulate_all_snps(self, cur: _Batch):
+        """functions.R:1099-1123 (1113-1120: the fetus) from the all-SNP round's ``hap_all``."""
+        gp = lambda a, b: np.stack([(1 - a) * (1 - b), (1 - a) * b + a * (1 - b), a * b])
+        for ch in cur.chains:
+            h1, h2 = ch.hap_all[0], ch.hap_all[1]
+            cur.dosage_all[ch.i_sample] += h1 + h2
+            cur.gp_t_all[ch.i_sample] += gp(h1, h2)
+            if self.params.method == "nipt":
+                h3 = ch.hap_all[2]
+                cur.fet_dosage[ch.i_sample] += h1 + h3
+                cur.fet_gp_t[ch.i_sample] += gp(h1, h3)
+            cur.nDosage_all[ch.i_sample] += 1
+
     def run_stream(self, batches):
         """``batches``: iterable of ``(samples, sample_offset)``; yields one list of SampleResult per batch, in order.
         The phasing rounds of a batch run fused with the main rounds of the next one; the last batch's run alone, or -- with
         a :class:`PhasingTail` shared by the host threads of a device -- together with the other threads' last batches."""
-        import time
-        P = self.params
-        prev: Optional[_Batch] = None
-        it = iter(batches)
-        tail = self.phasing_tail
+        prev, it, tail = None, iter(batches), self.phasing_tail
         reported = False          # this thread has told the tail that its stream drained
         taken = []                # (batch, Future) of other threads' last batches run here
         try:
             while True:
                 nxt = next(it, None)
-                t_nb = time.perf_counter()
-                cur = self._new_batch(*nxt) if nxt is not None else None
-                self.timing["new_batch"] += time.perf_counter() - t_nb
-                taken = []            # (batch, Future) of other threads' last batches run here
+                with self._timed("new_batch"):
+                    cur = self._new_batch(*nxt) if nxt is not None else None
+                taken = []
                 if cur is None and tail is not None and not reported:
                     reported = True
                     run, fut = tail.drained(prev)
                     if fut is not None:   # a later thread runs prev's phasing rounds with its own
-                        if self.gibbs_gate is not None and not getattr(self, "_gate_left", False):
+                        if self.gibbs_gate is not None and not self._gate_left:
                             self.gibbs_gate.leave()
                             self._gate_left = True
                         with span("tail:wait"):
                             b = fut.result()
-                        t0 = time.perf_counter()
-                        with span("finish"):
+                        with self._timed("finish", "finish"):
                             done = self._finish(b)
-                        self.timing["finish"] += time.perf_counter() - t0
                         yield done
                         return
                     taken = run
                 if cur is None and prev is None and not taken:
                     return
-                others = [ch for b, _ in taken for ch in b.phasing]
-                phasing = (prev.phasing if prev else []) + others
-                for i_it in range(1, P.n_seek_its + 1):
-                    chains = (cur.chains if cur else []) + phasing
-                    with span("round"):
-                        stored = self._round(chains, i_it)
-                    if stored and cur:   # functions.R:999-1020 (1009-1016: fetus = maternal transmitted + paternal transmitted)
-                        from .io import accumulate_dosage
-                        t_acc = time.perf_counter()
-                        n_cur = len(cur.chains)           # the round's chains: cur's first, then the phasing chains
-                        fetal = P.method == "nipt" and not P.impute_rare_common
-                        accumulate_dosage(np.ascontiguousarray(self._round_dosages[:n_cur], dtype=np.float64),
-                                          [ch.i_sample for ch in cur.chains], cur.dosage, cur.gp_t,
-                                          cur.fet_dosage if fetal else None, cur.fet_gp_t if fetal else None)
-                        for ch in cur.chains:
-                            cur.nDosage[ch.i_sample] += 1
-                        self.timing["accumulate"] += time.perf_counter() - t_acc
-                if P.impute_rare_common:   # functions.R:1042-1123
-                    self._rare_common_round((cur.chains if cur else []) + phasing)
-                    for ch in (cur.chains if cur else []):
-                        h1, h2 = ch.hap_all[0], ch.hap_all[1]
-                        cur.dosage_all[ch.i_sample] += h1 + h2
-                        cur.gp_t_all[ch.i_sample] += np.stack([(1 - h1) * (1 - h2), (1 - h1) * h2 + h1 * (1 - h2), h1 * h2])
-                        if P.method == "nipt":   # functions.R:1113-1120
-                            h3 = ch.hap_all[2]
-                            cur.fet_dosage[ch.i_sample] += h1 + h3
-                            cur.fet_gp_t[ch.i_sample] += np.stack([(1 - h1) * (1 - h3), (1 - h1) * h3 + h1 * (1 - h3), h1 * h3])
-                        cur.nDosage_all[ch.i_sample] += 1
+                self._seek_rounds(cur, (prev.phasing if prev else []) + [ch for b, _ in taken for ch in b.phasing])
                 # The other threads' batches go back to their owners, who finish them on their own threads.  Their phasing
                 # chains' dosages are rows of THIS backend's transfer buffer: it is not written again before the owners are
                 # done (this thread has no round left, and a later stream starts only after every result was handed out).
                 for b, fut in taken:
                     fut.set_result(b)
-                t0 = time.perf_counter()
-                with span("finish"):
+                with self._timed("finish", "finish"):
                     done = self._finish(prev) if prev else None
-                t1 = time.perf_counter()
                 if cur:
-                    with span("start_phasing"):
+                    with self._timed("consensus", "start_phasing"):
                         self._start_phasing(cur)
-                self.timing["finish"] += t1 - t0
-                self.timing["consensus"] += time.perf_counter() - t1
                 prev = cur
                 if done is not None:
                     yield done
@@ -1164,6 +1190,16 @@ class HipBackend:
         self._dosage_buf = None         # pinned host buffer of the dosage rounds (fullpass_reads_batch)
         self._hap_buf = None            # the same for the Gibbs call's own haploid dosages (use_mspbwt = TRUE)
 
+    def _pinned_view(self, attr: str, shape) -> np.ndarray:
+        """A ``shape`` view of the grow-only pinned buffer (``qa_host_alloc``) kept as ``attr``: a buffer too small is released
+        before the larger one, with an eighth of head-room, is allocated."""
+        need = int(np.prod(shape))
+        if getattr(self, attr) is None or getattr(self, attr).size < need:
+            from .native import pinned_empty
+            setattr(self, attr, None)
+            setattr(self, attr, pinned_empty((need + need // 8,)))
+        return getattr(self, attr)[:need].reshape(shape)
+
     def make_gl_bound(self, gl, minGLValue, to_fix):
         from .reference_single import Rcpp_make_gl_bound
         Rcpp_make_gl_bound(gl, minGLValue, to_fix)
@@ -1177,18 +1213,12 @@ class HipBackend:
                                                   seed_reads=seed_reads, seed_shard=seed_shards, return_hapProbs=True,
                                                   return_genProbs=False, disable_read_category_usage=True,
                                                   rare_common=self.drc, **kw)
-        want_hap = bool(kw.pop("return_hapProbs", False))   # use_mspbwt = TRUE: the call's own haploid dosages
         hap_out = None
-        if want_hap:
+        if kw.pop("return_hapProbs", False):   # use_mspbwt = TRUE: the call's own haploid dosages
             # label by label into this backend's pinned buffer (no staging copy, no per-chain transposes on the host): valid
             # until the next call that asks for dosages -- the driver consumes a round before it starts the next
             n_label = 3 if np.ndim(kw.get("ff", 0.0)) > 0 or kw.get("ff", 0.0) != 0 else 2
-            need = len(samples) * n_label * self.dev.panel.nSNPs
-            if self._hap_buf is None or self._hap_buf.size < need:
-                from .native import pinned_empty
-                self._hap_buf = None
-                self._hap_buf = pinned_empty((need + need // 8,))
-            hap_out = self._hap_buf[:need].reshape(len(samples), n_label, self.dev.panel.nSNPs)
+            hap_out = self._pinned_view("_hap_buf", (len(samples), n_label, self.dev.panel.nSNPs))
         return forwardBackwardGibbsNIPT_batch(self.dev, samples, which, starts, None, first_reads, None,
                                               seed_reads=seed_reads, seed_shard=seed_shards, return_hapProbs=False,
                                               return_hap_words=bool(kw.pop("return_hap_words", False)),
@@ -1253,35 +1283,21 @@ class HipBackend:
         The dosage array is a view of this backend's pinned transfer buffer (``qa_host_alloc``): it is valid until the
         next call that asks for dosages -- copy what must outlive that (the driver consumes a round before the next)."""
         import ctypes as C
+        from .impute import flatten_samples
         from .native import check, lib, ptr
-        lib().qa_fullpass_reads_batch.restype = C.c_int
-        lib().qa_fullpass_reads_select_batch.restype = C.c_int
         P = self.dev.panel
         T = P.nSNPs
         n_chain, n_sample = len(chain_sample), len(samples)
         cols = np.ascontiguousarray(cols, dtype=np.int32)
         n_thin = int((cols >= 0).sum())
-        read_off = np.zeros(n_sample + 1, dtype=np.int32)
-        for i, s in enumerate(samples):
-            read_off[i + 1] = read_off[i] + s.nReads
-        read_ptr = np.concatenate([np.asarray(s.read_ptr, dtype=np.int32) for s in samples])
-        u = np.concatenate([np.asarray(s.u, dtype=np.int32) for s in samples])
-        bq = np.concatenate([np.asarray(s.bq, dtype=np.int32) for s in samples])
+        read_off, read_ptr, u, bq, _ = flatten_samples(samples, wif=False)
         H = np.concatenate([np.asarray(h, dtype=np.int32) for h in labels])
         cs = np.ascontiguousarray(chain_sample, dtype=np.int32)
         wd = np.ascontiguousarray(want_dosage, dtype=np.int32)
         wt = np.ascontiguousarray(want_top, dtype=np.int32)
-        # The round's dosages land in this backend's pinned buffer (qa_host_alloc: no staging copy, no fresh pages for ~1 GB
-        # per dosage round) -- valid until the next dosage round of this backend; the driver consumes a round's rows
-        # (accumulation, read confidence, the phasing haplotypes) before it starts the next one.
-        dosage = None
+        dosage = None   # (pinned: no staging copy, no fresh pages for ~1 GB per dosage round)
         if wd.any():
-            need = n_chain * n_label * T
-            if self._dosage_buf is None or self._dosage_buf.size < need:
-                from .native import pinned_empty
-                self._dosage_buf = None   # (release the smaller one first)
-                self._dosage_buf = pinned_empty((need + need // 8,))
-            dosage = self._dosage_buf[:need].reshape(n_chain, n_label, T)
+            dosage = self._pinned_view("_dosage_buf", (n_chain, n_label, T))
             if not wd.all():
                 dosage[...] = 0.0
         cnt = np.zeros((n_chain, n_label, n_thin), dtype=np.int32)
@@ -1294,19 +1310,17 @@ class HipBackend:
             seeds = np.ascontiguousarray(select["seeds"], dtype=np.uint64)
             nxt = np.zeros((n_chain, Ks), dtype=np.int32)
             status = np.full(n_chain, -1, dtype=np.int32)
-            if gamma_grid is not None:
-                gamma = np.zeros((n_chain, n_label, P.K))
-                lib().qa_fullpass_reads_select_gamma_batch.restype = C.c_int
+            # (the lists stay on the device: no top_idx / top_val)
+            args = (*head, None, None, ptr(cnt), C.c_int32(Ks), C.c_int32(int(select["Knew"])), ptr(which), ptr(seeds), ptr(nxt),
+                    ptr(status))
+            if gamma_grid is None:
                 with span("device:fullpass"):
-                    check(lib().qa_fullpass_reads_select_gamma_batch(*head, None, None, ptr(cnt), C.c_int32(Ks),
-                                                                     C.c_int32(int(select["Knew"])), ptr(which), ptr(seeds), ptr(nxt),
-                                                                     ptr(status), C.c_int32(int(gamma_grid)), ptr(gamma)))
-                return dosage, None, cnt, nxt, status, gamma
+                    check(lib().qa_fullpass_reads_select_batch(*args))
+                return dosage, None, cnt, nxt, status
+            gamma = np.zeros((n_chain, n_label, P.K))
             with span("device:fullpass"):
-                check(lib().qa_fullpass_reads_select_batch(*head, None, None, ptr(cnt), C.c_int32(Ks),
-                                                           C.c_int32(int(select["Knew"])), ptr(which), ptr(seeds), ptr(nxt),
-                                                           ptr(status)))
-            return dosage, None, cnt, nxt, status
+                check(lib().qa_fullpass_reads_select_gamma_batch(*args, C.c_int32(int(gamma_grid)), ptr(gamma)))
+            return dosage, None, cnt, nxt, status, gamma
         if gamma_grid is not None:
             raise ValueError("gamma_grid: the gamma columns come with the device-side selection (select=...)")
         top = np.full((n_chain, n_label, n_thin, top_width), -1, dtype=np.int32)

@@ -16,6 +16,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import native
+from .impute import flatten_samples
 from .native import DevicePanel, check, lib, ptr
 from .trace import span
 
@@ -67,8 +68,6 @@ def forwardBackwardGibbsNIPT_batch(panel: DevicePanel, samples: Sequence, which_
     receives the haploid dosages label by label -- the layout the driver accumulates from -- instead of a per-chain
     ``hapProbs_t``; the dicts then carry views of its rows.
     """
-    lib().qa_gibbs_batch.restype = C.c_int
-    lib().qa_gibbs_batch_rare_common.restype = C.c_int
     import os, time
     ffc = None
     if np.ndim(ff) > 0:   # one fetal fraction per chain (NIPT)
@@ -84,15 +83,9 @@ def forwardBackwardGibbsNIPT_batch(panel: DevicePanel, samples: Sequence, which_
     n_its = n_gibbs_burn_in_its + n_gibbs_sample_its
     blocks = np.ascontiguousarray(block_gibbs_iterations, dtype=np.int32)
     nb = len(blocks) if perform_block_gibbs else 0
-    read_off = np.zeros(Cn + 1, dtype=np.int32)
-    for c, s in enumerate(samples):
-        read_off[c + 1] = read_off[c] + s.nReads
     which = np.ascontiguousarray(np.stack([np.asarray(w, dtype=np.int32) for w in which_haps_to_use]))
     assert which.shape == (Cn, Ks)
-    read_ptr = np.concatenate([np.asarray(s.read_ptr, dtype=np.int32) for s in samples])
-    u = np.concatenate([np.asarray(s.u, dtype=np.int32) for s in samples])
-    bq = np.concatenate([np.asarray(s.bq, dtype=np.int32) for s in samples])
-    wif = np.concatenate([np.asarray(s.wif, dtype=np.int32) for s in samples])
+    read_off, read_ptr, u, bq, wif = flatten_samples(samples)
     use_seeds = seed_reads is not None
     if use_seeds:
         ru = None
@@ -207,8 +200,6 @@ def calculate_eMatRead_t_vs_haplotypes_batch(panel: DevicePanel, samples: Sequen
     """``calculate_eMatRead_t_vs_haplotypes`` (QUILT/R/functions.R:2975-3020) for a batch: ``haps[c]`` is the
     list of K dense haplotype dosages of chain ``c``.  Returns one K x nReads matrix per chain.  ``nSNPs``: the
     length of the dosages when it is not the panel's (all-SNP reads, QUILT/R/rare_common.R:61-107)."""
-    lib().qa_rcpp_make_eMatRead_t_nsnps.restype = C.c_int
-    lib().qa_rcpp_make_eMatRead_t_hap_major.restype = C.c_int
     Cn = len(samples)
     T = panel.panel.nSNPs if nSNPs is None else int(nSNPs)
     fn = lib().qa_rcpp_make_eMatRead_t_nsnps
@@ -225,12 +216,7 @@ def calculate_eMatRead_t_vs_haplotypes_batch(panel: DevicePanel, samples: Sequen
         K = len(haps[0])
         e = np.ascontiguousarray(np.stack([np.stack([np.asarray(h, dtype=np.float64) for h in hs], axis=1) for hs in haps]))
         assert e.shape == (Cn, T, K)
-    read_off = np.zeros(Cn + 1, dtype=np.int32)
-    for c, s in enumerate(samples):
-        read_off[c + 1] = read_off[c] + s.nReads
-    read_ptr = np.concatenate([np.asarray(s.read_ptr, dtype=np.int32) for s in samples])
-    u = np.concatenate([np.asarray(s.u, dtype=np.int32) for s in samples])
-    bq = np.concatenate([np.asarray(s.bq, dtype=np.int32) for s in samples])
+    read_off, read_ptr, u, bq, _ = flatten_samples(samples, wif=False)
     out = np.zeros((int(read_off[-1]), K))
     with span("device:read_confidence"):
         check(fn(panel.handle, C.c_int32(T), C.c_int32(Cn), C.c_int32(K), ptr(e), ptr(read_off),
@@ -246,17 +232,11 @@ def calculate_eMatRead_t_rare_common_batch(panel: DevicePanel, rare_common, samp
     chains that name their sample.  ``samples_all[i]``: sample i's all-SNP reads; ``chain_sample[c]``: the sample of chain c;
     ``hap_common``: [chain, haplotype, common SNP] dosages (0.5 at the rare SNPs is supplied by the kernel).  Returns one
     K x nReads matrix per chain."""
-    lib().qa_rcpp_make_eMatRead_t_rare_common.restype = C.c_int
     cs = np.ascontiguousarray(chain_sample, dtype=np.int32)
     e = np.ascontiguousarray(hap_common, dtype=np.float64)
     Cn, NS, K = len(cs), len(samples_all), e.shape[1]
     assert e.shape == (Cn, K, panel.panel.nSNPs)
-    read_off = np.zeros(NS + 1, dtype=np.int32)
-    for i, s in enumerate(samples_all):
-        read_off[i + 1] = read_off[i] + s.nReads
-    read_ptr = np.concatenate([np.asarray(s.read_ptr, dtype=np.int32) for s in samples_all])
-    u = np.concatenate([np.asarray(s.u, dtype=np.int32) for s in samples_all])
-    bq = np.concatenate([np.asarray(s.bq, dtype=np.int32) for s in samples_all])
+    read_off, read_ptr, u, bq, _ = flatten_samples(samples_all, wif=False)
     n_out = np.r_[0, np.cumsum([samples_all[i].nReads if 0 <= i < NS else 0 for i in cs])]
     out = np.zeros((int(n_out[-1]), K))
     with span("device:read_confidence"):

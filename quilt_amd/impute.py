@@ -118,16 +118,18 @@ STAT_NAMES = ("underflow_retries", "full_list_refetches", "device_selections", "
               "ms_gibbs", "ms_fullpass", "ms_host", "ms_consensus", "ms_finish", "ms_accumulate")
 
 
-def flatten_samples(samples: Sequence):
+def flatten_samples(samples: Sequence, wif: bool = True):
     """``sampleReads`` of a range of samples in the flattened form of include/quilt_amd.h: read_off [n + 1], per sample
-    R + 1 read_ptr entries, bases and wif back to back."""
+    R + 1 read_ptr entries, bases and wif back to back (int32, contiguous).  The one Python packer of reads -- the mirror of
+    csrc/impute.cpp's ``PackedReads::fill`` -- for the range call and for every per-call entry (quilt_amd/gibbs_nipt.py,
+    ``HipBackend.fullpass_reads_batch``); ``wif`` = False: for a call that does not read it (None in its place)."""
     n = len(samples)
     read_off = np.zeros(n + 1, dtype=np.int32)
     for i, s in enumerate(samples):
         read_off[i + 1] = read_off[i] + s.nReads
     cat = lambda name: (np.concatenate([np.asarray(getattr(s, name), dtype=np.int32) for s in samples])
                         if n else np.zeros(0, dtype=np.int32))
-    return read_off, cat("read_ptr"), cat("u"), cat("bq"), cat("wif")
+    return read_off, cat("read_ptr"), cat("u"), cat("bq"), cat("wif") if wif else None
 
 
 def make_rare_common(rc, rc_handles, samples):

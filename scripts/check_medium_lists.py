@@ -19,14 +19,11 @@ for tag, be in (("gpu", HipBackend(dev)), ("cpu", OracleBackend(panel))):
     be.select_on_device = False
     d = Driver(panel, be, prm)
     ch = ChainState(smp, i_sample, i_chain, chain_rng(prm.seed, i_sample, i_chain))
-    # the first half of Driver._round: draws + the Gibbs call
+    # the first stages of Driver._round: the draws and the Gibbs call
     P = d.params
-    R = smp.nReads
-    ch.which_haps_to_use = np.sort(ch.rng.choice(panel.K, size=P.Ksubset, replace=False) + 1).astype(np.int32)
-    H0 = ch.rng.integers(1, 3, size=R).astype(np.int32)
-    sr, fr, ss = int(ch.rng.integers(0, 2 ** 63)), int(ch.rng.integers(0, R)), int(ch.rng.integers(0, 2 ** 63))
-    res = d._gibbs_with_retry([ch], [smp], [H0], [sr], [fr], [ss], gibbs_initialize_iteratively=True)
-    ch.read_labels = res[0]["double_list_of_ending_read_labels"][0][0].astype(np.int32)
+    starts, seed_reads, first_reads, seed_shards, any_first = d._draw([ch], 1)
+    res = d._gibbs_with_retry([ch], [smp], starts, seed_reads, first_reads, seed_shards, gibbs_initialize_iteratively=any_first)
+    d._adopt_labels([ch], res)
     lists = d._full_lists(ch)   # [label][thinned grid] -> 1-based haplotypes, best first
     # and the values: a thin pass again, raw
     per_base = np.repeat(ch.read_labels, np.diff(smp.read_ptr))

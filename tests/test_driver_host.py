@@ -650,3 +650,81 @@ def test_phred_eps_is_the_c_librarys_pow():
     from quilt_amd.driver import phred_eps
     q = np.arange(-93, 94)
     assert all(float(e) == math.pow(10.0, -abs(int(v)) / 10.0) for e, v in zip(phred_eps(q), q))
+
+
+def _design_stage_rows():
+    """(stage of quilt_amd/driver.py, when it runs) from the table of DESIGN section 5, "The specification in the same stages"."""
+    import os
+    import re
+    text = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "DESIGN.md")).read()
+    table = text.split("**The specification in the same stages.**")[1].split("\n\n")[1]
+    rows = [[c.strip() for c in line.strip("|").split("|")] for line in table.splitlines()[2:]]
+    return [(re.match(r"`(\w+)`", r[0]).group(1), r[2]) for r in rows]
+
+
+def test_flatten_samples_and_the_order_of_a_rounds_stages():
+    """impute.flatten_samples (the one Python packer of reads) against arrays built by hand; and the stages of Driver._round, in
+    the order they run, against the list in DESIGN section 5 -- for a first round, a last seek iteration, msPBWT and an hla
+    iteration."""
+    from quilt_amd.impute import flatten_samples
+    from quilt_amd.synth import SampleReads, make_synthetic_panel, make_synthetic_sample
+    from tests.hla_backend import OracleBackendHLA
+    from tests.oracle_backend import OracleBackend
+    i32 = lambda *a: np.array(a, dtype=np.int32)
+    a = SampleReads(read_ptr=i32(0, 2, 3), u=i32(4, 9, 7), bq=i32(30, -20, 11), wif=i32(0, 0))
+    b = SampleReads(read_ptr=i32(0, 1), u=i32(5), bq=i32(-7), wif=i32(1))
+    c = SampleReads(read_ptr=i32(0, 1, 3, 6), u=i32(1, 2, 3, 40, 41, 42), bq=i32(9, -9, 8, -8, 7, -7), wif=i32(0, 0, 1))
+    for smp, want in (([], (i32(0), i32(), i32(), i32(), i32())),
+                      ([b], (i32(0, 1), b.read_ptr, b.u, b.bq, b.wif)),
+                      ([a, b, c], (i32(0, 2, 3, 6), i32(0, 2, 3, 0, 1, 0, 1, 3, 6), i32(4, 9, 7, 5, 1, 2, 3, 40, 41, 42),
+                                   i32(30, -20, 11, -7, 9, -9, 8, -8, 7, -7), i32(0, 0, 1, 0, 0, 1)))):
+        got = flatten_samples(smp)
+        assert len(got) == 5
+        for g, w in zip(got, want):
+            assert g.dtype == np.int32 and g.flags.c_contiguous and np.array_equal(g, w)
+        assert flatten_samples(smp, wif=False)[4] is None
+        assert all(np.array_equal(g, w) for g, w in zip(flatten_samples(smp, wif=False)[:4], want))
+
+    rows = _design_stage_rows()
+    stages = sorted({name for name, _ in rows})
+    assert {"_draw", "_gibbs_with_retry", "_select_by_mspbwt", "_marshal_fullpass", "_call_fullpass", "_check_dosage_range",
+            "_adopt_selections", "_keep_round_haps"} <= set(stages)
+
+    class Recording(D.Driver):
+        rounds = None
+
+        def _round(self, chains, i_it):
+            self.rounds.append((i_it, []))
+            return super()._round(chains, i_it)
+
+    def record(name):
+        def stage(self, *a, **kw):
+            self.rounds[-1][1].append(name)
+            return getattr(super(Recording, self), name)(*a, **kw)
+        return stage
+    for name in stages:
+        assert callable(getattr(D.Driver, name)), name
+        setattr(Recording, name, record(name))
+
+    def expected(mspbwt, dosages_count, hla_it):
+        on = {"always": True, "msPBWT": mspbwt, "msPBWT, dosages count": mspbwt and dosages_count, "full-panel": not mspbwt,
+              "full-panel, hla iteration": not mspbwt and hla_it, "full-panel, dosages count": not mspbwt and dosages_count}
+        return [name for name, when in rows if on[when]]
+
+    panel = make_synthetic_panel(K=400, nSNPs=320, seed=21)
+    samples = [make_synthetic_sample(panel, seed=50, n_reads=50)]
+    base = dict(nGibbsSamples=2, Ksubset=64, Knew=64, seed=9)
+    runs = [("full-panel", OracleBackend(panel), D.DriverParams(**base)),
+            ("msPBWT", OracleBackend(panel), D.DriverParams(**base, use_mspbwt=True, mspbwt_nindices=2)),
+            ("hla", OracleBackendHLA(panel), D.HlaDriverParams(**base, hla_grid=panel.nGrids // 2))]
+    for kind, be, prm in runs:
+        drv = Recording(panel, be, prm)
+        drv.rounds = []
+        drv.run(samples)
+        n = drv.params.n_seek_its
+        assert [i for i, _ in drv.rounds] == list(range(1, n + 1)) * 2 and n == 3   # main rounds, then the phasing rounds
+        for i_it, got in drv.rounds:   # the first round, a burn-in round and the last seek iteration of both kinds of chains
+            want = expected(kind == "msPBWT", i_it > drv.params.n_burn_in_seek_its, kind == "hla" and i_it == n)
+            assert got == want, (kind, i_it, got, want)
+    # the kinds differ where the table says they do
+    assert expected(False, False, False) != expected(False, True, False) != expected(False, True, True) != expected(True, True, False)

@@ -2033,6 +2033,22 @@ void run_group(const ReadsCall &c, const Group &grp, ReadsWork &w) {
     }
 }
 
+// launch_select launched nothing (tables beyond the LDS): every chain is left to the caller's host path -- status 1 for a chain
+// that wanted a selection, -1 for one that did not, as k_select itself reports them
+void statuses_when_not_launched(const int32_t *want, int n_chain, int32_t *status) {
+    for (int i = 0; i < n_chain; i++) status[i] = want[i] ? 1 : -1;
+}
+
+// what a selection may be asked for: the public entries and the test hook (fullpass_testhook.h) refuse the same calls
+bool selection_sizes_ok(int K, int Ksubset, int Knew, int K_top_matches) {
+    return Ksubset >= 1 && Ksubset <= K && Knew >= 0 && Knew <= Ksubset && K_top_matches >= 1;
+}
+bool which_in_range(const int32_t *which, size_t n, int K) {
+    for (size_t i = 0; i < n; i++)
+        if (which[i] < 1 || which[i] > K) return false;
+    return true;
+}
+
 // everything_select_good_haps for every chain that asked for lists (select.hip), on the lists still on the device
 void select_on_device(const ReadsCall &c, ReadsWork &w) {
     const SelectArgs *sel = c.sel;
@@ -2057,8 +2073,8 @@ void select_on_device(const ReadsCall &c, ReadsWork &w) {
     if (launched) {
         a.next.download(sel->which_next, (size_t)n_chain * sel->Ksubset, st);
         a.stat.download(sel->status, n_chain, st);
-    } else {   // tables beyond the LDS: every chain is left to the caller's host path
-        for (int i = 0; i < n_chain; i++) sel->status[i] = want[i] ? 1 : -1;
+    } else {
+        statuses_when_not_launched(want.data(), n_chain, sel->status);
     }
     QA_HIP(hipStreamSynchronize(st));
     float ms = 0;
@@ -2078,8 +2094,8 @@ int fullpass_reads_impl(const ReadsCall &c) {
         qa::set_error("qa_fullpass_reads_batch: bad argument");
         return QA_ERR_INVALID;
     }
-    if (sel && (sel->Ksubset < 1 || sel->Ksubset > panel->K || sel->Knew < 0 || sel->Knew > sel->Ksubset || !sel->which ||
-                !sel->seed || !sel->which_next || !sel->status || c.K_top_matches < 1)) {
+    if (sel && (!selection_sizes_ok(panel->K, sel->Ksubset, sel->Knew, c.K_top_matches) || !sel->which || !sel->seed ||
+                !sel->which_next || !sel->status)) {
         qa::set_error("qa_fullpass_reads_select_batch: bad selection argument");
         return QA_ERR_INVALID;
     }
@@ -2091,12 +2107,10 @@ int fullpass_reads_impl(const ReadsCall &c) {
         const int st = qa::gamma_column_check(panel, "qa_fullpass_reads_select_gamma_batch");
         if (st != QA_OK) return st;
     }
-    if (sel)
-        for (size_t i = 0; i < (size_t)c.n_chain * sel->Ksubset; i++)
-            if (sel->which[i] < 1 || sel->which[i] > panel->K) {
-                qa::set_error("qa_fullpass_reads_select_batch: which_haps_to_use out of range");
-                return QA_ERR_INVALID;
-            }
+    if (sel && !which_in_range(sel->which, (size_t)c.n_chain * sel->Ksubset, panel->K)) {
+        qa::set_error("qa_fullpass_reads_select_batch: which_haps_to_use out of range");
+        return QA_ERR_INVALID;
+    }
     return qa::guarded([&] {
         QA_HIP(hipSetDevice(panel->device));
         if (!panel->scratch) panel->scratch = new qa_panel::Scratch(&panel->A());
@@ -2191,6 +2205,52 @@ int qa_fullpass_reads_select_gamma_batch(qa_panel_t *panel, int32_t n_chain, int
     return fullpass_reads_impl(ReadsCall{panel, n_chain, n_label, n_sample, chain_sample, read_off, read_ptr, u, bq, H, want_dosage,
                                          want_top, gammaSmall_cols_to_get, K_top_matches, minGLValue, dosage, top_width, top_idx,
                                          top_val, top_cnt, &sel, gamma_grid, gamma_col});
+}
+
+// fullpass_testhook.h: the selection kernel on lists the caller supplies
+int qa_select_from_lists(int32_t n_chain, int32_t n_label, int32_t n_thin, int32_t top_width, int32_t K_top_matches, int32_t K,
+                         int32_t Ksubset, int32_t Knew, const int32_t *top, const int32_t *which, const uint64_t *seed,
+                         const int32_t *want, int32_t *which_next, int32_t *status) {
+    if (!qa::device_ready()) return QA_ERR_NO_DEVICE;
+    if (n_chain <= 0 || n_label < 1 || n_label > 3 || n_thin < 1 || K < 1 || !top || !which || !seed || !want || !which_next || !status ||
+        top_width < K_top_matches || top_width > 64) {
+        qa::set_error("qa_select_from_lists: bad argument");
+        return QA_ERR_INVALID;
+    }
+    if (!selection_sizes_ok(K, Ksubset, Knew, K_top_matches)) {
+        qa::set_error("qa_select_from_lists: bad selection argument");
+        return QA_ERR_INVALID;
+    }
+    const size_t n_top = (size_t)n_chain * n_label * n_thin * top_width, n_which = (size_t)n_chain * Ksubset;
+    if (!which_in_range(which, n_which, K)) {
+        qa::set_error("qa_select_from_lists: which_haps_to_use out of range");
+        return QA_ERR_INVALID;
+    }
+    for (size_t i = 0; i < n_top; i++)   // (the product's table comes from k_topk; here from a caller)
+        if (top[i] < -1 || top[i] >= K) {
+            qa::set_error("qa_select_from_lists: list entry out of range");
+            return QA_ERR_INVALID;
+        }
+    return qa::guarded([&] {
+        qa::DBuf<int32_t> d_top(n_top), d_which(n_which), d_want(n_chain), d_next(n_which), d_stat(n_chain);
+        qa::DBuf<uint64_t> d_seed(n_chain);
+        hipStream_t st = nullptr;
+        d_top.upload(top, n_top, st); d_which.upload(which, n_which, st); d_want.upload(want, n_chain, st);
+        d_seed.upload(seed, n_chain, st);
+        d_next.upload(which_next, n_which, st);   // rows of chains that are not wanted, or handed back, stay as the caller filled them
+        qa::SelectParams sp{};
+        sp.n_label = n_label; sp.n_thin = n_thin; sp.top_width = top_width; sp.K_top_matches = K_top_matches; sp.K = K;
+        sp.Ksubset = Ksubset; sp.Knew = Knew; sp.top = d_top.p; sp.which = d_which.p; sp.seed = d_seed.p;
+        sp.want = d_want.p; sp.out = d_next.p; sp.status = d_stat.p;
+        if (qa::launch_select(sp, n_chain, st)) {
+            d_next.download(which_next, n_which, st);
+            d_stat.download(status, n_chain, st);
+        } else {
+            statuses_when_not_launched(want, n_chain, status);
+        }
+        QA_HIP(hipStreamSynchronize(st));
+        return (int)QA_OK;
+    });
 }
 
 }  // extern "C"

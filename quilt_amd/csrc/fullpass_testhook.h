@@ -26,6 +26,16 @@ int qa_fullpass_launch_set(qa_panel_t *panel, int32_t n_pass, const double *gl, 
                            const int32_t *gammaSmall_cols_to_get, int32_t K_top_matches, int32_t always_normalize,
                            double *dosage, double *c, int32_t *best_ptr, int32_t *best_idx, double *best_val, int64_t best_cap);
 
+/* The selection kernel (csrc/select.hip: qa::launch_select) on lists the CALLER supplies, without a full-panel pass in front:
+ * top [n_chain][n_label][n_thin][top_width] 0-based haplotypes, best first, -1 = no entry; which [n_chain][Ksubset] 1-based;
+ * seed, want [n_chain]; which_next [n_chain][Ksubset] and status [n_chain] as qa_fullpass_reads_select_batch returns them (a row
+ * of which_next whose chain is not wanted, or is handed back with status 1 before anything was written, keeps what the caller
+ * put there).  The argument checks are those of the public entry.  tests/test_support_geometry_gpu.py steers the kernel through
+ * it to the list shapes a real pass cannot be made to produce. */
+int qa_select_from_lists(int32_t n_chain, int32_t n_label, int32_t n_thin, int32_t top_width, int32_t K_top_matches, int32_t K,
+                         int32_t Ksubset, int32_t Knew, const int32_t *top, const int32_t *which, const uint64_t *seed,
+                         const int32_t *want, int32_t *which_next, int32_t *status);
+
 #ifdef __cplusplus
 }
 #endif

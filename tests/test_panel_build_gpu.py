@@ -4,26 +4,10 @@ and the hot path on a device-built panel against the oracle."""
 import numpy as np
 import pytest
 
+from tests.util import check_panel_tables as _check_tables
 from tests.util import label_gl, thin_cols
 
 pytestmark = pytest.mark.gpu
-
-
-def _check_tables(panel, nMaxDH):
-    from quilt_amd.native import DevicePanel
-    from quilt_amd.panel import make_rhb_t_equality
-    ref = make_rhb_t_equality(panel.rhb_t, nMaxDH, panel.nSNPs, panel.ref_error)
-    dev = DevicePanel.from_rhb(panel, nMaxDH=nMaxDH)
-    hm, B, off, sk, sw = dev.export_tables()
-    assert np.array_equal(hm, ref["hapMatcherR"])
-    assert np.array_equal(B, ref["distinctHapsB"])
-    # specials: per grid the haplotypes with code 0, ascending, with their words
-    G = panel.nGrids
-    for g in range(G):
-        ks = np.nonzero(ref["hapMatcherR"][:, g] == 0)[0]
-        assert np.array_equal(sk[off[g]:off[g + 1]], ks)
-        assert np.array_equal(sw[off[g]:off[g + 1]], panel.rhb_t[ks, g])
-    dev.close()
 
 
 @pytest.mark.parametrize("nMaxDH", [255, 40, 3])

@@ -120,3 +120,22 @@ def gibbs_compare(got, ref, Ks):
     np.testing.assert_allclose(got["hapProbs_t"], ref["hapProbs_t"], rtol=GIBBS_RTOL, atol=1e-14)
     np.testing.assert_allclose(got["genProbsM_t"], ref["genProbsM_t"], rtol=GIBBS_RTOL, atol=1e-14)
     np.testing.assert_allclose(got["genProbsF_t"], ref["genProbsF_t"], rtol=GIBBS_RTOL, atol=1e-14)
+
+
+def check_panel_tables(panel, nMaxDH):
+    """The tables of a device-built panel (qa_panel_create_from_rhb) against the host restatement of STITCH::make_rhb_t_equality:
+    hapMatcherR, distinctHapsB, and per grid the specials -- the haplotypes with code 0, ascending, with their words."""
+    from quilt_amd.native import DevicePanel
+    from quilt_amd.panel import make_rhb_t_equality
+    ref = make_rhb_t_equality(panel.rhb_t, nMaxDH, panel.nSNPs, panel.ref_error)
+    dev = DevicePanel.from_rhb(panel, nMaxDH=nMaxDH)
+    hm, B, off, sk, sw = dev.export_tables()
+    assert np.array_equal(hm, ref["hapMatcherR"])
+    assert np.array_equal(B, ref["distinctHapsB"])
+    # specials: per grid the haplotypes with code 0, ascending, with their words
+    G = panel.nGrids
+    for g in range(G):
+        ks = np.nonzero(ref["hapMatcherR"][:, g] == 0)[0]
+        assert np.array_equal(sk[off[g]:off[g + 1]], ks)
+        assert np.array_equal(sw[off[g]:off[g + 1]], panel.rhb_t[ks, g])
+    dev.close()

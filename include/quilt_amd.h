@@ -106,7 +106,9 @@ typedef struct {
     int32_t use_eMatDH_special_symbols; /* 1: decode specials from the matrix (with the
                                            reference's search, gibbs-small.cpp:69-105);
                                            0: from rhb_t                               */
-    const double *transMatRate_t; /* 2 x (nGrids-1): sigma, 1 - sigma                  */
+    const double *transMatRate_t; /* 2 x (nGrids-1): sigma, 1 - sigma (empty, and may
+                                     be NULL, when nGrids == 1; also in
+                                     qa_panel_create_from_rhb)                          */
     double ref_error;
 } qa_panel_desc_t;
 

@@ -106,6 +106,8 @@ __device__ __forceinline__ bool has_zero_byte2(uint32_t a, uint32_t b) { return 
 // of the grid's ascending list, starting at sp_chunk_at[grid][chunk] (precomputed at panel upload: no search here).
 // (Zero codes of the padding beyond K count as specials too: they come after the real ones and read the 16 zero entries
 // k_emat appends to every grid's list, which keeps their state at 0.)  Returns the number of zero codes seen.
+// APPLY = false: the count alone, for a step that applies no emission and still has to place the next half's specials.
+template <bool APPLY = true>
 __device__ __forceinline__ int special_half(double (&x)[8], uint32_t w0, uint32_t w1, const double *esp_at) {
     const uint32_t w[2] = {w0, w1};
     int at = 0;
@@ -113,7 +115,7 @@ __device__ __forceinline__ int special_half(double (&x)[8], uint32_t w0, uint32_
     for (int i = 0; i < 8; i++) {
         const uint32_t code = (w[i >> 2] >> ((i & 3) * 8)) & 0xffu;
         if (code == 0) {
-            x[i] *= esp_at[at];
+            if constexpr (APPLY) x[i] *= esp_at[at];
             at++;
         }
     }
@@ -995,6 +997,8 @@ __global__ __launch_bounds__(kNT) void k_bwd64d(PassParams prm, int n_last) {
                 if (EMIT) {
                     if (sp) n_sp += special_half(x, w0, w1, esp + at);
                     psum += sum8(x);
+                } else if (sp) {
+                    n_sp += special_half<false>(x, w0, w1, nullptr);   // grid 0's epilogue applies no emission: the second half's specials still follow the first's
                 }
             };
             if constexpr (j < NR) {
@@ -1060,6 +1064,8 @@ __global__ __launch_bounds__(kNT) void k_bwd64d(PassParams prm, int n_last) {
                         psum += sum8(x);
 #pragma unroll
                         for (int q = 0; q < 4; q++) st[q * NT] = make_double2(x[2 * q], x[2 * q + 1]);
+                    } else if (sp) {
+                        n_sp += special_half<false>(x, w0, w1, nullptr);
                     }
                 }
             }

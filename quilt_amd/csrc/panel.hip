@@ -289,7 +289,7 @@ int qa_panel_create(const qa_panel_desc_t *d, qa_panel_t **out) {
     *out = nullptr;
     if (!qa::device_ready()) return QA_ERR_NO_DEVICE;
     if (!d || d->K <= 0 || d->nGrids <= 0 || d->nSNPs <= 0 || d->nMaxDH <= 0 || !d->distinctHapsB ||
-        !d->transMatRate_t || !d->eMatDH_special_grid_which || (!d->hapMatcherR && !d->hapMatcher)) {
+        (!d->transMatRate_t && d->nGrids > 1) || !d->eMatDH_special_grid_which || (!d->hapMatcherR && !d->hapMatcher)) {
         qa::set_error("qa_panel_create: missing panel table");
         return QA_ERR_INVALID;
     }

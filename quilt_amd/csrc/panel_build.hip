@@ -247,7 +247,7 @@ int qa_panel_create_from_rhb(const int32_t *rhb_t, int32_t K, int32_t nGrids, in
     if (!out) return QA_ERR_INVALID;
     *out = nullptr;
     if (!qa::device_ready()) return QA_ERR_NO_DEVICE;
-    if (!rhb_t || K <= 0 || nGrids <= 0 || nSNPs <= 0 || !transMatRate_t || (nSNPs + 31) / 32 != nGrids) {
+    if (!rhb_t || K <= 0 || nGrids <= 0 || nSNPs <= 0 || (!transMatRate_t && nGrids > 1) || (nSNPs + 31) / 32 != nGrids) {
         qa::set_error("qa_panel_create_from_rhb: bad argument (nGrids must be ceil(nSNPs / 32))");
         return QA_ERR_INVALID;
     }

@@ -49,8 +49,8 @@ class RhbPanel:
 
 
 def trans_mat(G):
-    """transMatRate_t (2 x (G - 1)).  G = 1 has no transition: the array keeps ONE unused column there, because
-    qa_panel_create_from_rhb refuses a null pointer and reads G - 1 = 0 columns of whatever it is given."""
+    """transMatRate_t (2 x (G - 1)).  G = 1 has no transition: the array keeps ONE unused column there;
+    qa_panel_create_from_rhb reads G - 1 = 0 columns of whatever it is given (tests/test_grid_geometry_gpu.py passes it none)."""
     sigma = np.full(max(G - 1, 1), 0.97)
     return np.asfortranarray(np.stack([sigma, 1.0 - sigma], axis=0))
 

@@ -42,6 +42,11 @@ extern "C" {
 #define QA_KSUBSET_MAX 1024      /* two-label sampler: method = "diploid", common-SNP and rare + common form */
 #define QA_KSUBSET_MAX_NIPT 640  /* three-label sampler: method = "nipt" (ff > 0) */
 
+/* Largest K_top_matches the full-panel pickers are built for: every value in 1..64 runs (up to 8 the fp64 ranking kernels pick
+ * the lists themselves, beyond that the separate picker does); a larger one is refused with QA_ERR_UNSUPPORTED before any
+ * allocation or device work -- by the range call before its first sample. */
+#define QA_K_TOP_MATCHES_MAX 64
+
 /* ---- library ------------------------------------------------------------ */
 
 /* ABI version of this header (bumped on any signature change). */
@@ -242,7 +247,7 @@ int qa_panel_set_pass_priority(qa_panel_t *panel, int32_t on);
 
 /* Flags of Rcpp_haploid_dosage_versus_refs (QUILT/src/reference-single.cpp:2214-2227). */
 typedef struct {
-    int32_t K_top_matches;
+    int32_t K_top_matches;        /* 1..QA_K_TOP_MATCHES_MAX (64) when get_best_haps_from_thinned_sites is set */
     int32_t return_betaHat_t, return_dosage, return_gamma_t, return_gammaSmall_t;
     int32_t get_best_haps_from_thinned_sites;
     int32_t always_normalize;     /* honoured by every pass with fp64 state (the ranking passes, the dosage passes of a handle
@@ -306,7 +311,8 @@ int qa_Rcpp_make_gl_bound(double *gl, double minGLValue, const int32_t *to_fix, 
  * matrices; want_dosage[i] selects a "dosage" pass (else a "thin" pass: only
  * best-haps at the thinned grids, functions.R:748).  Outputs are stacked per pass:
  * dosage n_pass x nSNPs (rows of skipped passes untouched); best_* as above with
- * n_pass * n_thin entries (pass-major).
+ * n_pass * n_thin entries (pass-major).  K_top_matches: 0 (no lists) or 1..QA_K_TOP_MATCHES_MAX (64); QA_ERR_UNSUPPORTED
+ * beyond, before anything is allocated.
  */
 int qa_fullpass_batch(
     qa_panel_t *panel, int32_t n_pass, const double *gl, const int32_t *want_dosage,
@@ -331,6 +337,8 @@ int qa_fullpass_batch(
  *   dosage            n_chain x n_label x nSNPs (rows of thin passes untouched); may be NULL
  *   top_idx/top_val   n_chain x n_label x n_thin x top_width: 0-based haplotypes / values, best first, -1 padded
  *   top_cnt           n_chain x n_label x n_thin: full length of each list (> top_width means truncated)
+ *   K_top_matches     1..QA_K_TOP_MATCHES_MAX (64), and top_width in K_top_matches..64 (this entry and the two forms below);
+ *                     a larger K_top_matches is QA_ERR_UNSUPPORTED before anything is allocated
  */
 int qa_fullpass_reads_batch(qa_panel_t *panel, int32_t n_chain, int32_t n_label, int32_t n_sample,
                             const int32_t *chain_sample, const int32_t *read_off, const int32_t *read_ptr,
@@ -731,7 +739,8 @@ typedef struct {
     int32_t Ksubset, Knew;                      /* 600, 600; a panel with K < Ksubset: one seek iteration on all of it (quilt.R:453-471).
                                                    Ksubset AFTER that reset must be in 1..QA_KSUBSET_MAX (1024), with nipt set in
                                                    1..QA_KSUBSET_MAX_NIPT (640): QA_ERR_UNSUPPORTED before the first sample otherwise */
-    int32_t K_top_matches;                      /* 5 */
+    int32_t K_top_matches;                      /* 5; 1..QA_K_TOP_MATCHES_MAX (64): QA_ERR_UNSUPPORTED before the first sample
+                                                   otherwise (also with use_mspbwt, which never ranks the full panel) */
     double heuristic_match_thin;                /* 0.1 */
     int32_t small_ref_panel_gibbs_iterations;   /* 20 */
     int32_t n_gibbs_sample_its;                 /* 1 */

@@ -483,8 +483,19 @@ __global__ __launch_bounds__(MAXT) void k_bwd(PassParams prm) {
 // threshold = K_top-th largest gamma counted with multiplicity; every k with gamma >= threshold is
 // reported with gamma * not_jump_prob.  One block per (thinned column, pass); alpha and beta columns
 // are in the same lane-interleaved order, so gamma is an elementwise product of two coalesced streams.
+// WIDE (K_top in kMaxTop + 1 .. kMaxTopWide): the per-lane lists stay kMaxTop deep, so the K_top-th largest of the 256 x
+// kMaxTop retained values is only a lower bound T of the threshold.  It is the threshold unless some lane dropped a value
+// above it, i.e. unless a lane's whole list lies above T; then the values above T are gathered in LDS (a column pass) and
+// the threshold is their K_top-th largest by rank counting -- or T, when fewer than K_top lie above it.  A gather that
+// outgrows the LDS list raises T to the K_top-th largest of what it caught (still a lower bound: of a subset) and repeats;
+// each round drops at least kWideList - K_top values, and with at most 63 retained values above the first T no more than
+// 7 lanes can hold dropped ones, so up to Kq = 72 448 the first gather already fits.  Lists of up to 64 entries are put
+// in order by rank counting, an entry per thread (the narrow form: by thread 0).
 // ---------------------------------------------------------------------------------------------
-template <typename TS>
+constexpr int kMaxTopWide = 64;   // QA_K_TOP_MATCHES_MAX
+constexpr int kWideList = 2048;   // gathered values above the lower bound (LDS)
+
+template <typename TS, bool WIDE = false>
 __global__ __launch_bounds__(256) void k_topk(PassParams prm, int NT) {
     using V = typename Vec<TS>::V;
     constexpr int EPV = Vec<TS>::EPV, NV = 16 / EPV;
@@ -493,7 +504,8 @@ __global__ __launch_bounds__(256) void k_topk(PassParams prm, int NT) {
     const int tcol = prm.topk_todo ? prm.topk_todo[2 * blockIdx.x + 1] : blockIdx.x;
     const int p = prm.topk_todo ? prm.topk_todo[2 * blockIdx.x] : blockIdx.y;
     const int t = threadIdx.x, lane = t & 63;
-    __shared__ TS s_top[4][kMaxTop];
+    constexpr int kTopW = WIDE ? kMaxTopWide : kMaxTop;   // entries of a wave's merged list
+    __shared__ TS s_top[4][kTopW];
     __shared__ int s_cnt;
     __shared__ int s_g;
     if (t == 0) {
@@ -533,7 +545,7 @@ __global__ __launch_bounds__(256) void k_topk(PassParams prm, int NT) {
             TS x = (k_of(v, r) < prm.K) ? gq[r] : TS(0);
 #pragma unroll
             for (int z = 0; z < kMaxTop; z++) {
-                if (z < Ktop) {
+                if (WIDE || z < Ktop) {
                     const TS hi = ltop[z] > x ? ltop[z] : x;
                     x = ltop[z] > x ? x : ltop[z];
                     ltop[z] = hi;
@@ -541,6 +553,7 @@ __global__ __launch_bounds__(256) void k_topk(PassParams prm, int NT) {
             }
         }
     }
+    const TS lane_min = ltop[kMaxTop - 1];   // (WIDE) everything this lane dropped is <= this
     // wave merge: pop the maximum Ktop times
     for (int r = 0; r < Ktop; r++) {
         const TS m = wave_max(ltop[0]);
@@ -568,6 +581,40 @@ __global__ __launch_bounds__(256) void k_topk(PassParams prm, int NT) {
                 pos++;
                 head = (pos < Ktop) ? s_top[lane][pos] : TS(0);
             }
+        }
+    }
+    if constexpr (WIDE) {
+        __shared__ TS s_list[kWideList];
+        __shared__ TS s_thr;
+        bool dropped_above = lane_min > thr;
+        while (__syncthreads_or(dropped_above)) {   // (the barrier also covers s_cnt = 0 and the last round's reads of s_list)
+            for (int v = t; v < nvec; v += 256) {
+                if (k_of(v, 0) >= prm.K) continue;
+                TS gq[EPV];
+                gamma_of(v, gq);
+#pragma unroll
+                for (int r = 0; r < EPV; r++) {
+                    if (k_of(v, r) < prm.K && gq[r] > thr) {
+                        const int at = atomicAdd(&s_cnt, 1);
+                        if (at < kWideList) s_list[at] = gq[r];
+                    }
+                }
+            }
+            __syncthreads();
+            const int n_gt = s_cnt, n = min(n_gt, kWideList);
+            if (n >= Ktop) {
+                // the Ktop-th largest of the list, counted with multiplicity: x with #(> x) < Ktop <= #(>= x)
+                for (int i = t; i < n; i += 256) {
+                    const TS x = s_list[i];
+                    int gt = 0, ge = 0;
+                    for (int j = 0; j < n; j++) { const TS y = s_list[j]; gt += y > x; ge += y >= x; }
+                    if (gt < Ktop && Ktop <= ge) s_thr = x;   // (every writer writes the same value)
+                }
+            }
+            __syncthreads();
+            if (n >= Ktop) thr = s_thr;
+            if (t == 0) s_cnt = 0;
+            dropped_above = n_gt > kWideList;   // the list was a subset: thr is a better lower bound, gather again
         }
     }
     const TS fs = (g < prm.G - 1) ? (TS)prm.sigma[g] : TS(1);
@@ -635,6 +682,27 @@ __global__ __launch_bounds__(256) void k_topk(PassParams prm, int NT) {
             }
         }
         __syncthreads();
+    }
+    if constexpr (WIDE) {
+        // the same order by rank counting, an entry per thread: thread 0's insertion sort below moves a list of 64 through global
+        // memory about a thousand times (0.4 ms per block; a third of the kernel's time at K_top = 64)
+        __shared__ int32_t s_oi[64];
+        __shared__ TS s_ov[64];
+        const int n = min(min(s_cnt, prm.top_cap), n_all);
+        if (n <= 64 && (n_all <= prm.top_cap || prm.truncate_lists)) {   // (uniform over the block)
+            if (t < n) { s_oi[t] = oi[t]; s_ov[t] = ov[t]; }
+            __syncthreads();
+            if (t < n) {
+                const int ki = s_oi[t];
+                const TS vi = s_ov[t];
+                int rank = 0;
+                for (int j = 0; j < n; j++) rank += (s_ov[j] > vi || (s_ov[j] == vi && s_oi[j] < ki)) ? 1 : 0;
+                oi[rank] = ki;
+                ov[rank] = vi;
+            }
+        }
+        if (t == 0) prm.top_cnt[(size_t)p * prm.n_thin + tcol] = n_all;
+        return;
     }
     if (t == 0) {
         prm.top_cnt[(size_t)p * prm.n_thin + tcol] = n_all;
@@ -1087,6 +1155,14 @@ struct PassRun {
     size_t es() const { return L.es; }
 };
 
+// K_top_matches beyond what the pickers are built for (QA_K_TOP_MATCHES_MAX): said by every entry before it allocates
+static_assert(kMaxTopWide == QA_K_TOP_MATCHES_MAX, "k_topk's wide form covers the documented range");
+int check_k_top(const char *who, int K_top) {
+    if (K_top <= QA_K_TOP_MATCHES_MAX) return QA_OK;
+    qa::set_error("%s: K_top_matches = %d is not built: every K_top_matches in 1..%d runs", who, K_top, QA_K_TOP_MATCHES_MAX);
+    return QA_ERR_UNSUPPORTED;
+}
+
 // the request against what the kind can yield
 void check_request(const qa_panel *pn, PassKind kind, int P, const int32_t *h_flags, int K_top, const BatchOut &out) {
     if (kind == KIND_F64_RANK)
@@ -1234,6 +1310,19 @@ void launch_passes(PassRun &r) {
     QA_HIP(hipEventRecord(S.ev[4], st));
 }
 
+// k_topk over `grid` blocks: the state's element type, and the wide form beyond the per-lane lists' kMaxTop
+void launch_topk(const PassRun &r, dim3 grid) {
+    const bool wide = r.prm.K_top > kMaxTop;
+    if (r.geo.f64()) {
+        if (wide) hipLaunchKernelGGL((k_topk<double, true>), grid, dim3(256), 0, r.st, r.prm, r.geo.NT);
+        else hipLaunchKernelGGL(k_topk<double>, grid, dim3(256), 0, r.st, r.prm, r.geo.NT);
+    } else {
+        if (wide) hipLaunchKernelGGL((k_topk<float, true>), grid, dim3(256), 0, r.st, r.prm, r.geo.NT);
+        else hipLaunchKernelGGL(k_topk<float>, grid, dim3(256), 0, r.st, r.prm, r.geo.NT);
+    }
+    QA_HIP(hipGetLastError());
+}
+
 // fused: the backward kernel wrote the lists; the grids whose candidates overflowed its LDS list (top_cnt = -1: ties)
 // left their beta column for k_topk
 void finish_fused_lists(PassRun &r) {
@@ -1251,8 +1340,7 @@ void finish_fused_lists(PassRun &r) {
     S.todo.ensure(todo.size());
     S.todo.upload(todo.data(), todo.size(), st);
     prm.topk_todo = S.todo.p;
-    hipLaunchKernelGGL(k_topk<double>, dim3(r.n_handed_over), dim3(256), 0, st, prm, r.geo.NT);
-    QA_HIP(hipGetLastError());
+    launch_topk(r, dim3(r.n_handed_over));
     S.top_cnt.download(r.cnt.data(), r.cnt.size(), st);
     QA_HIP(hipStreamSynchronize(st));
     prm.topk_todo = nullptr;
@@ -1272,9 +1360,7 @@ void pick_lists_separately(PassRun &r) {
         }
         prm.top_cap = r.top_cap;
         prm.top_cnt = S.top_cnt.p; prm.top_idx = S.top_idx.p; prm.top_val = S.top_val.p;
-        if (r.geo.f64()) hipLaunchKernelGGL(k_topk<double>, dim3(n_thin, P), dim3(256), 0, st, prm, r.geo.NT);
-        else hipLaunchKernelGGL(k_topk<float>, dim3(n_thin, P), dim3(256), 0, st, prm, r.geo.NT);
-        QA_HIP(hipGetLastError());
+        launch_topk(r, dim3(n_thin, P));
         r.cnt.resize((size_t)P * n_thin);
         S.top_cnt.download(r.cnt.data(), r.cnt.size(), st);
         QA_HIP(hipStreamSynchronize(st));
@@ -1457,10 +1543,7 @@ void collect_lists(const PassRun &r) {
 int run_passes(qa_panel *pn, int P, const double *gl, const int32_t *h_flags, const int32_t *thin_col_h,
                int K_top, int normalize_emissions, const BatchOut &out, PassKind kind = KIND_F32,
                int always_normalize = 0, double norm_threshold = 1e-100) {
-    if (K_top > kMaxTop) {
-        qa::set_error("K_top_matches = %d > %d not supported", K_top, kMaxTop);
-        return QA_ERR_UNSUPPORTED;
-    }
+    if (const int st = check_k_top("full-panel passes", K_top)) return st;   // (the public entries have said so already)
     const Geometry geo = pick_geometry(pn->K, kind);
     if (geo.NT == 0) {
         qa::set_error("K = %d exceeds the on-chip capacity of the %s full-pass kernels", pn->K, kKindInfo[kind].name);
@@ -1478,7 +1561,8 @@ int run_passes(qa_panel *pn, int P, const double *gl, const int32_t *h_flags, co
     PassRun r{pn, S, st, P, h_flags, thin_col_h, out, geo,
               PassLayout(dims_of(pn), geo, qa::make_request(h_flags, P, thin, K_top, out.top_cap, out.gamma_col != nullptr, out.alpha_grid0)),
               thin.n_thin, any_top,
-              /* fused */ any_top && kind == KIND_F64_RANK && out.truncate_lists && out.top_cap <= 64,
+              /* fused: k_bwd64's picker merges its eight waves' K_top maxima in one wave, K_top <= kMaxTop; wider goes to k_topk */
+              any_top && kind == KIND_F64_RANK && out.truncate_lists && out.top_cap <= 64 && K_top <= kMaxTop,
               out.top_cap, PassParams{}};
 
     const std::vector<int32_t> slot = plan_alpha_slots(r);
@@ -1576,6 +1660,7 @@ int qa_fullpass_launch_set(qa_panel_t *panel, int32_t n_pass, const double *gl, 
         qa::set_error("qa_fullpass_launch_set: bad argument");
         return QA_ERR_INVALID;
     }
+    if (const int st = check_k_top("qa_fullpass_launch_set", K_top_matches)) return st;
     int32_t any = 0;
     for (int i = 0; i < n_pass; i++) {
         if (flags[i] != 0 && flags[i] != 1) {
@@ -1617,6 +1702,8 @@ int qa_Rcpp_haploid_dosage_versus_refs(
         qa::set_error("qa_Rcpp_haploid_dosage_versus_refs: null argument");
         return QA_ERR_INVALID;
     }
+    if (o->get_best_haps_from_thinned_sites)
+        if (const int st = check_k_top("qa_Rcpp_haploid_dosage_versus_refs", o->K_top_matches)) return st;
     // A C caller that zero-initialises the options would ask the lazily normalised fp64 passes never to renormalise between
     // grid 0 and the last grid: alpha underflows over a long region, 1 / run_total = inf, NaN dosages.  A threshold that is not
     // positive (or NaN) is therefore read as "not set" = the reference's default (reference-single.cpp:2216, 1e-100).
@@ -1728,6 +1815,7 @@ int qa_fullpass_batch(qa_panel_t *panel, int32_t n_pass, const double *gl, const
         qa::set_error("qa_fullpass_batch: bad argument");
         return QA_ERR_INVALID;
     }
+    if (const int st = check_k_top("qa_fullpass_batch", K_top_matches)) return st;
     return qa::guarded([&] {
         qa::GateHold hold;
         hold.acquire(panel->gate(), &panel->arena);
@@ -2089,6 +2177,7 @@ int fullpass_reads_impl(const ReadsCall &c) {
     qa_panel_t *panel = c.panel;
     const SelectArgs *sel = c.sel;
     if (!qa::device_ready()) return QA_ERR_NO_DEVICE;
+    if (const int st = check_k_top("qa_fullpass_reads_batch", c.K_top_matches)) return st;
     if (!panel || c.n_chain <= 0 || c.n_label < 1 || c.n_label > 3 || c.n_sample <= 0 || !c.chain_sample || !c.read_off || !c.read_ptr ||
         !c.u || !c.bq || !c.H || !c.want_dosage || !c.gammaSmall_cols_to_get || c.top_width < c.K_top_matches || c.top_width > 64) {
         qa::set_error("qa_fullpass_reads_batch: bad argument");
@@ -2212,6 +2301,7 @@ int qa_select_from_lists(int32_t n_chain, int32_t n_label, int32_t n_thin, int32
                          int32_t Ksubset, int32_t Knew, const int32_t *top, const int32_t *which, const uint64_t *seed,
                          const int32_t *want, int32_t *which_next, int32_t *status) {
     if (!qa::device_ready()) return QA_ERR_NO_DEVICE;
+    if (const int st = check_k_top("qa_select_from_lists", K_top_matches)) return st;
     if (n_chain <= 0 || n_label < 1 || n_label > 3 || n_thin < 1 || K < 1 || !top || !which || !seed || !want || !which_next || !status ||
         top_width < K_top_matches || top_width > 64) {
         qa::set_error("qa_select_from_lists: bad argument");

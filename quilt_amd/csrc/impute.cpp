@@ -1389,6 +1389,12 @@ int impute_impl(bool keep_buffers, const qa_impute_backend_t *be, void *const *h
                       QA_KSUBSET_MAX, QA_KSUBSET_MAX_NIPT);
         return QA_ERR_UNSUPPORTED;
     }
+    // ... and what the full-panel pickers are built for, not said by the first full-panel pass after a round of Gibbs calls
+    if (P.K_top_matches > QA_K_TOP_MATCHES_MAX) {
+        qa::set_error("qa_impute_samples: K_top_matches = %d is not built: every K_top_matches in 1..%d runs", P.K_top_matches,
+                      QA_K_TOP_MATCHES_MAX);
+        return QA_ERR_UNSUPPORTED;
+    }
     if (hla) {   // hla_run: what the range call covers (functions.R:713-724, :1261-1280 with method = "diploid", full-panel passes)
         const char *why = !select_gamma ? "no gamma-column entry point"
                           : !hla->gamma1 || !hla->gamma2 || !hla->gamma_total || !hla->list_of_gammas ? "missing output array"

@@ -33,6 +33,8 @@ from .trace import span
 
 # largest small panel the Gibbs samplers are built for (include/quilt_amd.h: QA_KSUBSET_MAX, QA_KSUBSET_MAX_NIPT)
 KSUBSET_MAX, KSUBSET_MAX_NIPT = 1024, 640
+# largest K_top_matches the full-panel pickers are built for (include/quilt_amd.h: QA_K_TOP_MATCHES_MAX)
+K_TOP_MATCHES_MAX = 64
 
 
 @dataclass
@@ -100,6 +102,8 @@ class DriverParams:
                              f"1..{KSUBSET_MAX}, method = 'nipt': 1..{KSUBSET_MAX_NIPT})")
         if p.K_top_matches < 1:
             raise ValueError("K_top_matches must be >= 1")
+        if p.K_top_matches > K_TOP_MATCHES_MAX:
+            raise ValueError(f"K_top_matches = {p.K_top_matches} is not built: every K_top_matches in 1..{K_TOP_MATCHES_MAX} runs")
         if p.diploid_block_gibbs != "reference_noop":
             raise ValueError("diploid_block_gibbs: only 'reference_noop' exists (the reference's diploid block pass never "
                              "relabels; an 'active' two-label block Gibbs is not built)")

@@ -458,8 +458,8 @@ int qa_last_fullpass_timing_ms(double out[5]);
  * caller varies (QUILT/R/functions.R:2566-2678).  Everything the caller holds constant is fixed at
  * the reference's production value: S = 1, n_gibbs_starts = 1, priorCurrent_m and
  * alphaMatCurrent_tc = 1/Ks, use_small_eHapsCurrent_tc = FALSE, calculate_gamma_on_the_fly = TRUE,
- * pass_in_alphaBeta = TRUE, record_read_set = TRUE, shard_check_every_pair = TRUE,
- * haploid_gibbs_equal_weighting = TRUE, use_starting_read_labels = TRUE. */
+ * pass_in_alphaBeta = TRUE, record_read_set = TRUE, haploid_gibbs_equal_weighting = TRUE,
+ * use_starting_read_labels = TRUE.  (shard_check_every_pair is the member shard_by_blocks below.) */
 typedef struct {
     int32_t Ks;                      /* length(which_haps_to_use) (Ksubset): every value in 1..QA_KSUBSET_MAX (1024) runs with
                                         ff == 0 and every value in 1..QA_KSUBSET_MAX_NIPT (640) with ff > 0; anything else is
@@ -521,6 +521,18 @@ typedef struct {
      * reference's unused runif_proposed / runif_total around what = 0), which keeps set.seed's stream in step with the CPU package. */
     void (*draw_uniforms)(void *ctx, int32_t chain, int32_t pass, int32_t what, int32_t n, double *out);
     void *draw_uniforms_ctx;
+    /* shard_check_every_pair = FALSE (quilt.R:178; appended within ABI 5, 0 = every pair, as before).  Diploid (ff = 0) with
+     * perform_block_gibbs and do_shard_block_gibbs: at every block iteration the blocks are defined from the state the sweep
+     * left (Rcpp_define_blocked_snps_using_gamma_on_the_fly, Rcpp_make_gibbs_considers: gibbs-nipt.cpp:3003-3049) and the shard
+     * pass decides a flip only where a block ends, with uniform b of the pass for block b (gibbs-nipt-block.cpp:2209-2246).
+     * L_grid, shuffle_bin_radius and block_gibbs_quantile_prob above are then required (a NULL L_grid is QA_ERR_INVALID and
+     * qa_last_error names it).  The pass's uniforms: entry j * (nGrids - 1) + b of the chain's runif_shard (or of its seed_shard
+     * stream) for block b of pass j -- entries at or beyond n_blocks - 1 of a pass are not read -- or, with draw_uniforms,
+     *     what = 2   before shard pass `pass` of chain `chain`: n = n_blocks - 1 uniforms (never called with n = 0)
+     * An R caller burns the reference's 8 * nReads unused draws of every block iteration (gibbs-nipt.cpp:3013-3018) before what = 2,
+     * those of the passes it was not asked for (n_blocks = 1) included: shim/quilt_amd_shim.c, draw_shard_uniforms_from_R.
+     * qa_gibbs_batch_rare_common refuses the flag (QA_ERR_UNSUPPORTED); with ff > 0 it is ignored. */
+    int32_t shard_by_blocks;
 } qa_gibbs_opts_t;
 
 /*
@@ -538,7 +550,9 @@ typedef struct {
  *                             what `Rcpp::runif(nReads * n_gibbs_full_its)` returns (gibbs-nipt.cpp:2845)
  *   first_read                per chain `Rcpp::sample(nReads, 1) - 1` (gibbs-nipt.cpp:2846-2848)
  *   runif_shard               n_chain x n_block_gibbs_iterations x (nGrids - 1): the
- *                             `Rcpp::runif(n_blocks - 1)` of each shard pass (gibbs-nipt-block.cpp:2054).
+ *                             `Rcpp::runif(n_blocks - 1)` of each shard pass (gibbs-nipt-block.cpp:2054): one per grid
+ *                             boundary, or (opts->shard_by_blocks) one per block end, the first n_blocks - 1 entries of
+ *                             the pass's nGrids - 1 -- the rest of them are then not read.
  *                             NIPT (ff > 0; no shard pass there): the uniforms of the block passes instead -- per
  *                             chain n_block_gibbs_iterations x 2 x R_c at offset read_off[c] * n_block_gibbs_iterations
  *                             * 2: per pass R_c `runif_block` values (gibbs-nipt.cpp:3016; entry b decides block b),
@@ -732,6 +746,14 @@ typedef struct {
  * Arguments of QUILT() the hot path sees (QUILT/R/quilt.R:97-186), as get_and_impute_one_sample receives them.
  * qa_impute_params_default fills in the reference's defaults.
  */
+/* shard_check_every_pair = FALSE for the loop's diploid Gibbs calls (qa_gibbs_opts_t.shard_by_blocks): what the block
+ * definition takes beyond the state */
+typedef struct {
+    const int32_t *L_grid;                      /* nGrids grid positions (bp) */
+    int32_t shuffle_bin_radius;                 /* quilt.R:134, 5000 */
+    double block_gibbs_quantile_prob;           /* functions.R:2393, 0.95 */
+} qa_impute_shard_blocks_t;
+
 typedef struct {
     int32_t nGibbsSamples;                      /* 7 */
     int32_t n_seek_its;                         /* 3 */
@@ -772,6 +794,11 @@ typedef struct {
     const qa_sample_source_t *sample_source;    /* NULL: every sample's reads are in the flat arrays of the call.  Else the reads are
                                                    handed over sample by sample WHEN THE LOOP REACHES THEM (qa_sample_source_t above):
                                                    the first launch set starts while later samples are still being read from disk */
+    const qa_impute_shard_blocks_t *shard_blocks;   /* NULL: the shard passes decide at every pair of grids (shard_check_every_pair =
+                                                   TRUE).  Else (appended within ABI 5) they go block by block, method = "diploid"
+                                                   only: with nipt set it is ignored (no shard pass there), with rare_common the
+                                                   range is refused with QA_ERR_UNSUPPORTED before the first sample (the all-SNP
+                                                   Gibbs call does not serve the mode); a NULL L_grid in it is QA_ERR_INVALID */
 } qa_impute_params_t;
 int qa_impute_params_default(qa_impute_params_t *params);
 

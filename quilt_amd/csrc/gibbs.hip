@@ -28,7 +28,9 @@
 // identity: c3 is all zero (gibbs-nipt.cpp:2678), so logC_after(2) is -inf and then NaN (:1819-1821,
 // :1896-1898), every choice_log_probs entry is NaN (:661-675), ir_chosen stays 0 (:741-752), the
 // "No change warranted" branch is taken (:830) and the final backward (:1947-1954) reproduces the beta
-// the sweep already holds.  The shard resampler is the active step and is implemented here.
+// the sweep already holds.  The shard resampler is the active step and is implemented here: deciding at every grid inside
+// k_gibbs (shard_check_every_pair = TRUE), or block by block (FALSE: qa_gibbs_opts_t.shard_by_blocks) as segments of sweeps
+// with k_shard_blocks between them (shard_block_sweeps).
 // NIPT (ff > 0): the three-label sampler and its block Gibbs are in gibbs3.hip / gibbs_blocks.hpp; this file drives
 // them (segments of sweeps with a block pass between them, gibbs_chunk) and holds the panel-facing kernels both modes
 // share, including the rare + common forms (k_ematread's rare branch in gibbs_dev.hpp, k_happrobs_rc).
@@ -42,6 +44,7 @@
 #include <cstdlib>
 #include <map>
 #include <memory>
+#include <type_traits>
 
 #include "gibbs_dev.hpp"
 #include "gibbs_blocks.hpp"
@@ -157,7 +160,12 @@ __device__ void backward_both(Chain<NE, NW> &ch) {
 #ifndef QA_LEAN_WAVES
 #define QA_LEAN_WAVES 2
 #endif
-template <int NE, int NW, bool LEAN>
+// SEG: the build for a call whose shard passes go block by block (qa_gibbs_opts_t.shard_by_blocks): the sweeps [it_begin, it_end)
+// of a call cut at its block iterations, as the three-label sampler's are.  A sweep starts from what the one before left in HBM
+// (eMatGrid, beta, c, the labels), so a segment with it_begin > 0 skips the initialisation and goes on; a segment's last sweep
+// keeps its alpha columns (the switch rate of the block definition reads them) and the pass itself is k_shard_blocks.  Every
+// SEG test is a compile-time constant: the builds without it are what they were.
+template <int NE, int NW, bool LEAN, bool SEG = false>
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(LEAN ? QA_LEAN_WAVES : 1))) void k_gibbs(GibbsParams p) {
     __shared__ double s_red[2 * NW * 4];
     // LEAN: the current grid's eMatGrid columns wait in LDS while the grid's reads are sampled (10 KB per chain, 80 KB per
@@ -177,6 +185,9 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(LEAN ? 
     // first_read < 0: this chain starts from its starting labels even in a launch that initialises iteratively
     const bool init_iteratively = p.init_iteratively && first_read >= 0;
 
+    if constexpr (SEG) {
+        if (p.it_begin > 0) goto sweeps;   // (no declaration at function scope lies between here and the label)
+    }
     // ---- c = 0 (arma::zeros, gibbs-nipt.cpp:2676-2678), H_class = 0
     for (int h = 0; h < 3; h++)
         for (int g = t; g < G; g += NT) ch.cv[h][g] = 0.0;
@@ -251,13 +262,18 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(LEAN ? 
     }
     chain_sync<NW>();
 
+sweeps:
     int shard_it = 0;
     int status = 0;
-    for (int it = 0; it < p.n_its && status == 0; it++) {
+    if constexpr (SEG) {
+        if (p.it_begin > 0) status = p.status[c];   // a chain that underflowed in an earlier segment stays stopped
+    }
+    for (int it = SEG ? p.it_begin : 0; it < (SEG ? p.it_end : p.n_its) && status == 0; it++) {
         // ================= rcpp_gibbs_nipt_iterate (:1756-1956) =================
         // H_class (record_read_set, :1142-1165) is overwritten for every sampled read in every sweep, so only
         // the last sweep's value is observable: it is computed there only.
         const bool last_sweep = it == p.n_its - 1;
+        const bool keep_alpha = SEG ? it == p.it_end - 1 : last_sweep;   // (SEG: the sweep a block-wise pass follows, or the last)
         const bool steady = !init_iteratively || it >= 2;   // every sampled read is in "normal progress" (:817-834)
         Col<NE> a[2];   // alpha of the current grid, both labels (also the reference's alphaHat_m)
         int iRead = 0;  // next unprocessed read
@@ -541,7 +557,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(LEAN ? 
             }
             // alphaHat_t is not read again inside the call (the shard pass runs its own forward): only the state left
             // by the last sweep is observable (hapProbs, state_out), so only that sweep writes it
-            if (last_sweep) {
+            if (keep_alpha) {
 #pragma unroll
                 for (int h = 0; h < 2; h++) ch.stm(a[h], ch.alpha[h] + (size_t)g * Ksp);
             }
@@ -591,7 +607,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(LEAN ? 
 #ifdef QA_DBG_SKIP_SHARD
         to_block = false;
 #endif
-        if (to_block && p.do_shard) {
+        if (!SEG && to_block && p.do_shard) {   // (SEG: the segment ends here and k_shard_blocks is the pass)
             // ============ Rcpp_shard_block_gibbs_resampler (gibbs-nipt-block.cpp:1975-2355), ff = 0,
             // shard_check_every_pair: one left-to-right pass deciding at every grid whether everything
             // to the right swaps haplotypes ============
@@ -729,6 +745,164 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(LEAN ? 
         }
     }
     if (t == 0) p.status[c] = status;
+}
+
+// ---------------------------------------------------------------------------------------------
+// k_shard_blocks: Rcpp_shard_block_gibbs_resampler (gibbs-nipt-block.cpp:1975-2355), ff = 0, shard_check_every_pair = FALSE --
+// the pass of k_gibbs above between two segments of sweeps (k_gibbs<.., SEG>), deciding only where a block of the host's table
+// ends (:2209-2214): at grid g with 0 <= where[g] < n_blocks - 1, with uniform where[g] of the pass (:2246).  Between two
+// decisions the flip mode stands.  where[] comes from HBM 64 grids at a time, lane-held like the other per-grid scalars; beta's
+// columns are fetched only at the grids that decide.  A chain whose status is set, or that got no table (n_blocks = 0), is left
+// as it is; with n_blocks = 1 the pass is the forward and backward recomputation alone.
+// The loop restates the pass inside k_gibbs on purpose.  One __forceinline__ body for both (the decision's predicate and the
+// uniform's index as compile-time choices) was built and compared: it changed the instruction stream of all 20 existing k_gibbs
+// builds (k_gibbs<10, 1, true>: 8 290 -> 8 480 instructions), and those stay byte for byte what they were.  A change to the
+// forward step or to the pA / pB decision belongs in both places; tests/test_shard_block_gpu.py and tests/test_gibbs_gpu.py
+// hold each against its own reference.
+// ---------------------------------------------------------------------------------------------
+template <int NE, int NW>
+__global__ __launch_bounds__(64 * NW) void k_shard_blocks(GibbsParams p) {
+    __shared__ double s_red[2 * NW * 4];
+    const int c = blockIdx.x, t = threadIdx.x;
+    using CH = Chain<NE, NW>;
+    CH ch(p, c, t, s_red);
+    constexpr int NT = CH::NT;
+    const int lane = ch.lane;
+    const int G = ch.G, Ksp = ch.Ksp, R = ch.R;
+    const double prior = ch.prior;
+    bool (&valid)[NE] = ch.valid;
+    const int n_decisions = p.blk_n[c] - 1;
+    if (p.status[c] != 0 || n_decisions < 0) return;
+    const int32_t *where = p.blk_where + (size_t)c * G;
+    const uint64_t seed_shard = p.seed_shard ? p.seed_shard[c] : 0;
+    // block b of pass j takes entry j * (G - 1) + b of the chain's uniforms (explicit, or of its counter-based stream)
+    const double *ru = p.runif_shard + ((size_t)c * p.n_block + p.blk_pass) * (G - 1);
+    const bool keep_alpha = p.it_end == p.n_its;   // (only what the call's last sweep leaves is observable, as in k_gibbs)
+    double mloc1, mloc2, mlc1 = 0, mlc2 = 0;
+    {
+        double s[2] = {0, 0};
+        for (int g = t; g < G; g += NT) { s[0] -= log(ch.cv[0][g]); s[1] -= log(ch.cv[1][g]); }
+        ch.template bsum<2>(s);
+        mloc1 = s[0]; mloc2 = s[1];
+    }
+    bool flip = false;
+    int ir = 0, wh = -1;
+    Col<NE> s_a[2];
+    GridStreams<CH> ss;
+    ReadStreams<CH> rr;
+    rr.base = -1;
+    bool rr_dirty = false;
+    for (int g = 0; g < G; g++) {
+        if ((g & 63) == 0) {
+            if (g) ss.store_c(ch);
+            ss.load_fwd(ch, g);
+            wh = (g + lane < G) ? where[g + lane] : -1;
+        }
+        const int jg = g & 63;
+        const double oc1 = rl_f64(ss.c0, jg), oc2 = rl_f64(ss.c1, jg);
+        const int blk = rl_i32(wh, jg);
+        const bool decide = blk >= 0 && blk < n_decisions;   // (never at the last grid: it ends block n_blocks - 1)
+        // in flip mode the grid's eMatGrid columns are fetched crosswise and written back in their new places
+        Col<NE> e2[2];
+        ch.ldm(e2[0], ch.eg[flip ? 1 : 0] + (size_t)g * Ksp);
+        ch.ldm(e2[1], ch.eg[flip ? 0 : 1] + (size_t)g * Ksp);
+        Col<NE> b1, b2;
+        if (decide) {
+            ch.ldm(b1, ch.beta[0] + (size_t)g * Ksp);
+            ch.ldm(b2, ch.beta[1] + (size_t)g * Ksp);
+        }
+        double cn[2];
+        if (g == 0) {
+#pragma unroll
+            for (int h = 0; h < 2; h++) {
+#pragma unroll
+                for (int i = 0; i < NE; i++) s_a[h].v[i] = valid[i] ? prior * e2[h].v[i] : 0.0;
+            }
+            double sm[2];
+            ch.sum_col2(s_a[0], s_a[1], sm[0], sm[1]);
+#pragma unroll
+            for (int h = 0; h < 2; h++) {
+                cn[h] = 1 / sm[h];
+#pragma unroll
+                for (int i = 0; i < NE; i++) s_a[h].v[i] *= cn[h];
+            }
+        } else {
+            if (flip) {
+                ch.stm(e2[0], ch.eg[0] + (size_t)g * Ksp);
+                ch.stm(e2[1], ch.eg[1] + (size_t)g * Ksp);
+            }
+            // rcpp_alpha_forward_one (gibbs-nipt.cpp:627-657), alphaMat = 1/Ks, normalize
+            const double x = rl_f64(ss.t0, jg), t1 = rl_f64(ss.t1, jg);
+            double sp[2];
+            ch.sum_col2(s_a[0], s_a[1], sp[0], sp[1]);
+#pragma unroll
+            for (int h = 0; h < 2; h++) {
+                const double alphaConst = t1 * sp[h];
+                const double c2 = (h == 0) ? oc1 : oc2;
+#pragma unroll
+                for (int i = 0; i < NE; i++)
+                    s_a[h].v[i] = valid[i] ? c2 * e2[h].v[i] * (x * s_a[h].v[i] + alphaConst * prior) : 0.0;
+            }
+            double sm[2];
+            ch.sum_col2(s_a[0], s_a[1], sm[0], sm[1]);
+#pragma unroll
+            for (int h = 0; h < 2; h++) {
+                const double c2 = (h == 0) ? oc1 : oc2;
+                const double aa = 1 / sm[h];
+                cn[h] = c2 * aa;
+#pragma unroll
+                for (int i = 0; i < NE; i++) s_a[h].v[i] *= aa;
+            }
+        }
+        if (keep_alpha) {
+            ch.stm(s_a[0], ch.alpha[0] + (size_t)g * Ksp);
+            ch.stm(s_a[1], ch.alpha[1] + (size_t)g * Ksp);
+        }
+        ss.set_c(lane, jg, cn[0], cn[1]);
+        mlc1 -= log(cn[0]);
+        mlc2 -= log(cn[1]);
+        while (ir < R) {
+            if ((ir & 63) == 0 && rr.base != ir) {
+                if (rr.base >= 0 && rr_dirty) rr.store(ch);
+                rr.load(ch, ir, nullptr, 0);
+                rr_dirty = false;
+            }
+            if (rl_i32(rr.wif, ir & 63) != g) break;
+            if (flip) {
+                if (lane == (ir & 63)) rr.H = 3 - rr.H;
+                rr_dirty = true;
+            }
+            ir++;
+        }
+        if (decide) {
+            double s[4] = {0, 0, 0, 0};
+#pragma unroll
+            for (int i = 0; i < NE; i++) {
+                s[0] += s_a[0].v[i] * b1.v[i];
+                s[1] += s_a[1].v[i] * b2.v[i];
+                s[2] += s_a[1].v[i] * b1.v[i];
+                s[3] += s_a[0].v[i] * b2.v[i];
+            }
+            ch.template bsum<4>(s);
+            const double pA1 = mlc1 + mloc1 + log(s[0]);
+            const double pA2 = mlc2 + mloc2 + log(s[1]);
+            const double pB1 = mlc2 + mloc1 + log(s[2]);
+            const double pB2 = mlc1 + mloc2 + log(s[3]);
+            const double diff = pB1 + pB2 - pA1 - pA2;
+            double probs1 = 1;
+            const double probs2 = exp(diff);
+            const double ps = probs1 + probs2;
+            probs1 /= ps;
+            const double ub = seed_shard ? stream_uniform(seed_shard, (uint64_t)p.blk_pass * (G - 1) + blk) : ru[blk];
+            flip = ub > probs1;
+        }
+        mloc1 += log(oc1);
+        mloc2 += log(oc2);
+    }
+    ss.store_c(ch);
+    if (rr.base >= 0 && rr_dirty) rr.store(ch);
+    chain_sync<NW>();
+    backward_both<NE, NW, false>(ch);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1072,9 +1246,15 @@ void launch_ematread(const GibbsParams &prm, int maxR, hipStream_t st) {
     QA_HIP(hipGetLastError());
 }
 
-template <int NE, int NW, bool LEAN = false>
+template <int NE, int NW, bool LEAN = false, bool SEG = false>
 void launch_gibbs_kernel(const GibbsParams &prm, hipStream_t st) {
-    hipLaunchKernelGGL((k_gibbs<NE, NW, LEAN>), dim3(prm.C), dim3(64 * NW), 0, st, prm);
+    hipLaunchKernelGGL((k_gibbs<NE, NW, LEAN, SEG>), dim3(prm.C), dim3(64 * NW), 0, st, prm);
+    QA_HIP(hipGetLastError());
+}
+
+template <int NE, int NW>
+void launch_shard_blocks_kernel(const GibbsParams &prm, hipStream_t st) {
+    hipLaunchKernelGGL((k_shard_blocks<NE, NW>), dim3(prm.C), dim3(64 * NW), 0, st, prm);
     QA_HIP(hipGetLastError());
 }
 
@@ -1112,8 +1292,53 @@ bool use_lean_build(int C) {
     return C > 1024;
 }
 
+// The built geometries of the two-label chain kernels (rows per lane, waves) in one place: f(NE, NW) as integral constants for
+// NE1 = Ksp / 64 rows per lane with one wave and the chosen number of waves (several waves exist for Ksp = 640 only)
+template <int N>
+using int_c = std::integral_constant<int, N>;
+template <class F>
+void for_chain_geometry(int NE1, int nw, F &&f) {
+    if (NE1 == 10 && nw == 10) return f(int_c<1>{}, int_c<10>{});
+    if (NE1 == 10 && nw == 5) return f(int_c<2>{}, int_c<5>{});
+    if (NE1 == 10 && nw == 2) return f(int_c<5>{}, int_c<2>{});
+    switch (NE1) {
+        case 1: return f(int_c<1>{}, int_c<1>{});
+        case 2: return f(int_c<2>{}, int_c<1>{});
+        case 3: return f(int_c<3>{}, int_c<1>{});
+        case 4: return f(int_c<4>{}, int_c<1>{});
+        case 5: return f(int_c<5>{}, int_c<1>{});
+        case 6: return f(int_c<6>{}, int_c<1>{});
+        case 7: return f(int_c<7>{}, int_c<1>{});
+        case 8: return f(int_c<8>{}, int_c<1>{});
+        case 9: return f(int_c<9>{}, int_c<1>{});
+        case 10: return f(int_c<10>{}, int_c<1>{});
+        case 11: return f(int_c<11>{}, int_c<1>{});
+        case 12: return f(int_c<12>{}, int_c<1>{});
+        case 13: return f(int_c<13>{}, int_c<1>{});
+        case 14: return f(int_c<14>{}, int_c<1>{});
+        case 15: return f(int_c<15>{}, int_c<1>{});
+        default: return f(int_c<16>{}, int_c<1>{});
+    }
+}
+
+// the sweeps of the two-label sampler: the whole call (SEG = false), or its sweeps [it_begin, it_end)
+template <bool SEG>
+void launch_gibbs_sweeps(const GibbsParams &prm, int nw, hipStream_t st) {
+    for_chain_geometry(prm.Ksp / 64, nw, [&](auto ne, auto w) {
+        constexpr int NE = decltype(ne)::value, NW = decltype(w)::value;
+        if constexpr (NE == 10 && NW == 1) {
+            if (use_lean_build(prm.C)) return launch_gibbs_kernel<10, 1, true, SEG>(prm, st);
+        }
+        launch_gibbs_kernel<NE, NW, false, SEG>(prm, st);
+    });
+}
+
+void launch_shard_blocks(const GibbsParams &prm, int nw, hipStream_t st) {
+    for_chain_geometry(prm.Ksp / 64, nw, [&](auto ne, auto w) { launch_shard_blocks_kernel<decltype(ne)::value, decltype(w)::value>(prm, st); });
+}
+
 void launch_gibbs(const GibbsParams &prm, int maxR, hipStream_t st, hipEvent_t *ev, bool want_probs, int nw,
-                  const std::function<void()> &nipt_sweeps) {
+                  const std::function<void()> &segmented_sweeps) {
     const int NE1 = prm.Ksp / 64;   // rows per lane with one wave
     QA_HIP(hipEventRecord(ev[0], st));
     switch (NE1) {
@@ -1142,33 +1367,10 @@ void launch_gibbs(const GibbsParams &prm, int maxR, hipStream_t st, hipEvent_t *
         default: throw std::runtime_error("Ksubset geometry not built (Ksubset / 64 rounded up must be 1..16)");
     }
     QA_HIP(hipEventRecord(ev[1], st));
-    if (prm.nH == 3) {
-        nipt_sweeps();   // three-label sampler (NIPT) with its block passes: gibbs3.hip, driven from gibbs_chunk
-    } else if (NE1 == 10) {
-        if (nw == 10) launch_gibbs_kernel<1, 10>(prm, st);
-        else if (nw == 5) launch_gibbs_kernel<2, 5>(prm, st);
-        else if (nw == 2) launch_gibbs_kernel<5, 2>(prm, st);
-        else if (use_lean_build(prm.C)) launch_gibbs_kernel<10, 1, true>(prm, st);
-        else launch_gibbs_kernel<10, 1>(prm, st);
-    } else {
-        switch (NE1) {
-            case 1: launch_gibbs_kernel<1, 1>(prm, st); break;
-            case 2: launch_gibbs_kernel<2, 1>(prm, st); break;
-            case 3: launch_gibbs_kernel<3, 1>(prm, st); break;
-            case 4: launch_gibbs_kernel<4, 1>(prm, st); break;
-            case 5: launch_gibbs_kernel<5, 1>(prm, st); break;
-            case 6: launch_gibbs_kernel<6, 1>(prm, st); break;
-            case 7: launch_gibbs_kernel<7, 1>(prm, st); break;
-            case 8: launch_gibbs_kernel<8, 1>(prm, st); break;
-            case 9: launch_gibbs_kernel<9, 1>(prm, st); break;
-            case 11: launch_gibbs_kernel<11, 1>(prm, st); break;
-            case 12: launch_gibbs_kernel<12, 1>(prm, st); break;
-            case 13: launch_gibbs_kernel<13, 1>(prm, st); break;
-            case 14: launch_gibbs_kernel<14, 1>(prm, st); break;
-            case 15: launch_gibbs_kernel<15, 1>(prm, st); break;
-            default: launch_gibbs_kernel<16, 1>(prm, st); break;
-        }
-    }
+    // segments of sweeps with a pass between them, driven from gibbs_chunk: the three-label sampler (NIPT, gibbs3.hip) with its
+    // block passes, or the two-label sampler with block-wise shard passes; otherwise the whole call is one launch
+    if (segmented_sweeps) segmented_sweeps();
+    else launch_gibbs_sweeps<false>(prm, nw, st);
     QA_HIP(hipEventRecord(ev[2], st));
     if (want_probs) {   // return_hapProbs / return_genProbs (functions.R:2566-2599): skipped when nobody asks
         // dynamic LDS: nH gamma columns of Ksp doubles + the panel words (+ the haplotype list for the rare + common form)
@@ -1601,17 +1803,36 @@ GibbsParams fill_params(const qa::GibbsScratch &S, const qa_panel_t *pn, const q
     return prm;
 }
 
-// The block tables of one NIPT block pass from the switch rates the device sent back (rate2, and the chains' statuses): chains
-// over n_thr host threads
-void nipt_block_tables(const qa_gibbs_opts_t *o, const GibbsLaunch &L, const ChunkHost &h, const std::vector<double> &rate2,
-                       const std::vector<int32_t> &seg_status, int n_thr, std::vector<int32_t> &h_where, std::vector<int32_t> &h_tab,
-                       std::vector<int32_t> &h_n) {
+// The sweeps after which a pass runs (0-based, ascending, each once): the call's block iterations that name a sweep of the call
+std::vector<int> block_pass_sweeps(const qa_gibbs_opts_t *o, int n_its) {
+    std::vector<int> passes;
+    if (o->perform_block_gibbs)
+        for (int i = 0; i < o->n_block_gibbs_iterations; i++) {
+            const int b = o->block_gibbs_iterations[i];
+            if (b >= 0 && b < n_its && std::find(passes.begin(), passes.end(), b) == passes.end()) passes.push_back(b);
+        }
+    std::sort(passes.begin(), passes.end());
+    return passes;
+}
+
+// The block tables of one pass -- a NIPT block pass or a block-wise shard pass of the two-label sampler -- from the switch rates
+// the device sent back (rate2, and the chains' statuses): chains over n_thr host threads.  An underflowed chain gets no table
+// (h_n = 0): it is stopped and the caller retries it.  A chain without reads gets none in NIPT mode; in the two-label mode such
+// a chain, and one with fewer than three grids (no boundary has a rate), gets one block over every grid, and its pass is then the
+// forward and backward recomputation with nothing to decide.
+void block_tables(const qa_gibbs_opts_t *o, const GibbsLaunch &L, const ChunkHost &h, const std::vector<double> &rate2,
+                  const std::vector<int32_t> &seg_status, int n_thr, std::vector<int32_t> &h_where, std::vector<int32_t> &h_tab,
+                  std::vector<int32_t> &h_n) {
     const int C = h.C, G = h.G;
     const int32_t *read_off = L.a.read_off;
     h_where.assign((size_t)C * G, -1); h_tab.assign((size_t)C * 4 * G, 0); h_n.assign(C, 0);
     qa::parallel_for((size_t)C, n_thr, [&](size_t c) {
         const int R = read_off[c + 1] - read_off[c];
-        if (seg_status[c] != 0 || R < 1) return;   // underflowed chain: stopped, the caller retries it
+        if (seg_status[c] != 0) return;
+        if (R < 1 || (h.nH == 2 && G < 3)) {
+            if (h.nH == 2) { h_n[c] = 1; h_tab[c * 4 * G + G] = G - 1; h_where[c * G + G - 1] = 0; }
+            return;
+        }
         const std::vector<int32_t> blocked = qa::define_blocked_grids(
             rate2.data() + c * G, o->L_grid, G, o->shuffle_bin_radius, o->block_gibbs_quantile_prob);
         const qa::BlockTable T = qa::make_gibbs_considers(blocked, L.a.wif + read_off[c], R);
@@ -1642,13 +1863,7 @@ void nipt_sweeps(const GibbsParams &prm, qa::GibbsScratch &S, const qa_gibbs_opt
     const bool lean3_on = lean3_env && atoi(lean3_env) != 0;
     q.lean3 = (h.Ksp == 640 && h.nw == 1 && lean3_on) ? 1 : 0;
     q.blk_n_pass = std::max(o->n_block_gibbs_iterations, 1);
-    std::vector<int> passes;
-    if (o->perform_block_gibbs)
-        for (int i = 0; i < o->n_block_gibbs_iterations; i++) {
-            const int b = o->block_gibbs_iterations[i];
-            if (b >= 0 && b < n_its && std::find(passes.begin(), passes.end(), b) == passes.end()) passes.push_back(b);
-        }
-    std::sort(passes.begin(), passes.end());
+    const std::vector<int> passes = block_pass_sweeps(o, n_its);
     if (!passes.empty()) {
         S.blk_rate2.ensure((size_t)C * G); S.blk_where.ensure((size_t)C * G);
         S.blk_tab.ensure((size_t)C * 4 * G); S.blk_n.ensure(C);
@@ -1670,7 +1885,7 @@ void nipt_sweeps(const GibbsParams &prm, qa::GibbsScratch &S, const qa_gibbs_opt
         QA_HIP(hipStreamSynchronize(st));
         const double tg0 = now_s();
         const int n_thr = std::max(1, std::min<int>(qa::host_threads(), C));
-        nipt_block_tables(o, L, h, rate2, seg_status, n_thr, h_where, h_tab, h_n);
+        block_tables(o, L, h, rate2, seg_status, n_thr, h_where, h_tab, h_n);
         const double tg1 = now_s();
         S.blk_where.upload(h_where.data(), h_where.size(), st);
         S.blk_tab.upload(h_tab.data(), h_tab.size(), st);
@@ -1720,6 +1935,61 @@ void nipt_sweeps(const GibbsParams &prm, qa::GibbsScratch &S, const qa_gibbs_opt
     if (passes.empty() || it0 < n_its || q.rebuild) {   // (also with no sweeps left: the rebuild after the last pass)
         q.it_begin = it0; q.it_end = n_its;
         qa::launch_gibbs3(&q, st);
+    }
+}
+
+// does this call run its shard passes block by block (qa_gibbs_opts_t.shard_by_blocks; two-label sampler only)
+bool shard_by_blocks(const qa_gibbs_opts_t *o) {
+    return o->ff == 0.0 && o->shard_by_blocks && o->perform_block_gibbs && o->do_shard_block_gibbs && o->n_block_gibbs_iterations > 0;
+}
+
+// Two-label sampler, shard_check_every_pair = FALSE (gibbs-nipt.cpp:3003-3049): the sweeps are cut at the block iterations as the
+// three-label sampler's are.  After a segment the switch rate per grid boundary (the two-label sums of k_block_rate3) comes back
+// to the host, which defines the blocks and their table -- the rules nipt_sweeps uses, block_tables -- and k_shard_blocks decides
+// where a block ends.  Pass j takes its uniforms from slot j of the chain's n_block_gibbs_iterations x (nGrids - 1): explicit,
+// counter-based, or drawn by opts->draw_uniforms (what = 2) once the table says how many the reference draws, n_blocks - 1.
+void shard_block_sweeps(const GibbsParams &prm, qa::GibbsScratch &S, const qa_gibbs_opts_t *o, const GibbsLaunch &L, const ChunkHost &h,
+                        hipStream_t st, bool tmg) {
+    const int C = h.C, G = h.G, n_its = h.n_its;
+    GibbsParams q = prm;
+    const std::vector<int> passes = block_pass_sweeps(o, n_its);
+    S.blk_rate2.ensure((size_t)C * G); S.blk_where.ensure((size_t)C * G); S.blk_n.ensure(C);
+    q.blk_rate2 = S.blk_rate2.p; q.blk_where = S.blk_where.p; q.blk_n = S.blk_n.p;
+    std::vector<double> rate2((size_t)C * G, 0.0), ub;
+    std::vector<int32_t> h_where, h_tab, h_n, seg_status(C);
+    int it0 = 0;
+    for (size_t j = 0; j < passes.size(); j++) {
+        q.it_begin = it0; q.it_end = passes[j] + 1;
+        launch_gibbs_sweeps<true>(q, h.nw, st);
+        if (G >= 3) {   // (fewer grids: no boundary has a rate, and block_tables does not look at it)
+            qa::launch_block_rate3(&q, st);
+            S.blk_rate2.download(rate2.data(), rate2.size(), st);
+        }
+        S.status.download(seg_status.data(), C, st);
+        QA_HIP(hipStreamSynchronize(st));
+        const double tg0 = now_s();
+        const int n_thr = std::max(1, std::min<int>(qa::host_threads(), C));
+        block_tables(o, L, h, rate2, seg_status, n_thr, h_where, h_tab, h_n);
+        const double tg1 = now_s();
+        S.blk_where.upload(h_where.data(), h_where.size(), st);
+        S.blk_n.upload(h_n.data(), h_n.size(), st);
+        q.blk_pass = (int)j;
+        if (o->draw_uniforms)   // chain by chain, from this (the calling) thread; never for nothing
+            for (int c = 0; c < C; c++) {
+                const int n = h_n[c] - 1;
+                if (n < 1) continue;
+                ub.assign((size_t)n, 0.0);
+                o->draw_uniforms(o->draw_uniforms_ctx, L.c0 + c, (int)j, 2, n, ub.data());
+                qa::staged_upload(S.runif_shard.p + ((size_t)c * q.n_block + j) * (size_t)(G - 1), ub.data(), sizeof(double) * (size_t)n, st);
+            }
+        launch_shard_blocks(q, h.nw, st);
+        if (tmg) fprintf(stderr, "[qa_gibbs C=%d] shard pass %d by blocks: device idle for the host's block tables %.1f ms (tables %.1f on %d threads, uploads enqueued %.1f)\n",
+                         C, (int)j, (now_s() - tg0) * 1e3, (tg1 - tg0) * 1e3, n_thr, (now_s() - tg1) * 1e3);
+        it0 = passes[j] + 1;
+    }
+    if (passes.empty() || it0 < n_its) {
+        q.it_begin = it0; q.it_end = n_its;
+        launch_gibbs_sweeps<true>(q, h.nw, st);
     }
 }
 
@@ -1825,7 +2095,10 @@ int gibbs_chunk(qa_panel_t *pn, size_t arena_need, const qa_rare_common *rc, con
     for (auto &e : g_gibbs->ev) if (!e) QA_HIP(hipEventCreate(&e));
     QA_HIP(hipStreamSynchronize(st));
     const double T2 = now_s();
-    launch_gibbs(prm, h.maxR, st, g_gibbs->ev, h.want_probs, h.nw, [&] { nipt_sweeps(prm, S, o, L, h, st, tmg); });
+    std::function<void()> segmented;   // (empty: the whole call is one launch of the two-label sampler)
+    if (h.nH == 3) segmented = [&] { nipt_sweeps(prm, S, o, L, h, st, tmg); };
+    else if (shard_by_blocks(o)) segmented = [&] { shard_block_sweeps(prm, S, o, L, h, st, tmg); };
+    launch_gibbs(prm, h.maxR, st, g_gibbs->ev, h.want_probs, h.nw, segmented);
     const std::vector<int32_t> status = download_labels(S, o, L, h, st);
     const double T3 = now_s();
     hold.mark();
@@ -1863,9 +2136,25 @@ int gibbs_batch_impl(qa_panel_t *pn, const qa_rare_common *rc, const qa_gibbs_op
                       "and the block passes' uniforms (runif_shard, seeds, or opts->draw_uniforms)");
         return QA_ERR_INVALID;
     }
-    if (o->draw_uniforms && (o->ff == 0.0 || a.seed_reads || a.seed_shard)) {
-        qa::set_error("qa_gibbs_batch: opts->draw_uniforms serves the NIPT block passes (ff > 0) of a call with explicit uniforms "
-                      "(runif_reads given, no seeds)");
+    if (shard_by_blocks(o)) {
+        if (rc) {
+            qa::set_error("qa_gibbs_batch_rare_common: opts->shard_by_blocks (shard_check_every_pair = FALSE) is served by "
+                          "qa_gibbs_batch only");
+            return QA_ERR_UNSUPPORTED;
+        }
+        if (!o->L_grid) {
+            qa::set_error("qa_gibbs_batch: opts->shard_by_blocks needs opts->L_grid (the block definition smooths the switch rate "
+                          "over base pairs); it is NULL");
+            return QA_ERR_INVALID;
+        }
+        if (o->shuffle_bin_radius <= 0 || !(o->block_gibbs_quantile_prob > 0 && o->block_gibbs_quantile_prob < 1)) {
+            qa::set_error("qa_gibbs_batch: opts->shard_by_blocks needs shuffle_bin_radius > 0 and block_gibbs_quantile_prob in (0, 1)");
+            return QA_ERR_INVALID;
+        }
+    }
+    if (o->draw_uniforms && ((o->ff == 0.0 && !shard_by_blocks(o)) || a.seed_reads || a.seed_shard)) {
+        qa::set_error("qa_gibbs_batch: opts->draw_uniforms serves the NIPT block passes (ff > 0) and the block-wise shard passes "
+                      "(ff = 0 with shard_by_blocks) of a call with explicit uniforms (runif_reads given, no seeds)");
         return QA_ERR_INVALID;
     }
     // the uniforms of the shard passes (diploid) / block passes (NIPT): explicit, or the per-chain seed of the counter-based
@@ -1876,7 +2165,7 @@ int gibbs_batch_impl(qa_panel_t *pn, const qa_rare_common *rc, const qa_gibbs_op
     }
     {
         const bool passes = o->perform_block_gibbs && o->n_block_gibbs_iterations > 0 && (o->ff != 0.0 || o->do_shard_block_gibbs);
-        if (passes && !a.runif_shard && !(a.seed_reads && a.seed_shard) && !(o->ff != 0.0 && o->draw_uniforms)) {
+        if (passes && !a.runif_shard && !(a.seed_reads && a.seed_shard) && !o->draw_uniforms) {
             qa::set_error("qa_gibbs_batch: block / shard passes requested without their uniforms (runif_shard, or seed_reads and "
                           "seed_shard)");
             return QA_ERR_INVALID;

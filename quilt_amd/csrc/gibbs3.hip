@@ -587,7 +587,8 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(LEAN ? 
 // ---------------------------------------------------------------------------------------------
 // NIPT block Gibbs (gibbs-nipt-block.cpp), between two segments of sweeps.
 //   k_block_rate3   rate2 of Rcpp_define_blocked_snps_using_gamma_on_the_fly (:347-363): per grid boundary
-//                   sum over labels of 1 - sigma * sum_k alpha(k, g) beta(k, g + 1) eMatGrid(k, g + 1).
+//                   sum over labels of 1 - sigma * sum_k alpha(k, g) beta(k, g + 1) eMatGrid(k, g + 1).  Over the call's nH
+//                   labels: the two-label sampler's block-wise shard pass (gibbs.hip) takes its rate from it too.
 //                   The smoothing / quantile / peak picking that turns it into blocks, and make_gibbs_considers, are
 //                   scalar integer logic per chain and run on the host (gibbs.hip), as they run in R-facing C++.
 //   k_block3        Rcpp_block_gibbs_resampler (:1636-1967), block_approach = 6: the forward recursion of all six

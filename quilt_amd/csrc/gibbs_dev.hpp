@@ -88,7 +88,9 @@ struct GibbsParams {
     const size_t *rc_pair_base;  // [C] where the chain's pairs start
     const uint16_t *rc_pairs;    // (SNP & 31) << 10 | row (row < 1 024)
     // NIPT (three labels): a call is cut into segments of sweeps [it_begin, it_end) with a block-Gibbs pass between
-    // them (gibbs3.hip); the state lives in HBM across the launches.  blk_*: the pass's block table per chain.
+    // them (gibbs3.hip); the state lives in HBM across the launches.  blk_*: the pass's block table per chain.  The two-label
+    // sampler with block-wise shard passes (gibbs.hip: k_gibbs<.., SEG>, k_shard_blocks) uses it_begin / it_end, blk_where,
+    // blk_n, blk_rate2 and blk_pass the same way.
     int it_begin, it_end;
     int rebuild;                // this segment follows a block pass: eMatGrid, forward, backward from the labels first
     int lean3;                  // the three-label sampler's 256-register build (two chains per SIMD): launches of more than 1 024 chains

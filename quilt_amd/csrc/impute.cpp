@@ -547,6 +547,12 @@ struct Worker {
         o.L_grid = cx.nipt ? (rare ? cx.rc->L_grid_all : cx.nipt->L_grid) : nullptr;
         o.shuffle_bin_radius = cx.nipt ? cx.nipt->shuffle_bin_radius : 5000;
         o.block_gibbs_quantile_prob = 0.95;
+        if (P.shard_blocks && !cx.nipt) {   // shard_check_every_pair = FALSE (never with rare: the range was refused)
+            o.shard_by_blocks = 1;
+            o.L_grid = P.shard_blocks->L_grid;
+            o.shuffle_bin_radius = P.shard_blocks->shuffle_bin_radius;
+            o.block_gibbs_quantile_prob = P.shard_blocks->block_gibbs_quantile_prob;
+        }
         return o;
     }
 
@@ -1388,6 +1394,19 @@ int impute_impl(bool keep_buffers, const qa_impute_backend_t *be, void *const *h
                       P.Ksubset, K, P.nipt ? "method = \"nipt\"" : "method = \"diploid\"", P.nipt ? QA_KSUBSET_MAX_NIPT : QA_KSUBSET_MAX,
                       QA_KSUBSET_MAX, QA_KSUBSET_MAX_NIPT);
         return QA_ERR_UNSUPPORTED;
+    }
+    // shard_check_every_pair = FALSE: what the Gibbs call would refuse, said before the first sample
+    if (P.shard_blocks && !P.nipt) {
+        if (P.rare_common) {
+            qa::set_error("qa_impute_samples: params->shard_blocks (shard_check_every_pair = FALSE) is not served with impute_rare_common = "
+                          "TRUE: the all-SNP Gibbs call decides at every pair of grids only");
+            return QA_ERR_UNSUPPORTED;
+        }
+        if (!P.shard_blocks->L_grid || P.shard_blocks->shuffle_bin_radius <= 0 ||
+            !(P.shard_blocks->block_gibbs_quantile_prob > 0 && P.shard_blocks->block_gibbs_quantile_prob < 1)) {
+            qa::set_error("qa_impute_samples: params->shard_blocks needs L_grid, shuffle_bin_radius > 0 and block_gibbs_quantile_prob in (0, 1)");
+            return QA_ERR_INVALID;
+        }
     }
     // ... and what the full-panel pickers are built for, not said by the first full-panel pass after a round of Gibbs calls
     if (P.K_top_matches > QA_K_TOP_MATCHES_MAX) {

@@ -38,6 +38,16 @@ K_TOP_MATCHES_MAX = 64
 
 
 @dataclass
+class ShardBlocks:
+    """QUILT(shard_check_every_pair = FALSE) for a sample range (qa_impute_shard_blocks_t): the diploid Gibbs calls' shard passes
+    decide only where a block ends; what the block definition takes beyond the state.  Not a member of DriverParams: it carries
+    the panel's grid positions, and both loops take it beside their parameters."""
+    L_grid: np.ndarray
+    shuffle_bin_radius: int = 5000            # quilt.R:134
+    block_gibbs_quantile_prob: float = 0.95   # functions.R:2393
+
+
+@dataclass
 class DriverParams:
     """Defaults of ``QUILT()`` (QUILT/R/quilt.R:97-186) for the arguments the hot path sees."""
 
@@ -661,13 +671,19 @@ class Driver:
     latency-bound launches.  Results do not depend on the batching: every chain owns its random stream.
     """
 
-    def __init__(self, panel, backend, params: Optional[DriverParams] = None, rare_common=None):
+    def __init__(self, panel, backend, params: Optional[DriverParams] = None, rare_common=None,
+                 shard_blocks: Optional[ShardBlocks] = None):
         """``rare_common`` (:class:`quilt_amd.panel.RareCommon`), with ``params.impute_rare_common``: every sample then
-        carries its all-SNP reads as ``sample.all_snp`` and the results cover all SNPs (functions.R:1306-1307)."""
+        carries its all-SNP reads as ``sample.all_snp`` and the results cover all SNPs (functions.R:1306-1307).
+        ``shard_blocks``: shard_check_every_pair = FALSE (method = "diploid"; ignored with "nipt", refused with
+        impute_rare_common, as qa_impute_samples does)."""
         self.panel = panel
         self.backend = backend
         self.params = (params or DriverParams()).resolved(panel.K)
         self.rare_common = rare_common
+        self.shard_blocks = shard_blocks if self.params.method != "nipt" else None
+        if self.shard_blocks is not None and self.params.impute_rare_common:
+            raise ValueError("shard_blocks (shard_check_every_pair = FALSE) is not served with impute_rare_common = TRUE")
         if self.params.impute_rare_common and rare_common is None:
             raise ValueError("impute_rare_common needs the panel's rare/common tables")
         if self.params.method not in ("diploid", "nipt"):
@@ -922,6 +938,10 @@ class Driver:
         """impute_one_sample's loop (functions.R:2612-2716): a chain whose call reports underflow is re-run with
         maxDifferenceBetweenReads / 10."""
         P = self.params
+        if self.shard_blocks is not None:   # shard_check_every_pair = FALSE
+            sb = self.shard_blocks
+            kw = dict(kw, shard_check_every_pair=False, L_grid=sb.L_grid, shuffle_bin_radius=sb.shuffle_bin_radius,
+                      block_gibbs_quantile_prob=sb.block_gibbs_quantile_prob)
         pending = list(range(len(chains)))
         maxdiff = [P.maxDifferenceBetweenReads] * len(chains)
         results = [None] * len(chains)

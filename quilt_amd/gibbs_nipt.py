@@ -33,8 +33,12 @@ class GibbsOpts(C.Structure):
         ("L_grid", C.c_void_p), ("shuffle_bin_radius", C.c_int32), ("block_gibbs_quantile_prob", C.c_double),
         ("ff_chain", C.c_void_p), ("per_it_out", C.c_void_p), ("hap_words_out", C.c_void_p),
         ("hap_major_out", C.c_void_p), ("hap_major_labels", C.c_int32), ("reads_same_as", C.c_void_p),
-        ("draw_uniforms", C.c_void_p), ("draw_uniforms_ctx", C.c_void_p),
+        ("draw_uniforms", C.c_void_p), ("draw_uniforms_ctx", C.c_void_p), ("shard_by_blocks", C.c_int32),
     ]
+
+
+# qa_gibbs_opts_t.draw_uniforms: (ctx, chain, pass, what, n, out)
+DrawUniforms = C.CFUNCTYPE(None, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double))
 
 
 def forwardBackwardGibbsNIPT_batch(panel: DevicePanel, samples: Sequence, which_haps_to_use: Sequence[np.ndarray],
@@ -50,7 +54,8 @@ def forwardBackwardGibbsNIPT_batch(panel: DevicePanel, samples: Sequence, which_
                                    return_genProbs: bool = True, rare_common=None, runif_block=None,
                                    runif_resample=None, L_grid=None, shuffle_bin_radius: int = 5000,
                                    block_gibbs_quantile_prob: float = 0.95, return_per_it: bool = False,
-                                   return_hap_words: bool = False, hap_major_out: Optional[np.ndarray] = None):
+                                   return_hap_words: bool = False, hap_major_out: Optional[np.ndarray] = None,
+                                   shard_check_every_pair: bool = True, draw_uniforms=None):
     """``n_chain`` independent calls of ``rcpp_forwardBackwardGibbsNIPT`` in one launch set.
 
     ``samples[c]`` is a :class:`quilt_amd.synth.SampleReads`-like object (``read_ptr``, ``u``, ``bq``,
@@ -63,6 +68,12 @@ def forwardBackwardGibbsNIPT_batch(panel: DevicePanel, samples: Sequence, which_
     NIPT (``ff`` > 0) with ``perform_block_gibbs``: ``runif_block[c]`` / ``runif_resample[c]`` hold
     ``len(block_gibbs_iterations) x nReads`` uniforms each (QUILT/src/gibbs-nipt.cpp:3016; gibbs-nipt-block.cpp:226-243)
     unless seeds are used; ``L_grid`` defaults to the panel's (the all-SNP grid's with ``rare_common``).
+
+    ``shard_check_every_pair = False`` (diploid, quilt.R:178): the shard passes decide only where a block of the state's own
+    block definition ends; ``runif_shard`` keeps its length, pass j reads entries ``j * (nGrids - 1) + b`` for its blocks b.
+    ``draw_uniforms(chain, pass, what, n)`` -> n uniforms: instead of ``runif_shard``, asked for ``n_blocks - 1`` values
+    (``what = 2``) before each such pass, chain by chain (qa_gibbs_opts_t.draw_uniforms).  What it raises, or a wrong number
+    of values, is raised after the call; with ``ff`` > 0 the keyword is refused.
 
     ``hap_major_out``: a C-contiguous float64 array [n_chain, n_label, nSNPs] (ideally from ``native.pinned_empty``) that
     receives the haploid dosages label by label -- the layout the driver accumulates from -- instead of a per-chain
@@ -110,6 +121,8 @@ def forwardBackwardGibbsNIPT_batch(panel: DevicePanel, samples: Sequence, which_
             rs = np.concatenate(parts)
         else:
             rs = np.zeros(1)
+    elif draw_uniforms is not None:
+        rs = None   # (the library asks for the passes' uniforms)
     elif nb > 0 and not use_seeds and perform_block_gibbs:   # (ff == 0: the shard passes, do_shard_block_gibbs below)
         parts = [np.ascontiguousarray(r, dtype=np.float64).ravel()[: nb * (G - 1)] for r in runif_shard]
         if len(parts) != Cn or any(len(x) != nb * (G - 1) for x in parts):   # (the library reads all of them)
@@ -143,6 +156,23 @@ def forwardBackwardGibbsNIPT_batch(panel: DevicePanel, samples: Sequence, which_
                      int(disable_read_category_usage), float(class_sum_cutoff), ptr(Lg), int(shuffle_bin_radius),
                      float(block_gibbs_quantile_prob), ptr(ffc), ptr(per_it), ptr(words), ptr(hap_major_out),
                      0 if hap_major_out is None else int(hap_major_out.shape[1]))
+    opts.shard_by_blocks = int(not shard_check_every_pair)
+    draw_failed = []
+    if draw_uniforms is not None:
+        if ff != 0:
+            raise ValueError("draw_uniforms: the keyword serves the diploid block-wise shard passes (shard_check_every_pair = False)")
+        def _draw(ctx, chain, pass_, what, n, out):
+            # (ctypes swallows what a callback raises: remembered here, raised after the native call)
+            try:
+                vals = np.asarray(draw_uniforms(chain, pass_, what, n), dtype=np.float64).ravel()
+                if vals.size != n:
+                    raise ValueError(f"draw_uniforms(chain={chain}, pass={pass_}, what={what}) returned {vals.size} values for n = {n}")
+                np.ctypeslib.as_array(out, shape=(n,))[:] = vals
+            except BaseException as e:   # noqa: B902
+                draw_failed.append(e)
+                np.ctypeslib.as_array(out, shape=(n,))[:] = 0.0
+        cb = DrawUniforms(_draw)   # (kept alive until the call returns)
+        opts.draw_uniforms = C.cast(cb, C.c_void_p)
     _t1 = time.perf_counter()
     tail = (C.byref(opts), C.c_int32(Cn), ptr(which), ptr(read_off), ptr(read_ptr), ptr(u), ptr(bq), ptr(wif), ptr(ru),
             ptr(fr), ptr(rs), ptr(H), ptr(Hc), ptr(hap), ptr(gm), ptr(gf), ptr(uf), ptr(state), ptr(sr), ptr(ss))
@@ -152,6 +182,8 @@ def forwardBackwardGibbsNIPT_batch(panel: DevicePanel, samples: Sequence, which_
     else:
         with span("device:gibbs"):
             st = lib().qa_gibbs_batch(panel.handle, *tail)
+    if draw_failed:
+        raise draw_failed[0]
     check(st)
     if os.environ.get("QA_TIMING"):
         print(f"[gibbs_batch py C={Cn}] marshal {_t1 - _t0:.3f} s, native call {time.perf_counter() - _t1:.3f} s", flush=True)

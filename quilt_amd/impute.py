@@ -29,7 +29,12 @@ class ImputeParams(C.Structure):
         ("samples_per_launch_set", C.c_int32), ("no_fused_tails", C.c_int32),
         ("rare_common", C.c_void_p), ("nipt", C.c_void_p), ("sample_index", C.c_void_p),
         ("on_samples_done", C.c_void_p), ("on_samples_done_ctx", C.c_void_p), ("sample_source", C.c_void_p),
+        ("shard_blocks", C.c_void_p),
     ]
+
+
+class ImputeShardBlocks(C.Structure):   # qa_impute_shard_blocks_t
+    _fields_ = [("L_grid", C.c_void_p), ("shuffle_bin_radius", C.c_int32), ("block_gibbs_quantile_prob", C.c_double)]
 
 
 class SampleView(C.Structure):
@@ -154,9 +159,11 @@ def make_nipt(panel, samples, shuffle_bin_radius: int, nSNPs_out: Optional[int] 
     return ImputeNipt(ptr(ff), ptr(Lg), int(shuffle_bin_radius), ptr(fd), ptr(fg)), fd, fg, (ff, Lg)
 
 
-def make_params(P: DriverParams, samples_per_launch_set: int, mspbwt_index=None, fuse_tails: bool = True, rare_common=None, nipt=None):
+def make_params(P: DriverParams, samples_per_launch_set: int, mspbwt_index=None, fuse_tails: bool = True, rare_common=None, nipt=None,
+                shard_blocks=None):
     """(ImputeParams, keep-alive objects) from the Python driver's parameters; ``rare_common``: an ImputeRareCommon (with
-    impute_rare_common); ``nipt``: an ImputeNipt (method = "nipt")."""
+    impute_rare_common); ``nipt``: an ImputeNipt (method = "nipt"); ``shard_blocks``: a quilt_amd.driver.ShardBlocks
+    (shard_check_every_pair = FALSE)."""
     if P.method == "nipt" and nipt is None:
         raise ValueError("method = 'nipt' needs make_nipt(...)")
     if P.impute_rare_common and rare_common is None:
@@ -172,7 +179,12 @@ def make_params(P: DriverParams, samples_per_launch_set: int, mspbwt_index=None,
                      int(samples_per_launch_set), 0 if fuse_tails else 1,
                      C.cast(C.pointer(rare_common), C.c_void_p) if (P.impute_rare_common and rare_common is not None) else None,
                      C.cast(C.pointer(nipt), C.c_void_p) if (P.method == "nipt" and nipt is not None) else None)
-    return q, (blocks, mspbwt_index, rare_common, nipt)
+    sbq = Lg = None
+    if shard_blocks is not None:
+        Lg = np.ascontiguousarray(shard_blocks.L_grid, dtype=np.int32)
+        sbq = ImputeShardBlocks(ptr(Lg), int(shard_blocks.shuffle_bin_radius), float(shard_blocks.block_gibbs_quantile_prob))
+        q.shard_blocks = C.cast(C.pointer(sbq), C.c_void_p)
+    return q, (blocks, mspbwt_index, rare_common, nipt, sbq, Lg)
 
 
 def wrap_results(samples, dosage, gp_t, haps, labels, nDosage, read_off, fet_dosage=None, fet_gp_t=None, hla=None, prob=None) -> List[SampleResult]:
@@ -201,7 +213,7 @@ class PreparedRange:
 
 
 def prepare_range(devs: Sequence, samples: Sequence, params: Optional[DriverParams] = None, sample_offset: int = 0,
-                  samples_per_launch_set: int = 256, fuse_tails: bool = True, drcs: Sequence = ()) -> PreparedRange:
+                  samples_per_launch_set: int = 256, fuse_tails: bool = True, drcs: Sequence = (), shard_blocks=None) -> PreparedRange:
     panel = devs[0].panel
     P = (params or DriverParams())
     idx = None
@@ -217,7 +229,7 @@ def prepare_range(devs: Sequence, samples: Sequence, params: Optional[DriverPara
     nq = fd = fg = keep_n = None
     if P.method == "nipt":
         nq, fd, fg, keep_n = make_nipt(panel, samples, P.shuffle_bin_radius, T)
-    q, keep = make_params(P, samples_per_launch_set, idx, fuse_tails, rcq, nq)
+    q, keep = make_params(P, samples_per_launch_set, idx, fuse_tails, rcq, nq, shard_blocks)
     read_off, read_ptr, u, bq, wif = flatten_samples(samples)
     nL = 3 if P.method == "nipt" else 2
     return PreparedRange(devs=list(devs), samples=list(samples), q=q, keep=(keep, keep_rc, keep_n), sample_offset=int(sample_offset),
@@ -269,13 +281,14 @@ def run_prepared(r: PreparedRange, return_stats: bool = False, one_by_one: bool 
 
 def impute_samples(devs: Sequence, samples: Sequence, params: Optional[DriverParams] = None, sample_offset: int = 0,
                    samples_per_launch_set: int = 256, fuse_tails: bool = True, return_stats: bool = False, drcs: Sequence = (),
-                   one_by_one: bool = False, output_read_label_prob: bool = False):
+                   one_by_one: bool = False, output_read_label_prob: bool = False, shard_blocks=None):
     """``devs``: one :class:`quilt_amd.native.DevicePanel` per host thread (replicas of one panel on one device; with more
-    than one, switch ``set_exclusive`` on).  ``drcs`` (with ``params.impute_rare_common``): one
+    than one, switch ``set_exclusive`` on).  ``shard_blocks`` (a quilt_amd.driver.ShardBlocks): shard_check_every_pair = FALSE.
+    ``drcs`` (with ``params.impute_rare_common``): one
     :class:`quilt_amd.native.DeviceRareCommon` per entry of ``devs``; every sample then carries its all-SNP reads as
     ``sample.all_snp`` and the results cover all SNPs.  Returns one SampleResult per sample (and the native counters)."""
-    return run_prepared(prepare_range(devs, samples, params, sample_offset, samples_per_launch_set, fuse_tails, drcs), return_stats, one_by_one,
-                        output_read_label_prob)
+    return run_prepared(prepare_range(devs, samples, params, sample_offset, samples_per_launch_set, fuse_tails, drcs, shard_blocks),
+                        return_stats, one_by_one, output_read_label_prob)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------

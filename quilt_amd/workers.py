@@ -62,7 +62,7 @@ class DeviceWorkers:
     def __init__(self, panel, params: Optional[DriverParams] = None, n_workers: int = 2, rare_common=None,
                  cu_partition: bool = False, fp64_dosage: bool = False, split: str = "halves", gibbs_gate: float = 0.0,
                  pass_priority: bool = False, exclusive: bool = False, fuse_tails: bool = True,
-                 split_remainder: bool = True):
+                 split_remainder: bool = True, shard_blocks=None):
         self.n = n_workers
         self.split_remainder = split_remainder   # split = "alternate": left-over batches are cut into one part per thread
         # the last batches' phasing rounds of all threads run together (driver.PhasingTail) instead of one after the other
@@ -84,7 +84,9 @@ class DeviceWorkers:
             if cu_partition and n_workers > 1:   # each thread's Gibbs chains on its own share of the CUs (measured slower: DESIGN.md 5)
                 d.set_cu_partition(w, n_workers)
         self.drcs = [DeviceRareCommon(d, rare_common) if rare_common is not None else None for d in self.devs]
-        self.drivers = [Driver(panel, HipBackend(d, r), params, rare_common=rare_common) for d, r in zip(self.devs, self.drcs)]
+        # (shard_blocks: shard_check_every_pair = FALSE, driver.ShardBlocks -- every thread's loop passes it to its Gibbs calls)
+        self.drivers = [Driver(panel, HipBackend(d, r), params, rare_common=rare_common, shard_blocks=shard_blocks)
+                        for d, r in zip(self.devs, self.drcs)]
         if gibbs_gate > 0 and n_workers > 1:
             gate = PairGate(n_workers, gibbs_gate)
             for d in self.drivers:
@@ -231,7 +233,8 @@ class NativeWorkers:
     (the batches' samples must be consecutive: they are one sample range).  ``n_workers`` panel handles = host threads."""
 
     def __init__(self, panel, params: Optional[DriverParams] = None, n_workers: int = 3, fp64_dosage: bool = False,
-                 exclusive: bool = True, fuse_tails: bool = True, rare_common=None, output_read_label_prob: bool = False):
+                 exclusive: bool = True, fuse_tails: bool = True, rare_common=None, output_read_label_prob: bool = False,
+                 shard_blocks=None):
         self.n = n_workers
         self.panel = panel
         self.output_read_label_prob = bool(output_read_label_prob)   # results carry read_label_prob (qa_impute_samples_reads)
@@ -248,7 +251,9 @@ class NativeWorkers:
                 d.set_dosage_precision(64)
         self.drcs = [DeviceRareCommon(d, rare_common) for d in self.devs] if rare_common is not None else []
         # (bench.py's stand-alone kernel timings drive single rounds through the Python statement of the loop)
-        self.drivers = [Driver(panel, HipBackend(self.devs[0], self.drcs[0] if self.drcs else None), params, rare_common=rare_common)]
+        self.shard_blocks = shard_blocks   # shard_check_every_pair = FALSE (driver.ShardBlocks): into qa_impute_params_t
+        self.drivers = [Driver(panel, HipBackend(self.devs[0], self.drcs[0] if self.drcs else None), params, rare_common=rare_common,
+                               shard_blocks=shard_blocks)]
         self.stats = {}
         self.reset_timing()
 
@@ -280,7 +285,7 @@ class NativeWorkers:
             flat.extend(samples)
             at += len(samples)
         r = prepare_range(self.devs, flat, self.params, sample_offset=batches[0][1], samples_per_launch_set=len(batches[0][0]),
-                          fuse_tails=self.fuse_tails, drcs=self.drcs)
+                          fuse_tails=self.fuse_tails, drcs=self.drcs, shard_blocks=self.shard_blocks)
         r.batch_sizes = [len(smp) for smp, _ in batches]
         return r
 

@@ -13,6 +13,9 @@ ap.add_argument("--chains", type=int, default=224); ap.add_argument("--reads", t
 ap.add_argument("--Ks", type=int, default=600); ap.add_argument("--reps", type=int, default=2)
 ap.add_argument("--init-iter", action="store_true"); ap.add_argument("--samples", type=int, default=0)
 ap.add_argument("--nipt", action="store_true", help="three read labels, block Gibbs (ff = 0.2)")
+ap.add_argument("--shard-blocks", action="store_true",
+                help="diploid: every repetition once with shard_check_every_pair = TRUE and once with FALSE (block-wise shard passes); "
+                     "QA_TIMING=1 adds the host-idle time per pass on stderr")
 a = ap.parse_args()
 panel = make_synthetic_panel(K=a.K, nSNPs=a.T, seed=4916)
 dev = DevicePanel(panel)
@@ -24,13 +27,15 @@ which = [np.sort(rng.choice(panel.K, a.Ks, replace=False)).astype(np.int32) + 1 
 H0 = [rng.integers(1, 4 if a.nipt else 3, size=s.nReads).astype(np.int32) for s in S]
 fr = [int(rng.integers(0, s.nReads)) for s in S]
 sr = rng.integers(0, 2**63, size=a.chains).astype(np.uint64); ss = rng.integers(0, 2**63, size=a.chains).astype(np.uint64)
-for r in range(a.reps):
+for r, every_pair in [(r, e) for r in range(a.reps) for e in ((True, False) if a.shard_blocks else (True,))]:
     native.lib().qa_profile_reset()
     t0 = time.time()
     out = forwardBackwardGibbsNIPT_batch(dev, S, which, H0, None, fr, None, seed_reads=sr, seed_shard=ss,
                                          gibbs_initialize_iteratively=a.init_iter, return_genProbs=False,
-                                         **({"ff": [0.2] * a.chains} if a.nipt else {}))
+                                         shard_check_every_pair=every_pair, **({"ff": [0.2] * a.chains} if a.nipt else {}))
     wall = time.time() - t0
+    if a.shard_blocks:
+        print(f"shard_check_every_pair = {every_pair}: {wall * 1e3:.1f} ms per call ({a.chains} chains)", flush=True)
     res = []
     L = native.lib()
     L.qa_profile_name.restype = C.c_char_p

@@ -128,7 +128,7 @@ R_RANGE_CALL = '''        ## libquilt_amd: the whole sample range as ONE call (q
                 minimum_number_of_sample_reads = minimum_number_of_sample_reads,
                 output_gt_phased_genotypes = output_gt_phased_genotypes,
                 hla_run = hla_run, gamma_physically_closest_to = gamma_physically_closest_to,
-                output_read_label_prob = output_read_label_prob
+                output_read_label_prob = output_read_label_prob, shard_check_every_pair = shard_check_every_pair
             )
             ## native I/O (quilt-amd.R, form (a)): the range's four count arrays come back summed (in sample order) -- added here
             ## once; the per-sample entries the loop below adds are exact zeros then

@@ -62,7 +62,8 @@ quilt_amd_range_is_covered <- function(
         !plot_per_sample_likelihoods && !plot_p1 && !make_heuristic_plot &&
         !estimate_bq_using_truth_read_labels && !addOptimalHapsToVCF &&
         !use_splitreadgl && !small_ref_panel_skip_equally_likely_reads &&
-        shard_check_every_pair && use_hapMatcherR && calculate_gamma_on_the_fly &&
+        (shard_check_every_pair || !impute_rare_common) &&   ## FALSE: block-wise shard passes; not in the all-SNP Gibbs call
+        use_hapMatcherR && calculate_gamma_on_the_fly &&
         rdata_ok && n_gibbs_sample_its == 1
     return(isTRUE(ok))
 }
@@ -134,7 +135,9 @@ quilt_amd_impute_sample_range <- function(
     ## hla_run (functions.R:1261-1280, :1489-1494)
     hla_run = FALSE, gamma_physically_closest_to = NA,
     ## output_read_label_prob (functions.R:318-319, :1164-1166, :1202-1204)
-    output_read_label_prob = FALSE
+    output_read_label_prob = FALSE,
+    ## quilt.R:178; FALSE: the diploid shard passes decide only where a block ends (block_gibbs_quantile_prob: functions.R:2393)
+    shard_check_every_pair = TRUE, block_gibbs_quantile_prob = 0.95
 ) {
     w <- sampleRange[1]:sampleRange[2]
     n <- length(w)
@@ -185,6 +188,10 @@ quilt_amd_impute_sample_range <- function(
     }
     if (method == "nipt") {
         params <- c(params, list(method = "nipt", shuffle_bin_radius = shuffle_bin_radius))
+        panel_objects[["L_grid"]] <- as.numeric(L_grid)
+    } else if (!shard_check_every_pair) {
+        params <- c(params, list(shard_check_every_pair = FALSE, shuffle_bin_radius = shuffle_bin_radius,
+                                 block_gibbs_quantile_prob = block_gibbs_quantile_prob))
         panel_objects[["L_grid"]] <- as.numeric(L_grid)
     }
     if (impute_rare_common) {

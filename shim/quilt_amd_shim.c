@@ -27,7 +27,8 @@
  * shim draws the same uniforms, in the same order, with unif_rand() (`sample(nReads, 1)` = one unif_rand() scaled by nReads,
  * as Rcpp's sugar EmpiricalSample does) between GetRNGstate() / PutRNGstate() and passes them down; the device never generates R-incompatible numbers on this
  * path.  The shard pass draws nGrids - 1 uniforms per block iteration: what gibbs-nipt-block.cpp:2054 draws with
- * shard_check_every_pair = TRUE, the production value (quilt.R:178); FALSE is rejected.  Where the reference's draw count depends on
+ * shard_check_every_pair = TRUE, the production value (quilt.R:178); with FALSE a pass draws n_blocks - 1, asked for through
+ * draw_shard_uniforms_from_R below once the pass's table exists (not with the rare + common call, which refuses FALSE).  Where the reference's draw count depends on
  * intermediate results (`Rcpp::sample(1:3, 1, prob)` per read whose class leaves a choice, in rcpp_sample_H_using_H_class, NIPT
  * only) the stream cannot be pre-drawn: since round 6 the library asks for those uniforms WHEN the reference draws them
  * (qa_gibbs_opts_t.draw_uniforms -> draw_uniforms_from_R below: runif_proposed / runif_block / runif_total before a block pass,
@@ -274,6 +275,21 @@ static void draw_uniforms_from_R(void *ctx, int32_t chain, int32_t pass, int32_t
     }
 }
 
+/* The same for a diploid call with shard_check_every_pair = FALSE (what = 2): at a block iteration the reference draws the
+ * 8 x nReads above, none of which a diploid call uses (gibbs-nipt.cpp:3013-3018), and then, inside the shard resampler,
+ * runif(n_blocks - 1) for the table it has just made (gibbs-nipt-block.cpp:2054).  The library asks only where n_blocks > 1, so
+ * the 8 x nReads of the passes it did not ask for are made up before the next pass's draws, and after the call. */
+typedef struct { int n_reads, next_pass; } shard_draws_t;
+static void burn_block_iterations(shard_draws_t *d, int upto_pass) {
+    for (; d->next_pass <= upto_pass; d->next_pass++)
+        for (long i = 0; i < 8L * d->n_reads; i++) (void)unif_rand();
+}
+static void draw_shard_uniforms_from_R(void *ctx, int32_t chain, int32_t pass, int32_t what, int32_t n, double *out) {
+    (void)chain; (void)what;
+    burn_block_iterations((shard_draws_t *)ctx, pass);
+    for (int b = 0; b < n; b++) out[b] = unif_rand();
+}
+
 static double lgamma1(double x) { return lgamma(x + 1.0); }
 static void fill_per_it_row(double *m, int nrow, int row, const double *rec, double ff, int it, double p_H_class) {
     const double prior[3] = {0.5, (1 - ff) / 2, ff / 2};
@@ -322,10 +338,11 @@ SEXP qa_QUILT_rcpp_forwardBackwardGibbsNIPT(
         !flag(pl, "use_starting_read_labels", 1) || flag(pl, "pass_in_eMatRead_t", 0) || flag(pl, "use_small_eHapsCurrent_tc", 0))
         Rf_error("quilt_amd: only the production form of rcpp_forwardBackwardGibbsNIPT is supported (n_gibbs_starts = 1, "
                  "run_fb_subset = FALSE, use_starting_read_labels = TRUE, pass_in_eMatRead_t = FALSE, packed panel)");
-    if (!flag(pl, "shard_check_every_pair", 1))
-        Rf_error("quilt_amd: shard_check_every_pair = FALSE is not supported (QUILT() passes TRUE, quilt.R:178)");
     const double ff = Rf_asReal(ffSEXP);
     const int rare_common = flag(pl, "make_eMatRead_t_rare_common", 0);
+    const int every_pair = flag(pl, "shard_check_every_pair", 1);
+    if (!every_pair && rare_common)
+        Rf_error("quilt_amd: shard_check_every_pair = FALSE is not supported with make_eMatRead_t_rare_common = TRUE");
     const int G_panel = Rf_ncols(distinctHapsBSEXP);
     /* transMatRate_tc_H: 2 x (G - 1) x S; with rare + common it is the all-SNP grid's and the panel's own is not passed:
      * the panel handle must then exist already (created by a full-panel call or an earlier common-SNP Gibbs call) */
@@ -415,7 +432,23 @@ SEXP qa_QUILT_rcpp_forwardBackwardGibbsNIPT(
         o.draw_uniforms = draw_uniforms_from_R;
         o.draw_uniforms_ctx = NULL;
     }
-    if (o.perform_block_gibbs && ff == 0) {
+    /* diploid, shard_check_every_pair = FALSE: a pass draws n_blocks - 1 uniforms for the table it makes itself -- through the
+     * callback as well (qa_gibbs_opts_t.shard_by_blocks) */
+    const int by_blocks = ff == 0 && !every_pair && o.perform_block_gibbs && o.do_shard_block_gibbs && nb > 0;
+    shard_draws_t shard_draws = {R, 0};
+    int n_passes = 0;   /* block iterations that name a sweep of the call, each once: the passes the library runs */
+    if (by_blocks) {
+        for (int ib = 0; ib < nb; ib++) {
+            const int b = INTEGER(block_gibbs_iterationsSEXP)[ib];
+            int seen = 0;
+            for (int jb = 0; jb < ib; jb++) seen |= INTEGER(block_gibbs_iterationsSEXP)[jb] == b;
+            n_passes += b >= 0 && b < n_its && !seen;
+        }
+        o.shard_by_blocks = 1;
+        o.draw_uniforms = draw_shard_uniforms_from_R;
+        o.draw_uniforms_ctx = &shard_draws;
+    }
+    if (o.perform_block_gibbs && ff == 0 && !by_blocks) {
         for (int ib = 0; ib < nb; ib++) {
             for (size_t i = 0; i < 6 * (size_t)R; i++) (void)unif_rand();                        /* :3013-3015 runif_proposed (unused by approach 6) */
             {
@@ -442,6 +475,7 @@ SEXP qa_QUILT_rcpp_forwardBackwardGibbsNIPT(
         : qa_gibbs_batch(panel, &o, 1, INTEGER(which_haps_to_useSEXP), read_off, read_ptr, u, bq, INTEGER(wif0SEXP), runif_reads,
                          &first_read, runif_pass, H, H_class, (want_hap || want_gen) ? REAL(hap) : NULL,
                          want_gen ? REAL(gm) : NULL, want_gen ? REAL(gf) : NULL, &underflow, state, NULL, NULL);
+    if (by_blocks && st >= 0 && !underflow) burn_block_iterations(&shard_draws, n_passes - 1);
     PutRNGstate();   /* (after the call: with NIPT block passes the library draws through draw_uniforms_from_R while it runs) */
     SEXP out = R_NilValue;
     if (st >= 0 && !underflow) {
@@ -675,6 +709,7 @@ typedef struct {
     int32_t *rare_snp, *L_grid_all, *L_grid;
     uint8_t *is_common;
     qa_impute_nipt_t nq;
+    qa_impute_shard_blocks_t sb;
     char msg[512];
 } range_ctx_t;
 
@@ -902,6 +937,23 @@ static int range_setup(range_ctx_t *cx, SEXP panelSEXP, SEXP paramsSEXP, int n_h
             cx->nq.L_grid = cx->L_grid;
             cx->nq.shuffle_bin_radius = (int)num_or(paramsSEXP, "shuffle_bin_radius", 5000);
             ip->nipt = &cx->nq;
+        }
+    }
+    /* shard_check_every_pair = FALSE (quilt.R:178; absent: TRUE), method = "diploid": the shard passes go block by block and the
+     * block definition needs the grid positions (qa_impute_params_t.shard_blocks) */
+    if (st == QA_OK && !cx->nipt && !flag(paramsSEXP, "shard_check_every_pair", 1)) {
+        SEXP lg = list_get(panelSEXP, "L_grid");
+        if (lg == R_NilValue || Rf_length(lg) != G) {
+            st = QA_ERR_INVALID;
+            snprintf(cx->msg, sizeof cx->msg, "shard_check_every_pair = FALSE: panel_objects$L_grid (nGrids) is needed");
+        } else {
+            cx->L_grid = (int32_t *)malloc(sizeof(int32_t) * (size_t)G);
+            if (!cx->L_grid) { st = QA_ERR_INVALID; snprintf(cx->msg, sizeof cx->msg, "out of memory"); }
+            for (int g = 0; cx->L_grid && g < G; g++) cx->L_grid[g] = TYPEOF(lg) == INTSXP ? INTEGER(lg)[g] : (int32_t)REAL(lg)[g];
+            cx->sb.L_grid = cx->L_grid;
+            cx->sb.shuffle_bin_radius = (int)num_or(paramsSEXP, "shuffle_bin_radius", 5000);
+            cx->sb.block_gibbs_quantile_prob = num_or(paramsSEXP, "block_gibbs_quantile_prob", 0.95);
+            ip->shard_blocks = &cx->sb;
         }
     }
     if (st != QA_OK) range_teardown(cx);

@@ -704,6 +704,7 @@ void qo_define_blocked_grids(const double *rate2 /* nGrids - 1 */, const int32_t
     int *to_keep = (int *)malloc(sizeof(int) * (size_t)(n + 3));
     int n_keep = 0;
     for (int g = 0; g < nGrids; g++) blocked_grid[g] = 0;
+    if (n < 1) goto done; /* one grid: no boundary has a rate (the reference takes a quantile of nothing); one block */
     qo_make_smoothed_rate(rate2, L_grid, nGrids, shuffle_bin_radius, sm);
     double break_thresh = 1;
     double d = qo_simple_quantile(sm, n, block_gibbs_quantile_prob);
@@ -813,6 +814,10 @@ int qo_make_gibbs_considers(const int32_t *blocked_grid_in, int nGrids, const in
         }
         n_blocks = o;
     }
+    /* A block whose reads were never recorded is a block without reads: every loop over its reads is empty.  Only a chain of
+     * one read (or none) gets here with such blocks -- the loop above starts at read 1, so nothing is recorded, and the removal
+     * is skipped because every block would go.  The reference leaves -1 / -1 and then indexes read -1 (:1387-1409). */
+    for (int b = 0; b < n_blocks; b++) if (reads_start[b] == -1) { reads_start[b] = 0; reads_end[b] = -1; }
     for (int g = 0; g < nGrids; g++) grid_where[g] = -1;
     for (int b = 0; b < n_blocks; b++) grid_where[grid_end[b]] = b;
     free(w); free(blocked_grid);
@@ -876,6 +881,7 @@ static void block_gibbs_resampler_nipt(sweep_t *S, double ff, const int32_t *blo
 {
     const int Ks = S->Ks, G = S->G, R = S->R;
     const double one_over_K = 1 / (double)Ks, prior = 1.0 / Ks;
+    if (R < 1) return;   /* no reads: nothing to relabel or to draw, and the state is what its (absent) labels give already */
     int32_t *gs = (int32_t *)malloc(sizeof(int32_t) * (size_t)G * 5);
     int32_t *ge = gs + G, *rs = ge + G, *re = rs + G, *where = re + G;
     const int n_blocks = qo_make_gibbs_considers(blocked_grid, G, S->wif, R, gs, ge, rs, re, where);
@@ -941,7 +947,9 @@ static void block_gibbs_resampler_nipt(sweep_t *S, double ff, const int32_t *blo
             }
             double d = 1 / tot;
             for (int ir = 0; ir < 6; ir++) cp[ir] *= d;
-            const double chance = runif_block[iBlock];
+            /* (a pass draws nReads uniforms, :3016: a table of more blocks than reads -- one read, several read-less blocks --
+             * has none for its later blocks and the reference reads past them; here they share the chain's last one) */
+            const double chance = runif_block[iBlock < R ? iBlock : R - 1];
             double cum[6];
             cum[0] = cp[0];
             for (int ir = 1; ir < 6; ir++) cum[ir] = cp[ir] + cum[ir - 1];
@@ -1222,6 +1230,12 @@ static void calc_hapProbs_rare_common(const qo_panel_t *p, const qo_rare_common_
     free(gam); free(L.ptr); free(L.k);
 }
 
+/* test aid: the blocked grids qo_define_blocked_grids returns inside qo_gibbs, pass by pass (NIPT block passes), copied into a
+ * caller's buffer of n_passes x nGrids; NULL switches it off.  Process-wide, like qo_set_sum_order. */
+static int32_t *qo_blocked_capture = NULL;
+static int qo_blocked_capture_passes = 0;
+void qo_capture_blocked_grids(int32_t *buf, int n_passes) { qo_blocked_capture = buf; qo_blocked_capture_passes = buf ? n_passes : 0; }
+
 /*
  * rcpp_forwardBackwardGibbsNIPT (gibbs-nipt.cpp:2395-3307), production path.
  * Returns 0 ok, 1 underflow_problem (:2959-2969), -2 unsupported (NIPT block Gibbs).
@@ -1326,6 +1340,8 @@ int qo_gibbs(const qo_panel_t *p, const qo_gibbs_args_t *a, int32_t *H, int32_t 
             int32_t *blocked = (int32_t *)malloc(sizeof(int32_t) * (size_t)G);
             block_rate2(&S, ff, rate2);
             qo_define_blocked_grids(rate2, a->L_grid, G, a->shuffle_bin_radius, a->block_gibbs_quantile_prob, blocked);
+            if (qo_blocked_capture && shard_it < qo_blocked_capture_passes)
+                memcpy(qo_blocked_capture + (size_t)shard_it * G, blocked, sizeof(int32_t) * (size_t)G);
             if (a->runif_stream) {
                 const double *blk = stream_at;   /* this pass's runif_block, then its draws */
                 stream_at += R;

@@ -265,7 +265,7 @@ def forwardBackwardGibbsNIPT(panel, sample, which_haps_to_use, H, runif_reads, f
                              disable_read_category_usage=False, maxDifferenceBetweenReads=1e10, Jmax=10000,
                              class_sum_cutoff=0.06, use_eMatDH_special_symbols=None, rare_common=None,
                              runif_block=None, runif_resample=None, shuffle_bin_radius=5000,
-                             block_gibbs_quantile_prob=0.95, L_grid=None, runif_stream=None):
+                             block_gibbs_quantile_prob=0.95, L_grid=None, runif_stream=None, return_blocked_grids=False):
     """Oracle twin of ``rcpp_forwardBackwardGibbsNIPT`` (gibbs-nipt.cpp:2395-3307), production path.
 
     ``H``: starting labels (1-based); returns a dict holding the ending labels and every state
@@ -330,11 +330,18 @@ def forwardBackwardGibbsNIPT(panel, sample, which_haps_to_use, H, runif_reads, f
     hap = np.zeros((3, T), order="F")
     gm = np.zeros((3, T), order="F")
     gf = np.zeros((3, T), order="F")
-    st = lib().qo_gibbs(C.byref(ps), C.byref(args), _p(Hout), _p(Hc), arr3(mats["alpha"]), arr3(mats["beta"]),
-                        arr3(mats["eg"]), arr3(cs), _p(eMatRead), _p(cat), _p(hap), _p(gm), _p(gf))
+    captured = np.full((len(blocks), G), -1, dtype=np.int32) if return_blocked_grids else None
+    if captured is not None:   # (``blocked_grids``: what the block definition returned inside the call, one row per NIPT block pass)
+        lib().qo_capture_blocked_grids(_p(captured), C.c_int(len(blocks)))
+    try:
+        st = lib().qo_gibbs(C.byref(ps), C.byref(args), _p(Hout), _p(Hc), arr3(mats["alpha"]), arr3(mats["beta"]),
+                            arr3(mats["eg"]), arr3(cs), _p(eMatRead), _p(cat), _p(hap), _p(gm), _p(gf))
+    finally:
+        if captured is not None:
+            lib().qo_capture_blocked_grids(None, C.c_int(0))
     return dict(status=st, underflow_problem=(st == 1), H=Hout, H_class=Hc, alphaHat_t=mats["alpha"],
                 betaHat_t=mats["beta"], eMatGrid_t=mats["eg"], c=cs, eMatRead_t=eMatRead, read_category=cat,
-                hapProbs_t=hap, genProbsM_t=gm, genProbsF_t=gf, runif_stream_used=int(stream_used[0]))
+                hapProbs_t=hap, genProbsM_t=gm, genProbsF_t=gf, runif_stream_used=int(stream_used[0]), blocked_grids=captured)
 
 
 def calculate_eMatRead_t_vs_haplotypes(sample, haps, maxDifferenceBetweenReads, rescale_eMatRead_t=False, Jmax=1000):

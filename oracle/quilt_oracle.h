@@ -249,6 +249,10 @@ double qo_get_log_p_H_class2(int n1, int n2, int n3, int n4, int n5, int n6, dou
 void qo_zero_based_swap(int ir_chosen, int swap[8]);
 int qo_sample3(const double probs[3], double u);
 
+/* test aid: while buf is not NULL, qo_gibbs copies the blocked grids of its NIPT block passes 0 .. n_passes - 1 (what
+ * qo_define_blocked_grids returned inside the call) into buf[pass * nGrids + grid] */
+void qo_capture_blocked_grids(int32_t *buf, int n_passes);
+
 /* rcpp_forwardBackwardGibbsNIPT (gibbs-nipt.cpp:2395-3307), production argument values.
  * H (1-based labels) is updated in place; alphaHat_t/betaHat_t/eMatGrid_t are Ks x nGrids each,
  * c_out nGrids each, eMatRead_t Ks x nReads (output), hapProbs_t / genProbs* 3 x nSNPs.

@@ -1877,9 +1877,11 @@ void nipt_sweeps(const GibbsParams &prm, qa::GibbsScratch &S, const qa_gibbs_opt
         q.it_begin = it0; q.it_end = passes[j] + 1;
         qa::launch_gibbs3(&q, st);
         q.rebuild = 1;   // (what follows a block pass starts by re-forming the state from its labels)
-        qa::launch_block_rate3(&q, st);
         rate2.resize((size_t)C * G);
-        S.blk_rate2.download(rate2.data(), rate2.size(), st);
+        if (G >= 2) {   // (one grid: no boundary, a launch of no workgroups; define_blocked_grids gives one block without the rate)
+            qa::launch_block_rate3(&q, st);
+            S.blk_rate2.download(rate2.data(), rate2.size(), st);
+        }
         std::vector<int32_t> seg_status(C);
         S.status.download(seg_status.data(), C, st);
         QA_HIP(hipStreamSynchronize(st));

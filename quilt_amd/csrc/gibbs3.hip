@@ -873,7 +873,9 @@ __global__ __launch_bounds__(64 * NW) void k_block3(GibbsParams p) {
                 tot += cp[ir];
             }
             const double dn = 1 / tot;
-            const double chance = rl_f64(u_block(iBlock), 0);
+            // (a pass has R uniforms for its blocks: a table of more blocks than reads -- one read, several read-less blocks --
+            // would read past them, as the reference does; its later blocks share the chain's last one)
+            const double chance = rl_f64(u_block(min(iBlock, R - 1)), 0);
             int ir_chosen = 0;
             {
                 double cum[6];

@@ -157,6 +157,11 @@ inline BlockTable make_gibbs_considers(const std::vector<int32_t> &blocked_in, c
         n_blocks = o;
         gs.resize(o); ge.resize(o); rs.resize(o); re.resize(o);
     }
+    // A block whose reads were never recorded is a block without reads: every loop over its reads is empty.  Only a chain of one
+    // read (or none) gets here with such blocks -- the pass above starts at read 1 and the removal is skipped because every block
+    // would go.  The reference leaves -1 / -1 and then indexes read -1 (:1387-1409); this is the project's definition.
+    for (int b = 0; b < n_blocks; b++)
+        if (rs[b] == -1) { rs[b] = 0; re[b] = -1; }
     T.n_blocks = n_blocks;
     T.grid_start = gs; T.grid_end = ge; T.reads_start = rs; T.reads_end = re;
     T.grid_where.assign(nGrids, -1);

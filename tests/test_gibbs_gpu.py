@@ -398,7 +398,7 @@ def test_nipt_edge_inputs(small_panel, oracle):
     which = np.sort(rng.choice(panel.K, 70, replace=False)).astype(np.int32) + 1
     G = panel.nGrids
     cases = []
-    for n_reads in (2, 3, 7):
+    for n_reads in (1, 2, 3, 7):   # (1: no block's reads are recorded and every block is one without reads)
         cases.append(make_synthetic_sample(panel, seed=60 + n_reads, n_reads=n_reads, ff=ff))
     s = copy.deepcopy(make_synthetic_sample(panel, seed=70, n_reads=40, ff=ff))
     s.wif[:20] = 0; s.u[: s.read_ptr[20]] %= 32

@@ -2352,6 +2352,9 @@ int qa_rare_common_create(qa_panel_t *pn, int32_t nSNPs_all, const uint8_t *snp_
         rc->h_rare_snp.resize(n_rare);
         for (int k = 0; k < pn->K; k++) {
             if (rare_ptr[k + 1] < rare_ptr[k]) throw std::runtime_error("bad rare_per_hap_info CSR");
+            // (h_rare_snp holds rare_ptr[K] entries: a row that ends beyond them would be copied past its end before a later row
+            // is seen to decrease)
+            if (rare_ptr[k + 1] > n_rare) throw std::runtime_error("rare_per_hap_info CSR: a row ends beyond the last entry");
             for (int64_t i = rare_ptr[k]; i < rare_ptr[k + 1]; i++) {
                 const int t = rare_snp_1based[i] - 1;
                 if (t < 0 || t >= nSNPs_all || snp_is_common[t]) throw std::runtime_error("rare_per_hap_info names a SNP that is not rare");

@@ -55,7 +55,7 @@ def forwardBackwardGibbsNIPT_batch(panel: DevicePanel, samples: Sequence, which_
                                    runif_resample=None, L_grid=None, shuffle_bin_radius: int = 5000,
                                    block_gibbs_quantile_prob: float = 0.95, return_per_it: bool = False,
                                    return_hap_words: bool = False, hap_major_out: Optional[np.ndarray] = None,
-                                   shard_check_every_pair: bool = True, draw_uniforms=None):
+                                   shard_check_every_pair: bool = True, draw_uniforms=None, reads_same_as=None):
     """``n_chain`` independent calls of ``rcpp_forwardBackwardGibbsNIPT`` in one launch set.
 
     ``samples[c]`` is a :class:`quilt_amd.synth.SampleReads`-like object (``read_ptr``, ``u``, ``bq``,
@@ -74,6 +74,10 @@ def forwardBackwardGibbsNIPT_batch(panel: DevicePanel, samples: Sequence, which_
     ``draw_uniforms(chain, pass, what, n)`` -> n uniforms: instead of ``runif_shard``, asked for ``n_blocks - 1`` values
     (``what = 2``) before each such pass, chain by chain (qa_gibbs_opts_t.draw_uniforms).  What it raises, or a wrong number
     of values, is raised after the call; with ``ff`` > 0 the keyword is refused.
+
+    ``reads_same_as``: one index per chain, the first chain of this call with the same reads (the chain itself for the first of a
+    sample): the bases of a chain that names an earlier one are not looked at (qa_gibbs_opts_t.reads_same_as); its ``read_ptr``
+    and ``wif`` must still be the representative's.  Results do not depend on it.
 
     ``hap_major_out``: a C-contiguous float64 array [n_chain, n_label, nSNPs] (ideally from ``native.pinned_empty``) that
     receives the haploid dosages label by label -- the layout the driver accumulates from -- instead of a per-chain
@@ -157,6 +161,12 @@ def forwardBackwardGibbsNIPT_batch(panel: DevicePanel, samples: Sequence, which_
                      float(block_gibbs_quantile_prob), ptr(ffc), ptr(per_it), ptr(words), ptr(hap_major_out),
                      0 if hap_major_out is None else int(hap_major_out.shape[1]))
     opts.shard_by_blocks = int(not shard_check_every_pair)
+    same = None
+    if reads_same_as is not None:
+        same = np.ascontiguousarray(reads_same_as, dtype=np.int32)   # (kept alive until the call returns)
+        if same.shape != (Cn,):
+            raise ValueError("reads_same_as: one index per chain")
+        opts.reads_same_as = ptr(same)
     draw_failed = []
     if draw_uniforms is not None:
         if ff != 0:

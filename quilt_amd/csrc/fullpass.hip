@@ -1067,6 +1067,32 @@ void launch_fb_any(const Geometry &geo, const PassParams &prm, hipStream_t st, h
     }
 }
 
+// whether launch_fb_any holds a case for the geometry (the cases of its two switches, restated; fullpass_testhook.h reports it)
+bool launcher_case_exists(const Geometry &geo, int K) {
+    if (geo.NT == 0) return false;
+    if (geo.kind == KIND_F64_RANK || geo.kind == KIND_F64_DOS) {
+        int g[6];
+        qa::fb64_launch_geometry(K, geo.kind == KIND_F64_DOS, g);
+        return g[5] != 0;
+    }
+    if (geo.kind == KIND_F64_REF) return true;   // NT and Kq at run time
+    if (geo.kind == KIND_F64_FULL)
+        switch (geo.NCH) {
+#ifndef QA_FAST_BUILD
+            case 1: case 4: case 6: case 8: case 10: case 12: case 14:
+#endif
+            case 2: case 13: return true;
+            default: return false;
+        }
+    switch (geo.NCH) {
+#ifndef QA_FAST_BUILD
+        case 1: case 3: case 4: case 5: case 6: case 8: case 10: case 12:
+#endif
+        case 2: case 7: return true;
+        default: return false;
+    }
+}
+
 // the kernels behind the dosage passes of a handle: fp32 state, or (qa_panel_set_dosage_precision(64)) the fp64 dosage
 // kernels -- the generic fp64 kernels when K exceeds those kernels' on-chip capacity
 PassKind dosage_kind(const qa_panel *pn) {
@@ -1549,6 +1575,10 @@ int run_passes(qa_panel *pn, int P, const double *gl, const int32_t *h_flags, co
         qa::set_error("K = %d exceeds the on-chip capacity of the %s full-pass kernels", pn->K, kKindInfo[kind].name);
         return QA_ERR_UNSUPPORTED;
     }
+    if (!launcher_case_exists(geo, pn->K)) {   // (a build without every variant: QA_FAST_BUILD) -- said before any device work
+        qa::set_error("K = %d: this build of the library holds no %s full-pass kernels of that geometry", pn->K, kKindInfo[kind].name);
+        return QA_ERR_UNSUPPORTED;
+    }
     check_request(pn, kind, P, h_flags, K_top, out);
     QA_HIP(hipSetDevice(pn->device));
     if (!pn->scratch) pn->scratch = new qa_panel::Scratch(&pn->A());
@@ -1649,6 +1679,22 @@ int qa_fullpass_last_plan(int64_t out[6]) {
     if (!out) return QA_ERR_INVALID;
     out[0] = g_last_plan.P; out[1] = g_last_plan.per_pass; out[2] = g_last_plan.fixed; out[3] = g_last_plan.carved;
     out[4] = PassLayout::N_BUF; out[5] = g_last_plan.kind;
+    return QA_OK;
+}
+
+int qa_fullpass_geometry(int32_t K, int32_t kind, int32_t out[8]) {
+    if (!out || K < 1 || kind < 0 || kind >= qa::KIND_COUNT) return QA_ERR_INVALID;
+    for (int i = 0; i < 8; i++) out[i] = 0;
+    const Geometry geo = pick_geometry(K, (PassKind)kind);
+    if (geo.NT == 0) return QA_OK;
+    out[0] = geo.NT; out[1] = geo.NCH;
+    if (kind == KIND_F64_RANK || kind == KIND_F64_DOS) {
+        int g[6];
+        qa::fb64_launch_geometry(K, kind == KIND_F64_DOS, g);
+        out[2] = g[1]; out[3] = g[2]; out[4] = g[3]; out[5] = g[4];
+    }
+    out[6] = geo.NT * geo.NCH * 16;   // PassLayout::Kq
+    out[7] = launcher_case_exists(geo, K);
     return QA_OK;
 }
 

@@ -1175,6 +1175,40 @@ void launch(const PassParams &prm, const Geo64 &geo, hipStream_t s, hipEvent_t e
     QA_HIP(hipGetLastError());
 }
 
+// The geometry each launcher runs K with, after its own choice between <4, 3> and <5, 2> for seven rows on chip.
+// (the dosage backward's LDS, not the ranking kernels', decides for the dosage pair: a <4, 3> geometry whose three LDS rows do not
+// fit beside k_bwd64d's histogram takes five rows in registers, as the ranking pair does)
+Geo64 dosage_geo(int K) {
+    Geo64 geo = geo64(K);
+    if (geo.NCH == 7 && geo.NS == 0 && geo.NR == 4 && lds_bytes_d(geo) > kLdsMax) { geo.NR = 5; geo.NL = 2; }
+    if (geo.NCH && lds_bytes_d(geo) > kLdsMax) geo.NCH = 0;
+    return geo;
+}
+
+// A seven-row panel (K = 50 000) fits as <4, 3> and as <5, 2>.  The ranking pair is bound by instruction issue (counters:
+// VALU 54 %, everything 77 % of SIMD cycles) and a row that lives in LDS costs a ds_read and a ds_write per two cells beside the
+// table gather, so it takes five rows in registers although that spills a little more: stand-alone, 256 passes, 200 thinned grids, k_fwd64 11.4 -> 10.6 ms, k_bwd64 16.9 -> 16.4
+// (10 thinned grids: 9.0 -> 7.8, 9.5 -> 8.6).  The dosage pair streams alpha through HBM and does not care (31.4 / 41.1 against
+// 32.0 / 40.9 ms): it keeps <4, 3>.  QA_FB64_FOUR_ROWS=1: the ranking pair as before.
+Geo64 rank_geo(int K) {
+    Geo64 geo = geo64(K);
+    static const bool four = [] { const char *e = getenv("QA_FB64_FOUR_ROWS"); return e && e[0] == '1'; }();
+    if (!four && geo.NS == 0 && geo.NCH == 7 && geo.NR == 4) { geo.NR = 5; geo.NL = 2; }
+    return geo;
+}
+
+// the <NR, NL> builds the two switches below hold (fullpass_testhook.h reports it beside the geometry)
+bool geo_built(const Geo64 &geo) {
+    if (geo.NS > 0) return true;
+    switch (geo.NR * 10 + geo.NL) {
+#ifndef QA_FAST_BUILD
+        case 10: case 20: case 30: case 40: case 41: case 42:
+#endif
+        case 52: case 43: return true;
+        default: return false;
+    }
+}
+
 template <bool GCOL>
 void launch_dos_geo(const PassParams &prm, const Geo64 &geo, hipStream_t st, hipEvent_t e_mid) {
     if (geo.NS > 0) {
@@ -1213,13 +1247,15 @@ size_t fb64_alpha_col_elems(int K) {
 }
 size_t fb64_dos_lds_bytes(int K) { return lds_bytes_d(geo64(K)); }
 
+void fb64_launch_geometry(int K, bool dosage, int out[6]) {
+    const Geo64 g = dosage ? dosage_geo(K) : rank_geo(K);
+    out[0] = g.NCH; out[1] = g.NR; out[2] = g.NL; out[3] = g.n_last; out[4] = g.NS; out[5] = g.NCH && geo_built(g);
+}
+
 void launch_fb64_dosage(const void *pass_params, hipStream_t st, hipEvent_t e_mid) {
     const PassParams &prm = *static_cast<const PassParams *>(pass_params);
-    Geo64 geo = geo64(prm.K);
-    // (the dosage backward's LDS, not the ranking kernels', decides here: a <4, 3> geometry whose three LDS rows do not fit beside
-    // k_bwd64d's histogram takes five rows in registers, as the ranking pair does)
-    if (geo.NCH == 7 && geo.NS == 0 && geo.NR == 4 && lds_bytes_d(geo) > kLdsMax) { geo.NR = 5; geo.NL = 2; }
-    if (geo.NCH == 0 || lds_bytes_d(geo) > kLdsMax) throw std::runtime_error("K exceeds the on-chip capacity of the fp64 dosage kernels");
+    const Geo64 geo = dosage_geo(prm.K);
+    if (geo.NCH == 0) throw std::runtime_error("K exceeds the on-chip capacity of the fp64 dosage kernels");
     if (prm.Kq != (geo.NCH + geo.NS) * kRowHaps) throw std::runtime_error("internal: Kq does not match the fp64 geometry");
     if (geo.NS > 0 && !prm.spill) throw std::runtime_error("internal: streamed chunk rows without their buffer");
     if (prm.gamma_col) launch_dos_geo<true>(prm, geo, st, e_mid);
@@ -1228,15 +1264,8 @@ void launch_fb64_dosage(const void *pass_params, hipStream_t st, hipEvent_t e_mi
 
 void launch_fb64(const void *pass_params, hipStream_t st, hipEvent_t e_mid) {
     const PassParams &prm = *static_cast<const PassParams *>(pass_params);
-    Geo64 geo = geo64(prm.K);
+    const Geo64 geo = rank_geo(prm.K);
     if (geo.NCH == 0) throw std::runtime_error("K exceeds the on-chip capacity of the fp64 ranking kernels");
-    // A seven-row panel (K = 50 000) fits as <4, 3> and as <5, 2>.  The ranking pair is bound by instruction issue (counters:
-    // VALU 54 %, everything 77 % of SIMD cycles) and a row that lives in LDS costs a ds_read and a ds_write per two cells beside the
-    // table gather, so it takes five rows in registers although that spills a little more: stand-alone, 256 passes, 200 thinned grids, k_fwd64 11.4 -> 10.6 ms, k_bwd64 16.9 -> 16.4
-    // (10 thinned grids: 9.0 -> 7.8, 9.5 -> 8.6).  The dosage pair streams alpha through HBM and does not care (31.4 / 41.1 against
-    // 32.0 / 40.9 ms): it keeps <4, 3>.  QA_FB64_FOUR_ROWS=1: the ranking pair as before.
-    static const bool four = [] { const char *e = getenv("QA_FB64_FOUR_ROWS"); return e && e[0] == '1'; }();
-    if (!four && geo.NS == 0 && geo.NCH == 7 && geo.NR == 4) { geo.NR = 5; geo.NL = 2; }
     if (prm.Kq != (geo.NCH + geo.NS) * kRowHaps) throw std::runtime_error("internal: Kq does not match the fp64 geometry");
     if (geo.NS > 0) {
         if (!prm.spill) throw std::runtime_error("internal: streamed chunk rows without their buffer");

@@ -200,6 +200,9 @@ void launch_fb64(const void *pass_params, hipStream_t st, hipEvent_t e_mid);
 size_t fb64_alpha_col_elems(int K);
 size_t fb64_dos_lds_bytes(int K);
 void launch_fb64_dosage(const void *pass_params, hipStream_t st, hipEvent_t e_mid);
+// what launch_fb64 (dosage: launch_fb64_dosage) runs K with: chunk rows on chip (0: beyond the capacity), NR, NL, n_last, streamed
+// rows, and whether the launcher holds that build (fullpass_testhook.h)
+void fb64_launch_geometry(int K, bool dosage, int out[6]);
 
 // fullpass_ref.hip: the VALIDATION kernels (qa_panel_set_sum_order): every K-wide sum in the reference's order
 size_t fb_ref_state_doubles(int Kq);

@@ -22,6 +22,7 @@ from .trace import span
 
 
 class GibbsOpts(C.Structure):
+    _c_name_ = "qa_gibbs_opts_t"
     _fields_ = [
         ("Ks", C.c_int32), ("ff", C.c_double), ("sample_is_diploid", C.c_int32), ("Jmax", C.c_int32),
         ("maxDifferenceBetweenReads", C.c_double), ("rescale_eMatRead_t", C.c_int32),

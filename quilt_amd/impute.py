@@ -16,6 +16,7 @@ from .native import check, lib, ptr
 
 
 class ImputeParams(C.Structure):
+    _c_name_ = "qa_impute_params_t"
     _fields_ = [
         ("nGibbsSamples", C.c_int32), ("n_seek_its", C.c_int32), ("n_burn_in_seek_its", C.c_int32),
         ("Ksubset", C.c_int32), ("Knew", C.c_int32), ("K_top_matches", C.c_int32),
@@ -33,12 +34,14 @@ class ImputeParams(C.Structure):
     ]
 
 
-class ImputeShardBlocks(C.Structure):   # qa_impute_shard_blocks_t
+class ImputeShardBlocks(C.Structure):
+    _c_name_ = "qa_impute_shard_blocks_t"
     _fields_ = [("L_grid", C.c_void_p), ("shuffle_bin_radius", C.c_int32), ("block_gibbs_quantile_prob", C.c_double)]
 
 
 class SampleView(C.Structure):
-    """qa_sample_view_t (include/quilt_amd.h): one sample's reads as a qa_sample_source_t hands them over."""
+    """One sample's reads as a qa_sample_source_t hands them over."""
+    _c_name_ = "qa_sample_view_t"
     _fields_ = [("n_reads", C.c_int32), ("read_ptr", C.c_void_p), ("u", C.c_void_p), ("bq", C.c_void_p), ("wif", C.c_void_p),
                 ("n_reads_all", C.c_int32), ("read_ptr_all", C.c_void_p), ("u_all", C.c_void_p), ("bq_all", C.c_void_p),
                 ("wif_all", C.c_void_p), ("read_labels", C.c_void_p)]
@@ -49,8 +52,9 @@ QA_END_OF_SAMPLES = 2
 
 
 class SampleSource(C.Structure):
-    """qa_sample_source_t: ``acquire(ctx, s, view)`` blocks until sample ``s`` of the call is there (QA_OK, view filled), reports
+    """``acquire(ctx, s, view)`` blocks until sample ``s`` of the call is there (QA_OK, view filled), reports
     that the range ended before it (QA_END_OF_SAMPLES) or fails (< 0)."""
+    _c_name_ = "qa_sample_source_t"
     _fields_ = [("acquire", ACQUIRE_SAMPLE), ("ctx", C.c_void_p)]
 
 
@@ -89,25 +93,30 @@ def sample_source_over(samples, labels_out, n_available=None, fail_at=None, orde
 
 
 class ImputeNipt(C.Structure):
+    _c_name_ = "qa_impute_nipt_t"
     _fields_ = [("ff", C.c_void_p), ("L_grid", C.c_void_p), ("shuffle_bin_radius", C.c_int32), ("fet_dosage", C.c_void_p),
                 ("fet_gp_t", C.c_void_p)]
 
 
 class ImputeRareCommon(C.Structure):
+    _c_name_ = "qa_impute_rare_common_t"
     _fields_ = [("handles", C.c_void_p), ("nSNPs_all", C.c_int32), ("nGrids_all", C.c_int32), ("snp_is_common", C.c_void_p),
                 ("read_off", C.c_void_p), ("read_ptr", C.c_void_p), ("u", C.c_void_p), ("bq", C.c_void_p), ("wif", C.c_void_p),
                 ("L_grid_all", C.c_void_p)]
 
 
-class BamRangeExtras(C.Structure):   # qa_bam_range_extras_t (include/quilt_amd_io.h)
+class BamRangeExtras(C.Structure):
+    _c_name_ = "qa_bam_range_extras_t"
     _fields_ = [("use_bx_tag", C.c_int32), ("bxTagUpperLimit", C.c_int32), ("output_read_label_prob", C.c_int32), ("hla_grid", C.c_int32)]
 
 
-class ImputeReadsOut(C.Structure):   # qa_impute_reads_out_t
+class ImputeReadsOut(C.Structure):
+    _c_name_ = "qa_impute_reads_out_t"
     _fields_ = [("read_label_prob", C.c_void_p), ("dest", C.c_void_p), ("ctx", C.c_void_p)]
 
 
-class ImputeHla(C.Structure):   # qa_impute_hla_t
+class ImputeHla(C.Structure):
+    _c_name_ = "qa_impute_hla_t"
     _fields_ = [("grid", C.c_int32), ("gamma1", C.c_void_p), ("gamma2", C.c_void_p), ("gamma_total", C.c_void_p),
                 ("list_of_gammas", C.c_void_p)]
 
@@ -248,8 +257,6 @@ def run_prepared(r: PreparedRange, return_stats: bool = False, one_by_one: bool 
     nDosage = np.zeros(n, dtype=np.int32)
     stats = np.zeros(11, dtype=np.int64)
     L = lib()
-    L.qa_impute_samples.restype = C.c_int
-    L.qa_impute_samples_hla.restype = C.c_int
     flat = (ptr(r.read_off), ptr(r.read_ptr), ptr(r.u), ptr(r.bq), ptr(r.wif))
     hq = hla = prob = None
     if getattr(r, "hla_grid", None) is not None:   # hla_run: qa_impute_samples_hla with the gamma outputs
@@ -268,7 +275,6 @@ def run_prepared(r: PreparedRange, return_stats: bool = False, one_by_one: bool 
                 raise ValueError("output_read_label_prob with one_by_one is not wired in this wrapper")
             prob = np.zeros(int(r.read_off[-1]))
             ro = ImputeReadsOut(prob.ctypes.data, None, None)
-            L.qa_impute_samples_reads.restype = C.c_int
             check(L.qa_impute_samples_reads(*args, None if hq is None else C.byref(hq), C.byref(ro)))
         else:
             check(L.qa_impute_samples(*args) if hq is None else L.qa_impute_samples_hla(*args, C.byref(hq)))
@@ -295,6 +301,7 @@ def impute_samples(devs: Sequence, samples: Sequence, params: Optional[DriverPar
 # a sample range from BAM paths to VCF columns in one native call (qa_impute_bam_range, include/quilt_amd_io.h)
 # ---------------------------------------------------------------------------------------------------------------------------
 class BamRangeIo(C.Structure):
+    _c_name_ = "qa_bam_range_io_t"
     from .io import BamOpts as _BamOpts
     _fields_ = [("chr", C.c_char_p), ("nSNPs", C.c_int32), ("L", C.c_void_p), ("ref", C.c_char_p), ("alt", C.c_char_p),
                 ("grid", C.c_void_p), ("nSNPs_all", C.c_int32), ("L_all", C.c_void_p), ("ref_all", C.c_char_p),
@@ -387,12 +394,6 @@ def impute_bam_range(devs: Sequence, bam_files: Sequence[str], chr: str, ref, al
     ffv = None if ff is None else np.ascontiguousarray(ff, dtype=np.float64)
     handles = (C.c_void_p * len(devs))(*[getattr(d, "handle", None) for d in devs])
     L = lib()
-    for name in ("qa_impute_bam_range_bx", "qa_impute_bam_range_ex", "qa_bam_range_read_label_prob", "qa_bam_range_hla", "qa_bam_range_column", "qa_bam_range_sample", "qa_bam_range_counts", "qa_bam_range_imputed",
-                 "qa_bam_range_n_reads", "qa_bam_range_n_snps", "qa_bam_range_n_samples"):
-        getattr(L, name).restype = C.c_int
-    L.qa_bam_range_destroy.restype = None
-    L.qa_bam_range_timings.restype = None
-    L.qa_bam_range_bx_stats.restype = None
     h = C.c_void_p()
     if _entry is not None:   # (tests: the same native host code with its imputation step on a checker -- impute_testhook.h)
         if extras:   # (an entry over the _ex form takes the whole struct)

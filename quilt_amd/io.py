@@ -20,30 +20,14 @@ import numpy as np
 from .native import QA_ERR_CAPACITY, QuiltAmdError, lib, ptr
 from .synth import SampleReads
 
+_io_lib = lib   # (the handle this module's callers and tests/ take: native.lib(), which declares every prototype)
+
 
 class BamOpts(C.Structure):
+    _c_name_ = "qa_bam_opts_t"
     _fields_ = [("bqFilter", C.c_int32), ("iSizeUpperLimit", C.c_int32), ("useSoftClippedBases", C.c_int32),
                 ("downsampleToCov", C.c_int32), ("chrStart", C.c_int32), ("chrEnd", C.c_int32),
                 ("merge_mates", C.c_int32), ("seed", C.c_uint64)]
-
-
-def _io_lib():
-    L = lib()
-    if not getattr(L, "_io_ready", False):
-        for name in ("qa_bam_load_sample_reads", "qa_bam_load_sample_reads_bx", "qa_bam_load_sample_reads_named",
-                     "qa_sample_reads_export_names", "qa_read_label_confidence", "qa_sample_reads_n_reads", "qa_sample_reads_export", "qa_vcf_column_diploid",
-                     "qa_vcf_column_nipt", "qa_vcf_info_column", "qa_vcf_write_body", "qa_vcf_write_text", "qa_hwe_exact",
-                     "qa_accumulate_dosage", "qa_consensus_read_labels"):
-            getattr(L, name).restype = C.c_int
-        L.qa_sample_reads_n_bases.restype = C.c_int64
-        L.qa_sample_reads_names_bytes.restype = C.c_int64
-        L.qa_vcf_missing_entry.restype = C.c_char_p
-        L.qa_sample_reads_destroy.restype = None
-        L.qa_sample_reads_stats.restype = None
-        L.qa_sample_reads_bx_stats.restype = None
-        L.qa_bam_opts_default.restype = None
-        L._io_ready = True
-    return L
 
 
 def _check(st: int, what: str):
@@ -51,9 +35,7 @@ def _check(st: int, what: str):
         detail = ""
         if st == -3:   # QA_ERR_UNSUPPORTED carries the library's explanation (e.g. CRAM input and how to convert it)
             try:
-                lb = _io_lib()
-                lb.qa_last_error.restype = C.c_char_p
-                detail = ": " + lb.qa_last_error().decode()
+                detail = ": " + lib().qa_last_error().decode()
             except Exception:
                 pass
         raise QuiltAmdError(st, what + detail)
@@ -68,7 +50,7 @@ def accumulate_dosage(hap: np.ndarray, chain_sample: np.ndarray, dosage: np.ndar
         if a is not None and (a.dtype != np.float64 or not a.flags.c_contiguous):
             raise ValueError("accumulate_dosage takes C-contiguous float64 arrays")
     cs = np.ascontiguousarray(chain_sample, dtype=np.int32)
-    _check(_io_lib().qa_accumulate_dosage(C.c_int32(n_chain), C.c_int32(n_label), C.c_int32(T), ptr(hap), ptr(cs),
+    _check(lib().qa_accumulate_dosage(C.c_int32(n_chain), C.c_int32(n_label), C.c_int32(T), ptr(hap), ptr(cs),
                                           C.c_int32(dosage.shape[0]), ptr(dosage), ptr(gp_t), ptr(fet_dosage), ptr(fet_gp_t)),
            "qa_accumulate_dosage")
 
@@ -83,7 +65,7 @@ def consensus_read_labels(labels: np.ndarray, p: np.ndarray, can_hap: int, minrp
     if p.shape[0] != n or p.shape[2] != R or p.shape[1] not in (2, 3):
         raise ValueError("p must be [n, 2 or 3, nReads]")
     out = np.zeros(R, dtype=np.int32)
-    _check(_io_lib().qa_consensus_read_labels(C.c_int32(R), C.c_int32(n), ptr(labels), ptr(p), C.c_int32(p.shape[1]),
+    _check(lib().qa_consensus_read_labels(C.c_int32(R), C.c_int32(n), ptr(labels), ptr(p), C.c_int32(p.shape[1]),
                                               C.c_double(minrp), C.c_int32(can_hap), ptr(out)), "qa_consensus_read_labels")
     return out
 
@@ -95,7 +77,7 @@ def read_label_confidence(p: np.ndarray) -> np.ndarray:
     if p.ndim != 2 or p.shape[0] not in (2, 3):
         raise ValueError("p must be [2 or 3, nReads]")
     out = np.zeros(p.shape[1])
-    _check(_io_lib().qa_read_label_confidence(C.c_int32(p.shape[1]), C.c_int32(p.shape[0]), ptr(p), ptr(out)), "qa_read_label_confidence")
+    _check(lib().qa_read_label_confidence(C.c_int32(p.shape[1]), C.c_int32(p.shape[0]), ptr(p), ptr(out)), "qa_read_label_confidence")
     return out
 
 
@@ -120,7 +102,7 @@ def loadBamAndConvert(bam_file: str, chr: str, L: np.ndarray, ref: Sequence[str]
     option.  ``return_bx_stats``: the rule's four counters come back as a dict behind the other return values.
     ``return_names``: one name per read (the rule is stated in include/quilt_amd_io.h: the query name of the first alignment of the
     fragment that holds the read's slot), as a list behind the other return values; the read arrays are the same either way."""
-    lb = _io_lib()
+    lb = lib()
     L = np.ascontiguousarray(L, dtype=np.int32)
     T = len(L)
     grid = (np.arange(T, dtype=np.int32) // 32) if grid is None else np.ascontiguousarray(grid, dtype=np.int32)
@@ -215,7 +197,7 @@ def make_per_sample_vcf_col(gp_t: np.ndarray, phasing_haps: np.ndarray, output_g
     T = gp.shape[1]
     if gp.shape[0] != 3 or hd.shape != (T, 2):
         raise ValueError("gp_t must be 3 x T and phasing_haps T x 2")
-    return _two_pass(_io_lib().qa_vcf_column_diploid, T, ptr(gp), ptr(hd), C.c_int32(int(bool(output_gt_phased_genotypes))))
+    return _two_pass(lib().qa_vcf_column_diploid, T, ptr(gp), ptr(hd), C.c_int32(int(bool(output_gt_phased_genotypes))))
 
 
 def make_per_sample_vcf_col_nipt(mat_gp_t, fet_gp_t, phasing_haps, mat_dosage, fet_dosage) -> VcfColumn:
@@ -224,11 +206,11 @@ def make_per_sample_vcf_col_nipt(mat_gp_t, fet_gp_t, phasing_haps, mat_dosage, f
     T = m.shape[1]
     if m.shape[0] != 3 or f.shape != m.shape or hd.shape != (T, 3):
         raise ValueError("mat_gp_t / fet_gp_t must be 3 x T and phasing_haps T x 3")
-    return _two_pass(_io_lib().qa_vcf_column_nipt, T, ptr(m), ptr(f), ptr(hd), ptr(_f64(mat_dosage)), ptr(_f64(fet_dosage)))
+    return _two_pass(lib().qa_vcf_column_nipt, T, ptr(m), ptr(f), ptr(hd), ptr(_f64(mat_dosage)), ptr(_f64(fet_dosage)))
 
 
 def missing_entry() -> str:
-    return _io_lib().qa_vcf_missing_entry().decode()
+    return lib().qa_vcf_missing_entry().decode()
 
 
 def per_sample_counts(gp_t: np.ndarray, sample: SampleReads, nSNPs: int):
@@ -302,7 +284,7 @@ class SummaryCounts:
         eaf = self.afCount / N
         hwe = np.zeros(self.nSNPs)
         counts = np.asfortranarray(self.hweCount, dtype=np.float64)
-        _check(_io_lib().qa_hwe_exact(C.c_int32(self.nSNPs), ptr(counts), ptr(hwe)), "qa_hwe_exact")
+        _check(lib().qa_hwe_exact(C.c_int32(self.nSNPs), ptr(counts), ptr(hwe)), "qa_hwe_exact")
         return dict(alleleCount=ac, info=info, estimatedAlleleFrequency=eaf, hwe=hwe)
 
 
@@ -348,7 +330,7 @@ def make_and_write_output_file(output_filename: str, sampleNames: Sequence[str],
                                output_gt_phased_genotypes: bool = True) -> dict:
     """writers.R:1-128: header, INFO from the summed counts, one line per SNP inside the region; ``.gz`` names are written
     as BGZF (what ``bgzip`` would make of the text).  A ``None`` column is a sample that was not imputed."""
-    lb = _io_lib()
+    lb = lib()
     T = counts.nSNPs
     N = len(sampleNames)
     if len(columns) != N:

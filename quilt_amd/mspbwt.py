@@ -30,7 +30,6 @@ def find_good_matches(dev, Zs: np.ndarray, nindices: int, min_len: int, max_matc
     """``qa_find_good_matches``: dense tables ``match`` [query, index, max_matches, 3] of (index0, start0, len1) in haplotype
     order and ``n`` [query, index], the rows in use."""
     from .native import check, lib, ptr
-    lib().qa_find_good_matches.restype = C.c_int
     Zs = np.ascontiguousarray(Zs, dtype=np.int32)
     nq, G = Zs.shape
     match = np.zeros((nq, nindices, max_matches, 3), dtype=np.int32)
@@ -51,15 +50,12 @@ class MsPbwtIndex:
         if panel.hapMatcherR is None:
             raise ValueError("the msPBWT index is built from hapMatcherR (nMaxDH <= 255)")
         L = lib()
-        L.qa_mspbwt_create.restype = C.c_void_p
-        L.qa_mspbwt_bytes.restype = C.c_int64
         hm = np.asfortranarray(panel.hapMatcherR, dtype=np.uint8)
         B = np.asfortranarray(panel.distinctHapsB, dtype=np.int32)
         self.K, self.nGrids, self.nindices = int(hm.shape[0]), int(hm.shape[1]), int(nindices)
         h = L.qa_mspbwt_create(C.c_int32(self.K), C.c_int32(self.nGrids), hm.ctypes.data_as(C.c_void_p), C.c_int32(B.shape[0]),
                                B.ctypes.data_as(C.c_void_p), C.c_int32(nindices))
         if not h:
-            L.qa_last_error.restype = C.c_char_p
             raise ValueError((L.qa_last_error() or b"qa_mspbwt_create failed").decode())
         self.handle = C.c_void_p(h)
         self.bytes = int(L.qa_mspbwt_bytes(self.handle))
@@ -80,7 +76,6 @@ class MsPbwtIndex:
         """``out[query][index]``: (haplotype0, start0, len1) rows, as tests/mspbwt_scan.py::find_good_matches_scan."""
         from .native import lib
         lb = lib()
-        lb.qa_mspbwt_find_good_matches.restype = C.c_int64
         Zs = np.ascontiguousarray(Zs, dtype=np.int32)
         nq = Zs.shape[0]
         row_ptr = np.zeros(nq * self.nindices + 1, dtype=np.int64)
@@ -102,7 +97,6 @@ class MsPbwtIndex:
         to back).  Returns [chain, Knew] 1-based haplotypes."""
         from .native import lib
         lb = lib()
-        lb.qa_mspbwt_select_new_haps.restype = C.c_int
         Zs = np.ascontiguousarray(Zs, dtype=np.int32)
         n_chain = Zs.shape[0] // n_label
         sd = np.ascontiguousarray(seeds, dtype=np.uint64)
@@ -149,7 +143,6 @@ def select_new_haps_mspbwt_batch(match: np.ndarray, n: np.ndarray, n_label: int,
     below, tested equal): ``match`` / ``n`` as :func:`find_good_matches` returns them, the chains' ``n_label`` haplotypes back to
     back.  Returns [chain, Knew] 1-based haplotypes."""
     from .native import lib, ptr
-    lib().qa_select_new_haps_mspbwt.restype = C.c_int
     match = np.ascontiguousarray(match, dtype=np.int32)
     n = np.ascontiguousarray(n, dtype=np.int32)
     nq, ni, mm, _ = match.shape
@@ -166,7 +159,6 @@ def select_new_haps_mspbwt_batch(match: np.ndarray, n: np.ndarray, n_label: int,
 def match_weights(start1: np.ndarray, end1: np.ndarray) -> np.ndarray:
     """mspbwt.R:418-427 (native: the loop is sequential in the matches)."""
     from .native import lib, ptr
-    lib().qa_mspbwt_weights.restype = C.c_int
     s1 = np.ascontiguousarray(start1, dtype=np.int64)
     e1 = np.ascontiguousarray(end1, dtype=np.int64)
     w = np.zeros(len(s1))

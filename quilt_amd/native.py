@@ -6,7 +6,9 @@ raises: the product path never routes through a CPU implementation.
 from __future__ import annotations
 
 import ctypes as C
+import glob
 import os
+import re
 import subprocess
 
 import numpy as np
@@ -56,7 +58,6 @@ preload_note = ""   # what _preload_hip_runtime decided, for diagnostics
 def _soname_in(path: str, stem: bytes):
     """The versioned soname ``<stem>.so.N`` a shared object carries (its own SONAME or a DT_NEEDED entry): the first match in
     the file's string table."""
-    import re
     try:
         with open(path, "rb") as f:
             m = re.search(re.escape(stem) + rb"\.so\.\d+", f.read())
@@ -108,6 +109,57 @@ def _preload_hip_runtime():
     preload_note = f"torch's {theirs.decode() if theirs else 'runtime'} mapped first"
 
 
+_SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "size_t": C.c_size_t, "double": C.c_double}
+
+
+def prototypes(text: str) -> dict:
+    """``{name: (restype, argtypes)}`` of every ``qa_*`` function a header's text declares.  Scalars map by name; whatever carries
+    a ``*`` or a ``[...]``, or has a function-pointer typedef for its type, is a ``c_void_p`` (``const char *`` returns: ``c_char_p``).
+    Anything else -- a scalar type this table does not hold, text that is no declaration -- raises, naming the function."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    text = re.sub(r"^\s*#.*$", " ", text, flags=re.M)
+    text = re.sub(r'extern\s+"C"\s*\{', " ", text)
+    text = re.sub(r"typedef\s+struct\s*\{[^{}]*\}\s*\w+\s*;|typedef\s+struct\s+\w+\s+\w+\s*;", " ", text)
+    fn_types = set(re.findall(r"typedef\s+[\w\s*]+\(\s*\*\s*(\w+)\s*\)\s*\([^()]*\)\s*;", text))
+    text = re.sub(r"typedef\s+[\w\s*]+\(\s*\*\s*\w+\s*\)\s*\([^()]*\)\s*;", " ", text)
+
+    def ctype(decl, name, is_return=False):
+        words = [w for w in re.sub(r"[*\[].*", "", decl, flags=re.S).split() if w != "const"]
+        if "*" in decl or "[" in decl:
+            return C.c_char_p if is_return and words == ["char"] else C.c_void_p
+        if is_return and words == ["void"]:
+            return None
+        if words and words[0] in fn_types:
+            return C.c_void_p
+        if not words or len(words) > 2 or words[0] not in _SCALARS:
+            raise TypeError(f"{name}: no ctypes type for '{' '.join(decl.split())}'")
+        return _SCALARS[words[0]]
+
+    out = {}
+    for decl in text.replace("}", " ").split(";"):
+        if not decl.strip():
+            continue
+        m = re.fullmatch(r"\s*([\w\s*]+?)\s*\b(qa_\w+)\s*\(([^()]*)\)\s*", decl)
+        if not m:
+            raise TypeError(f"not a function declaration: '{' '.join(decl.split())}'")
+        ret, name, params = m.groups()
+        params = [] if params.strip() == "void" else params.split(",")
+        out[name] = (ctype(ret, name, True), [ctype(p, name) for p in params])
+    return out
+
+
+def declare(header: str, L: C.CDLL = None) -> C.CDLL:
+    """Set ``restype`` and ``argtypes`` of every function ``header`` declares on ``L`` (default: :func:`lib`, which applies this
+    to include/*.h; tests/ apply it to the private test-hook headers of csrc/): with them a Python ``int`` reaches an ``int64_t``
+    parameter whole, and an argument of the wrong kind or width raises ``ctypes.ArgumentError``."""
+    L = lib() if L is None else L
+    with open(header) as f:
+        for name, (restype, argtypes) in prototypes(f.read()).items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
+    return L
+
+
 def lib() -> C.CDLL:
     global _lib
     if _lib is None:
@@ -116,18 +168,8 @@ def lib() -> C.CDLL:
                                 "(or __graft_entry__.build()); there is no CPU fallback")
         _preload_hip_runtime()
         L = C.CDLL(LIB_PATH)
-        L.qa_last_error.restype = C.c_char_p
-        for name in ("qa_abi_version", "qa_device_count", "qa_set_device", "qa_panel_create", "qa_gibbs_batch",
-                 "qa_rcpp_make_eMatRead_t", "qa_profile_reset", "qa_profile_get", "qa_fullpass_reads_batch",
-                     "qa_Rcpp_haploid_dosage_versus_refs", "qa_Rcpp_make_gl_bound", "qa_fullpass_batch",
-                     "qa_last_fullpass_timing_ms", "qa_panel_set_ranking_precision", "qa_panel_set_device_share", "qa_profile_get_busy", "qa_panel_create_from_rhb",
-                     "qa_panel_export_tables", "qa_rcpp_make_eMatRead_t_nsnps", "qa_rare_common_create", "qa_profile_count",
-                     "qa_profile_get_work", "qa_panel_set_dosage_precision", "qa_panel_set_sum_order", "qa_panel_set_sum_order_batched",
-                     "qa_gibbs_batch_rare_common", "qa_nipt_block_table", "qa_panel_set_cu_partition"):
-            getattr(L, name).restype = C.c_int
-        L.qa_profile_name.restype = C.c_char_p
-        L.qa_panel_destroy.restype = None
-        L.qa_rare_common_destroy.restype = None
+        for header in sorted(glob.glob(os.path.join(os.path.dirname(HEADER), "*.h"))):   # the one place prototypes are declared
+            declare(header, L)
         _lib = L
     return _lib
 
@@ -149,12 +191,9 @@ def pinned_empty(shape, dtype=np.float64) -> np.ndarray:
     if os.environ.get("QUILT_AMD_PAGEABLE"):   # measurement hook (bench.py --pageable): what a caller that cannot use
         return np.empty(shape, dtype=dtype)    # qa_host_alloc gets -- R allocates its own vectors -- the staged path
     L = lib()
-    L.qa_host_alloc.restype = C.c_void_p
-    L.qa_host_alloc.argtypes = [C.c_size_t]
-    L.qa_host_free.argtypes = [C.c_void_p]
     dt = np.dtype(dtype)
     n = int(np.prod(shape, dtype=np.int64)) * dt.itemsize
-    p = L.qa_host_alloc(C.c_size_t(max(n, 1)))
+    p = L.qa_host_alloc(max(n, 1))
     if not p:
         raise QuiltAmdError(QA_ERR_HIP, L.qa_last_error().decode())
     raw = (C.c_char * max(n, 1)).from_address(p)
@@ -163,6 +202,7 @@ def pinned_empty(shape, dtype=np.float64) -> np.ndarray:
 
 
 class PanelDesc(C.Structure):
+    _c_name_ = "qa_panel_desc_t"
     _fields_ = [
         ("K", C.c_int32), ("nGrids", C.c_int32), ("nSNPs", C.c_int32), ("nMaxDH", C.c_int32),
         ("hapMatcherR", C.c_void_p), ("hapMatcher", C.c_void_p), ("rhb_t", C.c_void_p),
@@ -175,6 +215,7 @@ class PanelDesc(C.Structure):
 
 
 class FullpassOpts(C.Structure):
+    _c_name_ = "qa_fullpass_opts_t"
     _fields_ = [
         ("K_top_matches", C.c_int32), ("return_betaHat_t", C.c_int32), ("return_dosage", C.c_int32),
         ("return_gamma_t", C.c_int32), ("return_gammaSmall_t", C.c_int32),
@@ -269,12 +310,10 @@ class DevicePanel:
     def set_exclusive(self, on: bool = True):
         """Exclusive device phases: this handle's launch sets run with the device to themselves, out of the device-wide arena,
         queueing in arrival order behind those of the other handles that opted in (include/quilt_amd.h)."""
-        lib().qa_panel_set_exclusive.restype = C.c_int
         check(lib().qa_panel_set_exclusive(self.handle, C.c_int32(int(on))))
 
     def set_pass_priority(self, on: bool = True):
         """Full-panel calls of this handle on a highest-priority stream (several handles sharing the device)."""
-        lib().qa_panel_set_pass_priority.restype = C.c_int
         check(lib().qa_panel_set_pass_priority(self.handle, C.c_int32(int(on))))
 
     def close(self):
@@ -301,7 +340,6 @@ class DeviceRareCommon:
         rare_snp = np.ascontiguousarray(rc.rare_snp, dtype=np.int32)
         tm = np.asfortranarray(rc.transMatRate_t_all, dtype=np.float64)
         h = C.c_void_p()
-        lib().qa_rare_common_create.restype = C.c_int
         check(lib().qa_rare_common_create(device_panel.handle, C.c_int32(rc.nSNPs_all), ptr(is_common), ptr(rare_ptr),
                                           ptr(rare_snp if rare_snp.size else np.zeros(1, dtype=np.int32)), ptr(tm),
                                           C.byref(h)))
@@ -309,7 +347,6 @@ class DeviceRareCommon:
 
     def close(self):
         if self.handle:
-            lib().qa_rare_common_destroy.restype = None
             lib().qa_rare_common_destroy(self.handle)
             self.handle = None
 
@@ -323,7 +360,6 @@ class DeviceRareCommon:
 def gate_stats(device: int = 0, reset: bool = False) -> dict:
     """Exclusive device phases (DevicePanel.set_exclusive): ms some handle held the device, ms callers queued, holds."""
     out = (C.c_double * 7)()
-    lib().qa_gate_stats.restype = C.c_int
     check(lib().qa_gate_stats(C.c_int32(device), out))
     if reset:
         lib().qa_gate_stats_reset(C.c_int32(device))
@@ -334,7 +370,6 @@ def gate_stats(device: int = 0, reset: bool = False) -> dict:
 def gate_trace(device: int = 0, on: bool = True, read: bool = True) -> np.ndarray:
     """qa_gate_trace: the finished holds since the last read as rows (request, admit, kernels done, release [ms], SIMD slots
     (0: exclusive), thread); ``read=False`` only switches the trace on / off."""
-    lib().qa_gate_trace.restype = C.c_int
     if not read:
         check(min(lib().qa_gate_trace(C.c_int32(device), C.c_int32(int(on)), None, C.c_int32(0)), 0))
         return np.zeros((0, 6))

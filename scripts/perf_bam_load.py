@@ -96,9 +96,6 @@ if args.alternate:
     Lc = np.ascontiguousarray(panel.L, dtype=np.int32)
     grid = np.ascontiguousarray(np.arange(panel.nSNPs) // 32, dtype=np.int32)
     o = BamOpts(1, 1000000, 0, 0, 0, 0, 1, 1)   # (bqFilter 1, no cap: the options of the headline's load)
-    for L_ in (here, parent):
-        L_.qa_sample_reads_n_reads.restype = C.c_int
-        L_.qa_sample_reads_destroy.restype = None
 
     def load(L_, path, bx):
         h = C.c_void_p()

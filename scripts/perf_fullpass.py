@@ -76,7 +76,6 @@ def sum_order_batched():
     import json
     dev.set_dosage_precision(64)
     dev.set_sum_order(1)
-    lib().qa_panel_set_sum_order_batched.restype = C.c_int
     rows = []
     for n in a.sets:
         for what, flag in (("ranking", 0), ("dosage", 1)):
@@ -117,7 +116,6 @@ def validation_large_k():
     forms' outputs compared.  A record, not a bar."""
     import json
     dev.set_dosage_precision(64)
-    lib().qa_panel_set_sum_order_batched.restype = C.c_int
     forms = (("production", 0, 0), ("validation", 1, 0), ("validation_batched", 1, 1))
     rows = []
     for n in a.sets:
@@ -160,7 +158,6 @@ def validation_large_k():
         f.write("\n")
 
 
-lib().qa_profile_name.restype = C.c_char_p
 if a.sum_order_batched:
     sum_order_batched()
     sys.exit(0)

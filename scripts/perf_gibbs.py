@@ -38,7 +38,6 @@ for r, every_pair in [(r, e) for r in range(a.reps) for e in ((True, False) if a
         print(f"shard_check_every_pair = {every_pair}: {wall * 1e3:.1f} ms per call ({a.chains} chains)", flush=True)
     res = []
     L = native.lib()
-    L.qa_profile_name.restype = C.c_char_p
     slots = {}
     for k in range(L.qa_profile_count()):   # (the sampler's 256-register build has a slot of its own: "k_gibbs<10, 1, true>")
         ms, n, b = C.c_double(), C.c_int64(), C.c_double()

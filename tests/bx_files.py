@@ -61,32 +61,15 @@ def write_tagged_files(tmp_path, panel, n_files=3, n_reads=300, seed=21, untagge
 
 
 def impute_bam_range_bx_on_oracle(panel, bam_files, chr, ref, alt, params, n_threads=1, **kw):
-    """qa_impute_bam_range_backend_bx: the product's loader (with the tag), bookkeeping, formatting and counts, the imputation step
-    on the oracle table -- tests/native_driver_backend.impute_bam_range_on_oracle with the pair of arguments."""
-    from quilt_amd.impute import impute_bam_range
-    from quilt_amd.native import lib, ptr
-    from tests.native_driver_backend import OracleTable
+    """qa_impute_bam_range_backend_bx over the oracle table: tests/native_driver_backend.impute_bam_range_on_oracle with the loader's
+    pair of tag arguments."""
+    from quilt_amd.native import ptr
+    from tests.native_driver_backend import OracleTable, bam_range_on_table
 
-    class _Dev:
-        def __init__(self, p):
-            self.panel, self.handle = p, None
-
-    tab = OracleTable(panel)
-    handles = (C.c_void_p * n_threads)(*[C.c_void_p(w + 1) for w in range(n_threads)])
-    L = lib()
-    L.qa_impute_bam_range_backend_bx.restype = C.c_int
-    L.qa_last_error.restype = C.c_char_p
-
-    def entry(q, io, n, paths, sidx, ffv, h, use_bx_tag=C.c_int32(0), bxTagUpperLimit=C.c_int32(0)):
-        st = L.qa_impute_bam_range_backend_bx(C.byref(tab.table), handles, C.c_int32(n_threads), C.c_int32(panel.K), C.c_int32(panel.nGrids),
-                                              C.byref(q), C.byref(io), use_bx_tag, bxTagUpperLimit, C.c_int32(n), paths, ptr(sidx), ptr(ffv),
-                                              C.byref(h))
-        if tab.error is not None:
-            raise tab.error
-        if st != 0:
-            raise RuntimeError(f"qa_impute_bam_range_backend_bx: status {st}: {L.qa_last_error().decode()}")
-
-    return impute_bam_range([_Dev(panel)] * n_threads, bam_files, chr, ref, alt, params, _entry=entry, **kw)
+    def call(fn, tab, handles, n_threads, q, io, n, paths, sidx, ffv, h, use_bx_tag=0, bxTagUpperLimit=0):
+        return fn(C.byref(tab.table), handles, n_threads, panel.K, panel.nGrids, C.byref(q), C.byref(io), use_bx_tag, bxTagUpperLimit, n,
+                  paths, ptr(sidx), ptr(ffv), C.byref(h))
+    return bam_range_on_table(OracleTable(panel), "qa_impute_bam_range_backend_bx", call, bam_files, chr, ref, alt, params, n_threads, **kw)
 
 
 def assert_same_range(got, rec, kept):

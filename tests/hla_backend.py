@@ -9,9 +9,10 @@ import numpy as np
 
 from oracle import oracle as O
 from quilt_amd.impute import STAT_NAMES, flatten_samples, make_hla, make_params, wrap_results
-from quilt_amd.native import lib, ptr
+from quilt_amd.native import ptr
 from tests.native_driver_backend import F32P, F64P, I32P, U64P, OracleTable
 from tests.oracle_backend import OracleBackend
+from tests.testhooks import hook_lib
 
 SELECT_GAMMA_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, I32P, I32P, I32P, I32P, I32P, I32P, I32P, I32P,
                               I32P, C.c_int32, C.c_double, F64P, C.c_int32, I32P, F32P, I32P, C.c_int32, C.c_int32, I32P, U64P, I32P,
@@ -129,9 +130,7 @@ def impute_samples_hla_on_oracle(panel, samples, params, grid, sample_offset=0, 
     nDosage = np.zeros(n, dtype=np.int32)
     stats = np.zeros(11, dtype=np.int64)
     handles = (C.c_void_p * n_threads)(*[C.c_void_p(w + 1) for w in range(n_threads)])
-    L = lib()
-    L.qa_impute_samples_backend_hla.restype = C.c_int
-    L.qa_last_error.restype = C.c_char_p
+    L = hook_lib()
     st = L.qa_impute_samples_backend_hla(C.byref(tab.table), tab.select_gamma_cb, handles, C.c_int32(n_threads), C.c_int32(K),
                                          C.c_int32(panel.nGrids), C.c_int32(T), C.byref(q), C.c_int32(n), C.c_int64(sample_offset),
                                          *((None,) * 5 if source else (ptr(read_off), ptr(read_ptr), ptr(u), ptr(bq), ptr(wif))),

@@ -46,9 +46,8 @@ PANEL_SEED = 8800        # (no search was needed: every K passes the CPU claims 
 # ---------------------------------------------------------------------------------------------------------------------------
 def geometry(K, kind):
     """qa_fullpass_geometry as a dict of FIELDS; NT == 0: the kind does not take this K."""
-    from quilt_amd.native import lib
-    f = lib().qa_fullpass_geometry
-    f.restype = C.c_int
+    from tests.testhooks import hook_lib
+    f = hook_lib().qa_fullpass_geometry
     out = (C.c_int32 * 8)()
     st = f(C.c_int32(int(K)), C.c_int32(KINDS[kind] if isinstance(kind, str) else kind), out)
     assert st == 0, st

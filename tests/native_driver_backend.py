@@ -12,6 +12,7 @@ from quilt_amd.gibbs_nipt import GibbsOpts
 from quilt_amd.impute import ImputeParams, STAT_NAMES, flatten_samples, make_nipt, make_params, make_rare_common, wrap_results
 from quilt_amd.native import lib, ptr
 from tests.oracle_backend import OracleBackend
+from tests.testhooks import hook_lib
 
 I32P, F64P, U64P, F32P = C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_float)
 
@@ -303,9 +304,7 @@ def impute_samples_on_oracle(panel, samples, params, sample_offset=0, samples_pe
     nDosage = np.zeros(n, dtype=np.int32)
     stats = np.zeros(11, dtype=np.int64)
     handles = (C.c_void_p * n_threads)(*[C.c_void_p(w + 1) for w in range(n_threads)])
-    L = lib()
-    L.qa_impute_samples_backend.restype = C.c_int
-    L.qa_last_error.restype = C.c_char_p
+    L = hook_lib()
     st = L.qa_impute_samples_backend(C.byref(tab.table), handles, C.c_int32(n_threads), C.c_int32(panel.K), C.c_int32(panel.nGrids),
                                      C.c_int32(panel.nSNPs), C.byref(q), C.c_int32(n), C.c_int64(sample_offset),
                                      *((None,) * 5 if source is not None else (ptr(read_off), ptr(read_ptr), ptr(u), ptr(bq), ptr(wif))),
@@ -320,32 +319,39 @@ def impute_samples_on_oracle(panel, samples, params, sample_offset=0, samples_pe
     return wrap_results(samples, dosage, gp_t, haps, labels, nDosage, read_off, fd, fg), dict(zip(STAT_NAMES, stats.tolist())), tab
 
 
-def impute_bam_range_on_oracle(panel, bam_files, chr, ref, alt, params, n_threads=1, rare_common=None, **kw):
-    """qa_impute_bam_range_backend (csrc/bamrange.cpp through the private test hook): the product's loader, kept-sample
-    bookkeeping, column formatting and count arrays, with the imputation step on the oracle table."""
+def bam_range_on_table(tab, name, call, bam_files, chr, ref, alt, params, n_threads=1, rare_common=None, **kw):
+    """quilt_amd.impute.impute_bam_range with the hook ``name`` of csrc/impute_testhook.h in place of the product's entry: the loader,
+    kept-sample bookkeeping, column formatting and count arrays are the product's, the imputation step runs on ``tab``.
+    ``call(fn, tab, handles, n_threads, q, io, n, paths, sidx, ffv, h, **options)`` passes the hook its arguments."""
     from quilt_amd.impute import impute_bam_range
+    panel = tab.panel
 
     class _Dev:   # (what impute_bam_range reads of a DevicePanel: the panel; there is no native handle on this path)
         def __init__(self, p):
             self.panel, self.handle = p, None
 
-    tab = OracleTable(panel, rare_common=rare_common)
     handles = (C.c_void_p * n_threads)(*[C.c_void_p(w + 1) for w in range(n_threads)])
     if rare_common is not None:   # (the checker needs no native all-SNP handle: any non-null value per thread)
         class _Drc:
             def __init__(self, w):
                 self.rc, self.handle = rare_common, C.c_void_p(100 + w)
         kw = dict(kw, drcs=[_Drc(w) for w in range(n_threads)])
-    L = lib()
-    L.qa_impute_bam_range_backend.restype = C.c_int
-    L.qa_last_error.restype = C.c_char_p
+    L = hook_lib()
 
-    def entry(q, io, n, paths, sidx, ffv, h):
-        st = L.qa_impute_bam_range_backend(C.byref(tab.table), handles, C.c_int32(n_threads), C.c_int32(panel.K), C.c_int32(panel.nGrids),
-                                           C.byref(q), C.byref(io), C.c_int32(n), paths, ptr(sidx), ptr(ffv), C.byref(h))
+    def entry(q, io, n, paths, sidx, ffv, h, **options):
+        st = call(getattr(L, name), tab, handles, n_threads, q, io, n, paths, sidx, ffv, h, **options)
         if tab.error is not None:
             raise tab.error
         if st != 0:
-            raise RuntimeError(f"qa_impute_bam_range_backend: status {st}: {L.qa_last_error().decode()}")
+            raise RuntimeError(f"{name}: status {st}: {L.qa_last_error().decode()}")
 
     return impute_bam_range([_Dev(panel)] * n_threads, bam_files, chr, ref, alt, params, _entry=entry, **kw)
+
+
+def impute_bam_range_on_oracle(panel, bam_files, chr, ref, alt, params, n_threads=1, rare_common=None, **kw):
+    """qa_impute_bam_range_backend over the oracle table."""
+    def call(fn, tab, handles, n_threads, q, io, n, paths, sidx, ffv, h):
+        return fn(C.byref(tab.table), handles, n_threads, panel.K, panel.nGrids, C.byref(q), C.byref(io), n, paths, ptr(sidx), ptr(ffv),
+                  C.byref(h))
+    return bam_range_on_table(OracleTable(panel, rare_common=rare_common), "qa_impute_bam_range_backend", call, bam_files, chr, ref, alt,
+                              params, n_threads, rare_common, **kw)

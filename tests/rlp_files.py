@@ -8,7 +8,8 @@ import numpy as np
 
 from quilt_amd.impute import (STAT_NAMES, ImputeReadsOut, flatten_samples, make_hla, make_nipt, make_params, make_rare_common,
                               wrap_results)
-from quilt_amd.native import lib, ptr
+from quilt_amd.native import ptr
+from tests.testhooks import hook_lib
 
 
 def impute_samples_reads_on_oracle(panel, samples, params, sample_offset=0, samples_per_launch_set=256, n_threads=1, rare_common=None,
@@ -36,9 +37,7 @@ def impute_samples_reads_on_oracle(panel, samples, params, sample_offset=0, samp
     if hla_grid is not None:
         hq, hla = make_hla(hla_grid, n, P.nGibbsSamples, K)
     handles = (C.c_void_p * n_threads)(*[C.c_void_p(w + 1) for w in range(n_threads)])
-    L = lib()
-    L.qa_impute_samples_backend_reads.restype = C.c_int
-    L.qa_last_error.restype = C.c_char_p
+    L = hook_lib()
     st = L.qa_impute_samples_backend_reads(C.byref(tab.table), tab.select_gamma_cb if hq is not None else None, handles, C.c_int32(n_threads),
                                            C.c_int32(K), C.c_int32(panel.nGrids), C.c_int32(panel.nSNPs), C.byref(q), C.c_int32(n),
                                            C.c_int64(sample_offset), ptr(read_off), ptr(read_ptr), ptr(u), ptr(bq), ptr(wif), ptr(dosage),
@@ -53,39 +52,18 @@ def impute_samples_reads_on_oracle(panel, samples, params, sample_offset=0, samp
 
 
 def impute_bam_range_ex_on_oracle(panel, bam_files, chr, ref, alt, params, n_threads=1, rare_common=None, **kw):
-    """qa_impute_bam_range_backend_ex: the product's loader (with names), bookkeeping, formatting and counts, the imputation step on
-    the oracle table (with the gamma-column entry)."""
-    from quilt_amd.impute import impute_bam_range
+    """qa_impute_bam_range_backend_ex over the oracle table with the gamma-column entry (the loader then keeps the names)."""
+    from quilt_amd.impute import BamRangeExtras
     from tests.hla_backend import OracleTableHLA
+    from tests.native_driver_backend import bam_range_on_table
 
-    class _Dev:
-        def __init__(self, p):
-            self.panel, self.handle = p, None
-
-    tab = OracleTableHLA(panel, rare_common=rare_common)
-    handles = (C.c_void_p * n_threads)(*[C.c_void_p(w + 1) for w in range(n_threads)])
-    if rare_common is not None:   # (the checker needs no native all-SNP handle: any non-null value per thread)
-        class _Drc:
-            def __init__(self, w):
-                self.rc, self.handle = rare_common, C.c_void_p(100 + w)
-        kw = dict(kw, drcs=[_Drc(w) for w in range(n_threads)])
-    L = lib()
-    L.qa_impute_bam_range_backend_ex.restype = C.c_int
-    L.qa_last_error.restype = C.c_char_p
-
-    def entry(q, io, n, paths, sidx, ffv, h, ex=None, **bx):
-        from quilt_amd.impute import BamRangeExtras
+    def call(fn, tab, handles, n_threads, q, io, n, paths, sidx, ffv, h, ex=None, **bx):
         if ex is None:   # (a call without an option: the zeroed struct, which is qa_impute_bam_range)
             ex = BamRangeExtras(int(bx["use_bx_tag"].value) if bx else 0, int(bx["bxTagUpperLimit"].value) if bx else 0, 0, -1)
-        st = L.qa_impute_bam_range_backend_ex(C.byref(tab.table), tab.select_gamma_cb, handles, C.c_int32(n_threads), C.c_int32(panel.K),
-                                              C.c_int32(panel.nGrids), C.byref(q), C.byref(io), C.byref(ex), C.c_int32(n), paths, ptr(sidx),
-                                              ptr(ffv), C.byref(h))
-        if tab.error is not None:
-            raise tab.error
-        if st != 0:
-            raise RuntimeError(f"qa_impute_bam_range_backend_ex: status {st}: {L.qa_last_error().decode()}")
-
-    return impute_bam_range([_Dev(panel)] * n_threads, bam_files, chr, ref, alt, params, _entry=entry, **kw)
+        return fn(C.byref(tab.table), tab.select_gamma_cb, handles, n_threads, panel.K, panel.nGrids, C.byref(q), C.byref(io), C.byref(ex), n,
+                  paths, ptr(sidx), ptr(ffv), C.byref(h))
+    return bam_range_on_table(OracleTableHLA(panel, rare_common=rare_common), "qa_impute_bam_range_backend_ex", call, bam_files, chr, ref,
+                              alt, params, n_threads, rare_common, **kw)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------

@@ -45,9 +45,111 @@ def test_no_cpu_fallback_without_a_device(lib):
     assert lib.qa_Rcpp_haploid_dosage_versus_refs(None, native.ptr(gl), None, None, None, None, None, None, None,
                                                   None, None, None, None, C.c_int64(0)) == native.QA_ERR_NO_DEVICE
     assert lib.qa_gibbs_batch(None, None, 1, None, None, None, None, None, None, None, None, None, None, None, None,
-                              None, None, None, None) == native.QA_ERR_NO_DEVICE
+                              None, None, None, None, None, None) == native.QA_ERR_NO_DEVICE
     with pytest.raises(native.QuiltAmdError):
         native.check(lib.qa_set_device(0))
+
+
+def _header_prototypes():
+    """{name: parameter count} of include/*.h, by a scan of its own (not native.prototypes): the text between a declared name's
+    parentheses, split at the commas."""
+    import glob
+    counts = {}
+    for header in glob.glob(os.path.join(os.path.dirname(native.HEADER), "*.h")):
+        text = re.sub(r"/\*.*?\*/", "", open(header).read(), flags=re.S)
+        for name, params in re.findall(r"\b(qa_[a-zA-Z0-9_]+)\s*\(([^()]*)\)\s*;", text):
+            counts[name] = 0 if params.strip() == "void" else params.count(",") + 1
+    return counts
+
+
+def test_every_declared_function_has_its_prototype(lib):
+    counts = _header_prototypes()
+    names = _declared_functions()
+    assert set(counts) == set(names)
+    for n in names:
+        f = getattr(lib, n)
+        assert f.argtypes is not None, f"{n} has no argtypes"
+        assert len(f.argtypes) == counts[n], f"{n}: {len(f.argtypes)} argtypes, {counts[n]} parameters in the header"
+    restype = lambda n: getattr(lib, n).restype
+    assert (restype("qa_host_alloc"), getattr(lib, "qa_host_alloc").argtypes) == (C.c_void_p, [C.c_size_t])
+    assert restype("qa_mspbwt_create") is C.c_void_p
+    for n in ("qa_mspbwt_bytes", "qa_mspbwt_find_good_matches", "qa_sample_reads_n_bases", "qa_sample_reads_names_bytes"):
+        assert restype(n) is C.c_int64, n
+    for n in ("qa_last_error", "qa_profile_name", "qa_vcf_missing_entry"):
+        assert restype(n) is C.c_char_p, n
+    text = "".join(open(os.path.join(os.path.dirname(native.HEADER), h)).read() for h in ("quilt_amd.h", "quilt_amd_io.h"))
+    void_functions = re.findall(r"^void\s+(qa_\w+)\s*\(", text, flags=re.M)
+    assert len(void_functions) >= 8
+    for n in names:
+        assert (restype(n) is None) == (n in void_functions), n
+
+
+def test_the_prototype_parser_reads_the_shapes_the_headers_use():
+    text = """
+    /* a comment with qa_not_a_function(int x); in it */
+    #include <stdint.h>
+    #ifdef __cplusplus
+    extern "C" {
+    #endif
+    typedef struct qa_thing qa_thing_t;   // opaque
+    typedef struct { int32_t a; void (*cb)(void *ctx, int32_t x); double v[4]; } qa_opts_t;
+    typedef int (*qa_visit_fn)(void *handle, int32_t n,
+                               double *out);
+    int qa_three_lines(qa_thing_t *t, int32_t n,
+                       const double *x, int64_t cap,
+                       size_t bytes, double q);
+    int qa_nothing(void);
+    int qa_array(int32_t device, double out[7]);
+    int qa_handles(qa_thing_t *const *things, int n, const qa_opts_t *opts);
+    const char *qa_text(void);
+    qa_thing_t *qa_make(const char *path);
+    void *qa_raw(size_t bytes);
+    void qa_drop(qa_thing_t *t);
+    int64_t qa_count(const qa_thing_t *t);
+    int qa_visit(qa_visit_fn visit, void *const *handles);
+    #ifdef __cplusplus
+    }
+    #endif
+    """
+    P, I32, I64, D = C.c_void_p, C.c_int32, C.c_int64, C.c_double
+    assert native.prototypes(text) == {
+        "qa_three_lines": (C.c_int, [P, I32, P, I64, C.c_size_t, D]), "qa_nothing": (C.c_int, []), "qa_array": (C.c_int, [I32, P]),
+        "qa_handles": (C.c_int, [P, C.c_int, P]), "qa_text": (C.c_char_p, []), "qa_make": (P, [P]), "qa_raw": (P, [C.c_size_t]),
+        "qa_drop": (None, [P]), "qa_count": (I64, [P]), "qa_visit": (C.c_int, [P, P]),
+    }
+    for bad in ("int qa_unknown_scalar(int32_t n, float x);", "unsigned qa_unknown_return(void);", "int qa_by_value(qa_opts_t opts);"):
+        with pytest.raises(TypeError, match=bad.split("(")[0].split()[-1]):
+            native.prototypes(bad)
+    with pytest.raises(TypeError):
+        native.prototypes("int qa_fine(void); static const int x = 3;")   # (text that is no declaration does not pass silently)
+
+
+def test_a_wrong_argument_raises_instead_of_passing(lib):
+    ms, n, b = C.c_double(), C.c_int64(), C.c_double()
+    with pytest.raises(C.ArgumentError):
+        lib.qa_profile_get(0.5, C.byref(ms), C.byref(n), C.byref(b))
+    gl = np.ones((2, 4))
+    with pytest.raises(C.ArgumentError):   # (best_cap is an int64_t: a 32-bit wrapper left the register's upper half undefined)
+        lib.qa_Rcpp_haploid_dosage_versus_refs(None, native.ptr(gl), None, None, None, None, None, None, None, None, None, None,
+                                               None, C.c_int32(0))
+    with pytest.raises(C.ArgumentError):
+        lib.qa_host_alloc(C.c_int64(64))
+
+
+def test_prototypes_are_declared_in_one_place():
+    """No file of the package, tests/, scripts/ or the build entry assigns restype / argtypes on a qa_* function: quilt_amd/native.py
+    takes every prototype from the headers when it loads the library (declare), the test-hook headers included."""
+    root = os.path.dirname(os.path.dirname(native.CSRC))
+    pat = re.compile(r"qa_\w+\.(restype|argtypes)\s*=[^=]")
+    files = [os.path.join(root, "__graft_entry__.py")]
+    for top in ("quilt_amd", "tests", "scripts"):
+        for dirpath, _, names in os.walk(os.path.join(root, top)):
+            files += [os.path.join(dirpath, f) for f in names if f.endswith((".py", ".sh", ".R"))]
+    assert len(files) > 50
+    for f in files:
+        if os.path.realpath(f) == os.path.realpath(native.__file__):
+            continue
+        assert not pat.search(open(f).read()), f"{os.path.relpath(f, root)} declares a prototype of its own"
 
 
 def test_product_path_never_imports_the_oracle():

@@ -92,8 +92,6 @@ def test_device_gate_admission_rules():
     import ctypes
     from quilt_amd import native
     lib = native.lib()
-    lib.qa_gate_selftest.restype = ctypes.c_int
-    lib.qa_last_error.restype = ctypes.c_char_p
     assert lib.qa_gate_selftest() == 0, lib.qa_last_error()
 
 

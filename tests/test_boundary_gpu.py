@@ -55,6 +55,5 @@ def test_pinned_host_buffers_take_the_same_bytes_as_staged_ones():
     assert np.array_equal(d1, d2)
     assert d1.min() >= 0 and d1.max() <= 1 and d1.std() > 0
     # errors: a pointer the library did not hand out
-    lib().qa_host_free.argtypes = [C.c_void_p]
     assert lib().qa_host_free(C.c_void_p(haps.ctypes.data)) < 0
     del pinned, b

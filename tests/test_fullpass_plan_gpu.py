@@ -10,6 +10,8 @@ import sys
 import numpy as np
 import pytest
 
+from tests.testhooks import last_plan
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -20,14 +22,6 @@ def _carve_align():
     """The arena's carve alignment, as common.hpp states it."""
     src = open(os.path.join(ROOT, "quilt_amd", "csrc", "common.hpp")).read()
     return int(re.search(r"kCarveAlign\s*=\s*(\d+)\s*;", src).group(1))
-
-
-def _last_plan():
-    from quilt_amd.native import check, lib
-    out = (C.c_int64 * 6)()
-    lib().qa_fullpass_last_plan.restype = C.c_int
-    check(lib().qa_fullpass_last_plan(out))
-    return dict(zip(("P", "planned", "fixed", "carved", "n_buf", "kind"), (int(v) for v in out)))
 
 
 @pytest.fixture(scope="module")
@@ -114,7 +108,7 @@ def test_plan_is_what_is_carved(kind, which_panel, small_panel, two_row_panel):
         for what, rank_bits, call in shapes:
             dev.set_ranking_precision(rank_bits)
             call(dev, panel, cols)
-            h = _last_plan()
+            h = last_plan()
             print(what, h)
             assert h["kind"] == kind, (what, h)
             assert h["P"] == (1 if call is _matrices else 6 if call is _gamma_column else 3), (what, h)
@@ -132,14 +126,14 @@ import numpy as np
 from quilt_amd.driver import thinned_grid_columns
 from quilt_amd.native import DevicePanel, QA_ERR_CAPACITY, check, lib, ptr
 from quilt_amd.synth import make_synthetic_panel
+from tests.testhooks import hook_lib
 panel = make_synthetic_panel(K=30011, nSNPs=6400, seed=21)
 T = panel.nSNPs
 cols = np.ascontiguousarray(thinned_grid_columns(panel.nGrids, 0.1), dtype=np.int32)
 n_thin = int((cols >= 0).sum())
 dev = DevicePanel(panel)
 dev.set_dosage_precision(64)
-L = lib()
-L.qa_fullpass_last_plan.restype = C.c_int
+L = hook_lib()
 hook = (C.c_int64 * 6)()
 rows = np.random.default_rng(7).uniform(0.05, 1.0, size=(5, T, 2))
 

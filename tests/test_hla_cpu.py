@@ -55,8 +55,6 @@ def test_new_symbols_are_exported_and_need_a_device():
     for name in ("qa_fullpass_reads_select_gamma_batch", "qa_impute_samples_hla", "qa_impute_samples_backend_hla"):
         assert hasattr(L, name), name
     from quilt_amd.impute import make_hla
-    L.qa_fullpass_reads_select_gamma_batch.restype = C.c_int
-    L.qa_impute_samples_hla.restype = C.c_int
     hq, keep = make_hla(0, 1, 1, 1)
     gcol = np.zeros(1)
     if L.qa_device_count() < 1:

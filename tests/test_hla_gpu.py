@@ -95,8 +95,6 @@ def test_fp32_dosage_passes_are_refused(small_panel):
     dev = DevicePanel(small_panel)
     dev.set_dosage_precision(32)
     L = lib()
-    L.qa_fullpass_reads_select_gamma_batch.restype = C.c_int
-    L.qa_last_error.restype = C.c_char_p
     n = len(cs)
     read_off = np.array([0, samples[0].nReads, samples[0].nReads + samples[1].nReads], dtype=np.int32)
     read_ptr = np.concatenate([np.asarray(s.read_ptr, dtype=np.int32) for s in samples])

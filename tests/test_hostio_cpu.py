@@ -489,7 +489,6 @@ def test_vcf_columns_reject_values_they_cannot_print():
     from quilt_amd.native import ptr
     from quilt_amd.io import _io_lib
     lib = _io_lib()
-    lib.qa_last_error.restype = C.c_char_p
     T = 4
     gp = np.tile(np.array([0.25, 0.5, 0.25]), T)
     hd = np.full(2 * T, 0.5)

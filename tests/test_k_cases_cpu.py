@@ -14,10 +14,9 @@ ROWS = (64, 128, 192, 256, 320, 384, 448, 512)
 # the table against the launchers' switches
 # ---------------------------------------------------------------------------------------------------------------------------
 def test_hook_needs_no_device_and_checks_its_arguments():
-    from quilt_amd.native import lib
+    from tests.testhooks import hook_lib
     import ctypes as C
-    f = lib().qa_fullpass_geometry
-    f.restype = C.c_int
+    f = hook_lib().qa_fullpass_geometry
     out = (C.c_int32 * 8)()
     assert f(C.c_int32(0), C.c_int32(0), out) != 0 and f(C.c_int32(5), C.c_int32(9), out) != 0 and f(C.c_int32(5), C.c_int32(0), None) != 0
     # (3 125 chunks of 16 over 7 per lane: 447 lanes, rounded up to whole waves)

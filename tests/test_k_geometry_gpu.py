@@ -25,13 +25,13 @@ addition rounds the same way and its c is off by up to 2e-12 -- measured on the 
 
 tests/test_k_cases_cpu.py proves on the oracle that the planted rows head every list in a stated order with gammas 1e-6 apart (or
 exact copies), so no comparison branches on the device's result, and nothing is skipped."""
-import ctypes as C
 
 import numpy as np
 import pytest
 
 from tests import k_cases as KC
 from tests.test_grid_geometry_gpu import _batch, _lists_equal, _reads_args, _select_both, _single
+from tests.testhooks import last_plan
 from tests.util import check_best_haps
 
 pytestmark = pytest.mark.gpu
@@ -60,14 +60,6 @@ def device_panel():
     yield get
     for _, dev in held.values():
         dev.close()
-
-
-def _last_kind():
-    from quilt_amd.native import check, lib
-    out = (C.c_int64 * 6)()
-    lib().qa_fullpass_last_plan.restype = C.c_int
-    check(lib().qa_fullpass_last_plan(out))
-    return int(out[5])
 
 
 def _singles(K):
@@ -175,7 +167,7 @@ def test_generic_fp64_passes(K, device_panel):
         try:
             ref = KC.oracle_ref(c, "full", 1, True)
             got = _single(dev, c, dosage=True, alpha=True, gamma=True, beta=True, always_normalize=True)
-            assert _last_kind() == KIND_F64_FULL
+            assert last_plan()["kind"] == KIND_F64_FULL
             for name in ("alphaHat_t", "betaHat_t", "gamma_t"):
                 np.testing.assert_allclose(got[name], ref[name], rtol=1e-9, atol=1e-300, err_msg=name)
             assert np.abs(got["dosage"] - ref["dosage"]).max() <= 1e-9

@@ -263,7 +263,6 @@ def test_handle_buffers_go_with_the_handle(medium_panel):
     from quilt_amd.synth import make_synthetic_sample
     L = lib()
     import ctypes
-    L.qa_impute_kept_buffers.restype = ctypes.c_int
     L.qa_impute_release_buffers()
     assert L.qa_impute_kept_buffers() == 0
     samples = [make_synthetic_sample(medium_panel, seed=4300 + i, n_reads=300) for i in range(2)]

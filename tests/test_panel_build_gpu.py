@@ -76,7 +76,6 @@ def test_make_rhb_t_from_rhi_t():
             rhi[:, 3] *= 7                     # any non-zero entry is an alternate allele
         G = (T + 31) // 32
         out = np.zeros((K, G), dtype=np.int32, order="F")
-        lib().qa_make_rhb_t_from_rhi_t.restype = C.c_int
         check(lib().qa_make_rhb_t_from_rhi_t(ptr(rhi), C.c_int32(K), C.c_int32(T), ptr(out)))
         pad = np.zeros((K, 32 * G), dtype=np.uint64)
         pad[:, :T] = rhi != 0

@@ -236,13 +236,11 @@ def test_dense_rare_common_entry_on_planted_layouts(dev, handle_of, oracle, fami
 def create(dev, nSNPs_all, is_common, rare_ptr, rare_snp, tm):
     from quilt_amd.native import lib, ptr
     h = C.c_void_p()
-    lib().qa_rare_common_create.restype = C.c_int
     keep = [None if a is None else np.ascontiguousarray(a, dtype=t) for a, t in ((is_common, np.uint8), (rare_ptr, np.int64),
                                                                                    (rare_snp, np.int32), (tm, np.float64))]
     st = lib().qa_rare_common_create(dev.handle, C.c_int32(nSNPs_all), *[ptr(a) for a in keep], C.byref(h))
     msg = lib().qa_last_error().decode() if st < 0 else ""
     if st >= 0:
-        lib().qa_rare_common_destroy.restype = None
         lib().qa_rare_common_destroy(h)
     return st, msg
 

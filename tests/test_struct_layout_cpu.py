@@ -14,15 +14,19 @@ INC = os.path.join(ROOT, "include")
 
 
 def _mirrors():
-    from quilt_amd.gibbs_nipt import GibbsOpts
-    from quilt_amd.impute import BamRangeIo, ImputeNipt, ImputeParams, ImputeRareCommon, SampleSource, SampleView
-    from quilt_amd.io import BamOpts
-    from quilt_amd.native import FullpassOpts, PanelDesc
-    return {
-        "qa_impute_params_t": ImputeParams, "qa_impute_nipt_t": ImputeNipt, "qa_impute_rare_common_t": ImputeRareCommon,
-        "qa_sample_view_t": SampleView, "qa_sample_source_t": SampleSource, "qa_gibbs_opts_t": GibbsOpts,
-        "qa_fullpass_opts_t": FullpassOpts, "qa_panel_desc_t": PanelDesc, "qa_bam_opts_t": BamOpts, "qa_bam_range_io_t": BamRangeIo,
-    }
+    """{C typedef: mirror} of every ctypes.Structure subclass the package's modules define: each names its struct in ``_c_name_``,
+    and one without the attribute fails here -- a mirror cannot be added without coming under the layout test."""
+    import importlib
+    import pkgutil
+    import quilt_amd
+    found = {}
+    for info in pkgutil.iter_modules(quilt_amd.__path__):
+        mod = importlib.import_module("quilt_amd." + info.name)
+        for cls in vars(mod).values():
+            if isinstance(cls, type) and issubclass(cls, C.Structure) and cls.__module__ == mod.__name__:
+                assert "_c_name_" in vars(cls), f"{mod.__name__}.{cls.__name__} does not name its C struct (_c_name_)"
+                assert found.setdefault(cls._c_name_, cls) is cls, f"two mirrors of {cls._c_name_}"
+    return found
 
 
 def _header_text():
@@ -55,6 +59,7 @@ def _members(struct_name, text):
 
 def test_python_mirrors_have_the_headers_layout(tmp_path):
     mirrors = _mirrors()
+    assert len(mirrors) >= 14, sorted(mirrors)   # (the walk found the package's mirrors, not an empty set)
     text = _header_text()
     members = {s: _members(s, text) for s in mirrors}
     lines = ["#include <stddef.h>", "#include <stdio.h>", '#include "quilt_amd.h"', '#include "quilt_amd_io.h"', "int main(void) {"]

@@ -15,6 +15,8 @@ import dataclasses
 import numpy as np
 import pytest
 
+from tests.testhooks import launch_set
+
 pytestmark = pytest.mark.gpu
 
 QA_ERR_INVALID = -2   # include/quilt_amd.h
@@ -29,7 +31,6 @@ def oracle():
 
 def _set_batched(dev, on):
     from quilt_amd.native import lib
-    lib().qa_panel_set_sum_order_batched.restype = C.c_int
     return lib().qa_panel_set_sum_order_batched(dev.handle, C.c_int32(on))
 
 
@@ -78,24 +79,6 @@ def _thin(G):
     return cols
 
 
-def _launch_set(dev, gl, flags, cols, K_top, always_normalize):
-    """qa_fullpass_launch_set (csrc/fullpass_testhook.h): c, dosage, list pointers / indices / values of one launch set"""
-    from quilt_amd.native import check, lib, ptr
-    panel = dev.panel
-    n, T, G = gl.shape[0], panel.nSNPs, panel.nGrids
-    n_thin = int((cols >= 0).sum()) if K_top > 0 else 0
-    cap = max(n * n_thin * panel.K, 1)
-    bptr = np.zeros(n * max(n_thin, 1) + 1, dtype=np.int32)
-    bidx, bval = np.zeros(cap, dtype=np.int32), np.zeros(cap)
-    dosage, c = np.zeros((n, T)), np.zeros((n, G))
-    lib().qa_fullpass_launch_set.restype = C.c_int
-    check(lib().qa_fullpass_launch_set(dev.handle, C.c_int32(n), ptr(gl), ptr(np.ascontiguousarray(flags, dtype=np.int32)), ptr(cols),
-                                       C.c_int32(K_top), C.c_int32(int(always_normalize)), ptr(dosage), ptr(c), ptr(bptr), ptr(bidx),
-                                       ptr(bval), C.c_int64(cap)))
-    total = int(bptr[n * n_thin]) if n_thin else 0
-    return dict(c=c, dosage=dosage, list_ptr=bptr[:n * n_thin + 1].copy(), list_idx=bidx[:total].copy(), list_val=bval[:total].copy())
-
-
 def _same(a, b, what):
     assert a.keys() == b.keys()
     for k in a:
@@ -109,9 +92,9 @@ def _mixed_flags(P):
 
 def _both_forms(dev, gl, flags, cols, K_top, an, what):
     _set_batched(dev, 0)
-    off = _launch_set(dev, gl, flags, cols, K_top, an)
+    off = launch_set(dev, gl, flags, cols, K_top, an)
     assert _set_batched(dev, 1) == 0
-    on = _launch_set(dev, gl, flags, cols, K_top, an)
+    on = launch_set(dev, gl, flags, cols, K_top, an)
     _set_batched(dev, 0)
     _same(on, off, what)
     return on
@@ -218,8 +201,8 @@ def test_switch_on_equals_the_oracle_bit_for_bit(oracle, K, G, symbols):
             oracle.set_sum_order(ltr)
             dev.set_sum_order(order)
             for an in (0, 1):
-                got = _launch_set(dev, gl, flags, cols, K_TOP, an)
-                alone = _launch_set(dev, gl, np.ones(P, dtype=np.int32), cols, 0, an)   # every pass a dosage pass, the one without reads too
+                got = launch_set(dev, gl, flags, cols, K_TOP, an)
+                alone = launch_set(dev, gl, np.ones(P, dtype=np.int32), cols, 0, an)   # every pass a dosage pass, the one without reads too
                 for p in range(P):
                     ref = oracle.haploid_dosage_versus_refs(panel, np.asfortranarray(gl[p].T), cols, K_top_matches=K_TOP,
                                                             always_normalize=bool(an), get_best_haps_from_thinned_sites=True,

@@ -14,11 +14,11 @@ variant), 57 345 (15 rows), 65 536 (16, exactly full) and 70 001 (18, ragged).  
 control failed with QA_ERR_UNSUPPORTED ("limited to K <= 57 344", "exceeds the on-chip capacity of the reference-order
 validation full-pass kernels") or "K exceeds the on-chip capacity of the full-pass kernels".
 """
-import ctypes as C
 
 import numpy as np
 import pytest
 
+from tests.testhooks import last_plan, launch_set
 from tests.util import label_gl, thin_cols
 
 pytestmark = pytest.mark.gpu
@@ -184,32 +184,6 @@ def test_tie_rich_panel(oracle):
 # ---------------------------------------------------------------------------------------------------------------------------
 # 4. launch sets, both forms of the kernels
 # ---------------------------------------------------------------------------------------------------------------------------
-def _launch_set(dev, gl, flags, cols, K_top, always_normalize):
-    """qa_fullpass_launch_set (csrc/fullpass_testhook.h): c, dosage, list pointers / indices / values of one launch set"""
-    from quilt_amd.native import check, lib, ptr
-    panel = dev.panel
-    n, T, G = gl.shape[0], panel.nSNPs, panel.nGrids
-    n_thin = int((cols >= 0).sum())
-    cap = n * n_thin * panel.K
-    bptr = np.zeros(n * n_thin + 1, dtype=np.int32)
-    bidx, bval = np.zeros(cap, dtype=np.int32), np.zeros(cap)
-    dosage, c = np.zeros((n, T)), np.zeros((n, G))
-    lib().qa_fullpass_launch_set.restype = C.c_int
-    check(lib().qa_fullpass_launch_set(dev.handle, C.c_int32(n), ptr(gl), ptr(np.ascontiguousarray(flags, dtype=np.int32)), ptr(cols),
-                                       C.c_int32(K_top), C.c_int32(int(always_normalize)), ptr(dosage), ptr(c), ptr(bptr), ptr(bidx),
-                                       ptr(bval), C.c_int64(cap)))
-    total = int(bptr[n * n_thin])
-    return dict(c=c, dosage=dosage, list_ptr=bptr.copy(), list_idx=bidx[:total].copy(), list_val=bval[:total].copy())
-
-
-def _last_plan():
-    from quilt_amd.native import check, lib
-    out = (C.c_int64 * 6)()
-    lib().qa_fullpass_last_plan.restype = C.c_int
-    check(lib().qa_fullpass_last_plan(out))
-    return dict(zip(("P", "planned", "fixed", "carved", "n_buf", "kind"), (int(v) for v in out)))
-
-
 @pytest.mark.parametrize("K", [57345, 65536])
 def test_launch_sets_in_both_forms_equal_the_oracle(oracle, K):
     """Three passes (dosage, lists only, dosage) in one launch set, always_normalize off and on: c, dosage, list pointers,
@@ -232,8 +206,8 @@ def test_launch_sets_in_both_forms_equal_the_oracle(oracle, K):
             res = {}
             for on in (0, 1):
                 dev.set_sum_order_batched(on)
-                res[on] = _launch_set(dev, gl, flags, cols, K_TOP, an)
-                h = _last_plan()
+                res[on] = launch_set(dev, gl, flags, cols, K_TOP, an)
+                h = last_plan()
                 assert h["kind"] == KIND_F64_REF and h["P"] == 3, h
                 assert h["carved"] <= h["fixed"] + h["P"] * h["planned"], h
             for key in res[0]:

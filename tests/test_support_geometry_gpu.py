@@ -63,7 +63,6 @@ def test_make_rhb_t_from_rhi_t(case):
     rhi = case.build()
     G = (case.nSNPs + 31) // 32
     out = np.full((case.K, G), -1, dtype=np.int32, order="F")
-    lib().qa_make_rhb_t_from_rhi_t.restype = C.c_int
     check(lib().qa_make_rhb_t_from_rhi_t(ptr(rhi), C.c_int32(case.K), C.c_int32(case.nSNPs), ptr(out)))
     assert np.array_equal(out, case.expected(rhi))
 
@@ -134,7 +133,8 @@ def test_more_positions_than_the_histogram_holds():
 # ---------------------------------------------------------------------------------------------------------------------------
 def select_from_lists(top, which, seeds, want, K, Ksubset, Knew, K_top_matches, top_width):
     """qa_select_from_lists (csrc/fullpass_testhook.h): which_next [chain][Ksubset], pre-filled with SENTINEL, and status."""
-    from quilt_amd.native import check, lib, ptr
+    from quilt_amd.native import check, ptr
+    from tests.testhooks import hook_lib
     top = np.ascontiguousarray(top, dtype=np.int32)
     n_chain, n_label, n_thin, width = top.shape
     assert width == top_width
@@ -143,8 +143,7 @@ def select_from_lists(top, which, seeds, want, K, Ksubset, Knew, K_top_matches, 
     want = np.ascontiguousarray(want, dtype=np.int32)
     nxt = np.full((n_chain, Ksubset), S.SENTINEL, dtype=np.int32)
     status = np.full(n_chain, -99, dtype=np.int32)
-    lib().qa_select_from_lists.restype = C.c_int
-    check(lib().qa_select_from_lists(C.c_int32(n_chain), C.c_int32(n_label), C.c_int32(n_thin), C.c_int32(top_width),
+    check(hook_lib().qa_select_from_lists(C.c_int32(n_chain), C.c_int32(n_label), C.c_int32(n_thin), C.c_int32(top_width),
                                      C.c_int32(K_top_matches), C.c_int32(K), C.c_int32(Ksubset), C.c_int32(Knew), ptr(top),
                                      ptr(which), ptr(seeds), ptr(want), ptr(nxt), ptr(status)))
     return nxt, status

@@ -288,7 +288,6 @@ def test_every_entry_refuses_K_top_matches_65(rig, device_panel):
         assert e.value.status == -3
     # the range call
     L = lib()
-    L.qa_impute_kept_buffers.restype = C.c_int
     panel, _, samples, P = MM.make_case(dict(WIDE_ROW, K_top_matches=65), reads=300, seed0=70)
     kept = L.qa_impute_kept_buffers()
     with pytest.raises(QuiltAmdError, match=r"1\.\.64") as e:

@@ -30,6 +30,7 @@
 #include "fullpass_dev.hpp"
 #include "fullpass_testhook.h"
 #include "pass_layout.hpp"
+#include "variants.hpp"
 
 #include <algorithm>
 #include <chrono>
@@ -930,8 +931,17 @@ constexpr KindInfo kKindInfo[qa::KIND_COUNT] = {
 // still get >= 2 chunks per lane for ILP.  KIND_F64_RANK: 512 threads, chunk rows of 8192 haplotypes (fullpass64.hip).
 // KIND_F64_FULL: 256 threads, NCH = ceil(K / 4096) rounded up to a built variant.  KIND_F64_REF: the same up to the largest
 // built variant (so that nothing moves there), NCH = ceil(K / 4096) beyond.
-constexpr int kNchList32[] = {1, 2, 3, 4, 5, 6, 7, 8, 10, 12};
-constexpr int kNchList64[] = {1, 2, 4, 6, 8, 10, 12, 13, 14};
+// The NCH values pick_geometry chooses from (whatever the build flavour: K -> geometry -> layout is the same in every build), and
+// those this build holds kernels for: all of them, or with QA_FAST_BUILD one of each kind.
+using Nch32 = qa::IntList<1, 2, 3, 4, 5, 6, 7, 8, 10, 12>;
+using Nch64 = qa::IntList<1, 2, 4, 6, 8, 10, 12, 13, 14>;
+#ifdef QA_FAST_BUILD
+using Nch32Built = qa::IntList<2, 7>;
+using Nch64Built = qa::IntList<2, 13>;
+#else
+using Nch32Built = Nch32;
+using Nch64Built = Nch64;
+#endif
 Geometry pick_geometry(int K, PassKind kind = KIND_F32) {
     const int chunks = (K + 15) / 16;
     if (kind == KIND_F64_RANK || kind == KIND_F64_DOS) {
@@ -941,7 +951,7 @@ Geometry pick_geometry(int K, PassKind kind = KIND_F32) {
     }
     if (kind == KIND_F64_FULL || kind == KIND_F64_REF) {   // (the validation kernels write the generic kernels' layout)
         const int need = (K + 4095) / 4096;
-        for (int nch : kNchList64) if (nch >= need) return {256, nch, kind};
+        for (int nch : Nch64::values) if (nch >= need) return {256, nch, kind};
         // The list is the generic kernels' BUILT variants.  The validation kernels take the layout's NT and Kq at run time and keep
         // a pass's state in HBM (PassParams::spill) once it exceeds LDS, so beyond the list they get the layout of exactly the
         // chunk rows K needs: any K.
@@ -955,7 +965,7 @@ Geometry pick_geometry(int K, PassKind kind = KIND_F32) {
         if (nch == 1 && chunks > 128) return 0;
         return nt;
     };
-    for (int nch : kNchList32) if (int nt = fit(nch)) return {nt, nch, kind};
+    for (int nch : Nch32::values) if (int nt = fit(nch)) return {nt, nch, kind};
     return {0, 0, kind};
 }
 
@@ -1033,42 +1043,14 @@ void launch_fb_any(const Geometry &geo, const PassParams &prm, hipStream_t st, h
         else qa::launch_fb_ref(&prm, geo.NT, st, e_mid);
         return;
     }
-    if (geo.kind == KIND_F64_FULL) {
-        switch (geo.NCH) {
-#ifndef QA_FAST_BUILD
-            case 1: launch_fb<double, 1, 256, true>(prm, geo.NT, st, e_mid); break;
-            case 4: launch_fb<double, 4, 256, true>(prm, geo.NT, st, e_mid); break;
-            case 6: launch_fb<double, 6, 256, true>(prm, geo.NT, st, e_mid); break;
-            case 8: launch_fb<double, 8, 256, true>(prm, geo.NT, st, e_mid); break;
-            case 10: launch_fb<double, 10, 256, true>(prm, geo.NT, st, e_mid); break;
-            case 12: launch_fb<double, 12, 256, true>(prm, geo.NT, st, e_mid); break;
-            case 14: launch_fb<double, 14, 256, true>(prm, geo.NT, st, e_mid); break;
-#endif
-            case 2: launch_fb<double, 2, 256, true>(prm, geo.NT, st, e_mid); break;
-            case 13: launch_fb<double, 13, 256, true>(prm, geo.NT, st, e_mid); break;
-            default: throw std::runtime_error("geometry not built");
-        }
-        return;
-    }
-    switch (geo.NCH) {
-#ifndef QA_FAST_BUILD
-        case 1: launch_fb<float, 1, 512, true>(prm, geo.NT, st, e_mid); break;
-        case 3: launch_fb<float, 3, 512, true>(prm, geo.NT, st, e_mid); break;
-        case 4: launch_fb<float, 4, 512, true>(prm, geo.NT, st, e_mid); break;
-        case 5: launch_fb<float, 5, 512, true>(prm, geo.NT, st, e_mid); break;
-        case 6: launch_fb<float, 6, 512, true>(prm, geo.NT, st, e_mid); break;
-        case 8: launch_fb<float, 8, 512, true>(prm, geo.NT, st, e_mid); break;
-        case 10: launch_fb<float, 10, 512, true>(prm, geo.NT, st, e_mid); break;
-        case 12: launch_fb<float, 12, 512, true>(prm, geo.NT, st, e_mid); break;
-#endif
-        case 2: launch_fb<float, 2, 512, true>(prm, geo.NT, st, e_mid); break;
-        case 7: launch_fb<float, 7, 512, true>(prm, geo.NT, st, e_mid); break;
-        default: throw std::runtime_error("geometry not built");
-    }
+    const bool built = geo.kind == KIND_F64_FULL
+        ? qa::dispatch(Nch64Built{}, geo.NCH, [&](auto nch) { launch_fb<double, decltype(nch)::value, 256, true>(prm, geo.NT, st, e_mid); })
+        : qa::dispatch(Nch32Built{}, geo.NCH, [&](auto nch) { launch_fb<float, decltype(nch)::value, 512, true>(prm, geo.NT, st, e_mid); });
+    if (!built) throw std::runtime_error("geometry not built");
 }
 
-// whether launch_fb_any holds a case for the geometry (the cases of its two switches, restated; fullpass_testhook.h reports it)
-bool launcher_case_exists(const Geometry &geo, int K) {
+// whether launch_fb_any holds a build for the geometry (fullpass_testhook.h reports it)
+bool geometry_built(const Geometry &geo, int K) {
     if (geo.NT == 0) return false;
     if (geo.kind == KIND_F64_RANK || geo.kind == KIND_F64_DOS) {
         int g[6];
@@ -1076,21 +1058,7 @@ bool launcher_case_exists(const Geometry &geo, int K) {
         return g[5] != 0;
     }
     if (geo.kind == KIND_F64_REF) return true;   // NT and Kq at run time
-    if (geo.kind == KIND_F64_FULL)
-        switch (geo.NCH) {
-#ifndef QA_FAST_BUILD
-            case 1: case 4: case 6: case 8: case 10: case 12: case 14:
-#endif
-            case 2: case 13: return true;
-            default: return false;
-        }
-    switch (geo.NCH) {
-#ifndef QA_FAST_BUILD
-        case 1: case 3: case 4: case 5: case 6: case 8: case 10: case 12:
-#endif
-        case 2: case 7: return true;
-        default: return false;
-    }
+    return geo.kind == KIND_F64_FULL ? qa::contains(Nch64Built{}, geo.NCH) : qa::contains(Nch32Built{}, geo.NCH);
 }
 
 // the kernels behind the dosage passes of a handle: fp32 state, or (qa_panel_set_dosage_precision(64)) the fp64 dosage
@@ -1575,7 +1543,7 @@ int run_passes(qa_panel *pn, int P, const double *gl, const int32_t *h_flags, co
         qa::set_error("K = %d exceeds the on-chip capacity of the %s full-pass kernels", pn->K, kKindInfo[kind].name);
         return QA_ERR_UNSUPPORTED;
     }
-    if (!launcher_case_exists(geo, pn->K)) {   // (a build without every variant: QA_FAST_BUILD) -- said before any device work
+    if (!geometry_built(geo, pn->K)) {   // (a build without every variant: QA_FAST_BUILD) -- said before any device work
         qa::set_error("K = %d: this build of the library holds no %s full-pass kernels of that geometry", pn->K, kKindInfo[kind].name);
         return QA_ERR_UNSUPPORTED;
     }
@@ -1694,7 +1662,7 @@ int qa_fullpass_geometry(int32_t K, int32_t kind, int32_t out[8]) {
         out[2] = g[1]; out[3] = g[2]; out[4] = g[3]; out[5] = g[4];
     }
     out[6] = geo.NT * geo.NCH * 16;   // PassLayout::Kq
-    out[7] = launcher_case_exists(geo, K);
+    out[7] = geometry_built(geo, K);
     return QA_OK;
 }
 

@@ -31,6 +31,7 @@
 // Algorithmic HBM bytes: per cell 1 B code forward + 1 B backward, plus 8 B of alpha written and read at
 // the thinned grids.
 #include "fullpass_dev.hpp"
+#include "variants.hpp"
 
 namespace {
 
@@ -1197,37 +1198,25 @@ Geo64 rank_geo(int K) {
     return geo;
 }
 
-// the <NR, NL> builds the two switches below hold (fullpass_testhook.h reports it beside the geometry)
-bool geo_built(const Geo64 &geo) {
-    if (geo.NS > 0) return true;
-    switch (geo.NR * 10 + geo.NL) {
-#ifndef QA_FAST_BUILD
-        case 10: case 20: case 30: case 40: case 41: case 42:
+// The <NR, NL> builds (rows in registers, rows in LDS) geo64 and the two launchers' seven-row choices can ask for, and those this
+// build holds: all of them, or with QA_FAST_BUILD the seven-row pair.  The streamed <5, 2, SP> build is always there.
+using Rows64 = qa::PairList<qa::Pair<1, 0>, qa::Pair<2, 0>, qa::Pair<3, 0>, qa::Pair<4, 0>, qa::Pair<4, 1>, qa::Pair<4, 2>, qa::Pair<4, 3>,
+                            qa::Pair<5, 2>>;
+#ifdef QA_FAST_BUILD
+using Rows64Built = qa::PairList<qa::Pair<4, 3>, qa::Pair<5, 2>>;
+#else
+using Rows64Built = Rows64;
 #endif
-        case 52: case 43: return true;
-        default: return false;
-    }
-}
 
-template <bool GCOL>
-void launch_dos_geo(const PassParams &prm, const Geo64 &geo, hipStream_t st, hipEvent_t e_mid) {
-    if (geo.NS > 0) {
-        launch_dos<5, 2, true, GCOL>(prm, geo, st, e_mid);
-        return;
-    }
-    switch (geo.NR * 10 + geo.NL) {
-#ifndef QA_FAST_BUILD
-        case 10: launch_dos<1, 0, false, GCOL>(prm, geo, st, e_mid); break;
-        case 20: launch_dos<2, 0, false, GCOL>(prm, geo, st, e_mid); break;
-        case 30: launch_dos<3, 0, false, GCOL>(prm, geo, st, e_mid); break;
-        case 40: launch_dos<4, 0, false, GCOL>(prm, geo, st, e_mid); break;
-        case 41: launch_dos<4, 1, false, GCOL>(prm, geo, st, e_mid); break;
-        case 42: launch_dos<4, 2, false, GCOL>(prm, geo, st, e_mid); break;
-#endif
-        case 52: launch_dos<5, 2, false, GCOL>(prm, geo, st, e_mid); break;
-        case 43: launch_dos<4, 3, false, GCOL>(prm, geo, st, e_mid); break;
-        default: throw std::runtime_error("fp64 geometry not built");
-    }
+// (fullpass_testhook.h reports it beside the geometry)
+bool geo_built(const Geo64 &geo) { return geo.NS > 0 || qa::contains(Rows64Built{}, geo.NR, geo.NL); }
+
+// f(NR, NL, streamed) as integral constants for the build that runs the geometry
+template <class F>
+void for_geo_build(const Geo64 &geo, F &&f) {
+    if (geo.NS > 0) return f(qa::int_c<5>{}, qa::int_c<2>{}, std::true_type{});
+    if (!qa::dispatch(Rows64Built{}, geo.NR, geo.NL, [&](auto nr, auto nl) { f(nr, nl, std::false_type{}); }))
+        throw std::runtime_error("fp64 geometry not built");
 }
 
 }  // namespace
@@ -1258,8 +1247,12 @@ void launch_fb64_dosage(const void *pass_params, hipStream_t st, hipEvent_t e_mi
     if (geo.NCH == 0) throw std::runtime_error("K exceeds the on-chip capacity of the fp64 dosage kernels");
     if (prm.Kq != (geo.NCH + geo.NS) * kRowHaps) throw std::runtime_error("internal: Kq does not match the fp64 geometry");
     if (geo.NS > 0 && !prm.spill) throw std::runtime_error("internal: streamed chunk rows without their buffer");
-    if (prm.gamma_col) launch_dos_geo<true>(prm, geo, st, e_mid);
-    else launch_dos_geo<false>(prm, geo, st, e_mid);
+    for_geo_build(geo, [&](auto nr, auto nl, auto sp) {
+        constexpr int NR = decltype(nr)::value, NL = decltype(nl)::value;
+        constexpr bool SP = decltype(sp)::value;
+        if (prm.gamma_col) launch_dos<NR, NL, SP, true>(prm, geo, st, e_mid);
+        else launch_dos<NR, NL, SP, false>(prm, geo, st, e_mid);
+    });
 }
 
 void launch_fb64(const void *pass_params, hipStream_t st, hipEvent_t e_mid) {
@@ -1267,24 +1260,8 @@ void launch_fb64(const void *pass_params, hipStream_t st, hipEvent_t e_mid) {
     const Geo64 geo = rank_geo(prm.K);
     if (geo.NCH == 0) throw std::runtime_error("K exceeds the on-chip capacity of the fp64 ranking kernels");
     if (prm.Kq != (geo.NCH + geo.NS) * kRowHaps) throw std::runtime_error("internal: Kq does not match the fp64 geometry");
-    if (geo.NS > 0) {
-        if (!prm.spill) throw std::runtime_error("internal: streamed chunk rows without their buffer");
-        launch<5, 2, true>(prm, geo, st, e_mid);
-        return;
-    }
-    switch (geo.NR * 10 + geo.NL) {
-#ifndef QA_FAST_BUILD
-        case 10: launch<1, 0>(prm, geo, st, e_mid); break;
-        case 20: launch<2, 0>(prm, geo, st, e_mid); break;
-        case 30: launch<3, 0>(prm, geo, st, e_mid); break;
-        case 40: launch<4, 0>(prm, geo, st, e_mid); break;
-        case 41: launch<4, 1>(prm, geo, st, e_mid); break;
-        case 42: launch<4, 2>(prm, geo, st, e_mid); break;
-#endif
-        case 52: launch<5, 2>(prm, geo, st, e_mid); break;
-        case 43: launch<4, 3>(prm, geo, st, e_mid); break;
-        default: throw std::runtime_error("fp64 geometry not built");
-    }
+    if (geo.NS > 0 && !prm.spill) throw std::runtime_error("internal: streamed chunk rows without their buffer");
+    for_geo_build(geo, [&](auto nr, auto nl, auto sp) { launch<decltype(nr)::value, decltype(nl)::value, decltype(sp)::value>(prm, geo, st, e_mid); });
 }
 
 }  // namespace qa

@@ -21,8 +21,8 @@ int qa_fullpass_last_plan(int64_t out[6]);
  * and <5, 2>) decide for a panel of K haplotypes and a PassKind (pass_layout.hpp), without a device: out[0] = NT, out[1] = NCH
  * (chunks per lane; the fp64 ranking / dosage kinds: chunk rows of 8 192 haplotypes, streamed ones included), out[2] = NR (rows in
  * registers), out[3] = NL (rows in LDS), out[4] = n_last (lanes of the last row), out[5] = NS (rows streamed through HBM) -- 2 .. 5
- * are 0 for the other kinds --, out[6] = Kq (haplotypes of the padded layout), out[7] = 1 when the launcher holds a case for that
- * build.  All 0 when the kind does not take this K.  For KIND_F64_DOS the fields are those of launch_fb64_dosage, after its
+ * are 0 for the other kinds --, out[6] = Kq (haplotypes of the padded layout), out[7] = 1 when the library holds that
+ * build (the kinds' built lists: all of what the tables choose from, fewer with QA_FAST_BUILD).  All 0 when the kind does not take this K.  For KIND_F64_DOS the fields are those of launch_fb64_dosage, after its
  * lds_bytes_d adjustment.  tests/k_cases.py derives its table of K values and the edge haplotypes of each K from it. */
 int qa_fullpass_geometry(int32_t K, int32_t kind, int32_t out[8]);
 

@@ -48,6 +48,7 @@
 
 #include "gibbs_dev.hpp"
 #include "gibbs_blocks.hpp"
+#include "variants.hpp"
 
 namespace qa {
 int gibbs3_waves(int Ksp, int C, int share);
@@ -1258,6 +1259,23 @@ void launch_shard_blocks_kernel(const GibbsParams &prm, hipStream_t st) {
     QA_HIP(hipGetLastError());
 }
 
+// The builds of the two-label chain kernels -- k_ematread, k_gibbs, k_shard_blocks -- in one place, as <rows per lane NE, waves NW>
+// with 64 * NE * NW == Ksp: one wave for every Ksp, several waves for Ksp = 640 only
+using qa::Pair;
+using Chain2 = qa::PairList<Pair<1, 1>, Pair<2, 1>, Pair<3, 1>, Pair<4, 1>, Pair<5, 1>, Pair<6, 1>, Pair<7, 1>, Pair<8, 1>, Pair<9, 1>, Pair<10, 1>,
+                            Pair<11, 1>, Pair<12, 1>, Pair<13, 1>, Pair<14, 1>, Pair<15, 1>, Pair<16, 1>, Pair<5, 2>, Pair<2, 5>, Pair<1, 10>>;
+static_assert(qa::max_over(Chain2{}, [](int ne, int nw) { return 64 * ne * nw; }) == QA_KSUBSET_MAX,
+              "the two-label sampler is built for the documented Ksubset range");
+
+// The build one launch runs, decided once (chunk_layout) and read by everything that depends on it: NE rows per lane x NW waves,
+// and whether it is the sampler's 256-register build
+struct ChainBuild {
+    int NE, NW;
+    bool lean;
+    int er_nt() const { return 64 * NW; }            // the read-emission patterns: lanes per read,
+    int er_padb() const { return padb_of(NE); }      // bytes per lane
+};
+
 // Geometry of one chain: NW waves x NE rows per thread with 64 * NW * NE == Ksp.
 // The single-wave kernel (10 columns per lane) holds 512 registers, i.e. one chain per SIMD, 1024 per device, and a
 // chain's time is its serial per-read latency: measured at Ksubset = 600 with 128 chains NW = 2 is fastest (0.64 s vs
@@ -1279,10 +1297,18 @@ int choose_gibbs_waves(int Ksp, int C, int share) {
     if (share == 0 && C <= 256) nw = 2;
     if (const char *forced = getenv("QA_GIBBS_NW")) {   // test hook: exercise every geometry
         const int f = atoi(forced);
-        if (f == 1 || f == 2 || f == 5 || f == 10) nw = f;
+        if (f > 0 && 10 % f == 0 && qa::contains(Chain2{}, 10 / f, f)) nw = f;
     }
     return nw;
 }
+
+// The most waves choose_gibbs_waves may answer with for some launch of a call: two by its own rules, every built count once the
+// test hook is in the environment -- and the pattern bytes per read, at most, of the builds with up to that many waves
+int max_gibbs_waves() { return getenv("QA_GIBBS_NW") ? qa::max_over(Chain2{}, [](int, int nw) { return nw; }) : 2; }
+constexpr int max_pattern_bytes(int max_nw) {
+    return qa::max_over(Chain2{}, [max_nw](int ne, int nw) { return nw <= max_nw ? 64 * nw * padb_of(ne) : 0; });
+}
+static_assert(max_pattern_bytes(2) == 1024 && max_pattern_bytes(10) == 2560, "what gibbs_batch_impl has always priced a read at");
 
 // More chains than SIMDs in one launch: the 256-register build, two chains per SIMD, all of them resident at once (2 048 chains:
 // 1.24 s against 2 x 0.72 s for two launches of the 512-register build; alone on a SIMD the lean build is the slower one,
@@ -1292,85 +1318,38 @@ bool use_lean_build(int C) {
     return C > 1024;
 }
 
-// The built geometries of the two-label chain kernels (rows per lane, waves) in one place: f(NE, NW) as integral constants for
-// NE1 = Ksp / 64 rows per lane with one wave and the chosen number of waves (several waves exist for Ksp = 640 only)
-template <int N>
-using int_c = std::integral_constant<int, N>;
+// f(NE, NW) as integral constants for the launch's build
 template <class F>
-void for_chain_geometry(int NE1, int nw, F &&f) {
-    if (NE1 == 10 && nw == 10) return f(int_c<1>{}, int_c<10>{});
-    if (NE1 == 10 && nw == 5) return f(int_c<2>{}, int_c<5>{});
-    if (NE1 == 10 && nw == 2) return f(int_c<5>{}, int_c<2>{});
-    switch (NE1) {
-        case 1: return f(int_c<1>{}, int_c<1>{});
-        case 2: return f(int_c<2>{}, int_c<1>{});
-        case 3: return f(int_c<3>{}, int_c<1>{});
-        case 4: return f(int_c<4>{}, int_c<1>{});
-        case 5: return f(int_c<5>{}, int_c<1>{});
-        case 6: return f(int_c<6>{}, int_c<1>{});
-        case 7: return f(int_c<7>{}, int_c<1>{});
-        case 8: return f(int_c<8>{}, int_c<1>{});
-        case 9: return f(int_c<9>{}, int_c<1>{});
-        case 10: return f(int_c<10>{}, int_c<1>{});
-        case 11: return f(int_c<11>{}, int_c<1>{});
-        case 12: return f(int_c<12>{}, int_c<1>{});
-        case 13: return f(int_c<13>{}, int_c<1>{});
-        case 14: return f(int_c<14>{}, int_c<1>{});
-        case 15: return f(int_c<15>{}, int_c<1>{});
-        default: return f(int_c<16>{}, int_c<1>{});
-    }
+void for_chain_build(const ChainBuild &b, F &&f) {
+    // (unreachable through the ABI: gibbs_batch_impl admits Ksubset 1..1024 only, i.e. 1..16 rows per lane)
+    if (!qa::dispatch(Chain2{}, b.NE, b.NW, f)) throw std::runtime_error("Ksubset geometry not built (Ksubset / 64 rounded up must be 1..16)");
 }
 
 // the sweeps of the two-label sampler: the whole call (SEG = false), or its sweeps [it_begin, it_end)
 template <bool SEG>
-void launch_gibbs_sweeps(const GibbsParams &prm, int nw, hipStream_t st) {
-    for_chain_geometry(prm.Ksp / 64, nw, [&](auto ne, auto w) {
+void launch_gibbs_sweeps(const GibbsParams &prm, const ChainBuild &b, hipStream_t st) {
+    for_chain_build(b, [&](auto ne, auto w) {
         constexpr int NE = decltype(ne)::value, NW = decltype(w)::value;
         if constexpr (NE == 10 && NW == 1) {
-            if (use_lean_build(prm.C)) return launch_gibbs_kernel<10, 1, true, SEG>(prm, st);
+            if (b.lean) return launch_gibbs_kernel<10, 1, true, SEG>(prm, st);
         }
         launch_gibbs_kernel<NE, NW, false, SEG>(prm, st);
     });
 }
 
-void launch_shard_blocks(const GibbsParams &prm, int nw, hipStream_t st) {
-    for_chain_geometry(prm.Ksp / 64, nw, [&](auto ne, auto w) { launch_shard_blocks_kernel<decltype(ne)::value, decltype(w)::value>(prm, st); });
+void launch_shard_blocks(const GibbsParams &prm, const ChainBuild &b, hipStream_t st) {
+    for_chain_build(b, [&](auto ne, auto w) { launch_shard_blocks_kernel<decltype(ne)::value, decltype(w)::value>(prm, st); });
 }
 
-void launch_gibbs(const GibbsParams &prm, int maxR, hipStream_t st, hipEvent_t *ev, bool want_probs, int nw,
+void launch_gibbs(const GibbsParams &prm, int maxR, hipStream_t st, hipEvent_t *ev, bool want_probs, const ChainBuild &b,
                   const std::function<void()> &segmented_sweeps) {
-    const int NE1 = prm.Ksp / 64;   // rows per lane with one wave
     QA_HIP(hipEventRecord(ev[0], st));
-    switch (NE1) {
-        case 1: launch_ematread<1, 1>(prm, maxR, st); break;
-        case 2: launch_ematread<2, 1>(prm, maxR, st); break;
-        case 3: launch_ematread<3, 1>(prm, maxR, st); break;
-        case 4: launch_ematread<4, 1>(prm, maxR, st); break;
-        case 5: launch_ematread<5, 1>(prm, maxR, st); break;
-        case 6: launch_ematread<6, 1>(prm, maxR, st); break;
-        case 7: launch_ematread<7, 1>(prm, maxR, st); break;
-        case 8: launch_ematread<8, 1>(prm, maxR, st); break;
-        case 9: launch_ematread<9, 1>(prm, maxR, st); break;
-        case 10:
-            if (nw == 10) launch_ematread<10, 10>(prm, maxR, st);
-            else if (nw == 5) launch_ematread<10, 5>(prm, maxR, st);
-            else if (nw == 2) launch_ematread<10, 2>(prm, maxR, st);
-            else launch_ematread<10, 1>(prm, maxR, st);
-            break;
-        case 11: launch_ematread<11, 1>(prm, maxR, st); break;
-        case 12: launch_ematread<12, 1>(prm, maxR, st); break;
-        case 13: launch_ematread<13, 1>(prm, maxR, st); break;
-        case 14: launch_ematread<14, 1>(prm, maxR, st); break;
-        case 15: launch_ematread<15, 1>(prm, maxR, st); break;
-        case 16: launch_ematread<16, 1>(prm, maxR, st); break;
-        // (unreachable through the ABI: gibbs_batch_impl admits Ksubset 1..1024 only, i.e. 1..16 rows per lane)
-        default: throw std::runtime_error("Ksubset geometry not built (Ksubset / 64 rounded up must be 1..16)");
-    }
+    for_chain_build(b, [&](auto ne, auto w) { launch_ematread<decltype(ne)::value * decltype(w)::value, decltype(w)::value>(prm, maxR, st); });
     QA_HIP(hipEventRecord(ev[1], st));
     // segments of sweeps with a pass between them, driven from gibbs_chunk: the three-label sampler (NIPT, gibbs3.hip) with its
     // block passes, or the two-label sampler with block-wise shard passes; otherwise the whole call is one launch
     if (segmented_sweeps) segmented_sweeps();
-    else launch_gibbs_sweeps<false>(prm, nw, st);
+    else launch_gibbs_sweeps<false>(prm, b, st);
     QA_HIP(hipEventRecord(ev[2], st));
     if (want_probs) {   // return_hapProbs / return_genProbs (functions.R:2566-2599): skipped when nobody asks
         // dynamic LDS: nH gamma columns of Ksp doubles + the panel words (+ the haplotype list for the rare + common form)
@@ -1498,7 +1477,8 @@ std::vector<int32_t> checked_folded_qualities(int n, const int32_t *read_off, co
 
 // What the host works out for one launch before anything is uploaded: sizes, per-chain offsets, the marshalled inputs
 struct ChunkHost {
-    int C, G, T, Ks, Ksp, NE, nH, n_its, nw, er_nt, er_padb, rc_words, totR, totB, maxR = 0;
+    int C, G, T, Ks, Ksp, nH, n_its, rc_words, totR, totB, maxR = 0;
+    ChainBuild build;
     bool want_probs, want_pairs;   // want_pairs: (SNP, row) pairs per chain for k_happrobs_rc (only when the probabilities are asked for)
     bool aliased = false;          // some chain's bases are another chain's, or lie elsewhere than base_off says
     size_t etot = 0, ixtot = 0;
@@ -1517,15 +1497,26 @@ ChunkHost chunk_layout(qa_panel_t *pn, const qa_rare_common *rc, const qa_gibbs_
     ChunkHost h;
     const int C = h.C = L.C;
     h.G = rc ? rc->G_all : pn->G; h.T = rc ? rc->T_all : pn->T; h.Ks = o->Ks;
-    h.Ksp = (h.Ks + 63) / 64 * 64; h.NE = h.Ksp / 64;
+    h.Ksp = (h.Ks + 63) / 64 * 64;
     h.nH = o->ff != 0.0 ? 3 : 2;
     h.rc_words = rc ? (h.T + 31) / 32 : 0;
     h.n_its = o->n_gibbs_burn_in_its + o->n_gibbs_sample_its;
     h.totR = L.a.read_off[C];
     h.want_probs = wants_probs(L.a, o);
     h.want_pairs = rc && h.want_probs && h.Ks <= 1024;
-    h.nw = o->ff != 0.0 ? qa::gibbs3_waves(h.Ksp, C, pn->sharers()) : choose_gibbs_waves(h.Ksp, C, pn->exclusive ? 0 : pn->share);
-    h.er_nt = 64 * h.nw; h.er_padb = padb_of(h.NE / h.nw);
+    if (o->ff != 0.0) {
+        // The three-label sampler's 256-register build (two chains per SIMD, gibbs3.hip) is built and tested but NOT chosen by
+        // default: alone on the device 1 792 chains take 2.33-2.58 s in it against 2 x 1.24 s for two launches of 896 at one
+        // chain per SIMD -- a sweep's grid steps are HBM-bound either way (5.6 TB/s) and the read visits, which two waves per
+        // SIMD should overlap, pay for eMatGrid's trips through LDS and ~600 bytes of scratch per lane.
+        // QA_GIBBS3_LEAN=1 selects it (tests, measurements).
+        const char *lean3_env = getenv("QA_GIBBS3_LEAN");   // (read per call: the tests switch it inside one process)
+        const int nw = qa::gibbs3_waves(h.Ksp, C, pn->sharers());
+        h.build = {h.Ksp / 64 / nw, nw, h.Ksp == 640 && nw == 1 && lean3_env && atoi(lean3_env) != 0};
+    } else {
+        const int nw = choose_gibbs_waves(h.Ksp, C, pn->exclusive ? 0 : pn->share);
+        h.build = {h.Ksp / 64 / nw, nw, h.Ksp == 640 && nw == 1 && use_lean_build(C)};
+    }
     h.rc_any.assign((size_t)C * h.rc_words, 0u);
     h.base_off.assign(C + 1, 0); h.which0.resize((size_t)C * h.Ks);
     h.eoff.resize(C); h.ixoff.resize(C);
@@ -1538,7 +1529,7 @@ ChunkHost chunk_layout(qa_panel_t *pn, const qa_rare_common *rc, const qa_gibbs_
         const int32_t *rp = L.a.read_ptr + L.a.read_off[c] + c;
         h.base_off[c + 1] = h.base_off[c] + rp[R];
         h.ixoff[c] = h.ixtot;
-        h.ixtot += (size_t)R * h.er_nt * h.er_padb;
+        h.ixtot += (size_t)R * h.build.er_nt() * h.build.er_padb();
     }
     h.totB = h.base_off[C];
     h.bq_eff.resize((size_t)std::max(h.totB, 1));
@@ -1768,7 +1759,7 @@ GibbsParams fill_params(const qa::GibbsScratch &S, const qa_panel_t *pn, const q
     prm.hm = pn->hm.p; prm.B = pn->B.p; prm.sp_off = pn->sp_off.p; prm.sp_k = pn->sp_k.p;
     prm.sp_word = pn->sp_word.p; prm.sigma = S.tm.p; prm.Kp = pn->Kp; prm.G = h.G; prm.T = h.T;
     prm.nMaxDH = pn->nMaxDH; prm.ref_error = pn->ref_error;
-    prm.C = C; prm.Ks = h.Ks; prm.Ksp = h.Ksp; prm.NE = h.NE; prm.which = S.which.p;
+    prm.C = C; prm.Ks = h.Ks; prm.Ksp = h.Ksp; prm.NE = h.Ksp / 64; prm.which = S.which.p;
     prm.read_off = S.read_off.p; prm.read_ptr = S.read_ptr.p; prm.base_off = S.base_off.p;
     prm.u = S.u.p; prm.bq = S.bq.p; prm.wif = S.wif.p; prm.grid_has_read = S.ghr.p;
     prm.pR_tab = S.tabs.p; prm.pA_tab = S.tabs.p + 512;
@@ -1791,7 +1782,7 @@ GibbsParams fill_params(const qa::GibbsScratch &S, const qa_panel_t *pn, const q
     prm.seed_shard = (L.a.seed_reads && L.a.seed_shard) ? S.seeds.p + C : nullptr;
     prm.eMatRead = S.eMatRead.p; prm.eread_off = S.eread_off.p; prm.is_cat1 = S.is_cat1.p; prm.er_nent = S.er_nent.p;
     prm.er_idx = S.er_idx.p; prm.eridx_off = S.eridx_off.p; prm.er_tab = S.er_tab.p; prm.dense_of = S.dense_of.p;
-    prm.er_nt = h.er_nt; prm.er_padb = h.er_padb;
+    prm.er_nt = h.build.er_nt(); prm.er_padb = h.build.er_padb();
     prm.alpha = S.alpha.p; prm.beta = S.beta.p; prm.eg = S.eg.p; prm.cvec = S.cvec.p;
     prm.H = S.H.p; prm.H_class = S.H_class.p; prm.status = S.status.p;
     prm.hapProbs = S.hap.p; prm.genProbsM = S.gm.p; prm.genProbsF = S.gf.p;
@@ -1854,14 +1845,7 @@ void nipt_sweeps(const GibbsParams &prm, qa::GibbsScratch &S, const qa_gibbs_opt
     const int32_t *read_off = L.a.read_off;
     GibbsParams q = prm;
     q.ff = o->ff;
-    // The three-label sampler's 256-register build (two chains per SIMD, gibbs3.hip) is built and tested but NOT chosen by
-    // default: alone on the device 1 792 chains take 2.33-2.58 s in it against 2 x 1.24 s for two launches of 896 at one
-    // chain per SIMD -- a sweep's grid steps are HBM-bound either way (5.6 TB/s) and the read visits, which two waves per
-    // SIMD should overlap, pay for eMatGrid's trips through LDS and ~600 bytes of scratch per lane.
-    // QA_GIBBS3_LEAN=1 selects it (tests, measurements).
-    const char *lean3_env = getenv("QA_GIBBS3_LEAN");   // (read per call: the tests switch it inside one process)
-    const bool lean3_on = lean3_env && atoi(lean3_env) != 0;
-    q.lean3 = (h.Ksp == 640 && h.nw == 1 && lean3_on) ? 1 : 0;
+    q.lean3 = h.build.lean ? 1 : 0;
     q.blk_n_pass = std::max(o->n_block_gibbs_iterations, 1);
     const std::vector<int> passes = block_pass_sweeps(o, n_its);
     if (!passes.empty()) {
@@ -1962,7 +1946,7 @@ void shard_block_sweeps(const GibbsParams &prm, qa::GibbsScratch &S, const qa_gi
     int it0 = 0;
     for (size_t j = 0; j < passes.size(); j++) {
         q.it_begin = it0; q.it_end = passes[j] + 1;
-        launch_gibbs_sweeps<true>(q, h.nw, st);
+        launch_gibbs_sweeps<true>(q, h.build, st);
         if (G >= 3) {   // (fewer grids: no boundary has a rate, and block_tables does not look at it)
             qa::launch_block_rate3(&q, st);
             S.blk_rate2.download(rate2.data(), rate2.size(), st);
@@ -1984,14 +1968,14 @@ void shard_block_sweeps(const GibbsParams &prm, qa::GibbsScratch &S, const qa_gi
                 o->draw_uniforms(o->draw_uniforms_ctx, L.c0 + c, (int)j, 2, n, ub.data());
                 qa::staged_upload(S.runif_shard.p + ((size_t)c * q.n_block + j) * (size_t)(G - 1), ub.data(), sizeof(double) * (size_t)n, st);
             }
-        launch_shard_blocks(q, h.nw, st);
+        launch_shard_blocks(q, h.build, st);
         if (tmg) fprintf(stderr, "[qa_gibbs C=%d] shard pass %d by blocks: device idle for the host's block tables %.1f ms (tables %.1f on %d threads, uploads enqueued %.1f)\n",
                          C, (int)j, (now_s() - tg0) * 1e3, (tg1 - tg0) * 1e3, n_thr, (now_s() - tg1) * 1e3);
         it0 = passes[j] + 1;
     }
     if (passes.empty() || it0 < n_its) {
         q.it_begin = it0; q.it_end = n_its;
-        launch_gibbs_sweeps<true>(q, h.nw, st);
+        launch_gibbs_sweeps<true>(q, h.build, st);
     }
 }
 
@@ -2047,7 +2031,7 @@ double profile_launch(hipEvent_t *ev, const ChunkHost &h, int n_block) {
     const double units = (double)n_its * totR + passes * (double)C * G;
     const double serial = (double)n_its * h.maxR + passes * (double)G;
     qa::profile_add(qa::PK_EMATREAD, ms[0], (double)totR * Ks * 8.0, t_e);
-    qa::profile_add(nH == 3 ? qa::PK_GIBBS3 : ((h.Ksp / 64 == 10 && h.nw == 1 && use_lean_build(C)) ? qa::PK_GIBBS_LEAN : qa::PK_GIBBS), ms[1],
+    qa::profile_add(nH == 3 ? qa::PK_GIBBS3 : (h.build.lean ? qa::PK_GIBBS_LEAN : qa::PK_GIBBS), ms[1],
                     sweeps * (nH / 2.0), t_e + ms[0], units, serial, (double)C);
     if (h.want_probs) qa::profile_add(qa::PK_HAPPROBS, ms[2], C * (double)nH * Ks * (double)G * 16.0, t_e + ms[0] + ms[1]);
     return ms[0] + ms[1] + ms[2];
@@ -2090,7 +2074,7 @@ int gibbs_chunk(qa_panel_t *pn, size_t arena_need, const qa_rare_common *rc, con
     // device (exclusive phases: queue behind the other handles' launch sets) and the arena
     const double hold_t0 = now_s();
     qa::GateHold hold;
-    hold.acquire(pn->gate(), &pn->arena, h.C * h.nw, arena_need);
+    hold.acquire(pn->gate(), &pn->arena, h.C * h.build.NW, arena_need);
     const double T1g = now_s();
     carve_arena(S, hold.arena(), arena_need, h);
     const GibbsParams prm = fill_params(S, pn, rc, o, L, h, st);
@@ -2100,7 +2084,7 @@ int gibbs_chunk(qa_panel_t *pn, size_t arena_need, const qa_rare_common *rc, con
     std::function<void()> segmented;   // (empty: the whole call is one launch of the two-label sampler)
     if (h.nH == 3) segmented = [&] { nipt_sweeps(prm, S, o, L, h, st, tmg); };
     else if (shard_by_blocks(o)) segmented = [&] { shard_block_sweeps(prm, S, o, L, h, st, tmg); };
-    launch_gibbs(prm, h.maxR, st, g_gibbs->ev, h.want_probs, h.nw, segmented);
+    launch_gibbs(prm, h.maxR, st, g_gibbs->ev, h.want_probs, h.build, segmented);
     const std::vector<int32_t> status = download_labels(S, o, L, h, st);
     const double T3 = now_s();
     hold.mark();
@@ -2213,9 +2197,9 @@ int gibbs_batch_impl(qa_panel_t *pn, const qa_rare_common *rc, const qa_gibbs_op
         const size_t budget = pn->plan_budget();
         // device bytes per chain: read emissions -- pattern bytes + table (512 B) per read, a dense Ks-column for the reads
         // with more bases than the pattern width (an upper bound of those that end up dense) -- and the state matrices.
-        // Pattern bytes per read: 64 lanes x padb_of(rows per lane) with one wave, 128 x 8 with two (the geometries the
-        // launcher picks: <= 1 024 B); the many-wave geometries of the QA_GIBBS_NW test hook take up to 2 560 B
-        const size_t pat_bytes = getenv("QA_GIBBS_NW") ? 2560 : 1024;
+        // Pattern bytes per read: 64 lanes x padb_of(rows per lane) with one wave, 128 x 8 with two, more with the test hook's
+        // many waves -- whatever the wave rule may answer with
+        const size_t pat_bytes = max_pattern_bytes(max_gibbs_waves());
         std::vector<size_t> adds(n_chain);
         // Rare + common form: a read is dense only when it covers more than kMaxPatternBits INFORMATIVE SNPs -- common SNPs and
         // rare SNPs some selected haplotype carries (gibbs_chunk below, k_ematread) -- which most all-SNP reads do not, although

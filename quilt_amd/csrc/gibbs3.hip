@@ -11,6 +11,7 @@
 // definition in gibbs_blocks.hpp, k_block3 -- below); the state lives in HBM across the launches.  Category 1 reads are
 // not skipped in this mode (:815) but leave every probability unchanged.
 #include "gibbs_dev.hpp"
+#include "variants.hpp"
 
 #include <type_traits>
 
@@ -1033,6 +1034,14 @@ void launch_one(const GibbsParams &prm, hipStream_t st) {
 
 namespace qa {
 
+// The builds of the three-label chain kernels as <rows per lane NE, waves NW> with 64 * NE * NW == Ksp, for the sampler and its block
+// pass alike: the three-label kernels hold three columns per row, so ten rows per lane fill a SIMD's register file and nothing
+// larger is built; Ksp = 640 also runs as two waves of five rows
+using Chain3 = PairList<Pair<1, 1>, Pair<2, 1>, Pair<3, 1>, Pair<4, 1>, Pair<5, 1>, Pair<6, 1>, Pair<7, 1>, Pair<8, 1>, Pair<9, 1>, Pair<10, 1>,
+                        Pair<5, 2>>;
+static_assert(max_over(Chain3{}, [](int ne, int nw) { return 64 * ne * nw; }) == QA_KSUBSET_MAX_NIPT,
+              "the three-label sampler is built for the documented Ksubset range of NIPT");
+
 // geometry at Ksp = 640: one wave per chain (10 columns per lane and label, a SIMD's whole register file) when the launch
 // fills the device's 1024 SIMDs anyway, two waves (5 columns, 256 registers) for few chains; one wave otherwise
 int gibbs3_waves(int Ksp, int C, int share) {
@@ -1040,31 +1049,23 @@ int gibbs3_waves(int Ksp, int C, int share) {
     int nw = ((long)C * 2 <= 1024 / share) ? 2 : 1;
     if (const char *forced = getenv("QA_GIBBS_NW")) {   // test hook
         const int f = atoi(forced);
-        if (f == 1 || f == 2) nw = f;
+        if (f > 0 && 10 % f == 0 && contains(Chain3{}, 10 / f, f)) nw = f;
     }
     return nw;
 }
 
+// (a miss is unreachable through the ABI: gibbs_batch_impl refuses a NIPT call above QA_KSUBSET_MAX_NIPT before any device work)
 void launch_gibbs3(const void *params, hipStream_t st) {
     const GibbsParams &prm = *static_cast<const GibbsParams *>(params);
-    switch (prm.Ksp / 64) {
-        case 1: launch_one<1, 1>(prm, st); break;
-        case 2: launch_one<2, 1>(prm, st); break;
-        case 3: launch_one<3, 1>(prm, st); break;
-        case 4: launch_one<4, 1>(prm, st); break;
-        case 5: launch_one<5, 1>(prm, st); break;
-        case 6: launch_one<6, 1>(prm, st); break;
-        case 7: launch_one<7, 1>(prm, st); break;
-        case 8: launch_one<8, 1>(prm, st); break;
-        case 9: launch_one<9, 1>(prm, st); break;
-        case 10:
-            if (prm.er_nt == 64 && prm.lean3) launch_one<10, 1, true>(prm, st);
-            else if (prm.er_nt == 64) launch_one<10, 1>(prm, st);
-            else launch_one<5, 2>(prm, st);
-            break;
-        // (unreachable through the ABI: gibbs_batch_impl refuses a NIPT call above kMaxKsubsetNipt before any device work)
-        default: throw std::runtime_error("NIPT sampler: Ksubset geometry not built (Ksubset / 64 rounded up must be 1..10)");
-    }
+    const int nw = prm.er_nt / 64;   // (the launch's build as gibbs_chunk laid the read emissions out for it, and prm.lean3)
+    const bool built = dispatch(Chain3{}, prm.Ksp / 64 / nw, nw, [&](auto ne, auto w) {
+        constexpr int NE = decltype(ne)::value, NW = decltype(w)::value;
+        if constexpr (NE == 10) {
+            if (prm.lean3) return launch_one<10, 1, true>(prm, st);
+        }
+        launch_one<NE, NW>(prm, st);
+    });
+    if (!built) throw std::runtime_error("NIPT sampler: Ksubset geometry not built (Ksubset / 64 rounded up must be 1..10)");
 }
 
 void launch_block_rate3(const void *params, hipStream_t st) {
@@ -1081,19 +1082,12 @@ void launch_resample3(const void *params, hipStream_t st) {
 
 void launch_block3(const void *params, hipStream_t st) {
     const GibbsParams &prm = *static_cast<const GibbsParams *>(params);
-    switch (prm.Ksp / 64) {
-        case 1: launch_block<1, 1>(prm, st); break;
-        case 2: launch_block<2, 1>(prm, st); break;
-        case 3: launch_block<3, 1>(prm, st); break;
-        case 4: launch_block<4, 1>(prm, st); break;
-        case 5: launch_block<5, 1>(prm, st); break;
-        case 6: launch_block<6, 1>(prm, st); break;
-        case 7: launch_block<7, 1>(prm, st); break;
-        case 8: launch_block<8, 1>(prm, st); break;
-        case 9: launch_block<9, 1>(prm, st); break;
-        case 10: launch_block<5, 2>(prm, st); break;
-        default: throw std::runtime_error("NIPT block Gibbs: Ksubset geometry not built (Ksubset / 64 rounded up must be 1..10)");
-    }
+    const int ne1 = prm.Ksp / 64;
+    const bool ten = ne1 == 10;   // k_block3 runs ten rows as <5, 2> whichever build the sampler ran
+    const bool built = dispatch(Chain3{}, ten ? 5 : ne1, ten ? 2 : 1, [&](auto ne, auto w) {
+        if constexpr (decltype(ne)::value < 10) launch_block<decltype(ne)::value, decltype(w)::value>(prm, st);
+    });
+    if (!built) throw std::runtime_error("NIPT block Gibbs: Ksubset geometry not built (Ksubset / 64 rounded up must be 1..10)");
 }
 
 }  // namespace qa

@@ -11,7 +11,7 @@ ROWS = (64, 128, 192, 256, 320, 384, 448, 512)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
-# the table against the launchers' switches
+# the table against the launchers' built lists
 # ---------------------------------------------------------------------------------------------------------------------------
 def test_hook_needs_no_device_and_checks_its_arguments():
     from tests.testhooks import hook_lib
@@ -28,8 +28,8 @@ def test_hook_needs_no_device_and_checks_its_arguments():
 
 
 def test_every_launcher_case_is_reached():
-    """Every case of the launchers' switches (csrc/fullpass.hip: launch_fb_any; csrc/fullpass64.hip: launch_fb64, launch_dos_geo)
-    is run by some K of the table.  The ranking pair's <4, 3> build is the one exception K cannot reach: launch_fb64 sends every
+    """Every entry of the launchers' built lists (csrc/fullpass.hip: Nch32Built, Nch64Built; csrc/fullpass64.hip: Rows64Built and
+    the streamed build) is run by some K of the table.  The ranking pair's <4, 3> build is the one exception K cannot reach: launch_fb64 sends every
     seven-row panel to <5, 2> unless QA_FB64_FOUR_ROWS=1 is in the environment when the library loads."""
     assert set(KC.reached("f32")) == {(n,) for n in (1, 2, 3, 4, 5, 6, 7, 8, 10, 12)}
     assert set(KC.reached("full")) == {(n,) for n in (1, 2, 4, 6, 8, 10, 12, 13, 14)}
@@ -70,8 +70,8 @@ def test_every_width_of_the_last_row(rows, variant):
 
 
 def test_no_K_reaches_a_geometry_that_is_not_built():
-    """Whatever pick_geometry / geo64 choose, the launcher has a case for: `geometry not built` cannot be reached by K (run_passes
-    refuses a build without that case with QA_ERR_UNSUPPORTED before any device work)."""
+    """Whatever pick_geometry / geo64 choose, the launcher's built list holds: `geometry not built` cannot be reached by K
+    (run_passes refuses a build without that entry with QA_ERR_UNSUPPORTED before any device work)."""
     for kind in KC.KINDS:
         for k in [*range(1, 40), *range(16, KC.K_SCAN + 1, 16), *range(17, KC.K_SCAN + 2, 16), 131072, 1 << 20]:
             g = KC.geometry(k, kind)

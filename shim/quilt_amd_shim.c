@@ -70,16 +70,172 @@ static int flag(SEXP param_list, const char *name, int dflt) {
     SEXP v = list_get(param_list, name);
     return v == R_NilValue ? dflt : Rf_asLogical(v);
 }
+static double num_or(SEXP list, const char *name, double dflt) {
+    SEXP v = list_get(list, name);
+    return (v == R_NilValue || Rf_length(v) < 1) ? dflt : Rf_asReal(v);
+}
+static const char *one_string(SEXP list, const char *name) {
+    SEXP v = list_get(list, name);
+    return (v != R_NilValue && TYPEOF(v) == STRSXP && Rf_length(v) == 1) ? CHAR(STRING_ELT(v, 0)) : NULL;
+}
 static void check_status(int st, const char *what) {
     if (st < 0) Rf_error("%s: libquilt_amd status %d: %s", what, st, qa_last_error());
 }
-static SEXP named_list(int n, const char **names) {
-    SEXP out = PROTECT(Rf_allocVector(VECSXP, n));
-    SEXP nm = PROTECT(Rf_allocVector(STRSXP, n));
-    for (int i = 0; i < n; i++) SET_STRING_ELT(nm, i, Rf_mkChar(names[i]));
-    Rf_setAttrib(out, R_NamesSymbol, nm);
-    UNPROTECT(2);
+static int is_nipt(SEXP paramsSEXP) {   /* params$method == "nipt" (absent: "diploid") */
+    const char *m = one_string(paramsSEXP, "method");
+    return m != NULL && strcmp(m, "nipt") == 0;
+}
+
+/* ---- each conversion of an R object, once -------------------------------------------------------------------------- */
+
+/* element i of an integer-or-double vector (every int32 is a double, so the integer case loses nothing) */
+static double num_at(SEXP v, int i) { return TYPEOF(v) == INTSXP ? INTEGER(v)[i] : REAL(v)[i]; }
+/* an integer-or-double vector of length n as int32_t[] / int64_t[] (malloc); NULL when it is not one, or out of memory */
+static int32_t *ints_of(SEXP v, int n) {
+    if (v == R_NilValue || (TYPEOF(v) != INTSXP && TYPEOF(v) != REALSXP) || Rf_length(v) != n) return NULL;
+    int32_t *out = (int32_t *)malloc(sizeof(int32_t) * (size_t)(n > 0 ? n : 1));
+    for (int i = 0; out && i < n; i++) out[i] = (int32_t)num_at(v, i);
     return out;
+}
+static int64_t *int64s_of(SEXP v, int n) {   /* (a sample's global index: kept as wide as the library takes it) */
+    if (v == R_NilValue || (TYPEOF(v) != INTSXP && TYPEOF(v) != REALSXP) || Rf_length(v) != n) return NULL;
+    int64_t *out = (int64_t *)malloc(sizeof(int64_t) * (size_t)(n > 0 ? n : 1));
+    for (int i = 0; out && i < n; i++) out[i] = (int64_t)num_at(v, i);
+    return out;
+}
+/* C arrays as fresh R vectors (the caller roots them: result_add below, or PROTECT) */
+static SEXP int_vector(const int32_t *v, int n) {
+    SEXP out = Rf_allocVector(INTSXP, n);
+    if (n > 0) memcpy(INTEGER(out), v, sizeof(int) * (size_t)n);
+    return out;
+}
+static SEXP real_vector(const double *v, int n) {
+    SEXP out = Rf_allocVector(REALSXP, n);
+    if (n > 0) memcpy(REAL(out), v, sizeof(double) * (size_t)n);
+    return out;
+}
+static void counters_to_real(const int64_t *v, int n, SEXP out) {   /* the library's int64 counters (stats, bx_stats) as R numbers */
+    for (int i = 0; i < n; i++) REAL(out)[i] = (double)v[i];
+}
+
+/* sites$<name>: one TRUE or FALSE (NA is neither); absent: dflt */
+static int strict_flag(SEXP sitesSEXP, const char *name, int dflt, const char *who) {
+    SEXP v = list_get(sitesSEXP, name);
+    if (v == R_NilValue) return dflt;
+    if (TYPEOF(v) != LGLSXP || Rf_length(v) != 1 || (LOGICAL(v)[0] != 0 && LOGICAL(v)[0] != 1))
+        Rf_error("quilt_amd: %s: sites$%s must be TRUE or FALSE", who, name);
+    return LOGICAL(v)[0] != 0;
+}
+/* hla_run (functions.R:1261-1280): params$hla_grid, the 0-based grid of gamma1 / gamma2; -1 when absent */
+static int hla_grid_of(SEXP paramsSEXP, const char *who, int G) {
+    SEXP hg = list_get(paramsSEXP, "hla_grid");
+    if (hg == R_NilValue) return -1;
+    const double v = Rf_length(hg) == 1 && (TYPEOF(hg) == INTSXP || TYPEOF(hg) == REALSXP) ? Rf_asReal(hg) : -1;
+    if (!(v >= 0 && v < G && v == floor(v)))   /* (NA and NaN fail every comparison) */
+        Rf_error("quilt_amd: %s: params$hla_grid must be one whole number in [0, nGrids = %d) (iGrid - 1)", who, G);
+    return (int)v;
+}
+
+/* A result list built by appending (name, value) pairs: names and values cannot go out of step and nobody counts positions.
+ * A value is reachable from the builder's protected slots from the moment it is added, so `result_add(&r, "x", Rf_alloc...)` needs
+ * no PROTECT of its own.  result_begin leaves ONE object on the PROTECT stack and result_end takes it off again: whatever a
+ * routine PROTECTs in between it UNPROTECTs in between. */
+#define RESULT_MAX 16
+typedef struct { SEXP slots; const char *names[RESULT_MAX]; int n; } result_t;
+static void result_begin(result_t *r) { r->slots = PROTECT(Rf_allocVector(VECSXP, RESULT_MAX)); r->n = 0; }
+static SEXP result_add(result_t *r, const char *name, SEXP value) {
+    r->names[r->n] = name;
+    return SET_VECTOR_ELT(r->slots, r->n++, value);
+}
+static SEXP result_end(result_t *r) {
+    SEXP out = PROTECT(Rf_allocVector(VECSXP, r->n)), nm = PROTECT(Rf_allocVector(STRSXP, r->n));
+    for (int i = 0; i < r->n; i++) {
+        SET_VECTOR_ELT(out, i, VECTOR_ELT(r->slots, i));
+        SET_STRING_ELT(nm, i, Rf_mkChar(r->names[i]));
+    }
+    Rf_setAttrib(out, R_NamesSymbol, nm);
+    UNPROTECT(3);
+    return out;
+}
+
+/* sampleReads (list over reads of list(J, wif, bq matrix, u matrix): copied-from-stitch.cpp:153-160) in the flattened form of
+ * include/quilt_amd.h: read_off n + 1; per sample read_ptr R + 1 (at read_off[i] + i); bases back to back; wif per read. */
+typedef struct { int32_t *read_off, *read_ptr, *wif, *u, *bq; } flat_reads_t;
+static void flat_reads_free(flat_reads_t *f) {
+    free(f->read_off); free(f->read_ptr); free(f->wif); free(f->u); free(f->bq);
+    memset(f, 0, sizeof *f);
+}
+/* `nested`: a list of sampleReads (the range call); otherwise ONE sampleReads (the per-call entries: read_off = {0, R}).  wif is
+ * filled only when asked for.  Returns 0, or -1 when an allocation failed -- everything it allocated is then freed again and the
+ * caller raises the R error.  Raises none itself: what the range call passes has been through validate_reads_list. */
+static int pack_reads(SEXP readsSEXP, int nested, int want_wif, flat_reads_t *f) {
+    const int n = nested ? Rf_length(readsSEXP) : 1;
+    memset(f, 0, sizeof *f);
+    f->read_off = (int32_t *)malloc(sizeof(int32_t) * ((size_t)n + 1));
+    if (!f->read_off) return -1;
+    f->read_off[0] = 0;
+    size_t nbases = 0;
+    for (int i = 0; i < n; i++) {
+        SEXP sr = nested ? VECTOR_ELT(readsSEXP, i) : readsSEXP;
+        const int R = Rf_length(sr);
+        f->read_off[i + 1] = f->read_off[i] + R;
+        for (int r = 0; r < R; r++) nbases += (size_t)Rf_length(VECTOR_ELT(VECTOR_ELT(sr, r), 3));
+    }
+    const int totR = f->read_off[n];
+    f->read_ptr = (int32_t *)malloc(sizeof(int32_t) * ((size_t)totR + (size_t)n + 1));
+    if (want_wif) f->wif = (int32_t *)malloc(sizeof(int32_t) * (size_t)(totR > 0 ? totR : 1));
+    f->u = (int32_t *)malloc(sizeof(int32_t) * (nbases > 0 ? nbases : 1));
+    f->bq = (int32_t *)malloc(sizeof(int32_t) * (nbases > 0 ? nbases : 1));
+    if (!f->read_ptr || (want_wif && !f->wif) || !f->u || !f->bq) {
+        flat_reads_free(f);
+        return -1;
+    }
+    size_t at = 0;
+    for (int i = 0; i < n; i++) {
+        SEXP sr = nested ? VECTOR_ELT(readsSEXP, i) : readsSEXP;
+        const int R = Rf_length(sr);
+        int32_t *rp = f->read_ptr + f->read_off[i] + i;
+        rp[0] = 0;
+        for (int r = 0; r < R; r++) {
+            SEXP rd = VECTOR_ELT(sr, r);
+            const int nb = Rf_length(VECTOR_ELT(rd, 3));
+            if (want_wif) f->wif[f->read_off[i] + r] = Rf_asInteger(VECTOR_ELT(rd, 1));
+            memcpy(f->bq + at, INTEGER(VECTOR_ELT(rd, 2)), sizeof(int) * (size_t)nb);
+            memcpy(f->u + at, INTEGER(VECTOR_ELT(rd, 3)), sizeof(int) * (size_t)nb);
+            at += (size_t)nb;
+            rp[r + 1] = rp[r] + nb;
+        }
+    }
+    return 0;
+}
+
+/* The rare + common inputs of qa_rare_common_create: rare_per_hap_info (list over the K haplotypes of 1-based all-SNP indices,
+ * rare_common.R:222-247) as CSR, snp_is_common as bytes.  0, or -1 when an allocation failed (nothing stays allocated then). */
+typedef struct { int64_t *rare_ptr; int32_t *rare_snp; uint8_t *is_common; } rare_inputs_t;
+static void rare_inputs_free(rare_inputs_t *ri) {
+    free(ri->rare_ptr); free(ri->rare_snp); free(ri->is_common);
+    memset(ri, 0, sizeof *ri);
+}
+static int rare_inputs_pack(SEXP rare_per_hap_infoSEXP, SEXP snp_is_commonSEXP, int K, rare_inputs_t *ri) {
+    const int T = Rf_length(snp_is_commonSEXP);
+    memset(ri, 0, sizeof *ri);
+    ri->is_common = (uint8_t *)malloc((size_t)(T > 0 ? T : 1));
+    ri->rare_ptr = (int64_t *)malloc(sizeof(int64_t) * ((size_t)K + 1));
+    if (ri->is_common && ri->rare_ptr) {
+        for (int t = 0; t < T; t++) ri->is_common[t] = LOGICAL(snp_is_commonSEXP)[t] ? 1 : 0;
+        ri->rare_ptr[0] = 0;
+        for (int k = 0; k < K; k++) ri->rare_ptr[k + 1] = ri->rare_ptr[k] + Rf_length(VECTOR_ELT(rare_per_hap_infoSEXP, k));
+        ri->rare_snp = (int32_t *)malloc(sizeof(int32_t) * (size_t)(ri->rare_ptr[K] > 0 ? ri->rare_ptr[K] : 1));
+    }
+    if (!ri->is_common || !ri->rare_ptr || !ri->rare_snp) {
+        rare_inputs_free(ri);
+        return -1;
+    }
+    for (int k = 0; k < K; k++)
+        if (ri->rare_ptr[k + 1] > ri->rare_ptr[k])
+            memcpy(ri->rare_snp + ri->rare_ptr[k], INTEGER(VECTOR_ELT(rare_per_hap_infoSEXP, k)),
+                   sizeof(int) * (size_t)(ri->rare_ptr[k + 1] - ri->rare_ptr[k]));
+    return 0;
 }
 
 /* ---- the prepared panel, uploaded once per process ---------------------------------------------------------------- */
@@ -237,17 +393,13 @@ SEXP qa_QUILT_Rcpp_haploid_dosage_versus_refs(
     }
     if (st >= 0 && o.get_best_haps_from_thinned_sites) {
         /* best_haps_stuff_list[[i]] <- list(top_matches = <0-based k>, top_matches_values = <gamma>) (reference-single.cpp:2024-2030) */
-        static const char *nm[2] = {"top_matches", "top_matches_values"};
         for (int i = 0; i < n_thin && i < Rf_length(best_haps_stuff_listSEXP); i++) {
             const int n = bptr[i + 1] - bptr[i];
-            SEXP e = PROTECT(named_list(2, nm));
-            SEXP tm = PROTECT(Rf_allocVector(INTSXP, n)), tv = PROTECT(Rf_allocVector(REALSXP, n));
-            memcpy(INTEGER(tm), bidx + bptr[i], sizeof(int) * (size_t)n);
-            memcpy(REAL(tv), bval + bptr[i], sizeof(double) * (size_t)n);
-            SET_VECTOR_ELT(e, 0, tm);
-            SET_VECTOR_ELT(e, 1, tv);
-            SET_VECTOR_ELT(best_haps_stuff_listSEXP, i, e);
-            UNPROTECT(3);
+            result_t e;
+            result_begin(&e);
+            result_add(&e, "top_matches", int_vector(bidx + bptr[i], n));
+            result_add(&e, "top_matches_values", real_vector(bval + bptr[i], n));
+            SET_VECTOR_ELT(best_haps_stuff_listSEXP, i, result_end(&e));
         }
     }
     free(bptr); free(bidx); free(bval);
@@ -309,6 +461,148 @@ static double log_p_H_class(const int *H_class, int n, double ff) {   /* rcpp_ge
     return out;
 }
 
+/* per_it_likelihoods: one row per sweep, the 13 columns of gibbs-nipt.cpp:2767-2768 */
+static SEXP per_it_likelihoods(const double *per_it, int n_its, const int32_t *H_class, int R, double ff) {
+    static const char *cn[13] = {"s", "i_samp", "i_it", "i_result_it", "p_O1_given_H1_L", "p_O2_given_H2_L", "p_O3_given_H3_L",
+                                 "p_O_given_H_L", "p_H_given_L", "p_O_H_given_L_up_to_C", "p_set_H_given_L", "relabel",
+                                 "p_H_class_given_L"};
+    SEXP pit = PROTECT(Rf_allocMatrix(REALSXP, n_its, 13));
+    for (int it = 0; it < n_its; it++)   /* H_class is recorded by the last sweep only: NA before */
+        fill_per_it_row(REAL(pit), n_its, it, per_it + (size_t)it * 8, ff, it,
+                        it == n_its - 1 ? log_p_H_class(H_class, R, ff) : NA_REAL);
+    SEXP dn = PROTECT(Rf_allocVector(VECSXP, 2)), cns = PROTECT(Rf_allocVector(STRSXP, 13));
+    for (int j = 0; j < 13; j++) SET_STRING_ELT(cns, j, Rf_mkChar(cn[j]));
+    SET_VECTOR_ELT(dn, 0, R_NilValue);
+    SET_VECTOR_ELT(dn, 1, cns);
+    Rf_setAttrib(pit, R_DimNamesSymbol, dn);
+    UNPROTECT(3);
+    return pit;
+}
+
+/* Everything one call of the 63-argument entry mallocs, freed in one place, and what its draws leave for the call */
+typedef struct {
+    flat_reads_t reads;
+    double *per_it, *runif_reads, *runif_pass, *state;
+    int32_t *H, *H_class, first_read;
+    int by_blocks, n_passes;   /* the block-wise shard passes (shard_check_every_pair = FALSE) and how many the library runs */
+    shard_draws_t shard_draws;
+} gibbs_call_t;
+static void gibbs_call_free(gibbs_call_t *c) {
+    flat_reads_free(&c->reads);
+    free(c->per_it); free(c->runif_reads); free(c->runif_pass); free(c->H); free(c->H_class); free(c->state);
+}
+
+/* stage 1: arguments the production caller holds constant with another value */
+static void gibbs_refuse_non_production(SEXP pl, SEXP n_gibbs_startsSEXP, SEXP generate_fb_snp_offsetsSEXP) {
+    if (Rf_asInteger(n_gibbs_startsSEXP) != 1 || flag(pl, "run_fb_subset", 0) || Rf_asLogical(generate_fb_snp_offsetsSEXP) ||
+        !flag(pl, "use_starting_read_labels", 1) || flag(pl, "pass_in_eMatRead_t", 0) || flag(pl, "use_small_eHapsCurrent_tc", 0))
+        Rf_error("quilt_amd: only the production form of rcpp_forwardBackwardGibbsNIPT is supported (n_gibbs_starts = 1, "
+                 "run_fb_subset = FALSE, use_starting_read_labels = TRUE, pass_in_eMatRead_t = FALSE, packed panel)");
+    if (!flag(pl, "shard_check_every_pair", 1) && flag(pl, "make_eMatRead_t_rare_common", 0))
+        Rf_error("quilt_amd: shard_check_every_pair = FALSE is not supported with make_eMatRead_t_rare_common = TRUE");
+}
+
+/* stage 2, rare + common: the all-SNP handle beside the cached panel, made on first use and kept while snp_is_common is the same
+ * R object.  transMatRate_tc_H is the all-SNP grid's here. */
+static void cache_rare_common(qa_panel_t *panel, SEXP rare_per_hap_infoSEXP, SEXP snp_is_commonSEXP, SEXP transMatRate_tc_HSEXP) {
+    if (g_cache.rc && g_cache.key_rare == (const void *)LOGICAL(snp_is_commonSEXP)) return;
+    if (g_cache.rc) { qa_rare_common_destroy(g_cache.rc); g_cache.rc = NULL; }
+    rare_inputs_t ri;
+    if (rare_inputs_pack(rare_per_hap_infoSEXP, snp_is_commonSEXP, g_cache.K, &ri) != 0)
+        Rf_error("quilt_amd: rcpp_forwardBackwardGibbsNIPT: out of memory");
+    const int st = qa_rare_common_create(panel, Rf_length(snp_is_commonSEXP), ri.is_common, ri.rare_ptr, ri.rare_snp,
+                                         REAL(transMatRate_tc_HSEXP), &g_cache.rc);
+    rare_inputs_free(&ri);
+    check_status(st, "qa_rare_common_create");
+    g_cache.key_rare = LOGICAL(snp_is_commonSEXP);
+}
+
+/* stage 5: the reference's draws, in its order (RcppExports.cpp:971 RNGScope).  Opens R's generator and leaves it open: the entry
+ * closes it after the call, because the library draws through the callbacks above while it runs. */
+static void gibbs_draw(gibbs_call_t *c, qa_gibbs_opts_t *o, SEXP pl, SEXP block_gibbs_iterationsSEXP, double ff, int R, int G,
+                       int n_its, int every_pair) {
+    const int nb = Rf_length(block_gibbs_iterationsSEXP);
+    const size_t n_pass_unif = ff != 0 ? (size_t)nb * 2 * (size_t)R : (size_t)nb * (size_t)(G - 1);
+    double *runif_reads = (double *)malloc(sizeof(double) * ((size_t)R * (size_t)n_its + 1));
+    double *runif_pass = (double *)calloc(n_pass_unif + 1, sizeof(double));   /* (NIPT: filled by the library through draw_uniforms) */
+    int32_t first_read = 0;
+    GetRNGstate();
+    for (size_t i = 0; i < (size_t)R * (size_t)n_its; i++) runif_reads[i] = unif_rand();         /* gibbs-nipt.cpp:2845 */
+    if (!flag(pl, "gibbs_initialize_at_first_read", 0) && R > 0) {
+        /* :2846-2848 Rcpp::sample(nReads, 1) - 1.  Rcpp's sugar (sugar/functions/sample.h, EmpiricalSample, size < 2) draws
+         * static_cast<int>(n * unif_rand() + 1): ONE unif_rand(), no rejection loop (R_unif_index under sample.kind =
+         * "Rejection" would consume a data-dependent number of draws and return another value). */
+        first_read = (int32_t)(unif_rand() * (double)R);
+        if (first_read >= R) first_read = R - 1;
+    }
+    if (o->perform_block_gibbs && ff != 0) {
+        /* NIPT: the block passes' draws depend on the passes' own results (one Rcpp::sample per read whose class leaves a choice),
+         * so they are made when the reference makes them, through the library's callback; the generator stays open until the call
+         * returns (PutRNGstate below the call) */
+        o->draw_uniforms = draw_uniforms_from_R;
+        o->draw_uniforms_ctx = NULL;
+    }
+    /* diploid, shard_check_every_pair = FALSE: a pass draws n_blocks - 1 uniforms for the table it makes itself -- through the
+     * callback as well (qa_gibbs_opts_t.shard_by_blocks) */
+    const int by_blocks = ff == 0 && !every_pair && o->perform_block_gibbs && o->do_shard_block_gibbs && nb > 0;
+    c->shard_draws.n_reads = R; c->shard_draws.next_pass = 0;
+    int n_passes = 0;   /* block iterations that name a sweep of the call, each once: the passes the library runs */
+    if (by_blocks) {
+        for (int ib = 0; ib < nb; ib++) {
+            const int b = INTEGER(block_gibbs_iterationsSEXP)[ib];
+            int seen = 0;
+            for (int jb = 0; jb < ib; jb++) seen |= INTEGER(block_gibbs_iterationsSEXP)[jb] == b;
+            n_passes += b >= 0 && b < n_its && !seen;
+        }
+        o->shard_by_blocks = 1;
+        o->draw_uniforms = draw_shard_uniforms_from_R;
+        o->draw_uniforms_ctx = &c->shard_draws;
+    }
+    if (o->perform_block_gibbs && ff == 0 && !by_blocks) {
+        for (int ib = 0; ib < nb; ib++) {
+            for (size_t i = 0; i < 6 * (size_t)R; i++) (void)unif_rand();                        /* :3013-3015 runif_proposed (unused by approach 6) */
+            {
+                for (size_t i = 0; i < 2 * (size_t)R; i++) (void)unif_rand();                    /* :3016-3017, no effect for diploid samples */
+                if (o->do_shard_block_gibbs)
+                    for (int g = 0; g < G - 1; g++) runif_pass[(size_t)ib * (G - 1) + g] = unif_rand();   /* gibbs-nipt-block.cpp:2054 */
+            }
+        }
+    }
+    c->runif_reads = runif_reads; c->runif_pass = runif_pass; c->first_read = first_read;
+    c->by_blocks = by_blocks; c->n_passes = n_passes;
+}
+
+/* stage 7: the matrices the reference mutates in place (pass_in_alphaBeta = TRUE: R's buffers, quilt.R:731-745) */
+static void gibbs_copy_state_back(const double *state, int Ks, int G, SEXP *dst, int n_dst) {
+    const size_t m = (size_t)Ks * G;
+    for (int i = 0; i < n_dst; i++)
+        if (Rf_nrows(dst[i]) == Ks && Rf_ncols(dst[i]) == G) memcpy(REAL(dst[i]), state + (size_t)i * m, sizeof(double) * m);
+}
+
+/* stage 8: the result list, names as gibbs-nipt.cpp:3217-3306 (gm / gf / hap are the caller's, protected there) */
+static SEXP gibbs_result_list(const gibbs_call_t *c, int R, int n_its, double ff, SEXP gm, SEXP gf, SEXP hap, int want_gen, int want_hap) {
+    result_t r;
+    result_begin(&r);
+    result_add(&r, "underflow_problem", Rf_ScalarLogical(0));
+    if (want_gen) { result_add(&r, "genProbsM_t", gm); result_add(&r, "genProbsF_t", gf); }
+    if (want_hap) result_add(&r, "hapProbs_t", hap);
+    SEXP Hs = result_add(&r, "H", int_vector(c->H, R));
+    SEXP l1 = result_add(&r, "double_list_of_ending_read_labels", Rf_allocVector(VECSXP, 1));   /* [[s]][[i_gibbs_sampling]] */
+    SEXP l2 = SET_VECTOR_ELT(l1, 0, Rf_allocVector(VECSXP, 1));
+    SET_VECTOR_ELT(l2, 0, Hs);
+    result_add(&r, "per_it_likelihoods", per_it_likelihoods(c->per_it, n_its, c->H_class, R, ff));
+    result_add(&r, "H_class", int_vector(c->H_class, R));
+    return result_end(&r);
+}
+/* ... or, after an underflow, only `underflow_problem = TRUE` (gibbs-nipt.cpp:2959-2969); impute_one_sample retries
+ * (functions.R:2704-2715) */
+static SEXP gibbs_underflow_list(void) {
+    result_t r;
+    result_begin(&r);
+    result_add(&r, "underflow_problem", Rf_ScalarLogical(1));
+    return result_end(&r);
+}
+
 SEXP qa_QUILT_rcpp_forwardBackwardGibbsNIPT(
     SEXP sampleReadsSEXP, SEXP eMatRead_tSEXP, SEXP priorCurrent_mSEXP, SEXP alphaMatCurrent_tcSEXP, SEXP eHapsCurrent_tcSEXP,
     SEXP transMatRate_tc_HSEXP, SEXP ffSEXP, SEXP blocks_for_outputSEXP, SEXP alphaHat_t1SEXP, SEXP betaHat_t1SEXP,
@@ -334,65 +628,28 @@ SEXP qa_QUILT_rcpp_forwardBackwardGibbsNIPT(
     (void)prev_list_of_alphaBetaBlocksSEXP; (void)i_snp_block_for_alpha_betaSEXP; (void)do_block_resamplingSEXP;
     (void)artificial_relabelSEXP; (void)common_snp_indexSEXP; (void)rare_per_snp_infoSEXP;
     SEXP pl = param_listSEXP;
-    if (Rf_asInteger(n_gibbs_startsSEXP) != 1 || flag(pl, "run_fb_subset", 0) || Rf_asLogical(generate_fb_snp_offsetsSEXP) ||
-        !flag(pl, "use_starting_read_labels", 1) || flag(pl, "pass_in_eMatRead_t", 0) || flag(pl, "use_small_eHapsCurrent_tc", 0))
-        Rf_error("quilt_amd: only the production form of rcpp_forwardBackwardGibbsNIPT is supported (n_gibbs_starts = 1, "
-                 "run_fb_subset = FALSE, use_starting_read_labels = TRUE, pass_in_eMatRead_t = FALSE, packed panel)");
+    /* 1. refuse non-production forms */
+    gibbs_refuse_non_production(pl, n_gibbs_startsSEXP, generate_fb_snp_offsetsSEXP);
     const double ff = Rf_asReal(ffSEXP);
-    const int rare_common = flag(pl, "make_eMatRead_t_rare_common", 0);
-    const int every_pair = flag(pl, "shard_check_every_pair", 1);
-    if (!every_pair && rare_common)
-        Rf_error("quilt_amd: shard_check_every_pair = FALSE is not supported with make_eMatRead_t_rare_common = TRUE");
-    const int G_panel = Rf_ncols(distinctHapsBSEXP);
-    /* transMatRate_tc_H: 2 x (G - 1) x S; with rare + common it is the all-SNP grid's and the panel's own is not passed:
-     * the panel handle must then exist already (created by a full-panel call or an earlier common-SNP Gibbs call) */
-    const int G = Rf_nrows(transMatRate_tc_HSEXP) == 2 ? (int)(Rf_xlength(transMatRate_tc_HSEXP) / 2) + 1 : G_panel;
+    const int rare_common = flag(pl, "make_eMatRead_t_rare_common", 0), every_pair = flag(pl, "shard_check_every_pair", 1);
+    /* 2. panel and rare + common handle from the cache.  transMatRate_tc_H: 2 x (G - 1) x S; with rare + common it is the all-SNP
+     * grid's and the panel's own is not passed: the panel handle must then exist already (created by a full-panel call or an
+     * earlier common-SNP Gibbs call) */
+    const int G = Rf_nrows(transMatRate_tc_HSEXP) == 2 ? (int)(Rf_xlength(transMatRate_tc_HSEXP) / 2) + 1 : Rf_ncols(distinctHapsBSEXP);
     if (rare_common && !g_cache.panel) Rf_error("quilt_amd: the rare + common call needs the panel of an earlier common-SNP call");
     qa_panel_t *panel = rare_common ? g_cache.panel :
         panel_for(hapMatcherSEXP, hapMatcherRSEXP, Rf_asLogical(use_hapMatcherRSEXP), distinctHapsBSEXP, distinctHapsIESEXP,
                   eMatDH_special_matrix_helperSEXP, eMatDH_special_matrixSEXP, R_NilValue, rhb_tSEXP, Rf_asReal(ref_errorSEXP),
                   flag(pl, "use_eMatDH_special_symbols", 0), REAL(transMatRate_tc_HSEXP));
+    if (rare_common) cache_rare_common(panel, rare_per_hap_infoSEXP, snp_is_commonSEXP, transMatRate_tc_HSEXP);
     const int T = rare_common ? Rf_length(snp_is_commonSEXP) : g_cache.T;
-    if (rare_common && (!g_cache.rc || g_cache.key_rare != (const void *)LOGICAL(snp_is_commonSEXP))) {
-        /* rare_per_hap_info: list over the K haplotypes of 1-based all-SNP indices (rare_common.R:222-247) */
-        if (g_cache.rc) { qa_rare_common_destroy(g_cache.rc); g_cache.rc = NULL; }
-        const int K = g_cache.K;
-        int64_t *rptr = (int64_t *)calloc((size_t)K + 1, sizeof(int64_t));
-        for (int k = 0; k < K; k++) rptr[k + 1] = rptr[k] + Rf_length(VECTOR_ELT(rare_per_hap_infoSEXP, k));
-        int32_t *rsnp = (int32_t *)malloc(sizeof(int32_t) * (size_t)(rptr[K] > 0 ? rptr[K] : 1));
-        for (int k = 0; k < K; k++)
-            memcpy(rsnp + rptr[k], INTEGER(VECTOR_ELT(rare_per_hap_infoSEXP, k)), sizeof(int) * (size_t)(rptr[k + 1] - rptr[k]));
-        uint8_t *isc = (uint8_t *)malloc((size_t)T);
-        for (int t = 0; t < T; t++) isc[t] = LOGICAL(snp_is_commonSEXP)[t] != 0;
-        const int st = qa_rare_common_create(panel, T, isc, rptr, rsnp, REAL(transMatRate_tc_HSEXP), &g_cache.rc);
-        free(rptr); free(rsnp); free(isc);
-        check_status(st, "qa_rare_common_create");
-        g_cache.key_rare = LOGICAL(snp_is_commonSEXP);
-    }
-
-    /* ---- sampleReads -> CSR (sampleReads[[r]] = list(J, wif, bq matrix, u matrix): copied-from-stitch.cpp:153-160) */
+    /* 3. pack reads (the central grids come as wif0) */
+    gibbs_call_t c;
+    memset(&c, 0, sizeof c);
     const int R = Rf_length(sampleReadsSEXP), Ks = Rf_length(which_haps_to_useSEXP);
-    int32_t *read_ptr = (int32_t *)malloc(sizeof(int32_t) * ((size_t)R + 1));
-    if (!read_ptr) Rf_error("quilt_amd: rcpp_make_eMatRead_t: out of memory");
-    read_ptr[0] = 0;
-    for (int r = 0; r < R; r++) read_ptr[r + 1] = read_ptr[r] + Rf_length(VECTOR_ELT(VECTOR_ELT(sampleReadsSEXP, r), 3));
-    const int nB = read_ptr[R];
-    int32_t *u = (int32_t *)malloc(sizeof(int32_t) * (size_t)(nB > 0 ? nB : 1)), *bq = (int32_t *)malloc(sizeof(int32_t) * (size_t)(nB > 0 ? nB : 1));
-    if (!u || !bq) {
-        free(read_ptr); free(u); free(bq);
-        Rf_error("quilt_amd: rcpp_make_eMatRead_t: out of memory");
-    }
-    for (int r = 0; r < R; r++) {
-        SEXP rd = VECTOR_ELT(sampleReadsSEXP, r);
-        const int n = read_ptr[r + 1] - read_ptr[r];
-        memcpy(bq + read_ptr[r], INTEGER(VECTOR_ELT(rd, 2)), sizeof(int) * (size_t)n);
-        memcpy(u + read_ptr[r], INTEGER(VECTOR_ELT(rd, 3)), sizeof(int) * (size_t)n);
-    }
-    int32_t read_off[2] = {0, R};
-
-    /* ---- options */
+    if (pack_reads(sampleReadsSEXP, 0, 0, &c.reads) != 0) Rf_error("quilt_amd: rcpp_forwardBackwardGibbsNIPT: out of memory");
+    /* 4. options */
     const int n_burn = Rf_asInteger(n_gibbs_burn_in_itsSEXP), n_samp = Rf_asInteger(n_gibbs_sample_itsSEXP), n_its = n_burn + n_samp;
-    const int nb = Rf_length(block_gibbs_iterationsSEXP);
     qa_gibbs_opts_t o;
     memset(&o, 0, sizeof o);
     o.Ks = Ks; o.ff = ff; o.sample_is_diploid = flag(pl, "sample_is_diploid", ff == 0);
@@ -400,7 +657,7 @@ SEXP qa_QUILT_rcpp_forwardBackwardGibbsNIPT(
     o.maxDifferenceBetweenReads = Rf_asReal(maxDifferenceBetweenReadsSEXP);
     o.rescale_eMatRead_t = flag(pl, "rescale_eMatRead_t", 1);
     o.n_gibbs_burn_in_its = n_burn; o.n_gibbs_sample_its = n_samp;
-    o.block_gibbs_iterations = INTEGER(block_gibbs_iterationsSEXP); o.n_block_gibbs_iterations = nb;
+    o.block_gibbs_iterations = INTEGER(block_gibbs_iterationsSEXP); o.n_block_gibbs_iterations = Rf_length(block_gibbs_iterationsSEXP);
     o.perform_block_gibbs = flag(pl, "perform_block_gibbs", 0);
     o.do_shard_block_gibbs = flag(pl, "do_shard_block_gibbs", 1);
     o.gibbs_initialize_iteratively = flag(pl, "gibbs_initialize_iteratively", 0);
@@ -408,126 +665,40 @@ SEXP qa_QUILT_rcpp_forwardBackwardGibbsNIPT(
     o.class_sum_cutoff = Rf_asReal(class_sum_cutoffSEXP);
     o.L_grid = INTEGER(L_gridSEXP); o.shuffle_bin_radius = Rf_asInteger(shuffle_bin_radiusSEXP);
     o.block_gibbs_quantile_prob = Rf_asReal(block_gibbs_quantile_probSEXP);
-    double *per_it = (double *)calloc((size_t)(n_its > 0 ? n_its : 1) * 8, sizeof(double));
-    o.per_it_out = per_it;
-
-    /* ---- the reference's draws, in its order (RcppExports.cpp:971 RNGScope) */
-    const size_t n_pass_unif = ff != 0 ? (size_t)nb * 2 * (size_t)R : (size_t)nb * (size_t)(G - 1);
-    double *runif_reads = (double *)malloc(sizeof(double) * ((size_t)R * (size_t)n_its + 1));
-    double *runif_pass = (double *)calloc(n_pass_unif + 1, sizeof(double));   /* (NIPT: filled by the library through draw_uniforms) */
-    int32_t first_read = 0;
-    GetRNGstate();
-    for (size_t i = 0; i < (size_t)R * (size_t)n_its; i++) runif_reads[i] = unif_rand();         /* gibbs-nipt.cpp:2845 */
-    if (!flag(pl, "gibbs_initialize_at_first_read", 0) && R > 0) {
-        /* :2846-2848 Rcpp::sample(nReads, 1) - 1.  Rcpp's sugar (sugar/functions/sample.h, EmpiricalSample, size < 2) draws
-         * static_cast<int>(n * unif_rand() + 1): ONE unif_rand(), no rejection loop (R_unif_index under sample.kind =
-         * "Rejection" would consume a data-dependent number of draws and return another value). */
-        first_read = (int32_t)(unif_rand() * (double)R);
-        if (first_read >= R) first_read = R - 1;
-    }
-    if (o.perform_block_gibbs && ff != 0) {
-        /* NIPT: the block passes' draws depend on the passes' own results (one Rcpp::sample per read whose class leaves a choice),
-         * so they are made when the reference makes them, through the library's callback; the generator stays open until the call
-         * returns (PutRNGstate below the call) */
-        o.draw_uniforms = draw_uniforms_from_R;
-        o.draw_uniforms_ctx = NULL;
-    }
-    /* diploid, shard_check_every_pair = FALSE: a pass draws n_blocks - 1 uniforms for the table it makes itself -- through the
-     * callback as well (qa_gibbs_opts_t.shard_by_blocks) */
-    const int by_blocks = ff == 0 && !every_pair && o.perform_block_gibbs && o.do_shard_block_gibbs && nb > 0;
-    shard_draws_t shard_draws = {R, 0};
-    int n_passes = 0;   /* block iterations that name a sweep of the call, each once: the passes the library runs */
-    if (by_blocks) {
-        for (int ib = 0; ib < nb; ib++) {
-            const int b = INTEGER(block_gibbs_iterationsSEXP)[ib];
-            int seen = 0;
-            for (int jb = 0; jb < ib; jb++) seen |= INTEGER(block_gibbs_iterationsSEXP)[jb] == b;
-            n_passes += b >= 0 && b < n_its && !seen;
-        }
-        o.shard_by_blocks = 1;
-        o.draw_uniforms = draw_shard_uniforms_from_R;
-        o.draw_uniforms_ctx = &shard_draws;
-    }
-    if (o.perform_block_gibbs && ff == 0 && !by_blocks) {
-        for (int ib = 0; ib < nb; ib++) {
-            for (size_t i = 0; i < 6 * (size_t)R; i++) (void)unif_rand();                        /* :3013-3015 runif_proposed (unused by approach 6) */
-            {
-                for (size_t i = 0; i < 2 * (size_t)R; i++) (void)unif_rand();                    /* :3016-3017, no effect for diploid samples */
-                if (o.do_shard_block_gibbs)
-                    for (int g = 0; g < G - 1; g++) runif_pass[(size_t)ib * (G - 1) + g] = unif_rand();   /* gibbs-nipt-block.cpp:2054 */
-            }
-        }
-    }
-
-    /* ---- starting labels in, ending labels out */
+    o.per_it_out = c.per_it = (double *)calloc((size_t)(n_its > 0 ? n_its : 1) * 8, sizeof(double));
+    /* 5. the reference's draws (R's generator stays open until the call has returned) */
+    gibbs_draw(&c, &o, pl, block_gibbs_iterationsSEXP, ff, R, G, n_its, every_pair);
+    /* 6. call: starting labels in, ending labels out */
     SEXP start = VECTOR_ELT(VECTOR_ELT(double_list_of_starting_read_labelsSEXP, 0), 0);
-    int32_t *H = (int32_t *)malloc(sizeof(int32_t) * (size_t)(R > 0 ? R : 1)), *H_class = (int32_t *)calloc((size_t)(R > 0 ? R : 1), sizeof(int32_t));
-    memcpy(H, INTEGER(start), sizeof(int) * (size_t)R);
+    c.H = (int32_t *)malloc(sizeof(int32_t) * (size_t)(R > 0 ? R : 1));
+    c.H_class = (int32_t *)calloc((size_t)(R > 0 ? R : 1), sizeof(int32_t));
+    memcpy(c.H, INTEGER(start), sizeof(int) * (size_t)R);
     const int want_hap = flag(pl, "return_hapProbs", 0), want_gen = flag(pl, "return_genProbs", 0);
     SEXP hap = PROTECT(Rf_allocMatrix(REALSXP, 3, T)), gm = PROTECT(Rf_allocMatrix(REALSXP, 3, T)), gf = PROTECT(Rf_allocMatrix(REALSXP, 3, T));
-    double *state = (double *)malloc(sizeof(double) * ((size_t)6 * Ks * G + (size_t)3 * G));
+    c.state = (double *)malloc(sizeof(double) * ((size_t)6 * Ks * G + (size_t)3 * G));
     int32_t underflow = 0;
+    const flat_reads_t *fr = &c.reads;
     const int st = rare_common
-        ? qa_gibbs_batch_rare_common(panel, g_cache.rc, &o, 1, INTEGER(which_haps_to_useSEXP), read_off, read_ptr, u, bq,
-                                     INTEGER(wif0SEXP), runif_reads, &first_read, runif_pass, H, H_class,
+        ? qa_gibbs_batch_rare_common(panel, g_cache.rc, &o, 1, INTEGER(which_haps_to_useSEXP), fr->read_off, fr->read_ptr, fr->u, fr->bq,
+                                     INTEGER(wif0SEXP), c.runif_reads, &c.first_read, c.runif_pass, c.H, c.H_class,
                                      (want_hap || want_gen) ? REAL(hap) : NULL, want_gen ? REAL(gm) : NULL,
-                                     want_gen ? REAL(gf) : NULL, &underflow, state, NULL, NULL)
-        : qa_gibbs_batch(panel, &o, 1, INTEGER(which_haps_to_useSEXP), read_off, read_ptr, u, bq, INTEGER(wif0SEXP), runif_reads,
-                         &first_read, runif_pass, H, H_class, (want_hap || want_gen) ? REAL(hap) : NULL,
-                         want_gen ? REAL(gm) : NULL, want_gen ? REAL(gf) : NULL, &underflow, state, NULL, NULL);
-    if (by_blocks && st >= 0 && !underflow) burn_block_iterations(&shard_draws, n_passes - 1);
+                                     want_gen ? REAL(gf) : NULL, &underflow, c.state, NULL, NULL)
+        : qa_gibbs_batch(panel, &o, 1, INTEGER(which_haps_to_useSEXP), fr->read_off, fr->read_ptr, fr->u, fr->bq, INTEGER(wif0SEXP),
+                         c.runif_reads, &c.first_read, c.runif_pass, c.H, c.H_class, (want_hap || want_gen) ? REAL(hap) : NULL,
+                         want_gen ? REAL(gm) : NULL, want_gen ? REAL(gf) : NULL, &underflow, c.state, NULL, NULL);
+    if (c.by_blocks && st >= 0 && !underflow) burn_block_iterations(&c.shard_draws, c.n_passes - 1);
     PutRNGstate();   /* (after the call: with NIPT block passes the library draws through draw_uniforms_from_R while it runs) */
     SEXP out = R_NilValue;
     if (st >= 0 && !underflow) {
-        /* the matrices the reference mutates in place (pass_in_alphaBeta = TRUE: R's buffers, quilt.R:731-745) */
-        const size_t m = (size_t)Ks * G;
+        /* 7. copy state back */
         SEXP dst[6] = {alphaHat_t1SEXP, alphaHat_t2SEXP, betaHat_t1SEXP, betaHat_t2SEXP, eMatGrid_t1SEXP, eMatGrid_t2SEXP};
-        for (int i = 0; i < 6; i++)
-            if (Rf_nrows(dst[i]) == Ks && Rf_ncols(dst[i]) == G) memcpy(REAL(dst[i]), state + (size_t)i * m, sizeof(double) * m);
-        /* the result list, names as gibbs-nipt.cpp:3217-3306 */
-        const char *nm[8];
-        int n = 0;
-        nm[n++] = "underflow_problem";
-        if (want_gen) { nm[n++] = "genProbsM_t"; nm[n++] = "genProbsF_t"; }
-        if (want_hap) nm[n++] = "hapProbs_t";
-        nm[n++] = "H"; nm[n++] = "double_list_of_ending_read_labels"; nm[n++] = "per_it_likelihoods"; nm[n++] = "H_class";
-        out = PROTECT(named_list(n, nm));
-        int at = 0;
-        SET_VECTOR_ELT(out, at++, Rf_ScalarLogical(0));
-        if (want_gen) { SET_VECTOR_ELT(out, at++, gm); SET_VECTOR_ELT(out, at++, gf); }
-        if (want_hap) SET_VECTOR_ELT(out, at++, hap);
-        SEXP Hs = PROTECT(Rf_allocVector(INTSXP, R)), Hc = PROTECT(Rf_allocVector(INTSXP, R));
-        memcpy(INTEGER(Hs), H, sizeof(int) * (size_t)R);
-        memcpy(INTEGER(Hc), H_class, sizeof(int) * (size_t)R);
-        SET_VECTOR_ELT(out, at++, Hs);
-        SEXP l1 = PROTECT(Rf_allocVector(VECSXP, 1)), l2 = PROTECT(Rf_allocVector(VECSXP, 1));   /* [[s]][[i_gibbs_sampling]] */
-        SET_VECTOR_ELT(l2, 0, Hs);
-        SET_VECTOR_ELT(l1, 0, l2);
-        SET_VECTOR_ELT(out, at++, l1);
-        /* per_it_likelihoods: one row per sweep, the 13 columns of gibbs-nipt.cpp:2767-2768 */
-        static const char *cn[13] = {"s", "i_samp", "i_it", "i_result_it", "p_O1_given_H1_L", "p_O2_given_H2_L", "p_O3_given_H3_L",
-                                     "p_O_given_H_L", "p_H_given_L", "p_O_H_given_L_up_to_C", "p_set_H_given_L", "relabel",
-                                     "p_H_class_given_L"};
-        SEXP pit = PROTECT(Rf_allocMatrix(REALSXP, n_its, 13));
-        for (int it = 0; it < n_its; it++)   /* H_class is recorded by the last sweep only: NA before */
-            fill_per_it_row(REAL(pit), n_its, it, per_it + (size_t)it * 8, ff, it,
-                            it == n_its - 1 ? log_p_H_class(H_class, R, ff) : NA_REAL);
-        SEXP dn = PROTECT(Rf_allocVector(VECSXP, 2)), cns = PROTECT(Rf_allocVector(STRSXP, 13));
-        for (int j = 0; j < 13; j++) SET_STRING_ELT(cns, j, Rf_mkChar(cn[j]));
-        SET_VECTOR_ELT(dn, 0, R_NilValue);
-        SET_VECTOR_ELT(dn, 1, cns);
-        Rf_setAttrib(pit, R_DimNamesSymbol, dn);
-        SET_VECTOR_ELT(out, at++, pit);
-        SET_VECTOR_ELT(out, at++, Hc);
-        UNPROTECT(8);
+        gibbs_copy_state_back(c.state, Ks, G, dst, 6);
+        /* 8. result list ... */
+        out = gibbs_result_list(&c, R, n_its, ff, gm, gf, hap, want_gen, want_hap);
     } else if (st >= 0) {
-        /* gibbs-nipt.cpp:2959-2969: only `underflow_problem = TRUE`; impute_one_sample retries (functions.R:2704-2715) */
-        static const char *nm[1] = {"underflow_problem"};
-        out = PROTECT(named_list(1, nm));
-        SET_VECTOR_ELT(out, 0, Rf_ScalarLogical(1));
-        UNPROTECT(1);
+        out = gibbs_underflow_list();   /* ... or the underflow list */
     }
-    free(read_ptr); free(u); free(bq); free(per_it); free(runif_reads); free(runif_pass); free(H); free(H_class); free(state);
+    gibbs_call_free(&c);
     UNPROTECT(3);
     check_status(st, "qa_gibbs_batch");
     return out;
@@ -565,22 +736,12 @@ SEXP qa_QUILT_rcpp_make_eMatRead_t(SEXP eMatRead_tSEXP, SEXP sampleReadsSEXP, SE
     if (Rf_length(dim) != 3 || INTEGER(dim)[0] != K || s < 0 || s >= INTEGER(dim)[2] || Rf_ncols(eMatRead_tSEXP) != R)
         Rf_error("quilt_amd: rcpp_make_eMatRead_t: eHapsCurrent_tc must be K x nSNPs x S with K = nrow(eMatRead_t), 0 <= s < S");
     const int T = INTEGER(dim)[1];
-    int32_t *read_ptr = (int32_t *)malloc(sizeof(int32_t) * ((size_t)R + 1));
-    read_ptr[0] = 0;
-    for (int r = 0; r < R; r++) read_ptr[r + 1] = read_ptr[r] + Rf_length(VECTOR_ELT(VECTOR_ELT(sampleReadsSEXP, r), 3));
-    const int nB = read_ptr[R];
-    int32_t *u = (int32_t *)malloc(sizeof(int32_t) * (size_t)(nB > 0 ? nB : 1)), *bq = (int32_t *)malloc(sizeof(int32_t) * (size_t)(nB > 0 ? nB : 1));
-    for (int r = 0; r < R; r++) {
-        SEXP rd = VECTOR_ELT(sampleReadsSEXP, r);
-        const int n = read_ptr[r + 1] - read_ptr[r];
-        memcpy(bq + read_ptr[r], INTEGER(VECTOR_ELT(rd, 2)), sizeof(int) * (size_t)n);
-        memcpy(u + read_ptr[r], INTEGER(VECTOR_ELT(rd, 3)), sizeof(int) * (size_t)n);
-    }
-    const int32_t read_off[2] = {0, R};
-    const int st = qa_rcpp_make_eMatRead_t_nsnps(g_cache.panel, T, 1, K, REAL(eHapsCurrent_tcSEXP) + (size_t)s * K * T, read_off,
-                                                 read_ptr, u, bq, Rf_asReal(maxDifferenceBetweenReadsSEXP), Rf_asInteger(JmaxSEXP),
+    flat_reads_t fr;
+    if (pack_reads(sampleReadsSEXP, 0, 0, &fr) != 0) Rf_error("quilt_amd: rcpp_make_eMatRead_t: out of memory");
+    const int st = qa_rcpp_make_eMatRead_t_nsnps(g_cache.panel, T, 1, K, REAL(eHapsCurrent_tcSEXP) + (size_t)s * K * T, fr.read_off,
+                                                 fr.read_ptr, fr.u, fr.bq, Rf_asReal(maxDifferenceBetweenReadsSEXP), Rf_asInteger(JmaxSEXP),
                                                  Rf_asLogical(rescale_eMatRead_tSEXP), REAL(eMatRead_tSEXP));
-    free(read_ptr); free(u); free(bq);
+    flat_reads_free(&fr);
     check_status(st, "qa_rcpp_make_eMatRead_t");
     return R_NilValue;
 }
@@ -620,14 +781,6 @@ SEXP qa_QUILT_rcpp_make_eMatRead_t(SEXP eMatRead_tSEXP, SEXP sampleReadsSEXP, SE
  * advancing in lock-step); `seed` plays set.seed's part.  use_mspbwt: the panel's msPBWT indices are built here by
  * qa_mspbwt_create (the `ms_indices` the reference loads are the mspbwt package's own structures). */
 
-static double num_or(SEXP list, const char *name, double dflt) {
-    SEXP v = list_get(list, name);
-    return (v == R_NilValue || Rf_length(v) < 1) ? dflt : Rf_asReal(v);
-}
-
-/* a list of sampleReads in the flattened form of include/quilt_amd.h (read_off n + 1; read_ptr R + 1 per sample; bases back to back) */
-typedef struct { int32_t *read_off, *read_ptr, *wif, *u, *bq; } flat_reads_t;
-static void flat_reads_free(flat_reads_t *f) { free(f->read_off); free(f->read_ptr); free(f->wif); free(f->u); free(f->bq); }
 /* Every R-level check of a list of sampleReads, BEFORE anything is allocated: an R error longjmps out of the routine, so it must
  * not be raised (by INTEGER() on a REALSXP, say) while panel handles, the msPBWT index or malloc'd buffers are live. */
 static void validate_reads_list(SEXP readsListSEXP, const char *what) {
@@ -651,49 +804,6 @@ static void validate_reads_list(SEXP readsListSEXP, const char *what) {
     }
 }
 
-/* returns 0, or -1 when an allocation failed (everything it allocated is then freed again).  The list has been validated. */
-static int flatten_reads(SEXP readsListSEXP, flat_reads_t *f) {
-    const int n = Rf_length(readsListSEXP);
-    memset(f, 0, sizeof *f);
-    f->read_off = (int32_t *)malloc(sizeof(int32_t) * ((size_t)n + 1));
-    if (!f->read_off) return -1;
-    f->read_off[0] = 0;
-    size_t nbases = 0;
-    for (int i = 0; i < n; i++) {
-        SEXP sr = VECTOR_ELT(readsListSEXP, i);
-        const int R = Rf_length(sr);
-        f->read_off[i + 1] = f->read_off[i] + R;
-        for (int r = 0; r < R; r++) nbases += (size_t)Rf_length(VECTOR_ELT(VECTOR_ELT(sr, r), 3));
-    }
-    const int totR = f->read_off[n];
-    f->read_ptr = (int32_t *)malloc(sizeof(int32_t) * ((size_t)totR + (size_t)n + 1));
-    f->wif = (int32_t *)malloc(sizeof(int32_t) * (size_t)(totR > 0 ? totR : 1));
-    f->u = (int32_t *)malloc(sizeof(int32_t) * (nbases > 0 ? nbases : 1));
-    f->bq = (int32_t *)malloc(sizeof(int32_t) * (nbases > 0 ? nbases : 1));
-    if (!f->read_ptr || !f->wif || !f->u || !f->bq) {
-        flat_reads_free(f);
-        memset(f, 0, sizeof *f);
-        return -1;
-    }
-    size_t at = 0;
-    for (int i = 0; i < n; i++) {
-        SEXP sr = VECTOR_ELT(readsListSEXP, i);
-        const int R = Rf_length(sr);
-        int32_t *rp = f->read_ptr + f->read_off[i] + i;
-        rp[0] = 0;
-        for (int r = 0; r < R; r++) {
-            SEXP rd = VECTOR_ELT(sr, r);
-            const int nb = Rf_length(VECTOR_ELT(rd, 3));
-            f->wif[f->read_off[i] + r] = Rf_asInteger(VECTOR_ELT(rd, 1));
-            memcpy(f->bq + at, INTEGER(VECTOR_ELT(rd, 2)), sizeof(int) * (size_t)nb);
-            memcpy(f->u + at, INTEGER(VECTOR_ELT(rd, 3)), sizeof(int) * (size_t)nb);
-            at += (size_t)nb;
-            rp[r + 1] = rp[r] + nb;
-        }
-    }
-    return 0;
-}
-
 /* What the two range routines share: the panel handles (one per host thread), the parameter struct with its msPBWT index,
  * all-SNP handles and NIPT block, from the R objects `panel_objects` and `params`. */
 typedef struct {
@@ -705,9 +815,8 @@ typedef struct {
     qa_impute_rare_common_t rcq;
     qa_rare_common_t *rcs[16];
     int n_rc;
-    int64_t *rare_ptr;
-    int32_t *rare_snp, *L_grid_all, *L_grid;
-    uint8_t *is_common;
+    rare_inputs_t rin;
+    int32_t *L_grid_all, *L_grid;
     qa_impute_nipt_t nq;
     qa_impute_shard_blocks_t sb;
     char msg[512];
@@ -752,8 +861,7 @@ static void range_validate(SEXP panelSEXP, SEXP paramsSEXP, const char *who) {
          * panel's size: refused here, before the panel is uploaded, not by the first sample's first Gibbs call */
         const int K = Rf_nrows(hapMatcherR);
         const double ks_asked = num_or(paramsSEXP, "Ksubset", 600), ks = K < ks_asked ? K : ks_asked;
-        SEXP m = list_get(paramsSEXP, "method");
-        const int nipt = m != R_NilValue && TYPEOF(m) == STRSXP && Rf_length(m) == 1 && strcmp(CHAR(STRING_ELT(m, 0)), "nipt") == 0;
+        const int nipt = is_nipt(paramsSEXP);
         const int ks_max = nipt ? QA_KSUBSET_MAX_NIPT : QA_KSUBSET_MAX;
         if (ks > ks_max)
             Rf_error("quilt_amd: %s: Ksubset = %d (the smaller of params$Ksubset and the panel's %d haplotypes) is not built for "
@@ -783,16 +891,18 @@ static void range_validate(SEXP panelSEXP, SEXP paramsSEXP, const char *who) {
 static void range_teardown(range_ctx_t *cx) {
     for (int i = 0; i < cx->n_rc; i++) if (cx->rcs[i]) qa_rare_common_destroy(cx->rcs[i]);
     if (cx->index) qa_mspbwt_destroy(cx->index);
-    free(cx->rare_ptr); free(cx->rare_snp); free(cx->is_common); free(cx->L_grid); free(cx->L_grid_all);
+    rare_inputs_free(&cx->rin);
+    free(cx->L_grid); free(cx->L_grid_all);
     for (int i = 0; i < cx->made; i++) if (cx->handles[i]) qa_panel_destroy(cx->handles[i]);
     cx->n_rc = 0; cx->made = 0; cx->index = NULL;
-    cx->rare_ptr = NULL; cx->rare_snp = NULL; cx->is_common = NULL; cx->L_grid = NULL; cx->L_grid_all = NULL;
+    cx->L_grid = NULL; cx->L_grid_all = NULL;
 }
 
-/* Raises no R error: returns a QA status with the text in cx->msg; on failure everything made so far is torn down again.
- * `n_sample`: what params$ff must have one entry of (method = "nipt"); the fetus' outputs and ff are the caller's to set. */
-static int range_setup(range_ctx_t *cx, SEXP panelSEXP, SEXP paramsSEXP, int n_handles, int n_sample) {
-    memset(cx, 0, sizeof *cx);
+/* The stages of range_setup, in its order.  None raises an R error: each returns a QA status with the text in cx->msg, and
+ * range_teardown undoes whatever the stages before a failure made. */
+
+/* 1. panel handles: one per host thread, replicas of the panel on this process's device, taking the device in turn */
+static int setup_panel_handles(range_ctx_t *cx, SEXP panelSEXP, SEXP paramsSEXP, int n_handles) {
     SEXP hapMatcherR = list_get(panelSEXP, "hapMatcherR"), distinctHapsB = list_get(panelSEXP, "distinctHapsB");
     SEXP distinctHapsIE = list_get(panelSEXP, "distinctHapsIE"), tm = list_get(panelSEXP, "transMatRate_t");
     SEXP helper = list_get(panelSEXP, "eMatDH_special_matrix_helper"), spmat = list_get(panelSEXP, "eMatDH_special_matrix");
@@ -802,7 +912,6 @@ static int range_setup(range_ctx_t *cx, SEXP panelSEXP, SEXP paramsSEXP, int n_h
     if (n_handles < 1) n_handles = 1;
     if (n_handles > 16) n_handles = 16;
     cx->n_handles = n_handles;
-    /* one handle per host thread: replicas of the panel on this process's device, taking the device in turn */
     qa_panel_desc_t d;
     memset(&d, 0, sizeof d);
     d.K = K; d.nGrids = G; d.nSNPs = T; d.nMaxDH = Rf_nrows(distinctHapsB);
@@ -841,11 +950,12 @@ static int range_setup(range_ctx_t *cx, SEXP panelSEXP, SEXP paramsSEXP, int n_h
         if (st == QA_OK && sum_order_batched) st = qa_panel_set_sum_order_batched(cx->handles[cx->made], 1);
     }
     free(which);
-    if (st != QA_OK) {
-        snprintf(cx->msg, sizeof cx->msg, "qa_panel_create: %s", qa_last_error());
-        range_teardown(cx);
-        return st;
-    }
+    if (st != QA_OK) snprintf(cx->msg, sizeof cx->msg, "qa_panel_create: %s", qa_last_error());
+    return st;
+}
+
+/* 2. plain parameters: params' numbers over the library's defaults */
+static void setup_plain_params(range_ctx_t *cx, SEXP paramsSEXP) {
     qa_impute_params_t *ip = &cx->ip;
     qa_impute_params_default(ip);
     ip->nGibbsSamples = (int)num_or(paramsSEXP, "nGibbsSamples", ip->nGibbsSamples);
@@ -866,96 +976,111 @@ static int range_setup(range_ctx_t *cx, SEXP panelSEXP, SEXP paramsSEXP, int n_h
     ip->Jmax = (int)num_or(paramsSEXP, "Jmax", ip->Jmax);
     ip->seed = (uint64_t)num_or(paramsSEXP, "seed", 1);   /* (range-checked by range_validate) */
     ip->samples_per_launch_set = (int)num_or(paramsSEXP, "samples_per_launch_set", 0);
-    /* use_mspbwt = TRUE (QUILT2's default; mspbwt.R:225-474): the panel's indices, built here */
-    if (flag(paramsSEXP, "use_mspbwt", 0)) {
-        ip->use_mspbwt = 1;
-        ip->mspbwtL = (int)num_or(paramsSEXP, "mspbwtL", ip->mspbwtL);
-        ip->mspbwtM = (int)num_or(paramsSEXP, "mspbwtM", ip->mspbwtM);
-        cx->index = qa_mspbwt_create(K, G, RAW(hapMatcherR), d.nMaxDH, INTEGER(distinctHapsB), (int)num_or(paramsSEXP, "mspbwt_nindices", 4));
-        if (!cx->index) { st = QA_ERR_INVALID; snprintf(cx->msg, sizeof cx->msg, "qa_mspbwt_create: %s", qa_last_error()); }
-        ip->mspbwt_index = cx->index;
-    }
-    /* impute_rare_common = TRUE (functions.R:1042-1123): one all-SNP handle per panel handle (the all-SNP reads are the caller's) */
+}
+
+/* 3. msPBWT index: use_mspbwt = TRUE (QUILT2's default; mspbwt.R:225-474): the panel's indices, built here */
+static int setup_mspbwt(range_ctx_t *cx, SEXP panelSEXP, SEXP paramsSEXP) {
+    if (!flag(paramsSEXP, "use_mspbwt", 0)) return QA_OK;
+    SEXP hapMatcherR = list_get(panelSEXP, "hapMatcherR"), distinctHapsB = list_get(panelSEXP, "distinctHapsB");
+    qa_impute_params_t *ip = &cx->ip;
+    ip->use_mspbwt = 1;
+    ip->mspbwtL = (int)num_or(paramsSEXP, "mspbwtL", ip->mspbwtL);
+    ip->mspbwtM = (int)num_or(paramsSEXP, "mspbwtM", ip->mspbwtM);
+    cx->index = qa_mspbwt_create(cx->K, cx->G, RAW(hapMatcherR), Rf_nrows(distinctHapsB), INTEGER(distinctHapsB),
+                                 (int)num_or(paramsSEXP, "mspbwt_nindices", 4));
+    ip->mspbwt_index = cx->index;
+    if (cx->index) return QA_OK;
+    snprintf(cx->msg, sizeof cx->msg, "qa_mspbwt_create: %s", qa_last_error());
+    return QA_ERR_INVALID;
+}
+
+/* 4. rare-and-common handles: impute_rare_common = TRUE (functions.R:1042-1123): one all-SNP handle per panel handle (the all-SNP
+ * reads are the caller's) */
+static int setup_rare_common(range_ctx_t *cx, SEXP panelSEXP, SEXP paramsSEXP) {
     cx->rare = flag(paramsSEXP, "impute_rare_common", 0);
-    if (st == QA_OK && cx->rare) {
-        SEXP rc = list_get(panelSEXP, "rare_common");
-        SEXP sic = rc == R_NilValue ? R_NilValue : list_get(rc, "snp_is_common"), rph = rc == R_NilValue ? R_NilValue : list_get(rc, "rare_per_hap_info");
-        SEXP tma = rc == R_NilValue ? R_NilValue : list_get(rc, "transMatRate_t"), lga = rc == R_NilValue ? R_NilValue : list_get(rc, "L_grid");
-        if (sic == R_NilValue || rph == R_NilValue || tma == R_NilValue || Rf_length(rph) != K) {
-            st = QA_ERR_INVALID;
-            snprintf(cx->msg, sizeof cx->msg, "impute_rare_common: panel_objects$rare_common needs snp_is_common, rare_per_hap_info (one entry per "
-                                              "haplotype), transMatRate_t");
-        } else {
-            const int T_out = cx->T_out = Rf_length(sic);
-            cx->is_common = (uint8_t *)malloc((size_t)(T_out > 0 ? T_out : 1));
-            cx->rare_ptr = (int64_t *)malloc(sizeof(int64_t) * ((size_t)K + 1));
-            if (cx->is_common && cx->rare_ptr) {
-                for (int t = 0; t < T_out; t++) cx->is_common[t] = LOGICAL(sic)[t] ? 1 : 0;
-                cx->rare_ptr[0] = 0;
-                for (int k = 0; k < K; k++) cx->rare_ptr[k + 1] = cx->rare_ptr[k] + Rf_length(VECTOR_ELT(rph, k));
-                cx->rare_snp = (int32_t *)malloc(sizeof(int32_t) * (size_t)(cx->rare_ptr[K] > 0 ? cx->rare_ptr[K] : 1));
-            }
-            if (!cx->is_common || !cx->rare_ptr || !cx->rare_snp) {
-                st = QA_ERR_INVALID;
-                snprintf(cx->msg, sizeof cx->msg, "out of memory preparing the rare + common inputs");
-            }
-            for (int k = 0; st == QA_OK && k < K; k++)
-                if (cx->rare_ptr[k + 1] > cx->rare_ptr[k])
-                    memcpy(cx->rare_snp + cx->rare_ptr[k], INTEGER(VECTOR_ELT(rph, k)), sizeof(int) * (size_t)(cx->rare_ptr[k + 1] - cx->rare_ptr[k]));
-            for (; cx->n_rc < n_handles && st == QA_OK; cx->n_rc++) {
-                cx->rcs[cx->n_rc] = NULL;
-                st = qa_rare_common_create(cx->handles[cx->n_rc], T_out, cx->is_common, cx->rare_ptr, cx->rare_snp, REAL(tma), &cx->rcs[cx->n_rc]);
-            }
-            if (st != QA_OK && !cx->msg[0]) snprintf(cx->msg, sizeof cx->msg, "qa_rare_common_create: %s", qa_last_error());
-            cx->rcq.handles = (const qa_rare_common_t *const *)cx->rcs;
-            cx->rcq.nSNPs_all = T_out;
-            cx->rcq.nGrids_all = (T_out + 31) / 32;
-            cx->rcq.snp_is_common = cx->is_common;
-            if (st == QA_OK && lga != R_NilValue && Rf_length(lga) == cx->rcq.nGrids_all) {
-                cx->L_grid_all = (int32_t *)malloc(sizeof(int32_t) * (size_t)cx->rcq.nGrids_all);
-                for (int g = 0; cx->L_grid_all && g < cx->rcq.nGrids_all; g++)
-                    cx->L_grid_all[g] = TYPEOF(lga) == INTSXP ? INTEGER(lga)[g] : (int32_t)REAL(lga)[g];
-                cx->rcq.L_grid_all = cx->L_grid_all;
-            }
-            ip->rare_common = &cx->rcq;
-        }
+    if (!cx->rare) return QA_OK;
+    SEXP rc = list_get(panelSEXP, "rare_common");
+    SEXP sic = rc == R_NilValue ? R_NilValue : list_get(rc, "snp_is_common"), rph = rc == R_NilValue ? R_NilValue : list_get(rc, "rare_per_hap_info");
+    SEXP tma = rc == R_NilValue ? R_NilValue : list_get(rc, "transMatRate_t"), lga = rc == R_NilValue ? R_NilValue : list_get(rc, "L_grid");
+    if (sic == R_NilValue || rph == R_NilValue || tma == R_NilValue || Rf_length(rph) != cx->K) {
+        snprintf(cx->msg, sizeof cx->msg, "impute_rare_common: panel_objects$rare_common needs snp_is_common, rare_per_hap_info (one entry per "
+                                          "haplotype), transMatRate_t");
+        return QA_ERR_INVALID;
     }
-    /* method = "nipt" (functions.R:586, :1009-1016, :1218-1231): one fetal fraction per sample, the block definition's grid */
-    SEXP methodSEXP = list_get(paramsSEXP, "method");
-    cx->nipt = methodSEXP != R_NilValue && TYPEOF(methodSEXP) == STRSXP && Rf_length(methodSEXP) == 1 &&
-               strcmp(CHAR(STRING_ELT(methodSEXP, 0)), "nipt") == 0;
-    if (st == QA_OK && cx->nipt) {
-        SEXP ff = list_get(paramsSEXP, "ff"), lg = list_get(panelSEXP, "L_grid");
-        if (ff == R_NilValue || TYPEOF(ff) != REALSXP || Rf_length(ff) != n_sample || lg == R_NilValue || Rf_length(lg) != G) {
-            st = QA_ERR_INVALID;
-            snprintf(cx->msg, sizeof cx->msg, "method = \"nipt\": params$ff (one per sample, numeric) and panel_objects$L_grid (nGrids) are needed");
-        } else {
-            cx->L_grid = (int32_t *)malloc(sizeof(int32_t) * (size_t)G);
-            if (!cx->L_grid) { st = QA_ERR_INVALID; snprintf(cx->msg, sizeof cx->msg, "out of memory"); }
-            for (int g = 0; cx->L_grid && g < G; g++) cx->L_grid[g] = TYPEOF(lg) == INTSXP ? INTEGER(lg)[g] : (int32_t)REAL(lg)[g];
-            cx->nq.ff = REAL(ff);
-            cx->nq.L_grid = cx->L_grid;
-            cx->nq.shuffle_bin_radius = (int)num_or(paramsSEXP, "shuffle_bin_radius", 5000);
-            ip->nipt = &cx->nq;
-        }
+    const int T_out = cx->T_out = Rf_length(sic);
+    if (rare_inputs_pack(rph, sic, cx->K, &cx->rin) != 0) {
+        snprintf(cx->msg, sizeof cx->msg, "out of memory preparing the rare + common inputs");
+        return QA_ERR_INVALID;
     }
-    /* shard_check_every_pair = FALSE (quilt.R:178; absent: TRUE), method = "diploid": the shard passes go block by block and the
-     * block definition needs the grid positions (qa_impute_params_t.shard_blocks) */
-    if (st == QA_OK && !cx->nipt && !flag(paramsSEXP, "shard_check_every_pair", 1)) {
-        SEXP lg = list_get(panelSEXP, "L_grid");
-        if (lg == R_NilValue || Rf_length(lg) != G) {
-            st = QA_ERR_INVALID;
-            snprintf(cx->msg, sizeof cx->msg, "shard_check_every_pair = FALSE: panel_objects$L_grid (nGrids) is needed");
-        } else {
-            cx->L_grid = (int32_t *)malloc(sizeof(int32_t) * (size_t)G);
-            if (!cx->L_grid) { st = QA_ERR_INVALID; snprintf(cx->msg, sizeof cx->msg, "out of memory"); }
-            for (int g = 0; cx->L_grid && g < G; g++) cx->L_grid[g] = TYPEOF(lg) == INTSXP ? INTEGER(lg)[g] : (int32_t)REAL(lg)[g];
-            cx->sb.L_grid = cx->L_grid;
-            cx->sb.shuffle_bin_radius = (int)num_or(paramsSEXP, "shuffle_bin_radius", 5000);
-            cx->sb.block_gibbs_quantile_prob = num_or(paramsSEXP, "block_gibbs_quantile_prob", 0.95);
-            ip->shard_blocks = &cx->sb;
-        }
+    int st = QA_OK;
+    for (; cx->n_rc < cx->n_handles && st == QA_OK; cx->n_rc++) {
+        cx->rcs[cx->n_rc] = NULL;
+        st = qa_rare_common_create(cx->handles[cx->n_rc], T_out, cx->rin.is_common, cx->rin.rare_ptr, cx->rin.rare_snp, REAL(tma), &cx->rcs[cx->n_rc]);
     }
+    if (st != QA_OK) {
+        snprintf(cx->msg, sizeof cx->msg, "qa_rare_common_create: %s", qa_last_error());
+        return st;
+    }
+    cx->rcq.handles = (const qa_rare_common_t *const *)cx->rcs;
+    cx->rcq.nSNPs_all = T_out;
+    cx->rcq.nGrids_all = (T_out + 31) / 32;
+    cx->rcq.snp_is_common = cx->rin.is_common;
+    cx->rcq.L_grid_all = cx->L_grid_all = ints_of(lga, cx->rcq.nGrids_all);   /* (optional: NULL when absent or of another length) */
+    cx->ip.rare_common = &cx->rcq;
+    return QA_OK;
+}
+
+/* the grid positions a block definition needs: panel_objects$L_grid (nGrids) into cx->L_grid; `missing` is the text when absent */
+static int setup_L_grid(range_ctx_t *cx, SEXP panelSEXP, int have_the_rest, const char *missing) {
+    SEXP lg = list_get(panelSEXP, "L_grid");
+    if (!have_the_rest || lg == R_NilValue || Rf_length(lg) != cx->G) {
+        snprintf(cx->msg, sizeof cx->msg, "%s", missing);
+        return QA_ERR_INVALID;
+    }
+    cx->L_grid = ints_of(lg, cx->G);
+    if (cx->L_grid) return QA_OK;
+    snprintf(cx->msg, sizeof cx->msg, "out of memory");
+    return QA_ERR_INVALID;
+}
+
+/* 5. NIPT block: method = "nipt" (functions.R:586, :1009-1016, :1218-1231): one fetal fraction per sample (`n_sample` of them;
+ * the fetus' outputs are the caller's to set), the block definition's grid */
+static int setup_nipt(range_ctx_t *cx, SEXP panelSEXP, SEXP paramsSEXP, int n_sample) {
+    cx->nipt = is_nipt(paramsSEXP);
+    if (!cx->nipt) return QA_OK;
+    SEXP ff = list_get(paramsSEXP, "ff");
+    const int st = setup_L_grid(cx, panelSEXP, ff != R_NilValue && TYPEOF(ff) == REALSXP && Rf_length(ff) == n_sample,
+                                "method = \"nipt\": params$ff (one per sample, numeric) and panel_objects$L_grid (nGrids) are needed");
+    if (st != QA_OK) return st;
+    cx->nq.ff = REAL(ff);
+    cx->nq.L_grid = cx->L_grid;
+    cx->nq.shuffle_bin_radius = (int)num_or(paramsSEXP, "shuffle_bin_radius", 5000);
+    cx->ip.nipt = &cx->nq;
+    return QA_OK;
+}
+
+/* 6. block-wise shard passes: shard_check_every_pair = FALSE (quilt.R:178; absent: TRUE), method = "diploid": the shard passes go
+ * block by block and the block definition needs the grid positions (qa_impute_params_t.shard_blocks) */
+static int setup_shard_blocks(range_ctx_t *cx, SEXP panelSEXP, SEXP paramsSEXP) {
+    if (cx->nipt || flag(paramsSEXP, "shard_check_every_pair", 1)) return QA_OK;
+    const int st = setup_L_grid(cx, panelSEXP, 1, "shard_check_every_pair = FALSE: panel_objects$L_grid (nGrids) is needed");
+    if (st != QA_OK) return st;
+    cx->sb.L_grid = cx->L_grid;
+    cx->sb.shuffle_bin_radius = (int)num_or(paramsSEXP, "shuffle_bin_radius", 5000);
+    cx->sb.block_gibbs_quantile_prob = num_or(paramsSEXP, "block_gibbs_quantile_prob", 0.95);
+    cx->ip.shard_blocks = &cx->sb;
+    return QA_OK;
+}
+
+/* Raises no R error: returns a QA status with the text in cx->msg; on failure everything made so far is torn down again. */
+static int range_setup(range_ctx_t *cx, SEXP panelSEXP, SEXP paramsSEXP, int n_handles, int n_sample) {
+    memset(cx, 0, sizeof *cx);
+    int st = setup_panel_handles(cx, panelSEXP, paramsSEXP, n_handles);
+    if (st == QA_OK) setup_plain_params(cx, paramsSEXP);
+    if (st == QA_OK) st = setup_mspbwt(cx, panelSEXP, paramsSEXP);
+    if (st == QA_OK) st = setup_rare_common(cx, panelSEXP, paramsSEXP);
+    if (st == QA_OK) st = setup_nipt(cx, panelSEXP, paramsSEXP, n_sample);
+    if (st == QA_OK) st = setup_shard_blocks(cx, panelSEXP, paramsSEXP);
     if (st != QA_OK) range_teardown(cx);
     return st;
 }
@@ -964,15 +1089,15 @@ static int range_setup(range_ctx_t *cx, SEXP panelSEXP, SEXP paramsSEXP, int n_h
  * form quilt-amd.R uses, so that a sample skipped for too few reads does not shift the streams of the samples behind it */
 static int64_t *sample_index_of(SEXP sample_offsetSEXP, int n) {
     if (Rf_length(sample_offsetSEXP) != n || n <= 1) return NULL;   /* (n == 1: offset and index are the same thing) */
-    int64_t *idx = (int64_t *)malloc(sizeof(int64_t) * (size_t)n);
-    for (int i = 0; idx && i < n; i++)
-        idx[i] = TYPEOF(sample_offsetSEXP) == INTSXP ? (int64_t)INTEGER(sample_offsetSEXP)[i] : (int64_t)REAL(sample_offsetSEXP)[i];
-    return idx;
+    return int64s_of(sample_offsetSEXP, n);
 }
 
-SEXP qa_impute_sample_range(SEXP readsListSEXP, SEXP panelSEXP, SEXP paramsSEXP, SEXP sample_offsetSEXP, SEXP n_handlesSEXP,
-                            SEXP allReadsListSEXP) {
-    static const char *who = "qa_impute_sample_range";
+/* what the caller asked for beyond the plain outputs; filled by the validation stage */
+typedef struct { int hla_grid, want_prob; } range_opts_t;
+
+/* stage 1: every R-level check of the six arguments, before anything is made */
+static void sample_range_validate(SEXP readsListSEXP, SEXP panelSEXP, SEXP paramsSEXP, SEXP sample_offsetSEXP, SEXP allReadsListSEXP,
+                                  const char *who, range_opts_t *opt) {
     const int n = Rf_length(readsListSEXP);
     validate_reads_list(readsListSEXP, "list_of_sampleReads");
     if (allReadsListSEXP != R_NilValue) validate_reads_list(allReadsListSEXP, "list_of_allSNP_sampleReads");
@@ -982,122 +1107,146 @@ SEXP qa_impute_sample_range(SEXP readsListSEXP, SEXP panelSEXP, SEXP paramsSEXP,
         Rf_error("quilt_amd: %s: sample_offset must be one number or one global index per sample", who);
     if (flag(paramsSEXP, "impute_rare_common", 0) && (allReadsListSEXP == R_NilValue || Rf_length(allReadsListSEXP) != n))
         Rf_error("quilt_amd: %s: impute_rare_common needs one allSNP_sampleReads per sample", who);
-    /* hla_run (functions.R:1261-1280): params$hla_grid, the 0-based grid of gamma1 / gamma2 -- checked before anything is made */
-    SEXP hgSEXP = list_get(paramsSEXP, "hla_grid");
-    const int hla = hgSEXP != R_NilValue;
-    int hla_grid = -1;
-    if (hla) {
-        const double hg = Rf_length(hgSEXP) == 1 && (TYPEOF(hgSEXP) == INTSXP || TYPEOF(hgSEXP) == REALSXP) ? Rf_asReal(hgSEXP) : -1;
-        const int G = Rf_ncols(list_get(panelSEXP, "hapMatcherR"));
-        if (!(hg >= 0 && hg < G && hg == floor(hg)))
-            Rf_error("quilt_amd: %s: params$hla_grid must be one whole number in [0, nGrids = %d) (iGrid - 1)", who, G);
-        hla_grid = (int)hg;
-    }
+    opt->hla_grid = hla_grid_of(paramsSEXP, who, Rf_ncols(list_get(panelSEXP, "hapMatcherR")));
     /* output_read_label_prob (functions.R:1164-1166): params$output_read_label_prob -> read_label_prob, one vector per sample */
-    const int want_prob = flag(paramsSEXP, "output_read_label_prob", 0);
+    opt->want_prob = flag(paramsSEXP, "output_read_label_prob", 0);
+}
+
+/* The range's outputs: the R objects the library writes into (each PROTECTed, `n_prot` of them) and the malloc'd per-read arrays */
+typedef struct {
+    SEXP dosage, gp_t, haps, nDosage, stats, fet_dosage, fet_gp_t, g1, g2, gtot, glist, lab, probs;
+    int n_prot;
+    int32_t *labels;
+    double *prob;
+    int64_t *sidx, st64[11];
+    qa_impute_hla_t hq;
+} range_out_t;
+static SEXP keep(range_out_t *o, SEXP x) { o->n_prot++; return PROTECT(x); }
+
+/* stage 4: allocate results (R's before the library runs; cx->nq gets the fetus' outputs).  QA_OK, or the status with `msg` set. */
+static int range_out_alloc(range_out_t *o, range_ctx_t *cx, const range_opts_t *opt, SEXP sample_offsetSEXP, int n, int totR, char *msg,
+                           size_t n_msg) {
+    const int T_out = cx->T_out, nL = cx->nipt ? 3 : 2;
+    memset(o, 0, sizeof *o);
+    o->fet_dosage = o->fet_gp_t = o->g1 = o->g2 = o->gtot = o->glist = R_NilValue;
+    if (cx->nipt) {
+        o->fet_dosage = keep(o, Rf_allocMatrix(REALSXP, T_out, n));
+        o->fet_gp_t = keep(o, Rf_allocMatrix(REALSXP, 3 * T_out, n));
+        cx->nq.fet_dosage = REAL(o->fet_dosage);
+        cx->nq.fet_gp_t = REAL(o->fet_gp_t);
+    }
+    o->dosage = keep(o, Rf_allocMatrix(REALSXP, T_out, n));
+    o->gp_t = keep(o, Rf_allocMatrix(REALSXP, 3 * T_out, n));
+    o->haps = keep(o, Rf_allocMatrix(REALSXP, nL * T_out, n));
+    o->nDosage = keep(o, Rf_allocVector(INTSXP, n));
+    o->stats = keep(o, Rf_allocVector(REALSXP, 11));
+    if (opt->hla_grid >= 0) {
+        o->g1 = keep(o, Rf_allocMatrix(REALSXP, cx->K, n)); o->g2 = keep(o, Rf_allocMatrix(REALSXP, cx->K, n));
+        o->gtot = keep(o, Rf_allocMatrix(REALSXP, cx->K, n));
+        o->glist = keep(o, Rf_allocMatrix(REALSXP, cx->K * 2 * cx->ip.nGibbsSamples, n));
+        o->hq.grid = opt->hla_grid;
+        o->hq.gamma1 = REAL(o->g1); o->hq.gamma2 = REAL(o->g2); o->hq.gamma_total = REAL(o->gtot); o->hq.list_of_gammas = REAL(o->glist);
+    }
+    o->labels = (int32_t *)malloc(sizeof(int32_t) * (size_t)(totR > 0 ? totR : 1));
+    o->prob = opt->want_prob ? (double *)malloc(sizeof(double) * (size_t)(totR > 0 ? totR : 1)) : NULL;
+    o->sidx = sample_index_of(sample_offsetSEXP, n);
+    if (o->labels && (!opt->want_prob || o->prob) && !(Rf_length(sample_offsetSEXP) == n && n > 1 && !o->sidx)) return QA_OK;
+    snprintf(msg, n_msg, "out of memory");
+    return QA_ERR_INVALID;
+}
+
+/* stage 5: call the library -- the entry of the options asked for */
+static int range_call(range_ctx_t *cx, const range_opts_t *opt, const flat_reads_t *fr, range_out_t *o, SEXP sample_offsetSEXP, int n,
+                      char *msg, size_t n_msg) {
+    const int hla = opt->hla_grid >= 0;
+    int st;
+    cx->ip.sample_index = o->sidx;
+    const int64_t off = o->sidx ? 0 : (int64_t)Rf_asReal(sample_offsetSEXP);
+    if (opt->want_prob) {
+        qa_impute_reads_out_t ro;
+        memset(&ro, 0, sizeof ro);
+        ro.read_label_prob = o->prob;
+        st = qa_impute_samples_reads(cx->handles, cx->n_handles, &cx->ip, n, off, fr->read_off, fr->read_ptr, fr->u, fr->bq, fr->wif,
+                                     REAL(o->dosage), REAL(o->gp_t), REAL(o->haps), o->labels, INTEGER(o->nDosage), o->st64,
+                                     hla ? &o->hq : NULL, &ro);
+    } else if (hla)
+        st = qa_impute_samples_hla(cx->handles, cx->n_handles, &cx->ip, n, off, fr->read_off, fr->read_ptr, fr->u, fr->bq, fr->wif,
+                                   REAL(o->dosage), REAL(o->gp_t), REAL(o->haps), o->labels, INTEGER(o->nDosage), o->st64, &o->hq);
+    else
+        st = qa_impute_samples(cx->handles, cx->n_handles, &cx->ip, n, off, fr->read_off, fr->read_ptr, fr->u, fr->bq, fr->wif,
+                               REAL(o->dosage), REAL(o->gp_t), REAL(o->haps), o->labels, INTEGER(o->nDosage), o->st64);
+    if (st != QA_OK) snprintf(msg, n_msg, "%s: %s", hla ? "qa_impute_samples_hla" : "qa_impute_samples", qa_last_error());
+    return st;
+}
+
+/* stage 6: label lists -- per sample the read labels and, when asked for, their confidences */
+static void range_label_lists(range_out_t *o, const int32_t *read_off, int n, int want_prob, int filled) {
+    o->lab = keep(o, Rf_allocVector(VECSXP, n));
+    o->probs = keep(o, want_prob ? Rf_allocVector(VECSXP, n) : R_NilValue);
+    for (int i = 0; filled && i < n; i++) {
+        const int R = read_off[i + 1] - read_off[i];
+        SET_VECTOR_ELT(o->lab, i, int_vector(o->labels + read_off[i], R));
+        if (want_prob) SET_VECTOR_ELT(o->probs, i, real_vector(o->prob + read_off[i], R));
+    }
+}
+
+/* stage 7: result list */
+static SEXP range_result_list(const range_out_t *o, int nipt, int hla, int want_prob) {
+    result_t r;
+    result_begin(&r);
+    result_add(&r, "dosage", o->dosage); result_add(&r, "gp_t", o->gp_t); result_add(&r, "phasing_haps", o->haps);
+    result_add(&r, "read_labels", o->lab); result_add(&r, "nDosage", o->nDosage); result_add(&r, "stats", o->stats);
+    if (hla) {
+        result_add(&r, "gamma1", o->g1); result_add(&r, "gamma2", o->g2);
+        result_add(&r, "gamma_total", o->gtot); result_add(&r, "list_of_gammas", o->glist);
+    } else if (nipt) {
+        result_add(&r, "fet_dosage", o->fet_dosage); result_add(&r, "fet_gp_t", o->fet_gp_t);
+    }
+    if (want_prob) result_add(&r, "read_label_prob", o->probs);
+    return result_end(&r);
+}
+
+SEXP qa_impute_sample_range(SEXP readsListSEXP, SEXP panelSEXP, SEXP paramsSEXP, SEXP sample_offsetSEXP, SEXP n_handlesSEXP,
+                            SEXP allReadsListSEXP) {
+    static const char *who = "qa_impute_sample_range";
+    const int n = Rf_length(readsListSEXP);
+    /* 1. validate */
+    range_opts_t opt;
+    sample_range_validate(readsListSEXP, panelSEXP, paramsSEXP, sample_offsetSEXP, allReadsListSEXP, who, &opt);
+    /* 2. set up */
     range_ctx_t cx;
     int st = range_setup(&cx, panelSEXP, paramsSEXP, Rf_asInteger(n_handlesSEXP), n);
     if (st != QA_OK) Rf_error("quilt_amd: %s: %s", who, cx.msg);
-    const int T_out = cx.T_out, nL = cx.nipt ? 3 : 2;
-    /* flatten the range's sampleReads */
+    /* 3. flatten reads: the range's sampleReads and, with rare + common, its all-SNP ones */
     flat_reads_t fr, fa;
     memset(&fa, 0, sizeof fa);
-    if (flatten_reads(readsListSEXP, &fr) != 0 || (cx.rare && flatten_reads(allReadsListSEXP, &fa) != 0)) {
-        if (fr.read_off) flat_reads_free(&fr);
+    if (pack_reads(readsListSEXP, 1, 1, &fr) != 0 || (cx.rare && pack_reads(allReadsListSEXP, 1, 1, &fa) != 0)) {
+        flat_reads_free(&fr);
         range_teardown(&cx);
         Rf_error("quilt_amd: %s: out of memory flattening the sampleReads", who);
     }
     if (cx.rare) { cx.rcq.read_off = fa.read_off; cx.rcq.read_ptr = fa.read_ptr; cx.rcq.u = fa.u; cx.rcq.bq = fa.bq; cx.rcq.wif = fa.wif; }
-    const int32_t *read_off = fr.read_off;
-    const int totR = read_off[n];
-    int n_prot = 0;
-    SEXP fet_dosage = R_NilValue, fet_gp_t = R_NilValue;
-    if (cx.nipt) {
-        fet_dosage = PROTECT(Rf_allocMatrix(REALSXP, T_out, n));
-        fet_gp_t = PROTECT(Rf_allocMatrix(REALSXP, 3 * T_out, n));
-        n_prot = 2;
-        cx.nq.fet_dosage = REAL(fet_dosage);
-        cx.nq.fet_gp_t = REAL(fet_gp_t);
-    }
-    SEXP dosage = PROTECT(Rf_allocMatrix(REALSXP, T_out, n)), gp_t = PROTECT(Rf_allocMatrix(REALSXP, 3 * T_out, n));
-    SEXP haps = PROTECT(Rf_allocMatrix(REALSXP, nL * T_out, n)), nDosage = PROTECT(Rf_allocVector(INTSXP, n));
-    SEXP stats = PROTECT(Rf_allocVector(REALSXP, 11));
-    SEXP g1 = R_NilValue, g2 = R_NilValue, gtot = R_NilValue, glist = R_NilValue;
-    qa_impute_hla_t hq;
-    memset(&hq, 0, sizeof hq);
-    if (hla) {
-        g1 = PROTECT(Rf_allocMatrix(REALSXP, cx.K, n));
-        g2 = PROTECT(Rf_allocMatrix(REALSXP, cx.K, n));
-        gtot = PROTECT(Rf_allocMatrix(REALSXP, cx.K, n));
-        glist = PROTECT(Rf_allocMatrix(REALSXP, cx.K * 2 * cx.ip.nGibbsSamples, n));
-        n_prot += 4;
-        hq.grid = hla_grid;
-        hq.gamma1 = REAL(g1); hq.gamma2 = REAL(g2); hq.gamma_total = REAL(gtot); hq.list_of_gammas = REAL(glist);
-    }
-    int32_t *labels = (int32_t *)malloc(sizeof(int32_t) * (size_t)(totR > 0 ? totR : 1));
-    double *prob = want_prob ? (double *)malloc(sizeof(double) * (size_t)(totR > 0 ? totR : 1)) : NULL;
-    int64_t *sidx = sample_index_of(sample_offsetSEXP, n);
+    /* 4. allocate results */
+    range_out_t o;
     char msg[512];
     msg[0] = 0;
-    if (!labels || (want_prob && !prob) || (Rf_length(sample_offsetSEXP) == n && n > 1 && !sidx)) { st = QA_ERR_INVALID; snprintf(msg, sizeof msg, "out of memory"); }
-    int64_t st64[11] = {0};
-    if (st == QA_OK) {
-        cx.ip.sample_index = sidx;
-        const int64_t off = sidx ? 0 : (int64_t)Rf_asReal(sample_offsetSEXP);
-        if (want_prob) {
-            qa_impute_reads_out_t ro;
-            memset(&ro, 0, sizeof ro);
-            ro.read_label_prob = prob;
-            st = qa_impute_samples_reads(cx.handles, cx.n_handles, &cx.ip, n, off, read_off, fr.read_ptr, fr.u, fr.bq, fr.wif, REAL(dosage),
-                                         REAL(gp_t), REAL(haps), labels, INTEGER(nDosage), st64, hla ? &hq : NULL, &ro);
-        } else if (hla)
-            st = qa_impute_samples_hla(cx.handles, cx.n_handles, &cx.ip, n, off, read_off, fr.read_ptr, fr.u, fr.bq, fr.wif, REAL(dosage),
-                                       REAL(gp_t), REAL(haps), labels, INTEGER(nDosage), st64, &hq);
-        else
-            st = qa_impute_samples(cx.handles, cx.n_handles, &cx.ip, n, off, read_off, fr.read_ptr, fr.u, fr.bq, fr.wif, REAL(dosage),
-                                   REAL(gp_t), REAL(haps), labels, INTEGER(nDosage), st64);
-        if (st != QA_OK) snprintf(msg, sizeof msg, "%s: %s", hla ? "qa_impute_samples_hla" : "qa_impute_samples", qa_last_error());
-    }
+    st = range_out_alloc(&o, &cx, &opt, sample_offsetSEXP, n, fr.read_off[n], msg, sizeof msg);
+    /* 5. call the library */
+    if (st == QA_OK) st = range_call(&cx, &opt, &fr, &o, sample_offsetSEXP, n, msg, sizeof msg);
     range_teardown(&cx);
-    free(sidx);
-    if (fa.read_off) flat_reads_free(&fa);
-    SEXP lab = PROTECT(Rf_allocVector(VECSXP, n));
-    SEXP probs = PROTECT(want_prob ? Rf_allocVector(VECSXP, n) : R_NilValue);
-    if (st == QA_OK)
-        for (int i = 0; i < n; i++) {
-            const int R = read_off[i + 1] - read_off[i];
-            SEXP v = PROTECT(Rf_allocVector(INTSXP, R));
-            memcpy(INTEGER(v), labels + read_off[i], sizeof(int) * (size_t)R);
-            SET_VECTOR_ELT(lab, i, v);
-            UNPROTECT(1);
-            if (!want_prob) continue;
-            SEXP pv = PROTECT(Rf_allocVector(REALSXP, R));
-            memcpy(REAL(pv), prob + read_off[i], sizeof(double) * (size_t)R);
-            SET_VECTOR_ELT(probs, i, pv);
-            UNPROTECT(1);
-        }
+    free(o.sidx); flat_reads_free(&fa);
+    /* 6. label lists */
+    range_label_lists(&o, fr.read_off, n, opt.want_prob, st == QA_OK);
     flat_reads_free(&fr);
-    free(labels);
-    free(prob);
+    free(o.labels); free(o.prob);
     if (st != QA_OK) {
-        UNPROTECT(7 + n_prot);
+        UNPROTECT(o.n_prot);
         Rf_error("quilt_amd: %s: %s", who, msg);
     }
-    for (int i = 0; i < 11; i++) REAL(stats)[i] = (double)st64[i];
-    const char *names[] = {"dosage", "gp_t", "phasing_haps", "read_labels", "nDosage", "stats", "fet_dosage", "fet_gp_t"};
-    const char *names_hla[] = {"dosage", "gp_t", "phasing_haps", "read_labels", "nDosage", "stats", "gamma1", "gamma2", "gamma_total",
-                               "list_of_gammas", "read_label_prob"};
-    const int n_names = hla ? 10 : cx.nipt ? 8 : 6;   /* (read_label_prob, when asked for, is the entry behind these) */
-    const char *names_all[11];
-    for (int i = 0; i < n_names; i++) names_all[i] = hla ? names_hla[i] : names[i];
-    names_all[n_names] = "read_label_prob";
-    SEXP out = PROTECT(named_list(n_names + (want_prob ? 1 : 0), names_all));
-    SET_VECTOR_ELT(out, 0, dosage); SET_VECTOR_ELT(out, 1, gp_t); SET_VECTOR_ELT(out, 2, haps);
-    SET_VECTOR_ELT(out, 3, lab); SET_VECTOR_ELT(out, 4, nDosage); SET_VECTOR_ELT(out, 5, stats);
-    if (hla) { SET_VECTOR_ELT(out, 6, g1); SET_VECTOR_ELT(out, 7, g2); SET_VECTOR_ELT(out, 8, gtot); SET_VECTOR_ELT(out, 9, glist); }
-    else if (cx.nipt) { SET_VECTOR_ELT(out, 6, fet_dosage); SET_VECTOR_ELT(out, 7, fet_gp_t); }
-    if (want_prob) SET_VECTOR_ELT(out, n_names, probs);
-    UNPROTECT(8 + n_prot);
+    counters_to_real(o.st64, 11, o.stats);
+    /* 7. result list */
+    SEXP out = range_result_list(&o, cx.nipt, opt.hla_grid >= 0, opt.want_prob);
+    UNPROTECT(o.n_prot);
     return out;
 }
 
@@ -1125,10 +1274,6 @@ SEXP qa_impute_sample_range(SEXP readsListSEXP, SEXP panelSEXP, SEXP paramsSEXP,
  * columns for files not imputed).  Both go through qa_impute_bam_range_ex (include/quilt_amd_io.h).  The loader is
  * csrc/hostio.cpp's (include/quilt_amd_io.h says where it is unpinned against STITCH: CRAM is refused); quilt-amd.R calls this
  * routine only for the options it implements and falls back to the R loader otherwise. */
-static const char *one_string(SEXP list, const char *name) {
-    SEXP v = list_get(list, name);
-    return (v != R_NilValue && TYPEOF(v) == STRSXP && Rf_length(v) == 1) ? CHAR(STRING_ELT(v, 0)) : NULL;
-}
 /* a character vector of single letters -> n bytes; NULL when an entry is not one letter (nothing allocated then) */
 static char *letters_of(SEXP v, int n) {
     if (v == R_NilValue || TYPEOF(v) != STRSXP || Rf_length(v) != n) return NULL;
@@ -1142,135 +1287,94 @@ static void range_result_finalizer(SEXP p) {
     if (r) qa_bam_range_destroy(r);
     R_ClearExternalPtr(p);
 }
-static int32_t *ints_of(SEXP v, int n) {
-    if (v == R_NilValue || (TYPEOF(v) != INTSXP && TYPEOF(v) != REALSXP) || Rf_length(v) != n) return NULL;
-    int32_t *out = (int32_t *)malloc(sizeof(int32_t) * (size_t)(n > 0 ? n : 1));
-    for (int i = 0; out && i < n; i++) out[i] = TYPEOF(v) == INTSXP ? INTEGER(v)[i] : (int32_t)REAL(v)[i];
-    return out;
-}
 
-SEXP qa_impute_bam_range_call(SEXP bamFilesSEXP, SEXP sitesSEXP, SEXP panelSEXP, SEXP paramsSEXP, SEXP sample_indexSEXP, SEXP n_handlesSEXP) {
-    static const char *who = "qa_impute_bam_range";
+/* the options of one call, all checked before anything is made */
+typedef struct { int use_bx_tag, bx_limit, want_prob, hla_grid, rare, T, Ta; const char *chr; } bam_opts_t;
+
+/* stage 1: validate options (and everything else that can raise an R error) */
+static void bam_range_validate(SEXP bamFilesSEXP, SEXP sitesSEXP, SEXP panelSEXP, SEXP paramsSEXP, SEXP sample_indexSEXP, const char *who,
+                               bam_opts_t *opt) {
     if (TYPEOF(bamFilesSEXP) != STRSXP) Rf_error("quilt_amd: %s: bam_files must be a character vector", who);
-    const int n = Rf_length(bamFilesSEXP);
-    if ((TYPEOF(sample_indexSEXP) != REALSXP && TYPEOF(sample_indexSEXP) != INTSXP) || Rf_length(sample_indexSEXP) != n)
+    if ((TYPEOF(sample_indexSEXP) != REALSXP && TYPEOF(sample_indexSEXP) != INTSXP) || Rf_length(sample_indexSEXP) != Rf_length(bamFilesSEXP))
         Rf_error("quilt_amd: %s: sample_index must hold one 0-based global index per file", who);
     range_validate(panelSEXP, paramsSEXP, who);
-    /* the BX pair, checked here: before anything is allocated (an R error longjmps out of the routine) */
-    int use_bx_tag = 0, bx_limit = 50000;
-    {
-        SEXP ub = list_get(sitesSEXP, "use_bx_tag"), bl = list_get(sitesSEXP, "bxTagUpperLimit");
-        if (ub != R_NilValue) {
-            if (TYPEOF(ub) != LGLSXP || Rf_length(ub) != 1 || (LOGICAL(ub)[0] != 0 && LOGICAL(ub)[0] != 1))   /* (NA is neither) */
-                Rf_error("quilt_amd: %s: sites$use_bx_tag must be TRUE or FALSE", who);
-            use_bx_tag = LOGICAL(ub)[0] != 0;
-        }
-        if (bl != R_NilValue) {
-            const double v = ((TYPEOF(bl) == INTSXP || TYPEOF(bl) == REALSXP) && Rf_length(bl) == 1) ? Rf_asReal(bl) : -1.0;
-            if (!(v >= 0 && v <= 2147483647.0 && v == (double)(int)v))   /* (NA and NaN fail every comparison) */
-                Rf_error("quilt_amd: %s: sites$bxTagUpperLimit must be one whole number >= 0 (below 2^31)", who);
-            bx_limit = (int)v;
-        }
+    /* the BX pair */
+    opt->use_bx_tag = strict_flag(sitesSEXP, "use_bx_tag", 0, who);
+    opt->bx_limit = 50000;
+    SEXP bl = list_get(sitesSEXP, "bxTagUpperLimit");
+    if (bl != R_NilValue) {
+        const double v = ((TYPEOF(bl) == INTSXP || TYPEOF(bl) == REALSXP) && Rf_length(bl) == 1) ? Rf_asReal(bl) : -1.0;
+        if (!(v >= 0 && v <= 2147483647.0 && v == (double)(int)v))   /* (NA and NaN fail every comparison) */
+            Rf_error("quilt_amd: %s: sites$bxTagUpperLimit must be one whole number >= 0 (below 2^31)", who);
+        opt->bx_limit = (int)v;
     }
     /* the two options of qa_bam_range_extras_t beyond the tag: sites$output_read_label_prob, params$hla_grid (0-based, as for
-     * qa_impute_sample_range) -- checked here too */
-    int want_prob = 0, hla_grid = -1;
-    {
-        SEXP op = list_get(sitesSEXP, "output_read_label_prob"), hg = list_get(paramsSEXP, "hla_grid");
-        if (op != R_NilValue) {
-            if (TYPEOF(op) != LGLSXP || Rf_length(op) != 1 || (LOGICAL(op)[0] != 0 && LOGICAL(op)[0] != 1))
-                Rf_error("quilt_amd: %s: sites$output_read_label_prob must be TRUE or FALSE", who);
-            want_prob = LOGICAL(op)[0] != 0;
-        }
-        if (hg != R_NilValue) {
-            const double v = Rf_length(hg) == 1 && (TYPEOF(hg) == INTSXP || TYPEOF(hg) == REALSXP) ? Rf_asReal(hg) : -1;
-            const int G = Rf_ncols(list_get(panelSEXP, "hapMatcherR"));
-            if (!(v >= 0 && v < G && v == floor(v)))
-                Rf_error("quilt_amd: %s: params$hla_grid must be one whole number in [0, nGrids = %d) (iGrid - 1)", who, G);
-            hla_grid = (int)v;
-        }
-    }
-    const char *chr = one_string(sitesSEXP, "chr");
+     * qa_impute_sample_range) */
+    opt->want_prob = strict_flag(sitesSEXP, "output_read_label_prob", 0, who);
+    opt->hla_grid = hla_grid_of(paramsSEXP, who, Rf_ncols(list_get(panelSEXP, "hapMatcherR")));
+    opt->chr = one_string(sitesSEXP, "chr");
     SEXP Lx = list_get(sitesSEXP, "L");
-    if (!chr || Lx == R_NilValue) Rf_error("quilt_amd: %s: sites needs chr, L, ref, alt, grid", who);
-    const int T = Rf_length(Lx);
-    if (T != Rf_ncols(list_get(panelSEXP, "distinctHapsIE"))) Rf_error("quilt_amd: %s: sites$L must have one entry per SNP of the panel", who);
-    const int rare = flag(paramsSEXP, "impute_rare_common", 0);
-    const int Ta = rare ? Rf_length(list_get(sitesSEXP, "L_all")) : 0;
-    /* the sites as plain arrays (malloc: freed below on every path; R errors are raised only before or after) */
-    int32_t *L = ints_of(Lx, T), *grid = ints_of(list_get(sitesSEXP, "grid"), T);
-    char *ref = letters_of(list_get(sitesSEXP, "ref"), T), *alt = letters_of(list_get(sitesSEXP, "alt"), T);
-    int32_t *La = rare ? ints_of(list_get(sitesSEXP, "L_all"), Ta) : NULL, *grida = rare ? ints_of(list_get(sitesSEXP, "grid_all"), Ta) : NULL;
-    char *refa = rare ? letters_of(list_get(sitesSEXP, "ref_all"), Ta) : NULL, *alta = rare ? letters_of(list_get(sitesSEXP, "alt_all"), Ta) : NULL;
-    const char **paths = (const char **)malloc(sizeof(char *) * (size_t)(n > 0 ? n : 1));
-    int64_t *sidx = (int64_t *)malloc(sizeof(int64_t) * (size_t)(n > 0 ? n : 1));
-    const int sites_ok = L && grid && ref && alt && paths && sidx && (!rare || (La && grida && refa && alta));
-    range_ctx_t cx;
-    memset(&cx, 0, sizeof cx);
-    int st = QA_OK;
-    char msg[512];
-    msg[0] = 0;
-    if (!sites_ok) {
-        st = QA_ERR_INVALID;
-        snprintf(msg, sizeof msg, "sites: L / grid numeric, ref / alt character vectors of single letters, all of the panel's length%s",
-                 rare ? " (and L_all / grid_all / ref_all / alt_all over all SNPs)" : "");
+    if (!opt->chr || Lx == R_NilValue) Rf_error("quilt_amd: %s: sites needs chr, L, ref, alt, grid", who);
+    opt->T = Rf_length(Lx);
+    if (opt->T != Rf_ncols(list_get(panelSEXP, "distinctHapsIE"))) Rf_error("quilt_amd: %s: sites$L must have one entry per SNP of the panel", who);
+    opt->rare = flag(paramsSEXP, "impute_rare_common", 0);
+    opt->Ta = opt->rare ? Rf_length(list_get(sitesSEXP, "L_all")) : 0;
+}
+
+/* stage 2: the sites, the paths and the sample indices as plain arrays (malloc; one free for every path) */
+typedef struct { int32_t *L, *grid, *La, *grida; char *ref, *alt, *refa, *alta; const char **paths; int64_t *sidx; } site_arrays_t;
+static void site_arrays_free(site_arrays_t *a) {
+    free(a->L); free(a->grid); free(a->ref); free(a->alt); free(a->La); free(a->grida); free(a->refa); free(a->alta);
+    free((void *)a->paths); free(a->sidx);
+    memset(a, 0, sizeof *a);
+}
+/* 1, or 0 when an entry of `sites` is of the wrong kind or length (or memory ran out): the caller frees and reports */
+static int site_arrays_make(site_arrays_t *a, SEXP sitesSEXP, SEXP bamFilesSEXP, SEXP sample_indexSEXP, const bam_opts_t *opt) {
+    const int n = Rf_length(bamFilesSEXP), T = opt->T, Ta = opt->Ta;
+    memset(a, 0, sizeof *a);
+    a->L = ints_of(list_get(sitesSEXP, "L"), T); a->grid = ints_of(list_get(sitesSEXP, "grid"), T);
+    a->ref = letters_of(list_get(sitesSEXP, "ref"), T); a->alt = letters_of(list_get(sitesSEXP, "alt"), T);
+    if (opt->rare) {
+        a->La = ints_of(list_get(sitesSEXP, "L_all"), Ta); a->grida = ints_of(list_get(sitesSEXP, "grid_all"), Ta);
+        a->refa = letters_of(list_get(sitesSEXP, "ref_all"), Ta); a->alta = letters_of(list_get(sitesSEXP, "alt_all"), Ta);
     }
-    if (st == QA_OK) {
-        st = range_setup(&cx, panelSEXP, paramsSEXP, Rf_asInteger(n_handlesSEXP), n);
-        if (st != QA_OK) snprintf(msg, sizeof msg, "%s", cx.msg);
-    }
-    qa_bam_range_result_t *res = NULL;
-    if (st == QA_OK) {
-        for (int i = 0; i < n; i++) {
-            paths[i] = CHAR(STRING_ELT(bamFilesSEXP, i));
-            sidx[i] = TYPEOF(sample_indexSEXP) == INTSXP ? (int64_t)INTEGER(sample_indexSEXP)[i] : (int64_t)REAL(sample_indexSEXP)[i];
-        }
-        qa_bam_range_io_t io;
-        memset(&io, 0, sizeof io);
-        io.chr = chr; io.nSNPs = T; io.L = L; io.ref = ref; io.alt = alt; io.grid = grid;
-        io.nSNPs_all = Ta; io.L_all = La; io.ref_all = refa; io.alt_all = alta; io.grid_all = grida;
-        qa_bam_opts_default(&io.bam);
-        io.bam.bqFilter = (int)num_or(sitesSEXP, "bqFilter", io.bam.bqFilter);
-        {
-            const double isz = num_or(sitesSEXP, "iSizeUpperLimit", io.bam.iSizeUpperLimit);
-            io.bam.iSizeUpperLimit = isz > 2147483647.0 ? 2147483647 : (int)isz;
-        }
-        io.bam.useSoftClippedBases = flag(sitesSEXP, "useSoftClippedBases", 0);
-        io.bam.downsampleToCov = (int)num_or(sitesSEXP, "downsampleToCov", io.bam.downsampleToCov);
-        io.bam.chrStart = (int)num_or(sitesSEXP, "chrStart", 0);
-        io.bam.chrEnd = (int)num_or(sitesSEXP, "chrEnd", 0);
-        io.minimum_number_of_sample_reads = (int)num_or(sitesSEXP, "minimum_number_of_sample_reads", 2);
-        io.output_gt_phased_genotypes = flag(sitesSEXP, "output_gt_phased_genotypes", 1);
-        io.n_io_threads = (int)num_or(sitesSEXP, "n_io_threads", 0);
-        io.discard_sample_arrays = 1;   /* (columns, labels and counts go back to R: the per-SNP numbers behind them are not kept) */
-        qa_bam_range_extras_t ex;
-        memset(&ex, 0, sizeof ex);
-        ex.use_bx_tag = use_bx_tag; ex.bxTagUpperLimit = bx_limit; ex.output_read_label_prob = want_prob; ex.hla_grid = hla_grid;
-        st = qa_impute_bam_range_ex(cx.handles, cx.n_handles, &cx.ip, &io, &ex, n, paths, sidx, cx.nipt ? cx.nq.ff : NULL, &res);
-        if (st != QA_OK) snprintf(msg, sizeof msg, "%s", qa_last_error());
-        range_teardown(&cx);
-    }
-    free(L); free(grid); free(ref); free(alt); free(La); free(grida); free(refa); free(alta); free((void *)paths); free(sidx);
-    if (st != QA_OK) {
-        if (res) qa_bam_range_destroy(res);
-        Rf_error("quilt_amd: %s: %s", who, msg);
-    }
-    /* results as R objects.  (An allocation failure inside R longjmps past the end of this routine: the result is handed to an
-     * external pointer with a finalizer first, so that the collector frees it in that case; it is freed explicitly below otherwise.) */
-    SEXP guard = PROTECT(R_MakeExternalPtr(res, R_NilValue, R_NilValue));
-    R_RegisterCFinalizerEx(guard, range_result_finalizer, TRUE);
+    a->paths = (const char **)malloc(sizeof(char *) * (size_t)(n > 0 ? n : 1));
+    a->sidx = int64s_of(sample_indexSEXP, n);
+    for (int i = 0; a->paths && i < n; i++) a->paths[i] = CHAR(STRING_ELT(bamFilesSEXP, i));
+    return a->L && a->grid && a->ref && a->alt && a->paths && a->sidx && (!opt->rare || (a->La && a->grida && a->refa && a->alta));
+}
+
+/* stage 4: qa_bam_range_io_t from the site arrays and sites' loader options, the extras from the checked options */
+static void bam_io_fill(qa_bam_range_io_t *io, qa_bam_range_extras_t *ex, SEXP sitesSEXP, const bam_opts_t *opt, const site_arrays_t *a) {
+    memset(io, 0, sizeof *io);
+    io->chr = opt->chr; io->nSNPs = opt->T; io->L = a->L; io->ref = a->ref; io->alt = a->alt; io->grid = a->grid;
+    io->nSNPs_all = opt->Ta; io->L_all = a->La; io->ref_all = a->refa; io->alt_all = a->alta; io->grid_all = a->grida;
+    qa_bam_opts_default(&io->bam);
+    io->bam.bqFilter = (int)num_or(sitesSEXP, "bqFilter", io->bam.bqFilter);
+    const double isz = num_or(sitesSEXP, "iSizeUpperLimit", io->bam.iSizeUpperLimit);
+    io->bam.iSizeUpperLimit = isz > 2147483647.0 ? 2147483647 : (int)isz;
+    io->bam.useSoftClippedBases = flag(sitesSEXP, "useSoftClippedBases", 0);
+    io->bam.downsampleToCov = (int)num_or(sitesSEXP, "downsampleToCov", io->bam.downsampleToCov);
+    io->bam.chrStart = (int)num_or(sitesSEXP, "chrStart", 0);
+    io->bam.chrEnd = (int)num_or(sitesSEXP, "chrEnd", 0);
+    io->minimum_number_of_sample_reads = (int)num_or(sitesSEXP, "minimum_number_of_sample_reads", 2);
+    io->output_gt_phased_genotypes = flag(sitesSEXP, "output_gt_phased_genotypes", 1);
+    io->n_io_threads = (int)num_or(sitesSEXP, "n_io_threads", 0);
+    io->discard_sample_arrays = 1;   /* (columns, labels and counts go back to R: the per-SNP numbers behind them are not kept) */
+    memset(ex, 0, sizeof *ex);
+    ex->use_bx_tag = opt->use_bx_tag; ex->bxTagUpperLimit = opt->bx_limit;
+    ex->output_read_label_prob = opt->want_prob; ex->hla_grid = opt->hla_grid;
+}
+
+/* stage 6, the result as R objects: each part appends its entries to the list and balances its own PROTECTs */
+
+/* sample_was_imputed, n_reads, per_sample_vcf_col, read_labels; returns read_labels (the confidences' lists share its vectors) */
+static SEXP bam_columns_and_labels(result_t *r, const qa_bam_range_result_t *res, int n) {
     const int T_out = qa_bam_range_n_snps(res);
-    const char *names[16] = {"sample_was_imputed", "n_reads", "per_sample_vcf_col", "read_labels", "infoCount", "afCount", "hweCount",
-                             "alleleCount", "seconds", "stats", "bx_stats"};
-    int n_names = 11;   /* (the options' entries follow the eleven a call without them returns) */
-    const int at_prob = want_prob ? n_names : -1;
-    if (want_prob) names[n_names++] = "final_read_labels_prob";
-    const int at_hla = hla_grid >= 0 ? n_names : -1;
-    if (hla_grid >= 0) { names[n_names++] = "gamma1"; names[n_names++] = "gamma2"; names[n_names++] = "gamma_total"; names[n_names++] = "list_of_gammas"; }
-    SEXP out = PROTECT(named_list(n_names, names));
-    SEXP imputed = PROTECT(Rf_allocVector(LGLSXP, n)), n_reads = PROTECT(Rf_allocVector(INTSXP, n));
-    SEXP cols = PROTECT(Rf_allocVector(VECSXP, n)), labs = PROTECT(Rf_allocVector(VECSXP, n));
-    SET_VECTOR_ELT(out, 0, imputed); SET_VECTOR_ELT(out, 1, n_reads); SET_VECTOR_ELT(out, 2, cols); SET_VECTOR_ELT(out, 3, labs);
+    SEXP imputed = result_add(r, "sample_was_imputed", Rf_allocVector(LGLSXP, n));
+    SEXP n_reads = result_add(r, "n_reads", Rf_allocVector(INTSXP, n));
+    SEXP cols = result_add(r, "per_sample_vcf_col", Rf_allocVector(VECSXP, n));
+    SEXP labs = result_add(r, "read_labels", Rf_allocVector(VECSXP, n));
     for (int i = 0; i < n; i++) {
         LOGICAL(imputed)[i] = qa_bam_range_imputed(res, i);
         INTEGER(n_reads)[i] = qa_bam_range_n_reads(res, i);
@@ -1285,70 +1389,119 @@ SEXP qa_impute_bam_range_call(SEXP bamFilesSEXP, SEXP sitesSEXP, SEXP panelSEXP,
         const int32_t *rl = NULL;
         int32_t nl = 0;
         qa_bam_range_sample(res, i, NULL, NULL, NULL, NULL, NULL, &rl, &nl, NULL);
-        SEXP v = PROTECT(Rf_allocVector(INTSXP, nl));
-        if (nl > 0) memcpy(INTEGER(v), rl, sizeof(int) * (size_t)nl);
-        SET_VECTOR_ELT(labs, i, v);
-        UNPROTECT(1);
+        SET_VECTOR_ELT(labs, i, int_vector(rl, nl));
     }
-    SEXP info = PROTECT(Rf_allocMatrix(REALSXP, T_out, 2)), af = PROTECT(Rf_allocVector(REALSXP, T_out));
-    SEXP hwe = PROTECT(Rf_allocMatrix(REALSXP, T_out, 3)), ac = PROTECT(Rf_allocMatrix(REALSXP, T_out, 2));
+    return labs;
+}
+/* infoCount, afCount, hweCount, alleleCount: the range's sums */
+static void bam_counts(result_t *r, const qa_bam_range_result_t *res) {
+    const int T_out = qa_bam_range_n_snps(res);
+    SEXP info = result_add(r, "infoCount", Rf_allocMatrix(REALSXP, T_out, 2)), af = result_add(r, "afCount", Rf_allocVector(REALSXP, T_out));
+    SEXP hwe = result_add(r, "hweCount", Rf_allocMatrix(REALSXP, T_out, 3)), ac = result_add(r, "alleleCount", Rf_allocMatrix(REALSXP, T_out, 2));
     qa_bam_range_counts(res, REAL(info), REAL(af), REAL(hwe), REAL(ac));
-    SET_VECTOR_ELT(out, 4, info); SET_VECTOR_ELT(out, 5, af); SET_VECTOR_ELT(out, 6, hwe); SET_VECTOR_ELT(out, 7, ac);
-    SEXP sec = PROTECT(Rf_allocVector(REALSXP, 4)), stats = PROTECT(Rf_allocVector(REALSXP, 11));
-    int64_t st64[11] = {0};
+}
+/* seconds, stats, bx_stats */
+static void bam_timings_and_stats(result_t *r, const qa_bam_range_result_t *res) {
+    SEXP sec = result_add(r, "seconds", Rf_allocVector(REALSXP, 4)), stats = result_add(r, "stats", Rf_allocVector(REALSXP, 11));
+    int64_t st64[11] = {0}, bx64[4] = {0};
     qa_bam_range_timings(res, REAL(sec), st64, NULL);
-    for (int i = 0; i < 11; i++) REAL(stats)[i] = (double)st64[i];
-    SET_VECTOR_ELT(out, 8, sec); SET_VECTOR_ELT(out, 9, stats);
-    SEXP bxs = PROTECT(Rf_allocVector(REALSXP, 4));
-    int64_t bx64[4] = {0};
+    counters_to_real(st64, 11, stats);
     qa_bam_range_bx_stats(res, bx64);
-    for (int i = 0; i < 4; i++) REAL(bxs)[i] = (double)bx64[i];
-    SET_VECTOR_ELT(out, 10, bxs);
-    if (want_prob) {   /* final_read_labels_prob: per sample list(names, prob, labels) (functions.R:318-319, :1165, :1203); NULL when not imputed */
-        SEXP frlp = PROTECT(Rf_allocVector(VECSXP, n));
-        SET_VECTOR_ELT(out, at_prob, frlp);
-        UNPROTECT(1);
+    counters_to_real(bx64, 4, result_add(r, "bx_stats", Rf_allocVector(REALSXP, 4)));
+}
+/* final_read_labels_prob: per sample list(names, prob, labels) (functions.R:318-319, :1165, :1203); NULL when not imputed */
+static void bam_read_label_prob(result_t *r, const qa_bam_range_result_t *res, int n, SEXP labs) {
+    SEXP frlp = result_add(r, "final_read_labels_prob", Rf_allocVector(VECSXP, n));
+    for (int i = 0; i < n; i++) {
+        const char *nb = NULL;
+        const int64_t *no = NULL;
+        const double *pr = NULL;
+        int32_t nr = 0;
+        qa_bam_range_read_label_prob(res, i, &nb, &no, &pr, &nr);
+        if (!no) continue;
+        SEXP three = SET_VECTOR_ELT(frlp, i, Rf_allocVector(VECSXP, 3));
+        SEXP nm = SET_VECTOR_ELT(three, 0, Rf_allocVector(STRSXP, nr));
+        for (int q = 0; q < nr; q++) SET_STRING_ELT(nm, q, Rf_mkChar(nb + no[q]));
+        SET_VECTOR_ELT(three, 1, real_vector(pr, nr));
+        SET_VECTOR_ELT(three, 2, VECTOR_ELT(labs, i));
+    }
+}
+/* gamma1, gamma2, gamma_total, list_of_gammas: the shapes of qa_impute_sample_range (K x n, and (K x 2 x nGibbsSamples) x n); NA
+ * for a file not imputed */
+static void bam_hla_matrices(result_t *r, const qa_bam_range_result_t *res, int n, int32_t K, int32_t nG) {
+    static const char *names[4] = {"gamma1", "gamma2", "gamma_total", "list_of_gammas"};
+    const size_t rows[4] = {(size_t)K, (size_t)K, (size_t)K, (size_t)K * 2 * (size_t)nG};
+    for (int q = 0; q < 4; q++) {
+        SEXP m = result_add(r, names[q], Rf_allocMatrix(REALSXP, (int)rows[q], n));
         for (int i = 0; i < n; i++) {
-            const char *nb = NULL;
-            const int64_t *no = NULL;
-            const double *pr = NULL;
-            int32_t nr = 0;
-            qa_bam_range_read_label_prob(res, i, &nb, &no, &pr, &nr);
-            if (!no) continue;
-            SEXP three = PROTECT(Rf_allocVector(VECSXP, 3));
-            SET_VECTOR_ELT(frlp, i, three);
-            UNPROTECT(1);
-            SEXP nm = PROTECT(Rf_allocVector(STRSXP, nr));
-            for (int r = 0; r < nr; r++) SET_STRING_ELT(nm, r, Rf_mkChar(nb + no[r]));
-            SET_VECTOR_ELT(three, 0, nm);
-            UNPROTECT(1);
-            SEXP pv = PROTECT(Rf_allocVector(REALSXP, nr));
-            if (nr > 0) memcpy(REAL(pv), pr, sizeof(double) * (size_t)nr);
-            SET_VECTOR_ELT(three, 1, pv);
-            UNPROTECT(1);
-            SET_VECTOR_ELT(three, 2, VECTOR_ELT(labs, i));
+            const double *g[4] = {NULL, NULL, NULL, NULL};
+            int32_t k2 = 0, g2 = 0;
+            qa_bam_range_hla(res, i, &g[0], &g[1], &g[2], &g[3], &k2, &g2);
+            double *dst = REAL(m) + (size_t)i * rows[q];
+            if (g[q] && k2 == K && g2 == nG) memcpy(dst, g[q], sizeof(double) * rows[q]);
+            else for (size_t k = 0; k < rows[q]; k++) dst[k] = NA_REAL;
         }
     }
-    if (hla_grid >= 0) {   /* the shapes of qa_impute_sample_range: K x n, and (K x 2 x nGibbsSamples) x n; NA for a file not imputed */
-        const int32_t K = cx.K, nG = cx.ip.nGibbsSamples;   /* (plain numbers of the context: they outlive its teardown) */
-        const size_t rows[4] = {(size_t)K, (size_t)K, (size_t)K, (size_t)K * 2 * (size_t)nG};
-        for (int q = 0; q < 4; q++) {
-            SEXP m = PROTECT(Rf_allocMatrix(REALSXP, (int)rows[q], n));
-            SET_VECTOR_ELT(out, at_hla + q, m);
-            UNPROTECT(1);
-            for (int i = 0; i < n; i++) {
-                const double *g[4] = {NULL, NULL, NULL, NULL};
-                int32_t k2 = 0, g2 = 0;
-                qa_bam_range_hla(res, i, &g[0], &g[1], &g[2], &g[3], &k2, &g2);
-                double *dst = REAL(m) + (size_t)i * rows[q];
-                if (g[q] && k2 == K && g2 == nG) memcpy(dst, g[q], sizeof(double) * rows[q]);
-                else for (size_t r = 0; r < rows[q]; r++) dst[r] = NA_REAL;
-            }
-        }
-    }
+}
+/* (An allocation failure inside R longjmps past the end of the routine: the result is handed to an external pointer with a
+ * finalizer first, so that the collector frees it in that case; it is freed explicitly at the end otherwise.) */
+static SEXP bam_result_to_R(qa_bam_range_result_t *res, int n, const bam_opts_t *opt, int32_t K, int32_t nG) {
+    SEXP guard = PROTECT(R_MakeExternalPtr(res, R_NilValue, R_NilValue));
+    R_RegisterCFinalizerEx(guard, range_result_finalizer, TRUE);
+    result_t r;
+    result_begin(&r);
+    SEXP labs = bam_columns_and_labels(&r, res, n);
+    bam_counts(&r, res);
+    bam_timings_and_stats(&r, res);
+    if (opt->want_prob) bam_read_label_prob(&r, res, n, labs);
+    if (opt->hla_grid >= 0) bam_hla_matrices(&r, res, n, K, nG);
+    SEXP out = result_end(&r);
     range_result_finalizer(guard);
-    UNPROTECT(13);
+    UNPROTECT(1);
     return out;
+}
+
+SEXP qa_impute_bam_range_call(SEXP bamFilesSEXP, SEXP sitesSEXP, SEXP panelSEXP, SEXP paramsSEXP, SEXP sample_indexSEXP, SEXP n_handlesSEXP) {
+    static const char *who = "qa_impute_bam_range";
+    /* 1. validate options */
+    bam_opts_t opt;
+    bam_range_validate(bamFilesSEXP, sitesSEXP, panelSEXP, paramsSEXP, sample_indexSEXP, who, &opt);
+    const int n = Rf_length(bamFilesSEXP);
+    /* 2. site arrays (R errors are raised only before they exist or after they are freed) */
+    site_arrays_t sa;
+    range_ctx_t cx;
+    memset(&cx, 0, sizeof cx);
+    int st = QA_OK;
+    char msg[512];
+    msg[0] = 0;
+    if (!site_arrays_make(&sa, sitesSEXP, bamFilesSEXP, sample_indexSEXP, &opt)) {
+        st = QA_ERR_INVALID;
+        snprintf(msg, sizeof msg, "sites: L / grid numeric, ref / alt character vectors of single letters, all of the panel's length%s",
+                 opt.rare ? " (and L_all / grid_all / ref_all / alt_all over all SNPs)" : "");
+    }
+    /* 3. set up */
+    if (st == QA_OK) {
+        st = range_setup(&cx, panelSEXP, paramsSEXP, Rf_asInteger(n_handlesSEXP), n);
+        if (st != QA_OK) snprintf(msg, sizeof msg, "%s", cx.msg);
+    }
+    qa_bam_range_result_t *res = NULL;
+    if (st == QA_OK) {
+        /* 4. fill qa_bam_range_io_t and the extras */
+        qa_bam_range_io_t io;
+        qa_bam_range_extras_t ex;
+        bam_io_fill(&io, &ex, sitesSEXP, &opt, &sa);
+        /* 5. call */
+        st = qa_impute_bam_range_ex(cx.handles, cx.n_handles, &cx.ip, &io, &ex, n, sa.paths, sa.sidx, cx.nipt ? cx.nq.ff : NULL, &res);
+        if (st != QA_OK) snprintf(msg, sizeof msg, "%s", qa_last_error());
+        range_teardown(&cx);
+    }
+    site_arrays_free(&sa);
+    if (st != QA_OK) {
+        if (res) qa_bam_range_destroy(res);
+        Rf_error("quilt_amd: %s: %s", who, msg);
+    }
+    /* 6. result to R objects (K and nGibbsSamples are plain numbers of the context: they outlive its teardown) */
+    return bam_result_to_R(res, n, &opt, cx.K, cx.ip.nGibbsSamples);
 }
 
 /* ---- registration (RcppExports.cpp:1703-1782) ----------------------------------------------------------------------

@@ -5,6 +5,8 @@ caching, error and registration code -- what `make -C shim check` only type-chec
 import numpy as np
 import pytest
 
+from tests.shim_calls import call_by_name as _call_by_name, panel_args as _panel_args, params as _params
+
 pytestmark = pytest.mark.gpu
 
 
@@ -21,17 +23,6 @@ def R():
 def panel():
     from quilt_amd.synth import make_synthetic_panel
     return make_synthetic_panel(K=1024, nSNPs=96 * 32, seed=21)
-
-
-def _params(R, prm, **more):
-    d = dict(nGibbsSamples=R.integer([prm.nGibbsSamples]), n_seek_its=R.integer([prm.n_seek_its]), Ksubset=R.integer([prm.Ksubset]),
-             Knew=R.integer([prm.Knew]), K_top_matches=R.integer([prm.K_top_matches]), heuristic_match_thin=R.real([prm.heuristic_match_thin]),
-             small_ref_panel_gibbs_iterations=R.integer([prm.small_ref_panel_gibbs_iterations]),
-             small_ref_panel_block_gibbs_iterations=R.integer(list(prm.small_ref_panel_block_gibbs_iterations)),
-             maxDifferenceBetweenReads=R.real([prm.maxDifferenceBetweenReads]), minGLValue=R.real([prm.minGLValue]), Jmax=R.integer([prm.Jmax]),
-             seed=R.real([float(prm.seed)]), samples_per_launch_set=R.integer([2]))
-    d.update(more)
-    return R.named(d)
 
 
 def _check(out, want, nL=2):
@@ -131,27 +122,6 @@ def test_sample_range_call_raises_r_errors(R, panel):
     with pytest.raises(RError, match="no reads"):
         R.dotcall("qa_impute_sample_range", R.list([R.sample_reads(s), R.list([])]), R.panel_objects(panel), _params(R, prm), R.real([0.0]),
                   R.integer([1]), R.nil)
-
-
-def _entry_args(name):
-    import json, os
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    return json.load(open(os.path.join(root, "tests", "golden", "callentries.json")))[name]["args"]
-
-
-def _call_by_name(R, name, vals):
-    """`.Call(name, ...)` with the arguments in the reference's order (tests/golden/callentries.json, from RcppExports.cpp);
-    arguments the test does not name are NULL."""
-    order = _entry_args(name)
-    assert set(vals) <= set(order), set(vals) - set(order)
-    return R.dotcall(name, *[vals.get(a, R.nil) for a in order])
-
-
-def _panel_args(R, panel):
-    return dict(hapMatcher=R.integer(np.zeros((1, 1), dtype=np.int32)), hapMatcherR=R.raw(panel.hapMatcherR), use_hapMatcherR=R.logical([1]),
-                distinctHapsB=R.integer(panel.distinctHapsB), distinctHapsIE=R.real(panel.distinctHapsIE),
-                eMatDH_special_matrix_helper=R.integer(panel.eMatDH_special_matrix_helper), eMatDH_special_matrix=R.integer(panel.eMatDH_special_matrix),
-                rhb_t=R.integer(panel.rhb_t), ref_error=R.real([panel.ref_error]))
 
 
 def test_full_panel_entry_38_arguments(R, panel):

@@ -164,6 +164,28 @@ int qa_panel_set_ranking_precision(qa_panel_t *panel, int32_t bits);
  * both from the one fp64 state. */
 int qa_panel_set_dosage_precision(qa_panel_t *panel, int32_t bits);
 
+/* Storage width of the small-panel Gibbs sampler's alphaHat_t / betaHat_t columns, for every Gibbs call made on this handle
+ * (qa_gibbs_batch, qa_gibbs_batch_rare_common, and the loops of qa_impute_*: their underflow retries and all-SNP calls included).
+ * 64 (default; 0 means the same): fp64 state, the kernels and the bytes of every release so far.  32: the four alpha / beta matrices
+ * of a chain (both labels) are STORED in device memory as fp32 -- widened to double on load, rounded to nearest-even on store --
+ * while every operation keeps its fp64 registers, the reference's operations and their order.  What is narrow: alphaHat_t and
+ * betaHat_t only.  Their columns are renormalised at every grid and recomputed from scratch by every forward and backward
+ * recursion, so an entry that rounds or underflows in fp32 is regenerated by the prior term at the next grid.  What is not:
+ * eMatGrid_t -- a label move updates it in place by multiply and divide and it can hold products far below 1e-38 -- and c stay
+ * fp64, as do the read emissions and the per-iteration record.  A chain's resident state is 4 of 6 matrices at half size: two
+ * thirds of the fp64 mode's.  Bars (E = the storage error of a column, 5.96e-8 relative): alphaHat_t / betaHat_t of
+ * state_out -- widened to double on the device before the download -- within rtol 4 E, atol 2^-126 of the reference's; eMatGrid_t
+ * and c within rtol 1e-6; hapProbs_t / genProbs within 2e-6 absolute, the bar of the fp32-state dosage passes
+ * (qa_panel_set_dosage_precision).  A read visit's probabilities move by a relative ~E, so a label differs from the fp64 run's
+ * only where a uniform lies that close to a threshold: labels are NOT bit-identical to the reference's over a whole pipeline.
+ * Two-label sampler only, every Ksubset and shard mode: on a handle at 32 a Gibbs call with ff > 0, and a qa_impute_* range with
+ * params->nipt (before its first sample), is QA_ERR_UNSUPPORTED.  Any value other than 0, 32 and 64 is QA_ERR_INVALID and leaves
+ * the handle as it was.  (A setter of the handle like the two above, not a member of qa_gibbs_opts_t / qa_impute_params_t: both
+ * structs keep the layout ABI 5 has.) */
+int qa_panel_set_gibbs_state_bits(qa_panel_t *panel, int32_t bits);
+/* what the handle is at: 32 or 64 (QA_ERR_INVALID for a NULL handle) */
+int qa_panel_get_gibbs_state_bits(qa_panel_t *panel);
+
 /* VALIDATION MODE.  reference_order = 1: every full-panel pass of this handle (lists, dosage, alphaHat_t / betaHat_t / gamma_t)
  * runs on kernels that form each K-wide sum in the order the reference's code adds it, by a single lane:
  *   - the forward column sum run_total (reference-single.cpp:1002-1075), the backward sum_e_times_b (:1899-1955) and

@@ -61,11 +61,11 @@ void launch_resample3(const void *gibbs_params, hipStream_t st);
 namespace {
 
 // Rcpp_run_forward_haploid (copied-from-stitch.cpp:340-387) for both labels, prior = alphaMat = 1/Ks
-template <int NE, int NW>
-__device__ void forward_full_both(Chain<NE, NW> &ch) {
+template <int NE, int NW, class TS>
+__device__ void forward_full_both(Chain<NE, NW, TS> &ch) {
     const int G = ch.G, Ksp = ch.Ksp;
     Col<NE> a[2], e[2];
-    GridStreams<Chain<NE, NW>> gs;
+    GridStreams<Chain<NE, NW, TS>> gs;
     for (int g = 0; g < G; g++) {
         if ((g & 63) == 0) {
             if (g) gs.store_c(ch);
@@ -100,12 +100,12 @@ __device__ void forward_full_both(Chain<NE, NW> &ch) {
 
 // Rcpp_run_backward_haploid (copied-from-stitch.cpp:392-409; FASTER = false) or
 // Rcpp_run_backward_haploid_QUILT_faster (:417-440; FASTER = true), both labels; beta(G-1) = c(G-1)
-template <int NE, int NW, bool FASTER>
-__device__ void backward_both(Chain<NE, NW> &ch) {
+template <int NE, int NW, bool FASTER, class TS>
+__device__ void backward_both(Chain<NE, NW, TS> &ch) {
     const int G = ch.G, Ksp = ch.Ksp;
     const double one_over_K = 1 / (double)ch.Ks;
     Col<NE> b[2], e[2];
-    GridStreams<Chain<NE, NW>> gs;
+    GridStreams<Chain<NE, NW, TS>> gs;
     gs.load_bwd(ch, (G - 1) & ~63);
     {
         const int j = (G - 1) & 63;
@@ -166,14 +166,16 @@ __device__ void backward_both(Chain<NE, NW> &ch) {
 // (eMatGrid, beta, c, the labels), so a segment with it_begin > 0 skips the initialisation and goes on; a segment's last sweep
 // keeps its alpha columns (the switch rate of the block definition reads them) and the pass itself is k_shard_blocks.  Every
 // SEG test is a compile-time constant: the builds without it are what they were.
-template <int NE, int NW, bool LEAN, bool SEG = false>
+// TS: what alpha and beta are stored as (Chain).  It reaches the kernel through the chain's ld / st / ldm / stm alone -- no
+// arithmetic statement below knows it -- and the TS = double builds are instruction for instruction what they were without it.
+template <int NE, int NW, bool LEAN, bool SEG = false, class TS = double>
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(LEAN ? QA_LEAN_WAVES : 1))) void k_gibbs(GibbsParams p) {
     __shared__ double s_red[2 * NW * 4];
     // LEAN: the current grid's eMatGrid columns wait in LDS while the grid's reads are sampled (10 KB per chain, 80 KB per
     // compute unit at two chains per SIMD): a move updates them there, and their 4 * NE registers are free in the read loop
     __shared__ double s_e[LEAN ? 2 * NE * 64 * NW : 1];
     const int c = blockIdx.x, t = threadIdx.x;
-    using CH = Chain<NE, NW>;
+    using CH = Chain<NE, NW, TS>;
     CH ch(p, c, t, s_red);
     constexpr int NT = CH::NT;
     const int lane = ch.lane;
@@ -761,11 +763,11 @@ sweeps:
 // forward step or to the pA / pB decision belongs in both places; tests/test_shard_block_gpu.py and tests/test_gibbs_gpu.py
 // hold each against its own reference.
 // ---------------------------------------------------------------------------------------------
-template <int NE, int NW>
+template <int NE, int NW, class TS = double>
 __global__ __launch_bounds__(64 * NW) void k_shard_blocks(GibbsParams p) {
     __shared__ double s_red[2 * NW * 4];
     const int c = blockIdx.x, t = threadIdx.x;
-    using CH = Chain<NE, NW>;
+    using CH = Chain<NE, NW, TS>;
     CH ch(p, c, t, s_red);
     constexpr int NT = CH::NT;
     const int lane = ch.lane;
@@ -909,8 +911,9 @@ __global__ __launch_bounds__(64 * NW) void k_shard_blocks(GibbsParams p) {
 // ---------------------------------------------------------------------------------------------
 // k_happrobs: gamma = alpha * beta / c on the fly, scattered to the 32 SNPs of the grid by each
 // haplotype's word (gibbs-small.cpp:540-634).  One 256-thread block per (grid, chain): thread =
-// (bit b, slice of 8 over k).
+// (bit b, slice of 8 over k).  TS: what alpha and beta are stored as (widened before the product).
 // ---------------------------------------------------------------------------------------------
+template <class TS>
 __global__ __launch_bounds__(256) void k_happrobs(GibbsParams p) {
     const int g = blockIdx.x, c = blockIdx.y;
     const int b = threadIdx.x & 31, part = threadIdx.x >> 5;
@@ -924,6 +927,7 @@ __global__ __launch_bounds__(256) void k_happrobs(GibbsParams p) {
     auto gk = [&](int h, int k) -> double & { return s_gk0[(size_t)h * Ksp + k]; };
     const int32_t *which = p.which + (size_t)c * Ks;
     const size_t mat = (size_t)G * Ksp;
+    const TS *const alpha = reinterpret_cast<const TS *>(p.alpha), *const beta = reinterpret_cast<const TS *>(p.beta);
     // gamma once per (label, haplotype), read with consecutive lanes on consecutive haplotypes (it used to be re-formed by
     // each of the 32 bit lanes from broadcast loads: 70 ms per launch, load-issue bound); the sums below keep their order
     for (int k = threadIdx.x; k < Ks; k += 256) {
@@ -932,7 +936,7 @@ __global__ __launch_bounds__(256) void k_happrobs(GibbsParams p) {
         for (int h = 0; h < p.nH; h++) {
             const size_t o = ((size_t)c * p.nH + h) * mat + (size_t)g * Ksp + k;
             const double x = 1 / p.cvec[((size_t)c * 3 + h) * G + g];
-            gk(h, k) = (p.alpha[o] * p.beta[o]) * x;
+            gk(h, k) = ((double)alpha[o] * (double)beta[o]) * x;
         }
     }
     __syncthreads();
@@ -993,7 +997,9 @@ __global__ __launch_bounds__(256) void k_happrobs(GibbsParams p) {
 // (all-SNP grid, chain): gamma of the grid's column goes to LDS once; thread = (SNP b of the grid, slice of 8 over k).
 // A common SNP reads its allele from the panel word of its common grid (the block's 32 SNPs span at most two of them);
 // a rare SNP from the haplotype's rare list, or is ref_error outright when no selected haplotype carries it.
+// TS: what alpha and beta are stored as.
 // ---------------------------------------------------------------------------------------------
+template <class TS>
 __global__ __launch_bounds__(256) void k_happrobs_rc(GibbsParams p) {
     const int g = blockIdx.x, c = blockIdx.y;
     const int b = threadIdx.x & 31, part = threadIdx.x >> 5;
@@ -1030,10 +1036,10 @@ __global__ __launch_bounds__(256) void k_happrobs_rc(GibbsParams p) {
             sw(q, k) = (cg >= 0 && gq < p.rc_Gc) ? panel_word(p, gq, kk, p.hm[(size_t)gq * p.Kp + kk]) : 0u;
         }
         for (int h = 0; h < p.nH; h++) {
-            const double *a = p.alpha + ((size_t)c * p.nH + h) * mat + (size_t)g * Ksp;
-            const double *be = p.beta + ((size_t)c * p.nH + h) * mat + (size_t)g * Ksp;
+            const TS *a = reinterpret_cast<const TS *>(p.alpha) + ((size_t)c * p.nH + h) * mat + (size_t)g * Ksp;
+            const TS *be = reinterpret_cast<const TS *>(p.beta) + ((size_t)c * p.nH + h) * mat + (size_t)g * Ksp;
             const double x = 1 / p.cvec[((size_t)c * 3 + h) * G + g];
-            gam(h, k) = (a[k] * be[k]) * x;
+            gam(h, k) = ((double)a[k] * (double)be[k]) * x;
         }
     }
     __syncthreads();
@@ -1212,7 +1218,7 @@ struct GibbsScratch {
     DBuf<uint16_t> rc_pairs;
     DBuf<int32_t> rc_pair_off;
     DBuf<size_t> rc_pair_base;
-    DBuf<double> blk_rate2, ff_chain, per_it;
+    DBuf<double> blk_rate2, ff_chain, per_it, widen;
     DBuf<int32_t> blk_where, blk_tab, blk_n;
 };
 
@@ -1247,16 +1253,22 @@ void launch_ematread(const GibbsParams &prm, int maxR, hipStream_t st) {
     QA_HIP(hipGetLastError());
 }
 
-template <int NE, int NW, bool LEAN = false, bool SEG = false>
+template <int NE, int NW, bool LEAN, bool SEG, class TS>
 void launch_gibbs_kernel(const GibbsParams &prm, hipStream_t st) {
-    hipLaunchKernelGGL((k_gibbs<NE, NW, LEAN, SEG>), dim3(prm.C), dim3(64 * NW), 0, st, prm);
+    hipLaunchKernelGGL((k_gibbs<NE, NW, LEAN, SEG, TS>), dim3(prm.C), dim3(64 * NW), 0, st, prm);
     QA_HIP(hipGetLastError());
 }
 
-template <int NE, int NW>
+template <int NE, int NW, class TS>
 void launch_shard_blocks_kernel(const GibbsParams &prm, hipStream_t st) {
-    hipLaunchKernelGGL((k_shard_blocks<NE, NW>), dim3(prm.C), dim3(64 * NW), 0, st, prm);
+    hipLaunchKernelGGL((k_shard_blocks<NE, NW, TS>), dim3(prm.C), dim3(64 * NW), 0, st, prm);
     QA_HIP(hipGetLastError());
+}
+
+// alphaHat_t / betaHat_t of state_out in the fp32 mode: widened on the device, before the download
+__global__ __launch_bounds__(256) void k_widen_state(const float *src, double *dst, size_t n) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) dst[i] = (double)src[i];
 }
 
 // The builds of the two-label chain kernels -- k_ematread, k_gibbs, k_shard_blocks -- in one place, as <rows per lane NE, waves NW>
@@ -1266,12 +1278,18 @@ using Chain2 = qa::PairList<Pair<1, 1>, Pair<2, 1>, Pair<3, 1>, Pair<4, 1>, Pair
                             Pair<11, 1>, Pair<12, 1>, Pair<13, 1>, Pair<14, 1>, Pair<15, 1>, Pair<16, 1>, Pair<5, 2>, Pair<2, 5>, Pair<1, 10>>;
 static_assert(qa::max_over(Chain2{}, [](int ne, int nw) { return 64 * ne * nw; }) == QA_KSUBSET_MAX,
               "the two-label sampler is built for the documented Ksubset range");
+// ... and what k_gibbs, k_shard_blocks, k_happrobs, k_happrobs_rc (and k_block_rate3 of gibbs3.hip for the block-wise shard pass)
+// store alphaHat_t and betaHat_t as: every geometry above is built for each (qa_panel_set_gibbs_state_bits; k_ematread does not
+// touch the state and has one build per geometry)
+using ChainState = qa::TypeList<double, float>;
 
 // The build one launch runs, decided once (chunk_layout) and read by everything that depends on it: NE rows per lane x NW waves,
-// and whether it is the sampler's 256-register build
+// whether it is the sampler's 256-register build, and the width alpha and beta are stored at
 struct ChainBuild {
     int NE, NW;
     bool lean;
+    int state_bits = 64;
+    size_t state_bytes() const { return (size_t)state_bits / 8; }   // sizeof(TS)
     int er_nt() const { return 64 * NW; }            // the read-emission patterns: lanes per read,
     int er_padb() const { return padb_of(NE); }      // bytes per lane
 };
@@ -1325,20 +1343,32 @@ void for_chain_build(const ChainBuild &b, F &&f) {
     if (!qa::dispatch(Chain2{}, b.NE, b.NW, f)) throw std::runtime_error("Ksubset geometry not built (Ksubset / 64 rounded up must be 1..16)");
 }
 
+// f(NE, NW, type_c<TS>) for the launch's build of a kernel that reads or writes alpha / beta
+template <class F>
+void for_chain_state_build(const ChainBuild &b, F &&f) {
+    for_chain_build(b, [&](auto ne, auto w) {
+        // (unreachable through the ABI: qa_panel_set_gibbs_state_bits admits 0, 32 and 64 only)
+        if (!qa::dispatch(ChainState{}, b.state_bits, [&](auto ts) { f(ne, w, ts); })) throw std::runtime_error("state width not built (32 or 64 bits)");
+    });
+}
+
 // the sweeps of the two-label sampler: the whole call (SEG = false), or its sweeps [it_begin, it_end)
 template <bool SEG>
 void launch_gibbs_sweeps(const GibbsParams &prm, const ChainBuild &b, hipStream_t st) {
-    for_chain_build(b, [&](auto ne, auto w) {
+    for_chain_state_build(b, [&](auto ne, auto w, auto ts) {
         constexpr int NE = decltype(ne)::value, NW = decltype(w)::value;
+        using TS = typename decltype(ts)::type;
         if constexpr (NE == 10 && NW == 1) {
-            if (b.lean) return launch_gibbs_kernel<10, 1, true, SEG>(prm, st);
+            if (b.lean) return launch_gibbs_kernel<10, 1, true, SEG, TS>(prm, st);
         }
-        launch_gibbs_kernel<NE, NW, false, SEG>(prm, st);
+        launch_gibbs_kernel<NE, NW, false, SEG, TS>(prm, st);
     });
 }
 
 void launch_shard_blocks(const GibbsParams &prm, const ChainBuild &b, hipStream_t st) {
-    for_chain_build(b, [&](auto ne, auto w) { launch_shard_blocks_kernel<decltype(ne)::value, decltype(w)::value>(prm, st); });
+    for_chain_state_build(b, [&](auto ne, auto w, auto ts) {
+        launch_shard_blocks_kernel<decltype(ne)::value, decltype(w)::value, typename decltype(ts)::type>(prm, st);
+    });
 }
 
 void launch_gibbs(const GibbsParams &prm, int maxR, hipStream_t st, hipEvent_t *ev, bool want_probs, const ChainBuild &b,
@@ -1355,8 +1385,13 @@ void launch_gibbs(const GibbsParams &prm, int maxR, hipStream_t st, hipEvent_t *
         // dynamic LDS: nH gamma columns of Ksp doubles + the panel words (+ the haplotype list for the rare + common form)
         const size_t lds_hp = (size_t)prm.nH * prm.Ksp * 8 + (size_t)prm.Ksp * 4;
         const size_t lds_rc = (size_t)prm.nH * prm.Ksp * 8 + (size_t)2 * prm.Ksp * 4 + (size_t)prm.Ksp * 4;
-        if (prm.rc_common) hipLaunchKernelGGL(k_happrobs_rc, dim3(prm.G, prm.C), dim3(256), lds_rc, st, prm);
-        else hipLaunchKernelGGL(k_happrobs, dim3(prm.G, prm.C), dim3(256), lds_hp, st, prm);
+        // (the three-label sampler's state is fp64: gibbs_batch_impl refuses the fp32 mode with ff > 0)
+        if (!qa::dispatch(ChainState{}, b.state_bits, [&](auto ts) {
+                using TS = typename decltype(ts)::type;
+                if (prm.rc_common) hipLaunchKernelGGL(k_happrobs_rc<TS>, dim3(prm.G, prm.C), dim3(256), lds_rc, st, prm);
+                else hipLaunchKernelGGL(k_happrobs<TS>, dim3(prm.G, prm.C), dim3(256), lds_hp, st, prm);
+            }))
+            throw std::runtime_error("state width not built (32 or 64 bits)");
         QA_HIP(hipGetLastError());
     }
     QA_HIP(hipEventRecord(ev[3], st));
@@ -1515,7 +1550,7 @@ ChunkHost chunk_layout(qa_panel_t *pn, const qa_rare_common *rc, const qa_gibbs_
         h.build = {h.Ksp / 64 / nw, nw, h.Ksp == 640 && nw == 1 && lean3_env && atoi(lean3_env) != 0};
     } else {
         const int nw = choose_gibbs_waves(h.Ksp, C, pn->exclusive ? 0 : pn->share);
-        h.build = {h.Ksp / 64 / nw, nw, h.Ksp == 640 && nw == 1 && use_lean_build(C)};
+        h.build = {h.Ksp / 64 / nw, nw, h.Ksp == 640 && nw == 1 && use_lean_build(C), pn->gibbs_state_bits};
     }
     h.rc_any.assign((size_t)C * h.rc_words, 0u);
     h.base_off.assign(C + 1, 0); h.which0.resize((size_t)C * h.Ks);
@@ -1745,7 +1780,9 @@ void carve_arena(qa::GibbsScratch &S, qa::Arena &arena, size_t arena_need, const
     S.eMatRead.ensure(std::max<size_t>(h.etot, 1));
     S.er_idx.ensure(std::max<size_t>(h.ixtot, 1));
     S.er_tab.ensure(std::max<size_t>((size_t)h.totR * 64, 1));
-    S.alpha.ensure(mat); S.beta.ensure(mat); S.eg.ensure(mat);
+    // alpha and beta hold `mat` entries of sizeof(TS) bytes each (carved in doubles: half as many in the fp32 mode)
+    const size_t mat_ab = (mat * h.build.state_bytes() + 7) / 8;
+    S.alpha.ensure(mat_ab); S.beta.ensure(mat_ab); S.eg.ensure(mat);
     S.cvec.ensure((size_t)h.C * 3 * h.G);
     if (h.want_probs) {
         S.hap.ensure((size_t)h.C * h.T * 3); S.gm.ensure((size_t)h.C * h.T * 3); S.gf.ensure((size_t)h.C * h.T * 3);
@@ -1772,6 +1809,7 @@ GibbsParams fill_params(const qa::GibbsScratch &S, const qa_panel_t *pn, const q
     prm.nH = h.nH;
     prm.it_begin = 0; prm.it_end = h.n_its;
     prm.ff = o->ff;
+    prm.state32 = h.build.state_bits == 32;
     if (o->per_it_out) {
         QA_HIP(hipMemsetAsync(S.per_it.p, 0, sizeof(double) * C * h.n_its * 8, st));
         prm.per_it = S.per_it.p;
@@ -2038,14 +2076,27 @@ double profile_launch(hipEvent_t *ev, const ChunkHost &h, int n_block) {
 }
 
 // debugging / test aid (one-chain calls): alpha, beta, eMatGrid of both labels ([6][G][Ks]) then c ([3][G])
-void dump_state(const qa::GibbsScratch &S, const ChunkHost &h, double *state_out) {
+// (fp32 mode: alpha and beta are widened to double on the device first -- k_widen_state, into S.widen -- so that what is
+// downloaded and copied out is the same [G][Ksp] doubles per matrix either way)
+void dump_state(qa::GibbsScratch &S, const ChunkHost &h, hipStream_t st, double *state_out) {
     const int G = h.G, Ks = h.Ks, Ksp = h.Ksp;
-    std::vector<double> tmp((size_t)G * Ksp);
+    const size_t n_mat = (size_t)G * Ksp;
+    std::vector<double> tmp(n_mat);
     const qa::ABuf<double> *src[3] = {&S.alpha, &S.beta, &S.eg};
+    const bool narrow = h.build.state_bits == 32;
+    if (narrow) S.widen.ensure(n_mat);
     size_t o2 = 0;
     for (int m = 0; m < 3; m++)
         for (int hl = 0; hl < 2; hl++) {
-            QA_HIP(hipMemcpy(tmp.data(), src[m]->p + (size_t)hl * G * Ksp, sizeof(double) * tmp.size(),
+            const double *from = src[m]->p + (size_t)hl * n_mat;
+            if (narrow && m < 2) {
+                hipLaunchKernelGGL(k_widen_state, dim3((unsigned)((n_mat + 255) / 256)), dim3(256), 0, st,
+                                   reinterpret_cast<const float *>(src[m]->p) + (size_t)hl * n_mat, S.widen.p, n_mat);
+                QA_HIP(hipGetLastError());
+                QA_HIP(hipStreamSynchronize(st));
+                from = S.widen.p;
+            }
+            QA_HIP(hipMemcpy(tmp.data(), from, sizeof(double) * tmp.size(),
                              hipMemcpyDeviceToHost));
             for (int g = 0; g < G; g++)
                 for (int k = 0; k < Ks; k++) state_out[o2 + (size_t)g * Ks + k] = tmp[(size_t)g * Ksp + k];
@@ -2100,7 +2151,7 @@ int gibbs_chunk(qa_panel_t *pn, size_t arena_need, const qa_rare_common *rc, con
         if (L.a.underflow_problem) L.a.underflow_problem[c] = status[c];
         if (status[c]) ret = QA_UNDERFLOW;
     }
-    if (dump) dump_state(S, h, L.a.state_out);
+    if (dump) dump_state(S, h, st, L.a.state_out);
     return ret;
 }
 
@@ -2114,6 +2165,12 @@ int gibbs_batch_impl(qa_panel_t *pn, const qa_rare_common *rc, const qa_gibbs_op
     if ((o->ff != 0.0) != (o->sample_is_diploid == 0) || o->ff < 0 || o->ff >= 1) {
         qa::set_error("qa_gibbs_batch: ff > 0 goes with sample_is_diploid = 0 (NIPT), ff = 0 with sample_is_diploid = 1");
         return QA_ERR_INVALID;
+    }
+    static_assert(qa::contains(ChainState{}, 32) && qa::contains(ChainState{}, 64), "the widths qa_panel_set_gibbs_state_bits admits are built");
+    if (pn->gibbs_state_bits == 32 && o->ff != 0.0) {
+        qa::set_error("qa_gibbs_batch: this handle stores the Gibbs state as fp32 (qa_panel_set_gibbs_state_bits = 32), which the "
+                      "two-label sampler (ff = 0) serves only; with ff > 0 (NIPT) a handle at 0 or 64 runs");
+        return QA_ERR_UNSUPPORTED;
     }
     if (o->ff != 0.0 && o->perform_block_gibbs && o->n_block_gibbs_iterations > 0 &&
         (!o->L_grid || o->shuffle_bin_radius <= 0 || !(o->block_gibbs_quantile_prob > 0 && o->block_gibbs_quantile_prob < 1) ||
@@ -2245,9 +2302,12 @@ int gibbs_batch_impl(qa_panel_t *pn, const qa_rare_common *rc, const qa_gibbs_op
                 }
             });
         }
+        // the state matrices per cell of [G][Ksp]: alpha, beta and eMatGrid of each label in fp64 (72 / 48 bytes), or in the fp32
+        // mode (two labels) eMatGrid in fp64 and alpha and beta at four bytes each (32 bytes)
+        const size_t state_bytes_per_cell = o->ff != 0.0 ? 9 * 8 : (pn->gibbs_state_bits == 32 ? 2 * 8 + 4 * 4 : 6 * 8);
         for (int c = 0; c < n_chain; c++) {
             const size_t R = read_off[c + 1] - read_off[c];
-            adds[c] = R * (pat_bytes + 512) + n_long_of[c] * Ksp * 8 + (size_t)(o->ff != 0.0 ? 9 : 6) * G * Ksp * 8 + (size_t)3 * G * 8 +
+            adds[c] = R * (pat_bytes + 512) + n_long_of[c] * Ksp * 8 + state_bytes_per_cell * G * Ksp + (size_t)3 * G * 8 +
                       (want_probs ? (size_t)9 * T * 8 : 0) + 8192;
         }
         // A launch costs a chain's serial latency whatever it carries, so when the chains do not fit one launch they are cut

@@ -598,6 +598,8 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(LEAN ? 
 //                   then labels re-drawn from their classes (rcpp_sample_H_using_H_class, :213-246), eMatGrid, forward
 //                   and backward redone.  One workgroup per chain, like the sampler.
 // ---------------------------------------------------------------------------------------------
+// TS: what alpha and beta are stored as -- float for the two-label sampler's fp32 mode (GibbsParams.state32), else double
+template <class TS = double>
 __global__ __launch_bounds__(256) void k_block_rate3(GibbsParams p) {
     const int c = blockIdx.y, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int g = blockIdx.x * 4 + wave;
@@ -608,11 +610,11 @@ __global__ __launch_bounds__(256) void k_block_rate3(GibbsParams p) {
         const size_t mat = (size_t)G * Ksp;
         const double d = p.sigma[g];
         for (int h = 0; h < p.nH; h++) {
-            const double *a = p.alpha + ((size_t)c * p.nH + h) * mat + (size_t)g * Ksp;
-            const double *b = p.beta + ((size_t)c * p.nH + h) * mat + (size_t)(g + 1) * Ksp;
+            const TS *a = reinterpret_cast<const TS *>(p.alpha) + ((size_t)c * p.nH + h) * mat + (size_t)g * Ksp;
+            const TS *b = reinterpret_cast<const TS *>(p.beta) + ((size_t)c * p.nH + h) * mat + (size_t)(g + 1) * Ksp;
             const double *e = p.eg + ((size_t)c * p.nH + h) * mat + (size_t)(g + 1) * Ksp;
             double s = 0;
-            for (int k = lane; k < Ks; k += 64) s += a[k] * b[k] * e[k];
+            for (int k = lane; k < Ks; k += 64) s += (double)a[k] * (double)b[k] * e[k];
             s = wsum(s);
             out += 1 - d * s;
         }
@@ -1070,7 +1072,8 @@ void launch_gibbs3(const void *params, hipStream_t st) {
 
 void launch_block_rate3(const void *params, hipStream_t st) {
     const GibbsParams &prm = *static_cast<const GibbsParams *>(params);
-    hipLaunchKernelGGL(k_block_rate3, dim3((prm.G - 1 + 3) / 4, prm.C), dim3(256), 0, st, prm);
+    if (prm.state32) hipLaunchKernelGGL(k_block_rate3<float>, dim3((prm.G - 1 + 3) / 4, prm.C), dim3(256), 0, st, prm);
+    else hipLaunchKernelGGL(k_block_rate3<double>, dim3((prm.G - 1 + 3) / 4, prm.C), dim3(256), 0, st, prm);
     QA_HIP(hipGetLastError());
 }
 

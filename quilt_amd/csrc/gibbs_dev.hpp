@@ -68,7 +68,7 @@ struct GibbsParams {
     int er_nt, er_padb;
     uint8_t *is_cat1;        // [sum R]
     uint8_t *er_nent;        // [sum R] table entries a compact read refers to (2^informative SNPs; 64: unknown / all)
-    double *alpha, *beta, *eg;  // [C][2][G][Ksp]
+    double *alpha, *beta, *eg;  // [C][2][G][Ksp]; with state32, alpha and beta hold [C][2][G][Ksp] floats behind the same pointers
     double *cvec;            // [C][3][G]
     int32_t *H;              // [sum R] labels 1-based (in/out)
     int32_t *H_class;        // [sum R]
@@ -103,6 +103,7 @@ struct GibbsParams {
     double ff;
     const double *ff_chain;     // [C] or null: per-chain fetal fraction overriding ff
     double *per_it;             // [C][n_its][8] or null: per sweep -sum(log c_h) and the label counts (qa_gibbs_opts_t.per_it_out)
+    int state32;                // qa_panel_set_gibbs_state_bits(32): alpha / beta are stored as fp32 (two-label sampler only)
 };
 
 // does panel haplotype `hap` carry the alt allele of rare SNP `snp` (rare_per_hap_info)
@@ -425,6 +426,13 @@ __device__ __forceinline__ void buf_st_f64(__amdgpu_buffer_rsrc_t r, uint32_t by
     __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(__attribute__((__vector_size__(2 * sizeof(unsigned int)))) unsigned int, v), r,
                                           (int)byte_off, 0, 0);
 }
+// the fp32-stored state columns (Chain's TS = float): a dword per row, widened on load, rounded to nearest-even on store
+__device__ __forceinline__ double buf_ld_f32(__amdgpu_buffer_rsrc_t r, uint32_t byte_off) {
+    return (double)__builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)byte_off, 0, 0));
+}
+__device__ __forceinline__ void buf_st_f32(__amdgpu_buffer_rsrc_t r, uint32_t byte_off, double v) {
+    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned int, (float)v), r, (int)byte_off, 0, 0);
+}
 
 template <int NE>
 __device__ __forceinline__ void load_col(Col<NE> &c, const double *src, int t, int NT) {
@@ -447,12 +455,16 @@ __device__ __forceinline__ double fast_rcp(double e) {
     return r;
 }
 
-template <int NE, int NW>
+// TS: the type alpha and beta are STORED as -- double, or float on a handle at qa_panel_set_gibbs_state_bits(32) (two-label sampler only).
+// Nothing else depends on it: a column in registers is a Col<NE> of doubles either way, and eMatGrid, c and the read emissions
+// are doubles in memory too.
+template <int NE, int NW, class TS = double>
 struct Chain {
     static constexpr int NT = 64 * NW;
     const GibbsParams &p;
     int c, t, lane, wave, R, G, Ks, Ksp;
-    double *alpha[3], *beta[3], *eg[3], *cv[3];   // state matrices of the chain's nH labels
+    TS *alpha[3], *beta[3];       // state matrices of the chain's nH labels: alpha and beta as stored,
+    double *eg[3], *cv[3];        // eMatGrid and c always fp64
     const double *eMatRead;   // dense columns of the reads that have one
     const uint8_t *eridx;     // compact read emissions (GibbsParams)
     const double *ertab;
@@ -472,8 +484,8 @@ struct Chain {
         const size_t mat = (size_t)G * Ksp;
         for (int h = 0; h < 3; h++) {
             const size_t at = ((size_t)c * p.nH + min(h, p.nH - 1)) * mat;
-            alpha[h] = p.alpha + at;
-            beta[h] = p.beta + at;
+            alpha[h] = reinterpret_cast<TS *>(p.alpha) + at;
+            beta[h] = reinterpret_cast<TS *>(p.beta) + at;
             eg[h] = p.eg + at;
         }
         for (int h = 0; h < 3; h++) cv[h] = p.cvec + ((size_t)c * 3 + h) * G;
@@ -617,6 +629,26 @@ struct Chain {
         const __amdgpu_buffer_rsrc_t r = buf_rsrc(dst, (uint32_t)Ks * 8);
 #pragma unroll
         for (int i = 0; i < NE; i++) buf_st_f64(r, (uint32_t)(t + NT * i) * 8, c.v[i]);
+    }
+    // alpha / beta stored as fp32 (TS = float).  ld / st move all Ksp rows of a column -- the padding rows keep their 0 --
+    // ldm / stm the Ks real rows through a resource of Ks * 4 bytes.
+    __device__ __forceinline__ void ld(Col<NE> &c, const float *src) const {
+#pragma unroll
+        for (int i = 0; i < NE; i++) c.v[i] = (double)src[t + NT * i];
+    }
+    __device__ __forceinline__ void st(const Col<NE> &c, float *dst) const {
+#pragma unroll
+        for (int i = 0; i < NE; i++) dst[t + NT * i] = (float)c.v[i];
+    }
+    __device__ __forceinline__ void ldm(Col<NE> &c, const float *src) const {
+        const __amdgpu_buffer_rsrc_t r = buf_rsrc(src, (uint32_t)Ks * 4);
+#pragma unroll
+        for (int i = 0; i < NE; i++) c.v[i] = buf_ld_f32(r, (uint32_t)(t + NT * i) * 4);
+    }
+    __device__ __forceinline__ void stm(const Col<NE> &c, float *dst) const {
+        const __amdgpu_buffer_rsrc_t r = buf_rsrc(dst, (uint32_t)Ks * 4);
+#pragma unroll
+        for (int i = 0; i < NE; i++) buf_st_f32(r, (uint32_t)(t + NT * i) * 4, c.v[i]);
     }
 };
 

@@ -1660,6 +1660,9 @@ int qa_impute_params_default(qa_impute_params_t *p) {
 
 // the product's loop over the library's own entry points: qa_impute_samples, and (hla, select_gamma) qa_impute_samples_hla of
 // csrc/impute_hla.cpp -- internal to the library, not exported
+extern "C" int qa_panel_get_gibbs_state_bits(qa_panel_t *panel) __attribute__((weak));
+static int (*const panel_gibbs_state_bits)(qa_panel_t *) = qa_panel_get_gibbs_state_bits;
+
 int qa::impute_samples_product(qa_panel_t *const *panels, int32_t n_panels, const qa_impute_params_t *params, int32_t n_sample,
                               int64_t sample_offset, const int32_t *read_off, const int32_t *read_ptr, const int32_t *u, const int32_t *bq,
                               const int32_t *wif, double *dosage, double *gp_t, double *phasing_haps, int32_t *read_labels,
@@ -1687,6 +1690,17 @@ int qa::impute_samples_product(qa_panel_t *const *panels, int32_t n_panels, cons
             if (panels[i] == panels[j]) {
                 qa::set_error("qa_impute_samples: every host thread needs a handle of its own");
                 return QA_ERR_INVALID;
+            }
+    // the Gibbs state's storage width is the handles' (qa_panel_set_gibbs_state_bits): what the three-label sampler would refuse at
+    // its first call, likewise before the first sample
+    // (asked through a weak reference: this file also links without the device library, in the host sanitizers' harness, where
+    // no handle has a width)
+    if (params && params->nipt && panel_gibbs_state_bits)
+        for (int i = 0; i < n_panels; i++)
+            if (panel_gibbs_state_bits(panels[i]) == 32) {
+                qa::set_error("qa_impute_samples: panel handle %d stores the Gibbs state as fp32 (qa_panel_set_gibbs_state_bits = 32), which "
+                              "is served with method = \"diploid\" only; method = \"nipt\" runs on handles at 0 or 64", i);
+                return QA_ERR_UNSUPPORTED;
             }
     return impute_impl(true, &kProduct, reinterpret_cast<void *const *>(panels), n_panels, K, G, T, params, n_sample, sample_offset, read_off,
                        read_ptr, u, bq, wif, dosage, gp_t, phasing_haps, read_labels, nDosage, stats, hla, select_gamma, reads_out);

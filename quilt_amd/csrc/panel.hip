@@ -555,6 +555,17 @@ int qa_panel_set_dosage_precision(qa_panel_t *panel, int32_t bits) {
     return QA_OK;
 }
 
+int qa_panel_set_gibbs_state_bits(qa_panel_t *panel, int32_t bits) {
+    if (!panel || (bits != 0 && bits != 32 && bits != 64)) {
+        qa::set_error("qa_panel_set_gibbs_state_bits: bits = %d; 0 or 64 (fp64 alphaHat_t / betaHat_t) and 32 (fp32) run", bits);
+        return QA_ERR_INVALID;
+    }
+    panel->gibbs_state_bits = bits == 32 ? 32 : 64;
+    return QA_OK;
+}
+
+int qa_panel_get_gibbs_state_bits(qa_panel_t *panel) { return panel ? panel->gibbs_state_bits : (int)QA_ERR_INVALID; }
+
 int qa_panel_set_sum_order(qa_panel_t *panel, int32_t reference_order) {
     if (!panel || reference_order < 0 || reference_order > 2) {
         qa::set_error("qa_panel_set_sum_order: reference_order must be 0, 1 or 2");

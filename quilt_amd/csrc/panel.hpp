@@ -34,6 +34,7 @@ struct qa_panel {
     int share = 1;              // host threads / panel handles sharing this device (qa_panel_set_device_share)
     bool rank_fp64 = true;      // best-haplotype lists from fp64-state passes (qa_panel_set_ranking_precision)
     bool dosage_fp64 = false;   // dosage / alpha / beta / gamma outputs from fp64-state passes (qa_panel_set_dosage_precision)
+    int gibbs_state_bits = 64;  // what the two-label Gibbs sampler stores alphaHat_t / betaHat_t as (qa_panel_set_gibbs_state_bits)
     bool sum_order_ref = false; // VALIDATION MODE: full-panel passes by the reference-order kernels (qa_panel_set_sum_order, fullpass_ref.hip)
     bool sum_order_batched = false; // ... launch sets of two or more such passes by the one-wave-per-pass kernels (qa_panel_set_sum_order_batched, fullpass_ord.hip)
     bool sum_order_grid0_ltr = false; // ... with grid 0's sum(alphaHat_t_col) left to right instead of Armadillo's two accumulators (mode 2)

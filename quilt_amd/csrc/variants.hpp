@@ -20,14 +20,26 @@ struct Pair { static constexpr int a = A, b = B; };
 template <class... P>
 struct PairList {};
 
+// one type per build: TypeList<double, float> (what a kernel family stores its state as); the run-time key is the type's width in bits
+template <class T>
+struct type_c { using type = T; };
+template <class... T>
+struct TypeList {};
+template <class T>
+constexpr int bits_of = 8 * (int)sizeof(T);
+
 // f(the matching entry as integral constants); whether one matched
 template <int... N, class F>
 bool dispatch(IntList<N...>, int key, F &&f) { return ((key == N && (f(int_c<N>{}), true)) || ...); }
 template <class... P, class F>
 bool dispatch(PairList<P...>, int a, int b, F &&f) { return ((a == P::a && b == P::b && (f(int_c<P::a>{}, int_c<P::b>{}), true)) || ...); }
+template <class... T, class F>
+bool dispatch(TypeList<T...>, int bits, F &&f) { return ((bits == bits_of<T> && (f(type_c<T>{}), true)) || ...); }
 
 template <int... N>
 constexpr bool contains(IntList<N...>, int key) { return ((key == N) || ...); }
+template <class... T>
+constexpr bool contains(TypeList<T...>, int bits) { return ((bits == bits_of<T>) || ...); }
 template <class... P>
 constexpr bool contains(PairList<P...>, int a, int b) { return ((a == P::a && b == P::b) || ...); }
 

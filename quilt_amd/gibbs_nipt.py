@@ -56,7 +56,8 @@ def forwardBackwardGibbsNIPT_batch(panel: DevicePanel, samples: Sequence, which_
                                    runif_resample=None, L_grid=None, shuffle_bin_radius: int = 5000,
                                    block_gibbs_quantile_prob: float = 0.95, return_per_it: bool = False,
                                    return_hap_words: bool = False, hap_major_out: Optional[np.ndarray] = None,
-                                   shard_check_every_pair: bool = True, draw_uniforms=None, reads_same_as=None):
+                                   shard_check_every_pair: bool = True, draw_uniforms=None, reads_same_as=None,
+                                   state_bits: Optional[int] = None):
     """``n_chain`` independent calls of ``rcpp_forwardBackwardGibbsNIPT`` in one launch set.
 
     ``samples[c]`` is a :class:`quilt_amd.synth.SampleReads`-like object (``read_ptr``, ``u``, ``bq``,
@@ -79,6 +80,11 @@ def forwardBackwardGibbsNIPT_batch(panel: DevicePanel, samples: Sequence, which_
     ``reads_same_as``: one index per chain, the first chain of this call with the same reads (the chain itself for the first of a
     sample): the bases of a chain that names an earlier one are not looked at (qa_gibbs_opts_t.reads_same_as); its ``read_ptr``
     and ``wif`` must still be the representative's.  Results do not depend on it.
+
+    ``state_bits``: None -- the width ``panel`` is set to (``DevicePanel.set_gibbs_state_bits``; fp64 unless set) -- or the
+    width of this call alone, the handle's restored afterwards: 0 or 64 = fp64 state, 32 = alphaHat_t and betaHat_t stored as
+    fp32 on the device (qa_panel_set_gibbs_state_bits: diploid only; eMatGrid_t and c stay fp64; with ``return_state`` the two
+    come back widened to float64).  The library refuses other values (status -2) and 32 with ``ff`` > 0 (status -3).
 
     ``hap_major_out``: a C-contiguous float64 array [n_chain, n_label, nSNPs] (ideally from ``native.pinned_empty``) that
     receives the haploid dosages label by label -- the layout the driver accumulates from -- instead of a per-chain
@@ -187,12 +193,20 @@ def forwardBackwardGibbsNIPT_batch(panel: DevicePanel, samples: Sequence, which_
     _t1 = time.perf_counter()
     tail = (C.byref(opts), C.c_int32(Cn), ptr(which), ptr(read_off), ptr(read_ptr), ptr(u), ptr(bq), ptr(wif), ptr(ru),
             ptr(fr), ptr(rs), ptr(H), ptr(Hc), ptr(hap), ptr(gm), ptr(gf), ptr(uf), ptr(state), ptr(sr), ptr(ss))
-    if rare_common is not None:
-        with span("device:gibbs_rare_common"):
-            st = lib().qa_gibbs_batch_rare_common(panel.handle, rare_common.handle, *tail)
-    else:
-        with span("device:gibbs"):
-            st = lib().qa_gibbs_batch(panel.handle, *tail)
+    restore = None
+    if state_bits is not None:   # this call alone at that width
+        restore = panel.gibbs_state_bits()
+        panel.set_gibbs_state_bits(state_bits)
+    try:
+        if rare_common is not None:
+            with span("device:gibbs_rare_common"):
+                st = lib().qa_gibbs_batch_rare_common(panel.handle, rare_common.handle, *tail)
+        else:
+            with span("device:gibbs"):
+                st = lib().qa_gibbs_batch(panel.handle, *tail)
+    finally:
+        if restore is not None:
+            panel.set_gibbs_state_bits(restore)
     if draw_failed:
         raise draw_failed[0]
     check(st)

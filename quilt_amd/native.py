@@ -283,6 +283,15 @@ class DevicePanel:
         throughout, as the reference (a verification mode, several times slower)."""
         check(lib().qa_panel_set_dosage_precision(self.handle, C.c_int32(bits)))
 
+    def set_gibbs_state_bits(self, bits: int):
+        """What every small-panel Gibbs call on this handle stores alphaHat_t / betaHat_t as: 64 (default; 0 means the same) =
+        fp64; 32 = fp32 storage with fp64 arithmetic (diploid only; eMatGrid_t and c stay fp64): two thirds of a chain's state.
+        Other values are refused (status -2)."""
+        check(lib().qa_panel_set_gibbs_state_bits(self.handle, C.c_int32(bits)))
+
+    def gibbs_state_bits(self) -> int:
+        return check(lib().qa_panel_get_gibbs_state_bits(self.handle))
+
     def set_sum_order(self, reference_order):
         """VALIDATION MODE (``True`` / 1): the full-panel passes form every K-wide sum in the order the reference's code adds
         it, by one lane (fullpass_ref.hip): the explicit loops with the grid's special haplotypes first, then k = 0 .. K-1;

@@ -62,7 +62,7 @@ class DeviceWorkers:
     def __init__(self, panel, params: Optional[DriverParams] = None, n_workers: int = 2, rare_common=None,
                  cu_partition: bool = False, fp64_dosage: bool = False, split: str = "halves", gibbs_gate: float = 0.0,
                  pass_priority: bool = False, exclusive: bool = False, fuse_tails: bool = True,
-                 split_remainder: bool = True, shard_blocks=None):
+                 split_remainder: bool = True, shard_blocks=None, gibbs_state_bits: int = 0):
         self.n = n_workers
         self.split_remainder = split_remainder   # split = "alternate": left-over batches are cut into one part per thread
         # the last batches' phasing rounds of all threads run together (driver.PhasingTail) instead of one after the other
@@ -79,6 +79,8 @@ class DeviceWorkers:
                 d.set_exclusive(True)
             if fp64_dosage:   # dosage passes with fp64 state, as the reference (verification mode)
                 d.set_dosage_precision(64)
+            if gibbs_state_bits:   # 32: the samplers' alphaHat_t / betaHat_t stored as fp32 (method = "diploid" only; 64: the default)
+                d.set_gibbs_state_bits(gibbs_state_bits)
             if pass_priority and n_workers > 1:   # full-panel calls ahead of the other threads' Gibbs launches
                 d.set_pass_priority(True)
             if cu_partition and n_workers > 1:   # each thread's Gibbs chains on its own share of the CUs (measured slower: DESIGN.md 5)
@@ -234,7 +236,7 @@ class NativeWorkers:
 
     def __init__(self, panel, params: Optional[DriverParams] = None, n_workers: int = 3, fp64_dosage: bool = False,
                  exclusive: bool = True, fuse_tails: bool = True, rare_common=None, output_read_label_prob: bool = False,
-                 shard_blocks=None):
+                 shard_blocks=None, gibbs_state_bits: int = 0):
         self.n = n_workers
         self.panel = panel
         self.output_read_label_prob = bool(output_read_label_prob)   # results carry read_label_prob (qa_impute_samples_reads)
@@ -249,6 +251,8 @@ class NativeWorkers:
                 d.set_exclusive(True)
             if fp64_dosage:
                 d.set_dosage_precision(64)
+            if gibbs_state_bits:   # (as DeviceWorkers: a setting of the handles, which both loops' Gibbs calls run on)
+                d.set_gibbs_state_bits(gibbs_state_bits)
         self.drcs = [DeviceRareCommon(d, rare_common) for d in self.devs] if rare_common is not None else []
         # (bench.py's stand-alone kernel timings drive single rounds through the Python statement of the loop)
         self.shard_blocks = shard_blocks   # shard_check_every_pair = FALSE (driver.ShardBlocks): into qa_impute_params_t

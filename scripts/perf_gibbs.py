@@ -16,9 +16,14 @@ ap.add_argument("--nipt", action="store_true", help="three read labels, block Gi
 ap.add_argument("--shard-blocks", action="store_true",
                 help="diploid: every repetition once with shard_check_every_pair = TRUE and once with FALSE (block-wise shard passes); "
                      "QA_TIMING=1 adds the host-idle time per pass on stderr")
+ap.add_argument("--state-bits", type=int, default=0, choices=(0, 32, 64),
+                help="storage width of alphaHat_t / betaHat_t (qa_panel_set_gibbs_state_bits): 32 = fp32 storage, diploid only; "
+                     "QA_TIMING=1 shows the chains per launch the planner made of it")
 a = ap.parse_args()
 panel = make_synthetic_panel(K=a.K, nSNPs=a.T, seed=4916)
 dev = DevicePanel(panel)
+if a.state_bits:
+    dev.set_gibbs_state_bits(a.state_bits)
 ns = a.samples or max(1, a.chains // 7)
 samples = [make_synthetic_sample(panel, seed=1000 + i, n_reads=a.reads, **({"ff": 0.2} if a.nipt else {})) for i in range(ns)]
 rng = np.random.default_rng(0)

@@ -26,6 +26,9 @@
 ## QUILT_AMD_SUM_ORDER (environment, default 0): 1 runs the full-panel passes in the library's VALIDATION MODE -- every K-wide sum
 ## in the order the reference's C++ adds it, bit-identical best-haplotype lists to the CPU package's on tie-rich panels, 20-50x
 ## slower passes (INTEGRATION.md 3a); 2: the same with grid 0's Armadillo sum() read left to right (include/quilt_amd.h).
+## QUILT_AMD_GIBBS_STATE_BITS (environment, default 0): 32 stores the small-panel Gibbs sampler's alphaHat_t / betaHat_t as fp32
+## (fp64 arithmetic; eMatGrid_t and c stay fp64): two thirds of a chain's state, passed on for method = "diploid" only
+## (include/quilt_amd.h, qa_panel_set_gibbs_state_bits).  The per-call entries stay at fp64.
 ##
 ## Random draws: 2 048 chains advancing together cannot consume ONE R stream in the reference's order, so the range call uses
 ## the library's counter streams keyed by (seed, global sample index, Gibbs sample); `seed` plays set.seed's part, and a
@@ -162,6 +165,7 @@ quilt_amd_impute_sample_range <- function(
     }
     sum_order <- as.integer(Sys.getenv("QUILT_AMD_SUM_ORDER", "0"))
     sum_order_batched <- as.integer(Sys.getenv("QUILT_AMD_SUM_ORDER_BATCHED", "0"))   ## with sum_order 1 or 2: the batched kernels, same bits
+    gibbs_state_bits <- as.integer(Sys.getenv("QUILT_AMD_GIBBS_STATE_BITS", "0"))   ## 32: fp32 alpha / beta storage (method = "diploid" only)
     panel_objects <- list(
         hapMatcherR = hapMatcherR, distinctHapsB = distinctHapsB, distinctHapsIE = distinctHapsIE,
         eMatDH_special_matrix_helper = eMatDH_special_matrix_helper, eMatDH_special_matrix = eMatDH_special_matrix,
@@ -189,7 +193,10 @@ quilt_amd_impute_sample_range <- function(
     if (method == "nipt") {
         params <- c(params, list(method = "nipt", shuffle_bin_radius = shuffle_bin_radius))
         panel_objects[["L_grid"]] <- as.numeric(L_grid)
-    } else if (!shard_check_every_pair) {
+    } else {
+        if (gibbs_state_bits != 0L) params[["gibbs_state_bits"]] <- gibbs_state_bits   ## (never with "nipt": the library refuses it there)
+    }
+    if (method != "nipt" && !shard_check_every_pair) {
         params <- c(params, list(shard_check_every_pair = FALSE, shuffle_bin_radius = shuffle_bin_radius,
                                  block_gibbs_quantile_prob = block_gibbs_quantile_prob))
         panel_objects[["L_grid"]] <- as.numeric(L_grid)

@@ -939,6 +939,11 @@ static int setup_panel_handles(range_ctx_t *cx, SEXP panelSEXP, SEXP paramsSEXP,
     /* params$sum_order_batched (QUILT_AMD_SUM_ORDER_BATCHED) beside a sum_order of 1 or 2: the same sums, hence the same bits, from
      * the kernels laid out for many passes at once (qa_panel_set_sum_order_batched) */
     const int sum_order_batched = sum_order ? (int)num_or(paramsSEXP, "sum_order_batched", 0) : 0;
+    /* params$gibbs_state_bits (quilt-amd.R takes it from QUILT_AMD_GIBBS_STATE_BITS): 0 / 64 = fp64 Gibbs state; 32 = alphaHat_t and
+     * betaHat_t stored as fp32 (qa_panel_set_gibbs_state_bits: method = "diploid" only -- the library refuses a "nipt" range on such
+     * handles before its first sample, and any other value here).  Both range entries; the per-call entries' handle stays at fp64
+     * (set.seed parity). */
+    const int gibbs_state_bits = (int)num_or(paramsSEXP, "gibbs_state_bits", 0);
     int st = QA_OK;
     for (; cx->made < n_handles && st == QA_OK; cx->made++) {
         cx->handles[cx->made] = NULL;
@@ -948,6 +953,7 @@ static int setup_panel_handles(range_ctx_t *cx, SEXP panelSEXP, SEXP paramsSEXP,
         if (st == QA_OK) st = qa_panel_set_dosage_precision(cx->handles[cx->made], 64);   /* the reference computes in double */
         if (st == QA_OK && sum_order) st = qa_panel_set_sum_order(cx->handles[cx->made], sum_order);
         if (st == QA_OK && sum_order_batched) st = qa_panel_set_sum_order_batched(cx->handles[cx->made], 1);
+        if (st == QA_OK && gibbs_state_bits) st = qa_panel_set_gibbs_state_bits(cx->handles[cx->made], gibbs_state_bits);
     }
     free(which);
     if (st != QA_OK) snprintf(cx->msg, sizeof cx->msg, "qa_panel_create: %s", qa_last_error());
